@@ -114,8 +114,12 @@ def parse():
                     help="northstar: the sweep on a second stream beside the solve (the default of this mode is stream order: "
                          "its kernels fill the chip)")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="the barrier-bracketed timed region (the same K frames) runs this many times back to back; value / "
-                         "ms_per_step are those of the MEDIAN region (a 20-step region is 13 ms: one region alone moves by percents)")
+                    help="the K timed steps run in this many barrier-bracketed regions back to back (K / repeats consecutive "
+                         "frames each, every step once); value / ms_per_step are those of the MEDIAN region (a 13 ms region "
+                         "alone moves by percents)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (float32 .npy, at most 64 MB in all: the "
+                         "fused volume as a fixed seeded sample of its voxels) to DIR/<name>.npy (rank 0)")
     ap.add_argument("--force-launcher", action="store_true",
                     help="--gpus 1: go through the rank launcher anyway (a fresh child with WORLD_SIZE=1, its core slice, rank 0's "
                          "line forwarded, the wall-clock limit) - the path every N > 1 run takes")
@@ -210,7 +214,7 @@ class Sequence:
         self.params = A.SolveParams(num_iter=cfg["gn_iters"], nonlinear_iter=1, linear_iter=256, pcg_tol=1e-6,
                                     gn_tol=0.0, **synth.SOLVER)
         self.s_fuse = concurrent_stream(device)
-        self.warped = None
+        self.warped = self.warped_n = None
         self.fuse_events = []
 
     def fuse(self, f, timed_events=None):
@@ -236,7 +240,7 @@ class Sequence:
         self.solver.solve(self.params)
         # post-solve warpToLive of the canonical frame, through the plan's k-NN graph (same output as the stand-alone
         # dfa_warp_to_live, which would search the 262 144 x 2 048 neighbours a second time)
-        self.warped, _ = self.solver.warp_to_live(self.normals)
+        self.warped, self.warped_n = self.solver.warp_to_live(self.normals)
 
     def frame(self, f, serial=False, timed_events=None):
         torch = self.torch
@@ -354,7 +358,7 @@ class Sequence:
         if shadows and not self._pipe_built:  # a solve with a single Gauss-Newton iteration has no second shadow
             self.s_graph.wait_stream(cur)
             self._build_graph(f + 1)
-        self.warped, _ = self.solver.warp_to_live(self.normals)
+        self.warped, self.warped_n = self.solver.warp_to_live(self.normals)
         ev = torch.cuda.Event()
         ev.record(cur)
         self.plan_free[i] = ev
@@ -462,6 +466,36 @@ class SequenceLive(Sequence):
         self.solver.solve(self.params)
         self.warped, _ = self.solver.warp_to_live(None)
         self.live_last = live
+
+
+DUMP_VOXELS = 1 << 21  # voxels of the volume sample --dump-outputs writes: 8 MB per array (a 512^3 volume is 512 MB)
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(seq, out_dir):
+    """--dump-outputs: what the last timed frame left its caller, as float32 arrays out_dir/<name>.npy — the solved node
+    transforms (and translations), the warped canonical vertices (and normals), the live cloud of --live depth, the frame's
+    distance image and the fused volume decoded into tsdf / weight at a fixed seeded sample of DUMP_VOXELS voxels (every
+    voxel of a smaller volume).  The inputs are synthetic and seeded: two builds run with the same arguments compare array
+    for array."""
+    torch = seq.torch
+    torch.cuda.synchronize()
+    n = seq.vol.numel()
+    vox = seq.vol.view(-1)
+    if n > DUMP_VOXELS:
+        vox = vox[torch.from_numpy(np.unique(np.random.default_rng(0).integers(0, n, DUMP_VOXELS))).to(vox.device)]
+    vox = vox.cpu().numpy().view(np.uint32)
+    out = dict(node_dq=seq.solver.node_dq(), translations=seq.solver.translations() if hasattr(seq.solver, "translations") else None,
+               warped_vertices=seq.warped, warped_normals=seq.warped_n, live_vertices=getattr(seq, "live_last", None),
+               dists=seq.dists, tsdf=(vox & 0xFFFF).astype(np.uint16).view(np.float16), tsdf_weight=vox >> 16)
+    out = {k: np.ascontiguousarray(v.cpu().numpy() if isinstance(v, torch.Tensor) else v, np.float32)
+           for k, v in out.items() if v is not None}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def multi_sequence_probe(cfg_name, device, counts=(1, 2, 4), rounds=60, warmup=8, threads=False):
@@ -850,27 +884,28 @@ def main_northstar(args, torch, replicas, rank, world, device):
         seq.frame(f, ser)
     fuse_events = []
 
-    def timed():
+    def timed(f):
         # (the per-phase hipEvents only around the LAST timed frame: an event costs ~5 us of stream time, and a C3 frame has
         # sixty of them — bracketed on every frame the line read 325 frames/s where the same frames run at 410)
-        for f in range(K):
-            if f == K - 1:
-                seq.solver.enable_timing(True)
-            seq.frame(Wm + f, ser, fuse_events if f % TIMING_SAMPLE == 0 else None)
+        if f == K - 1:
+            seq.solver.enable_timing(True)
+        seq.frame(Wm + f, ser, fuse_events if f % TIMING_SAMPLE == 0 else None)
 
-    dt_max, regions = median_region(replicas, timed, device, args.repeats)
+    step_s, regions, counts = median_region(replicas, timed, K, device, args.repeats)
     st = seq.solver.stats()
     tm = seq.solver.timing()  # hipEvents on the solve stream around every launch group of the LAST timed frame
     seq.solver.enable_timing(False)
     if rank != 0:
         replicas.shutdown()
         return
+    if args.dump_outputs:
+        dump_outputs(seq, args.dump_outputs)
     dim, Wd, Hd = cfg["dim"], cfg["width"], cfg["height"]
     fuse_ms = float(np.mean([a.elapsed_time(b) for a, b in fuse_events])) if fuse_events else float("nan")
     rl = northstar_rooflines(seq, args.config, st, tm, fuse_ms)
     out = dict(metric="frames/sec (warp-solve + TSDF fuse), 512^3 vol / 2k nodes / VGA depth",
-               value=round(n_gpus * K / dt_max, 2), unit="frames/s", n_gpus=n_gpus, steps=K, warmup=Wm,
-               ms_per_step=round(dt_max / K * 1e3, 4), higher_is_better=True, scaling="weak", vs_baseline=None,
+               value=round(n_gpus / step_s, 2), unit="frames/s", n_gpus=n_gpus, steps=K, warmup=Wm,
+               ms_per_step=round(step_s * 1e3, 4), higher_is_better=True, scaling="weak", vs_baseline=None,
                dtype="f32", data="synthetic",
                config=dict(workload="%s north-star: %d^3 TSDF, %dx%d depth, %d nodes, k=%d, %d vertices, <=%d GN (gn_tol %g) x "
                                     "block-Jacobi PCG<=%d, 6-DoF / point-to-plane / ARAP"
@@ -883,7 +918,7 @@ def main_northstar(args, torch, replicas, rank, world, device):
                                    if not seq.overlap or args.serial else ("fuse || graph build + solve on two HIP streams" if args.fuse_first else
                                                                            "graph build, then fuse || solve on two HIP streams"),
                            last_frame=northstar_fields(seq, st)),
-               region_ms=[round(r * 1e3, 4) for r in regions], roofline=rl[0], roofline_other=rl[1:])
+               region_ms=[round(r * 1e3, 4) for r in regions], region_steps=counts, roofline=rl[0], roofline_other=rl[1:])
     if not args.no_cpu_baseline and world == 1:
         params = seq.params
         del seq
@@ -1317,12 +1352,17 @@ def finish(out, args):
     emit(contract_line(out, shown))
 
 
-def median_region(replicas, fn, device, repeats):
-    """the barrier + synchronize-bracketed region `fn` `repeats` times back to back (the same frames every time);
-    returns (median seconds, [seconds of every region]) — MAX over ranks each (replicas.timed_region), so every rank gets the
-    same list"""
-    regions = [replicas.timed_region(fn, device) for _ in range(max(1, repeats))]
-    return sorted(regions)[len(regions) // 2], regions
+def median_region(replicas, step, steps, device, repeats):
+    """the `steps` timed steps step(0) .. step(steps - 1), once each, in min(repeats, steps) barrier + synchronize-bracketed
+    regions back to back (consecutive steps of as equal a count as divides); returns (median over the regions of seconds per
+    step, [seconds of every region], [steps of every region]) — MAX over ranks each (replicas.timed_region), so every rank
+    gets the same lists"""
+    n = max(1, min(repeats, steps))
+    bounds = [steps * r // n for r in range(n + 1)]
+    counts = [b - a for a, b in zip(bounds, bounds[1:])]
+    regions = [replicas.timed_region(lambda a=a, b=b: [step(i) for i in range(a, b)], device) for a, b in zip(bounds, bounds[1:])]
+    per_step = sorted(t / c for t, c in zip(regions, counts))
+    return per_step[len(per_step) // 2], regions, counts
 
 
 def under_profiler():
@@ -1442,16 +1482,16 @@ def main_dry_run(args):
     if rank == args.dry_run_hang_rank:
         time.sleep(1e6)
     K, Wm = args.steps, args.warmup
-    dt_max, regions = median_region(replicas, lambda: time.sleep(0.02 * K), None, args.repeats)
+    step_s, regions, counts = median_region(replicas, lambda i: time.sleep(0.02), K, None, args.repeats)
     if rank == 0:
         finish(dict(metric="frames/sec (warp-solve + TSDF fuse), 512^3 vol / 2k nodes / VGA depth",
-                              value=round(seen * K / dt_max, 2), unit="frames/s", n_gpus=seen, steps=K, warmup=Wm,
-                              ms_per_step=round(dt_max / K * 1e3, 4), higher_is_better=True, scaling="weak", vs_baseline=None,
+                              value=round(seen / step_s, 2), unit="frames/s", n_gpus=seen, steps=K, warmup=Wm,
+                              ms_per_step=round(step_s * 1e3, 4), higher_is_better=True, scaling="weak", vs_baseline=None,
                               dtype="f32", data="none (dry run: sleeps)",
                               config=dict(workload="dry run of the rank launcher (no GPU work)", ranks_seen=seen,
                                           rccl_selfcheck=rccl_selfcheck(), repeats=len(regions), launcher=launcher_mark(),
                                           parallelism="replicas x%d (no collective; counted by all-reduce, %s)" % (seen, args.backend)),
-                              region_ms=[round(r * 1e3, 4) for r in regions]), args)
+                              region_ms=[round(r * 1e3, 4) for r in regions], region_steps=counts), args)
     replicas.shutdown()
 
 
@@ -1504,15 +1544,17 @@ def main():
         seq = SequenceLive(args.config, device)
         dt_max = replicas.timed_region(lambda: [seq.frame(f) for f in range(args.warmup)], device)  # warm-up, untimed below
         K = args.steps
-        dt_max, regions = median_region(replicas, lambda: [seq.frame(args.warmup + f) for f in range(K)], device, args.repeats)
+        step_s, regions, counts = median_region(replicas, lambda f: seq.frame(args.warmup + f), K, device, args.repeats)
         if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(seq, args.dump_outputs)
             rec = live_depth_probe(args.config, device, steps=min(K, 30), warmup=0, seq=seq)
-            rec.update(metric="frames/sec (warp-solve + TSDF fuse), 512^3 vol / 2k nodes / VGA depth", value=round(n_gpus * K / dt_max, 2),
-                       n_gpus=n_gpus, steps=K, warmup=args.warmup, ms_per_step=round(dt_max / K * 1e3, 4), higher_is_better=True,
+            rec.update(metric="frames/sec (warp-solve + TSDF fuse), 512^3 vol / 2k nodes / VGA depth", value=round(n_gpus / step_s, 2),
+                       n_gpus=n_gpus, steps=K, warmup=args.warmup, ms_per_step=round(step_s * 1e3, 4), higher_is_better=True,
                        scaling="weak", vs_baseline=None, dtype="f32", data="synthetic",
                        config=dict(workload=rec.pop("workload"), ranks_seen=n_gpus, repeats=len(regions), rccl_selfcheck=rccl_selfcheck(),
                                    parallelism="replicas x%d (one sequence per GPU, no collective)" % n_gpus),
-                       region_ms=[round(r * 1e3, 4) for r in regions])
+                       region_ms=[round(r * 1e3, 4) for r in regions], region_steps=counts)
             finish(rec, args)
         replicas.shutdown()
         return
@@ -1537,15 +1579,14 @@ def main():
         plan.enable_timing(1)  # new measurement ...
         plan.enable_timing(0)  # ... paused
 
-    def timed():
-        for f in range(K):
-            sampled = f % TIMING_SAMPLE == 0
-            for plan in plans:
-                plan.enable_timing(2 if sampled else 0)
-            seq.frame(Wm + f, args.serial, fuse_events if sampled else None)
+    def timed(f):
+        sampled = f % TIMING_SAMPLE == 0
+        for plan in plans:
+            plan.enable_timing(2 if sampled else 0)
+        seq.frame(Wm + f, args.serial, fuse_events if sampled else None)
 
     # barrier + synchronize on both sides, MAX over ranks
-    dt_max, regions = median_region(replicas, timed, device, args.repeats)
+    step_s, regions, counts = median_region(replicas, timed, K, device, args.repeats)
     for plan in plans:
         plan.enable_timing(0)
     tm = max((plan.timing() for plan in plans), key=lambda t: t["solves"])  # sums over the sampled frames
@@ -1557,6 +1598,8 @@ def main():
     if rank != 0:
         replicas.shutdown()
         return
+    if args.dump_outputs:
+        dump_outputs(seq, args.dump_outputs)
 
     # ---- per-frame latency (SURVEY.md §8d asks for median and p95): a separate pass OUTSIDE the timed region, every
     # frame bracketed by two events and synchronised, so that a frame cannot hide behind the launches of the next
@@ -1635,8 +1678,8 @@ def main():
     dominant, other = (pcg_entry, fuse_entry) if pcg_total_ms > fuse_ms else (fuse_entry, pcg_entry)
 
     out = dict(metric="frames/sec (warp-solve + TSDF fuse), 512^3 vol / 2k nodes / VGA depth",
-               value=round(n_gpus * K / dt_max, 2), unit="frames/s", n_gpus=n_gpus, steps=K, warmup=Wm,
-               ms_per_step=round(dt_max / K * 1e3, 4), higher_is_better=True, scaling="weak", vs_baseline=None,
+               value=round(n_gpus / step_s, 2), unit="frames/s", n_gpus=n_gpus, steps=K, warmup=Wm,
+               ms_per_step=round(step_s * 1e3, 4), higher_is_better=True, scaling="weak", vs_baseline=None,
                dtype="f32", data="synthetic",
                config=dict(workload="%s: %d^3 TSDF, %dx%d depth, %d nodes, k=%d, %d vertices, %d GN x PCG<=256 (tol 1e-6), "
                                     "reference-parity energy (energy.t), lambda=200"
@@ -1658,7 +1701,7 @@ def main():
                            max_abs_translation_error_vs_ground_truth_m=round(t_err, 6)),
                frame_latency_ms=dict(median=round(lat[len(lat) // 2], 4), p95=round(lat[min(len(lat) - 1, int(0.95 * len(lat)))], 4),
                                      frames=len(lat), note="each frame synchronised, measured after the timed region"),
-               region_ms=[round(r * 1e3, 4) for r in regions],
+               region_ms=[round(r * 1e3, 4) for r in regions], region_steps=counts,
                roofline=dominant, roofline_other=[other],
                solve_kernels_ms_per_frame=dict(pcg=round(pcg_total_ms, 4), assemble=round(tm["assemble_ms"] / frames_timed, 4)))
     if world == 1:

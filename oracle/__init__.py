@@ -20,9 +20,8 @@ def build(force=False):
     srcs = [os.path.join(_HERE, f) for f in os.listdir(_HERE) if f.endswith((".c", ".h", ".inc", ".cpp"))]
     stale = force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs)
     ref_so = os.path.join(_HERE, "_ref", "libref_knn.so")
-    ref_mc = os.path.join(_HERE, "_ref", "mc_tables.bin")
     have_ref = os.path.exists("/root/reference/include/nanoflann/nanoflann.hpp")
-    if stale or (have_ref and not (os.path.exists(ref_so) and os.path.exists(ref_mc))):
+    if stale or (have_ref and not os.path.exists(ref_so)):
         subprocess.check_call(["make", "-C", _HERE, "-s", "all"])
     return so
 
@@ -36,7 +35,8 @@ def lib():
 
 
 def ref_lib():
-    """The reference's own nanoflann k-NN (oracle/_ref/libref_knn.so); None if not built."""
+    """The reference's own nanoflann k-NN (oracle/_ref/libref_knn.so); None if not built.  The tests read its answers from
+    tests/golden/ref_knn.npz (tests/golden/make_reference_outputs.py), not from this library."""
     global _REF
     if _REF is None:
         p = os.path.join(_HERE, "_ref", "libref_knn.so")
@@ -48,18 +48,6 @@ def ref_lib():
         _REF.ref_knn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _REF.ref_knn.restype = None
     return _REF
-
-
-def ref_mc_tables():
-    """The reference's marching-cubes case tables (oracle/_ref/mc_tables.bin, extracted from the
-    reference checkout at build time); None if not built.  Returns (tri 256x16, num_verts 256) int32."""
-    p = os.path.join(_HERE, "_ref", "mc_tables.bin")
-    if not os.path.exists(p):
-        build()
-    if not os.path.exists(p):
-        return None
-    a = np.fromfile(p, dtype="<i4")
-    return np.ascontiguousarray(a[:4096].reshape(256, 16)), np.ascontiguousarray(a[4096:])
 
 
 class SolveParams(C.Structure):

@@ -1,8 +1,8 @@
-"""Build step of oracle/_ref (test infrastructure only): read the marching-cubes case tables out of
-the reference checkout, where they lie (src/kfusion/marching_cubes.cpp:86-343 triTable,
-:344-354 numVertsTable), into the binary oracle/_ref/mc_tables.bin = int32 little-endian
-triTable[256][16] followed by numVertsTable[256].  The binary is git-ignored and travels to the GPU
-box like the other _ref artefacts; no text of the reference enters the repository.
+"""Test infrastructure only: read the marching-cubes case tables out of the reference checkout, where
+they lie (src/kfusion/marching_cubes.cpp:86-343 triTable, :344-354 numVertsTable), into the binary
+tests/golden/ref_mc_tables.bin = int32 little-endian triTable[256][16] followed by
+numVertsTable[256] (run by tests/golden/make_reference_outputs.py).  The tables enter the
+repository as that data fixture only; no text of the reference does.
 
 usage: python extract_ref_mc_tables.py <reference root> <output file>"""
 import re

@@ -117,6 +117,19 @@ def test_gpus_2_starts_two_ranks_by_itself():
     assert 40.0 < d["value"] < 100.5  # (a loaded host stretches the sleeps; never faster than the sleeps allow)
 
 
+def test_steps_is_the_number_of_timed_steps():
+    """--steps K runs K timed steps in all, split over the `repeats` regions; ms_per_step is one step's time"""
+    r = _bench("--gpus", "1", "--backend", "gloo", "--dry-run", "--steps", "7", "--warmup", "0", "--repeats", "3")
+    assert r.returncode == 0, r.stderr[-2000:]
+    line, d = _line(r.stdout), _detail()
+    assert line["steps"] == 7 and d["region_steps"] == [2, 2, 3] and len(d["region_ms"]) == 3
+    per_step = sorted(t / n for t, n in zip(d["region_ms"], d["region_steps"]))
+    assert line["ms_per_step"] == pytest.approx(per_step[1], rel=1e-3) and 20.0 <= line["ms_per_step"] < 40.0  # 20 ms sleeps
+    assert line["value"] == pytest.approx(1e3 / line["ms_per_step"], rel=1e-3)
+    r = _bench("--gpus", "1", "--backend", "gloo", "--dry-run", "--steps", "2", "--warmup", "0")  # fewer steps than regions
+    assert r.returncode == 0 and _detail()["region_steps"] == [1, 1]
+
+
 def test_launcher_fails_when_a_rank_dies():
     r = _bench("--gpus", "2", "--backend", "gloo", "--dry-run", "--steps", "5", "--warmup", "1", "--dry-run-fail-rank", "1")
     assert r.returncode != 0
@@ -224,9 +237,9 @@ def test_bench_line_has_the_contract_fields():
     assert line["detail_file"]
     assert d["steps"] == 5 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["scaling"] == "weak" and d["vs_baseline"] is None
     assert "workload" in line["config"] and d["value"] > 30.0  # the north-star target
-    # value / ms_per_step are those of the median of `repeats` back-to-back regions over the same frames
-    assert line["config"]["repeats"] == 5 and len(d["region_ms"]) == 5
-    assert sorted(d["region_ms"])[2] == pytest.approx(d["ms_per_step"] * d["steps"], rel=1e-3)
+    # value / ms_per_step are those of the median of `repeats` back-to-back regions that together run the K steps once
+    assert line["config"]["repeats"] == 5 and len(d["region_ms"]) == 5 and sum(d["region_steps"]) == d["steps"]
+    assert sorted(r / n for r, n in zip(d["region_ms"], d["region_steps"]))[2] == pytest.approx(d["ms_per_step"], rel=1e-3)
     # N = 1 drives a one-rank RCCL process group: init with device_id, a device-tensor all-reduce, the timed region's barriers
     sc = d["config"]["rccl_selfcheck"]
     assert sc["ok"] is True and sc["backend"] == "nccl" and sc["ranks_seen"] == 1 and sc["barriers"] >= 2, sc
@@ -331,6 +344,43 @@ def test_forced_launcher_on_the_gpu_box():
     assert line["n_gpus"] == 1 and line["config"]["ranks_seen"] == 1 and line["config"]["launcher"] == "bench.py"
     assert line["config"]["rccl_selfcheck"]["ok"] is True and line["config"]["rccl_selfcheck"]["backend"] == "nccl"
     assert line["value"] > 30.0 and line["steps"] == 5
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: what the last of the K timed steps computed, float32, at most 64 MB in all.  The same arguments
+    give the same inputs: a second run writes the same arrays (the fused volume and the distance image bit for bit, the
+    solve within float noise)."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    from dynfu_amd import synth
+    lite = ("--no-cpu-baseline", "--no-end-to-end", "--no-other-configs", "--no-northstar", "--no-live-depth",
+            "--no-multi-sequence", "--no-raycast", "--no-pipelined-probe")
+    K, Wm = 6, 2
+    dumps = []
+    for run in range(2):
+        out = tmp_path / ("run%d" % run)
+        r = _bench("--steps", str(K), "--warmup", str(Wm), "--repeats", "3", "--dump-outputs", str(out), *lite, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line, d = _line(r.stdout), _detail()
+        assert line["steps"] == K and d["region_steps"] == [2, 2, 2]
+        a = {p.stem: np.load(p) for p in out.glob("*.npy")}
+        assert set(a) == {"node_dq", "translations", "warped_vertices", "warped_normals", "dists", "tsdf", "tsdf_weight"}
+        assert all(v.dtype == np.float32 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+        cfg = synth.CONFIGS["C2"]  # (the default configuration)
+        assert a["node_dq"].shape == (cfg["D"], 8) and a["dists"].shape == (cfg["height"], cfg["width"])
+        assert a["warped_vertices"].shape == a["warped_normals"].shape == (len(synth.canonical(cfg)["verts"]), 3)
+        assert a["tsdf"].shape == a["tsdf_weight"].shape and (a["tsdf_weight"] > 0).any()
+        # the last timed step is frame Wm + K - 1: its ground truth is what the line's parity figure measured against
+        t_true = synth.true_translations(synth.canonical(cfg)["node_pos"], (Wm + K - 1) % synth.N_FRAMES, cfg["k"])
+        err = float(np.abs(a["translations"] - t_true).max())
+        assert err == pytest.approx(d["config"]["max_abs_translation_error_vs_ground_truth_m"], abs=2e-6) and err < 1e-4
+        dumps.append(a)
+    for name in ("dists", "tsdf", "tsdf_weight"):
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+    for name in ("node_dq", "translations", "warped_vertices", "warped_normals"):
+        np.testing.assert_allclose(dumps[0][name], dumps[1][name], rtol=0, atol=1e-5, err_msg=name)
 
 
 @pytest.mark.gpu

@@ -2,7 +2,7 @@
 
 Bar: BIT-EXACT — vertex count, order (ascending linear voxel index) and the float bits of every
 point, with the library's default case tables and with the reference's own tables
-(oracle/_ref/mc_tables.bin, extracted at build time).  The oracle is unpinned (the reference has
+(tests/golden/ref_mc_tables.bin).  The oracle is unpinned (the reference has
 no marching-cubes test), see oracle/mc_oracle.c."""
 import numpy as np
 import pytest
@@ -10,6 +10,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import oracle as O  # noqa: E402
+import reference_data  # noqa: E402
 from dynfu_amd import synth  # noqa: E402
 from gpu_util import bits, dev, host  # noqa: E402
 from mc_util import blob_volume, default_tables, pack  # noqa: E402
@@ -23,12 +24,7 @@ def A():
 
 
 def _tables(which):
-    if which == "default":
-        return default_tables()
-    t = O.ref_mc_tables()
-    if t is None:
-        pytest.skip("oracle/_ref/mc_tables.bin not built")
-    return t
+    return default_tables() if which == "default" else reference_data.mc_tables()
 
 
 def _run(A, vol, cell, tri, nv, cap):

@@ -9,6 +9,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import oracle as O  # noqa: E402
+import reference_data  # noqa: E402
 from dynfu_amd import synth  # noqa: E402
 from gpu_util import bits, dev, host  # noqa: E402
 
@@ -152,34 +153,19 @@ def test_warp_empty_and_errors(A):
 
 
 # ------------------------------------------------------------------ correspondence (dyn_fusion.cpp:212-242)
-def _surface_clouds(n_canon, n_live, seed):
-    """canonical = points on the synthetic sphere cap, live = a displaced, differently sampled set"""
-    rng = np.random.default_rng(seed)
-    def cap(n):
-        d = rng.normal(size=(n, 3))
-        d[:, 2] = -np.abs(d[:, 2])
-        d /= np.linalg.norm(d, axis=1, keepdims=True)
-        return (synth.SPHERE_C + 0.5 * d).astype(np.float32), d.astype(np.float32)
-    cv, cn = cap(n_canon)
-    lv, _ = cap(n_live)
-    lv += rng.normal(0, 0.004, lv.shape).astype(np.float32)
-    return cv, cn, lv
-
-
-@pytest.mark.parametrize("n_canon,n_live", [(65536, 65536), (3000, 10000), (17, 1000), (1, 5), (40000, 129)])
+@pytest.mark.parametrize("n_canon,n_live", reference_data.CORRESPOND_CASES)
 def test_correspond_bit_exact(A, n_canon, n_live):
-    cv, cn, lv = _surface_clouds(n_canon, n_live, n_canon + n_live)
-    lv[: min(n_live, n_canon) // 2] = cv[: min(n_live, n_canon) // 2]  # exact hits
+    cv, cn, lv = reference_data.correspond_clouds(n_canon, n_live)  # (half of the live points are exact hits)
     ov, on, idx = A.correspond(dev(cv), dev(cn), dev(lv))
     rv, rn, ridx = O.correspond(cv, cn, lv, threads=8)
     assert np.array_equal(host(idx), ridx)
     assert np.array_equal(host(ov), rv) and np.array_equal(host(on), rn)
-    # the reference's own KD-tree (nanoflann, oracle/_ref) agrees wherever the nearest point is unique
-    ref = O.ref_knn(cv, lv[:20000], 1)
-    if ref is not None:
-        d = ((lv[:20000].astype(np.float64) - cv[ref[0][:, 0]].astype(np.float64)) ** 2).sum(1)
-        dm = ((lv[:20000].astype(np.float64) - rv[:20000].astype(np.float64)) ** 2).sum(1)
-        assert np.all((ref[0][:, 0] == ridx[:20000]) | (np.abs(d - dm) <= 1e-12))
+    # the reference's own KD-tree (nanoflann: tests/golden/ref_knn.npz) agrees wherever the nearest point is unique
+    nq = reference_data.CORRESPOND_QUERIES
+    ref = reference_data.knn("correspond_%d_%d" % (n_canon, n_live), cv, lv[:nq], 1)[:, 0]
+    d = ((lv[:nq].astype(np.float64) - cv[ref].astype(np.float64)) ** 2).sum(1)
+    dm = ((lv[:nq].astype(np.float64) - rv[:nq].astype(np.float64)) ** 2).sum(1)
+    assert np.all((ref == ridx[:nq]) | (np.abs(d - dm) <= 1e-12))
 
 
 @pytest.mark.parametrize("n,shift_cells", [(120000, 1.6), (120000, 2.7), (600000, 2.2), (120000, 6.0)])
@@ -187,7 +173,7 @@ def test_correspond_a_surface_that_has_moved_by_cells(A, n, shift_cells):
     """A live surface one to a few grid cells away from the canonical one (along its normal: the 3 x 3 x 3 block of a query
     is then empty or holds only far points): the search leaves shells 0 / 1 and takes the exact ball of cells around the
     query (up to four cells of reach) or, beyond that, the shell walk.  Same indices as the oracle's exhaustive scan."""
-    cv, cn, lv = _surface_clouds(n, 40000, n + int(10 * shift_cells))
+    cv, cn, lv = reference_data.surface_clouds(n, 40000, n + int(10 * shift_cells))
     # the grid's cell size as pgrid_finalize_kernel picks it: the cap of 128 (256 above half a million points) cells per axis
     ext = cv.max(0) - cv.min(0)
     cs = max((0.5 if n > 500000 else 0.7) * float(np.cbrt(ext.prod() / n)), float(ext.max()) / (256 if n > 500000 else 128))
@@ -207,7 +193,7 @@ def test_correspond_a_sparse_neighbourhood_grows_its_ball_without_scanning_it_ag
     as the oracle's exhaustive scan and as the first form; not slower than it."""
     import torch
     n = 600000
-    cv, cn, lv = _surface_clouds(n, 200000, n + 5)
+    cv, cn, lv = reference_data.surface_clouds(n, 200000, n + 5)
     ext = cv.max(0) - cv.min(0)
     cs = max(0.5 * float(np.cbrt(ext.prod() / n)), float(ext.max()) / 256)
     d = lv - synth.SPHERE_C
@@ -235,9 +221,10 @@ def test_correspond_a_sparse_neighbourhood_grows_its_ball_without_scanning_it_ag
 
 def test_correspond_a_million_points_against_the_reference_kd_tree(A):
     """Clouds of more than half a million points switch to the finer grid (up to 256 cells per axis): a million canonical
-    points on the synthetic surface, checked against the reference's own nanoflann KD-tree (oracle/_ref) on 60 000 queries
-    and by the defining property on all of them (no canonical point of a random sample is closer than the one returned)."""
-    cv, cn, lv = _surface_clouds(1 << 20, 300000, 77)
+    points on the synthetic surface, checked against the reference's own nanoflann KD-tree (tests/golden/ref_knn.npz) on
+    60 000 queries and by the defining property on all of them (no canonical point of a random sample is closer than the
+    one returned)."""
+    cv, cn, lv = reference_data.surface_clouds(*reference_data.MILLION)
     ov, on, idx = A.correspond(dev(cv), dev(cn), dev(lv))
     idx_h, ov_h = host(idx), host(ov)
     assert np.array_equal(ov_h, cv[idx_h]) and np.array_equal(host(on), cn[idx_h])
@@ -246,12 +233,11 @@ def test_correspond_a_million_points_against_the_reference_kd_tree(A):
     for _ in range(4):  # random canonical points are never closer than the returned one
         cand = cv[rng.integers(0, len(cv), len(lv))]
         assert np.all(((lv.astype(np.float64) - cand.astype(np.float64)) ** 2).sum(1) >= d_ret - 1e-12)
-    ref = O.ref_knn(cv, lv[:60000], 1)
-    if ref is not None:
-        r = ref[0][:, 0]
-        d_ref = ((lv[:60000].astype(np.float64) - cv[r].astype(np.float64)) ** 2).sum(1)
-        assert np.all((r == idx_h[:60000]) | (np.abs(d_ref - d_ret[:60000]) <= 1e-12))
-        assert (r == idx_h[:60000]).mean() > 0.999
+    nq = reference_data.MILLION_QUERIES
+    r = reference_data.knn("correspond_million", cv, lv[:nq], 1)[:, 0]
+    d_ref = ((lv[:nq].astype(np.float64) - cv[r].astype(np.float64)) ** 2).sum(1)
+    assert np.all((r == idx_h[:nq]) | (np.abs(d_ref - d_ret[:nq]) <= 1e-12))
+    assert (r == idx_h[:nq]).mean() > 0.999
 
 
 def test_correspond_duplicates_optional_outputs_and_errors(A):

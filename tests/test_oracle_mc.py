@@ -7,18 +7,14 @@ import numpy as np
 import pytest
 
 import oracle as O
+import reference_data
 from mc_util import blob_volume, default_tables, pack
 
 EDGES = [(0, 1), (1, 2), (2, 3), (3, 0), (4, 5), (5, 6), (6, 7), (7, 4), (0, 4), (1, 5), (2, 6), (3, 7)]
 
 
 def _tables(which):
-    if which == "default":
-        return default_tables()
-    t = O.ref_mc_tables()
-    if t is None:
-        pytest.skip("oracle/_ref/mc_tables.bin not built (no reference checkout)")
-    return t
+    return default_tables() if which == "default" else reference_data.mc_tables()
 
 
 @pytest.mark.parametrize("which", ["default", "reference"])
@@ -45,11 +41,10 @@ def test_case_tables_are_consistent(which):
 def test_default_tables_match_the_reference_conventions():
     tri, nv = default_tables()
     assert tri[1, :3].tolist() == [0, 8, 3] and tri[254, :3].tolist() == [0, 3, 8]  # winding of the classic table
-    ref = O.ref_mc_tables()
-    if ref is not None:
-        assert np.array_equal(nv, ref[1])  # same vertex count in every case
-        for c in range(256):
-            assert set(tri[c, :nv[c]].tolist()) == set(ref[0][c, :ref[1][c]].tolist())
+    ref = reference_data.mc_tables()
+    assert np.array_equal(nv, ref[1])  # same vertex count in every case
+    for c in range(256):
+        assert set(tri[c, :nv[c]].tolist()) == set(ref[0][c, :ref[1][c]].tolist())
 
 
 @pytest.mark.parametrize("which", ["default", "reference"])

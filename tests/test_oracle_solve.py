@@ -1,10 +1,11 @@
 """Pins oracle/solve_oracle.c against the end-state assertions of the reference's 8 OptTest
 cases (test/opt_optimisation_test.cpp:212-698, tolerance 1e-3) and the k-NN restatement
-against the reference's own vendored nanoflann (oracle/_ref)."""
+against the reference's own vendored nanoflann (its answers: tests/golden/ref_knn.npz)."""
 import numpy as np
 import pytest
 
 import oracle as O
+import reference_data
 from opt_scene_runner import SCN, run_scene, scene_ids
 
 
@@ -48,15 +49,12 @@ def _random_nodes(rng, D):
     return rng.uniform(-1, 1, (D, 3)).astype(np.float32)
 
 
-@pytest.mark.parametrize("D,k", [(8, 8), (18, 8), (500, 4), (2048, 8), (5, 8)])
+@pytest.mark.parametrize("D,k", reference_data.RANDOM_KNN_CASES)
 def test_knn_matches_reference_nanoflann(D, k):
-    if O.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (no reference checkout)")
-    rng = np.random.default_rng(D * 31 + k)
-    nodes = _random_nodes(rng, D)
-    query = rng.uniform(-1.2, 1.2, (3000, 3)).astype(np.float32)
+    nodes, query = reference_data.random_knn_case(D, k)
     ours = O.knn(nodes, query, k)
-    ref, d = O.ref_knn(nodes, query, k)
+    ref = reference_data.knn("random_D%d_k%d" % (D, k), nodes, query, k)
+    d = reference_data.nanoflann_dist2(nodes, query, ref)
     # identical except where two candidates are at exactly the same float distance
     diff = np.argwhere(ours != ref)
     for v, j in diff:
@@ -66,11 +64,8 @@ def test_knn_matches_reference_nanoflann(D, k):
 
 
 def test_knn_on_opttest_nodes_matches_reference():
-    if O.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (no reference checkout)")
-    nodes = np.array(SCN["nodes"]["g1"] + SCN["nodes"]["g2"], np.float32)
-    q = np.array([v for s in SCN["scenes"] for vs in s["sets"].values() for v in vs], np.float32)
-    ours, (ref, d) = O.knn(nodes, q, 8), O.ref_knn(nodes, q, 8)
+    nodes, q = reference_data.opttest_knn_case(SCN)
+    ours, ref = O.knn(nodes, q, 8), reference_data.knn("opttest", nodes, q, 8)
     # integer lattice nodes produce exact distance ties: compare as distance-sorted sets
     dist = lambda idx: np.sort(((q[:, None, :] - nodes[idx]) ** 2).sum(-1), axis=1)
     np.testing.assert_allclose(dist(ours), dist(ref), rtol=1e-6)
