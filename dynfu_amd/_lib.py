@@ -9,7 +9,7 @@ _LIB = None
 # every symbol include/dynfu_amd.h declares (tests/test_capi_symbols.py checks the .so exports them)
 SYMBOLS = [
     "dfa_last_error", "dfa_version", "dfa_abi_version", "dfa_abi_struct_size", "dfa_compute_dists", "dfa_tsdf_clear", "dfa_tsdf_integrate",
-    "dfa_tsdf_clear_integrate", "dfa_tsdf_raycast_points", "dfa_tsdf_raycast_depth", "dfa_tsdf_raycast_tally", "dfa_tsdf_vertex_normals", "dfa_correspond_projective", "dfa_knn", "dfa_warp_to_live",
+    "dfa_tsdf_clear_integrate", "dfa_tsdf_raycast_points", "dfa_tsdf_raycast_depth", "dfa_tsdf_raycast_tally", "dfa_tsdf_vertex_normals", "dfa_tsdf_extract_cloud", "dfa_tsdf_extract_cloud_occ", "dfa_tsdf_extract_normals", "dfa_correspond_projective", "dfa_knn", "dfa_warp_to_live",
     "dfa_calc_dqb", "dfa_unsupported_vertices", "dfa_icp_sums", "dfa_repack_points", "dfa_compact_points", "dfa_transform_points", "dfa_warp_to_live_graph",
     "dfa_correspond", "dfa_marching_cubes", "dfa_mc_default_tables",
     "dfa_tsdf_occupancy_bytes", "dfa_tsdf_clear_occ", "dfa_tsdf_integrate_occ", "dfa_tsdf_clear_integrate_occ", "dfa_tsdf_clear_integrate_known_occ", "dfa_marching_cubes_occ",
@@ -165,6 +165,9 @@ def load(path=None):
     L.dfa_tsdf_raycast_depth.argtypes = ray
     L.dfa_tsdf_raycast_tally.argtypes = [vp, i, i, i, vp, f, vp, vp, f, f, f, f, f, f, i, i, vp, vp, vp]
     L.dfa_tsdf_vertex_normals.argtypes = [vp, i, i, i, vp, f, vp, i, vp, vp]
+    L.dfa_tsdf_extract_cloud.argtypes = [vp, i, i, i, vp, vp, vp, i, vp, vp]
+    L.dfa_tsdf_extract_cloud_occ.argtypes = [vp, vp, i, i, i, vp, vp, vp, i, vp, vp]
+    L.dfa_tsdf_extract_normals.argtypes = [vp, i, i, i, vp, vp, vp, f, vp, i, vp, vp]
     L.dfa_correspond_projective.argtypes = [vp, vp, i, vp, i, vp, i, i, i, f, f, f, f, f, f, vp, vp, vp, vp]
     L.dfa_knn.argtypes = [vp, vp, i, vp, i, i, vp, vp, vp]
     L.dfa_warp_to_live.argtypes = [vp, vp, vp, i, i, vp, vp, i, vp, vp, vp]
@@ -394,6 +397,41 @@ def tsdf_vertex_normals(vol, voxel_size, delta_factor, points):
     _check(load().dfa_tsdf_vertex_normals(_dev(vol), X, Y, Z, _farr(voxel_size, 3), float(delta_factor),
                                           _dev(points, torch.float32, "points") if n else None, n,
                                           _dev(normals) if n else None, _stream()))
+    return normals[:n]
+
+
+def tsdf_extract_cloud(vol, voxel_size, vol2world, max_points, occupancy=None):
+    """TsdfVolume::fetchCloud: a point on every voxel edge the zero level crosses, mapped by vol2world (the volume's pose:
+    12 floats or a 3x4 / 4x4 [R|t]).  Returns (points (max_points, 4) float32 CUDA tensor {x, y, z, 0}, total int32 CUDA
+    tensor of 1 element); the first min(total, max_points) points are written, in ascending voxel order.  occupancy: the
+    volume's occupancy map (tsdf_occupancy, kept by the *_occ sweeps) — the same output without reading the empty part."""
+    torch = _torch()
+    X, Y, Z = _vol_dims(vol)
+    pts = torch.empty((max(max_points, 1), 4), dtype=torch.float32, device=vol.device)
+    total = torch.zeros((1,), dtype=torch.int32, device=vol.device)
+    tail = (_farr(voxel_size, 3), _aff12(vol2world), _dev(pts) if max_points > 0 else None, max_points, _dev(total), _stream())
+    if occupancy is None:
+        _check(load().dfa_tsdf_extract_cloud(_dev(vol), X, Y, Z, *tail))
+    else:
+        _check(load().dfa_tsdf_extract_cloud_occ(_dev(vol), _dev(occupancy, torch.uint8, "occupancy"), X, Y, Z, *tail))
+    return pts, total
+
+
+def tsdf_extract_normals(vol, voxel_size, vol2world, delta_factor, points, Rinv=None):
+    """TsdfVolume::fetchNormals: normals (n x 4 float32 CUDA tensor {nx, ny, nz, 0}, world frame) of the points of
+    tsdf_extract_cloud (n x 4 float32 CUDA tensor); NaN where the point's voxel is within 2 of the volume's border.
+    Rinv: inverse of vol2world's rotation (default: computed here, in float64)."""
+    import numpy as np
+    torch = _torch()
+    X, Y, Z = _vol_dims(vol)
+    aff = _aff12(vol2world)
+    if Rinv is None:
+        Rinv = np.linalg.inv(np.asarray(list(aff)[:9], np.float64).reshape(3, 3)).astype(np.float32)
+    n = int(points.shape[0])
+    normals = torch.empty((max(n, 1), 4), dtype=torch.float32, device=vol.device)
+    _check(load().dfa_tsdf_extract_normals(_dev(vol), X, Y, Z, _farr(voxel_size, 3), aff, _farr(list(map(float, _flat(Rinv))), 9),
+                                           float(delta_factor), _dev(points, torch.float32, "points") if n else None, n,
+                                           _dev(normals) if n else None, _stream()))
     return normals[:n]
 
 

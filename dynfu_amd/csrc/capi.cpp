@@ -547,6 +547,51 @@ int dfa_marching_cubes_occ(const uint32_t* volume, const uint8_t* occupancy, int
                                  total_vertices, occupancy, stream);
 }
 
+// -------------------------------------------------------------- TSDF seam: point-cloud extraction
+
+static int extract_cloud_common(const uint32_t* volume, int X, int Y, int Z, const float voxel_size[3],
+                                const float vol2world[12], float* out_points, int max_points, int32_t* total_points,
+                                const uint8_t* occupancy, dfa_stream_t stream) {
+    REQUIRE(volume_args_ok(volume, X, Y, Z), "bad volume");
+    REQUIRE(voxel_size && vol2world, "null voxel_size / vol2world");
+    REQUIRE(max_points >= 0 && (max_points == 0 || out_points), "bad output buffer");
+    REQUIRE(((uintptr_t)out_points & 15) == 0, "out_points must be 16-byte aligned");
+    REQUIRE((long)X * Y * Z / 64 < (1L << 31), "volume too large");
+    const bool vec4  = (X % 4 == 0) && (((uintptr_t)volume & 15) == 0);
+    McScratch& scratch = stream_scratch<McScratch>(S(stream));  // (the row segments and the scan are marching cubes')
+    HIP_TRY(scratch.reserve(dfa::mc_segments(X, Y, Z, vec4)));
+    HIP_TRY(dfa::launch_extract_cloud(volume, X, Y, Z, voxel_size, vol2world, out_points, max_points, total_points,
+                                      scratch.seg_off, scratch.chunk_sums, occupancy, S(stream)));
+    return DFA_OK;
+}
+
+int dfa_tsdf_extract_cloud(const uint32_t* volume, int X, int Y, int Z, const float voxel_size[3], const float vol2world[12],
+                           float* out_points, int max_points, int32_t* total_points, dfa_stream_t stream) {
+    return extract_cloud_common(volume, X, Y, Z, voxel_size, vol2world, out_points, max_points, total_points, nullptr, stream);
+}
+
+int dfa_tsdf_extract_cloud_occ(const uint32_t* volume, const uint8_t* occupancy, int X, int Y, int Z,
+                               const float voxel_size[3], const float vol2world[12], float* out_points, int max_points,
+                               int32_t* total_points, dfa_stream_t stream) {
+    REQUIRE(occupancy, "null occupancy map");
+    return extract_cloud_common(volume, X, Y, Z, voxel_size, vol2world, out_points, max_points, total_points, occupancy,
+                                stream);
+}
+
+int dfa_tsdf_extract_normals(const uint32_t* volume, int X, int Y, int Z, const float voxel_size[3], const float vol2world[12],
+                             const float Rinv[9], float gradient_delta_factor, const float* points, int n, float* normals,
+                             dfa_stream_t stream) {
+    REQUIRE(volume_args_ok(volume, X, Y, Z), "bad volume");
+    REQUIRE(voxel_size && vol2world && Rinv, "null voxel_size / vol2world / Rinv");
+    REQUIRE(n >= 0 && (n == 0 || (points && normals)), "null points / normals");
+    REQUIRE(voxel_size[0] > 0.f && voxel_size[1] > 0.f && voxel_size[2] > 0.f && gradient_delta_factor > 0.f,
+            "voxel size and gradient delta must be positive");
+    REQUIRE((((uintptr_t)points | (uintptr_t)normals) & 15) == 0, "points / normals must be 16-byte aligned");
+    HIP_TRY(dfa::launch_extract_normals(volume, X, Y, Z, voxel_size, vol2world, Rinv, gradient_delta_factor, points, n,
+                                        normals, S(stream)));
+    return DFA_OK;
+}
+
 int dfa_mc_default_tables(int32_t* tri_table, int32_t* num_verts_table) {
     REQUIRE(tri_table && num_verts_table, "null table");
     dfa::mc_default_tables(tri_table, num_verts_table);

@@ -109,6 +109,18 @@ hipError_t launch_marching_cubes(const uint32_t* vol, int X, int Y, int Z, const
                                  int max_vertices, int32_t* total_vertices, int32_t* seg_off, int32_t* chunk_sums,
                                  const uint8_t* occ /* occupancy map of the volume or null */, hipStream_t s);
 void mc_default_tables(int32_t tri_table[256 * 16], int32_t num_verts_table[256]);
+// exclusive scan of n segment counts in place (counts: n + 1 entries; counts[n] and *total (device, optional) receive the
+// sum; chunk_sums: mc_scan_chunks(n) entries) — marching cubes' step 2, shared with the point-cloud extraction
+void launch_segment_scan(int32_t* counts, long n, int32_t* chunk_sums, int32_t* total, hipStream_t s);
+
+// extract.hip — TsdfVolume::fetchCloud (kfusion extract_kernel); the row segments are marching cubes' (mc_segments)
+hipError_t launch_extract_cloud(const uint32_t* vol, int X, int Y, int Z, const float voxel_size[3], const float vol2world[12],
+                                float* out_points, int max_points, int32_t* total_points, int32_t* seg_off, int32_t* chunk_sums,
+                                const uint8_t* occ /* occupancy map of the volume or null */, hipStream_t s);
+// tsdf.hip (beside the raycaster's interpolate) — TsdfVolume::fetchNormals (kfusion extract_normals_kernel)
+hipError_t launch_extract_normals(const uint32_t* vol, int X, int Y, int Z, const float voxel_size[3], const float vol2world[12],
+                                  const float Rinv[9], float delta_factor, const float* points, int n, float* normals,
+                                  hipStream_t s);
 
 // img.hip
 hipError_t launch_bilateral(const uint16_t* src, int src_step, uint16_t* dst, int dst_step, int cols, int rows, int ksz,

@@ -29,6 +29,7 @@
 #include "device_math.hpp"
 #include "dev_switch.hpp"
 #include "kernels.hpp"
+#include "vol_rows.hpp"
 
 namespace dfa {
 
@@ -46,71 +47,8 @@ struct McArgs {
     int ox, oy, oz;
 };
 
-// the VX voxels a lane owns in one row plus the voxel after them; zeros (weight 0 -> "no cube",
-// marching_cubes.cu:38-60) wherever the row or the voxel does not exist
-template <int VX>
-struct Row {
-    uint32_t v[VX + 1];
-};
-
-template <int VX>
-__device__ __forceinline__ Row<VX> load_row(const McArgs& a, int x0, int y, int z) {
-    Row<VX> r;
-#pragma unroll
-    for (int i = 0; i <= VX; ++i) r.v[i] = 0u;
-    const bool row_ok = y < a.Y && z < a.Z;
-    const uint32_t* p = a.vol + (size_t)a.X * ((size_t)y + (size_t)a.Y * (size_t)z);
-    if (row_ok && x0 < a.X) {
-        if (VX == 4) {
-            const uint4 q = *reinterpret_cast<const uint4*>(p + x0);
-            r.v[0] = q.x, r.v[1] = q.y, r.v[2] = q.z, r.v[3] = q.w;
-        } else {
-            r.v[0] = p[x0];
-        }
-    }
-    // the neighbour's first voxel; the last lane of the wave reads it from memory
-    const uint32_t next = __shfl_down(r.v[0], 1, 64);
-    if ((threadIdx.x & 63) == 63) {
-        if (row_ok && x0 + VX < a.X) r.v[VX] = p[x0 + VX];
-    } else {
-        r.v[VX] = next;
-    }
-    return r;
-}
-
-// NR consecutive rows y .. y + NR - 1 of slice z.  The voxel after the wave's last one is fetched for
-// all NR rows by ONE load instruction (lane r reads row r's) and handed to lane 63 by a readlane —
-// the sweep is bound by vector-memory instruction issue, not by bytes.
-template <int VX, int NR>
-__device__ __forceinline__ void load_rows(const McArgs& a, int x0, int y, int z, Row<VX> (&out)[NR]) {
-    const int lane = threadIdx.x & 63;
-    const bool z_ok = z < a.Z;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        Row<VX>& o = out[r];
-#pragma unroll
-        for (int i = 0; i <= VX; ++i) o.v[i] = 0u;
-        const uint32_t* p = a.vol + (size_t)a.X * ((size_t)(y + r) + (size_t)a.Y * (size_t)z);
-        if (z_ok && y + r < a.Y && x0 < a.X) {
-            if (VX == 4) {
-                const uint4 q = *reinterpret_cast<const uint4*>(p + x0);
-                o.v[0] = q.x, o.v[1] = q.y, o.v[2] = q.z, o.v[3] = q.w;
-            } else {
-                o.v[0] = p[x0];
-            }
-        }
-    }
-    const int xend = (x0 - lane * VX) + 64 * VX;  // first voxel of the next segment
-    uint32_t extra = 0u;
-    if (lane < NR && z_ok && y + lane < a.Y && xend < a.X)
-        extra = a.vol[(size_t)xend + (size_t)a.X * ((size_t)(y + lane) + (size_t)a.Y * (size_t)z)];
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const uint32_t next = __shfl_down(out[r].v[0], 1, 64);
-        const uint32_t last = __shfl(extra, r, 64);
-        out[r].v[VX]        = lane == 63 ? last : next;
-    }
-}
+// Row / load_row / load_rows: vol_rows.hpp (zeros — weight 0 -> "no cube", marching_cubes.cu:38-60 — wherever the row
+// or the voxel does not exist)
 
 // bit c of `neg`: f < 0 (isoValue = 0, internal.hpp:72); returns false if any weight is 0
 __device__ __forceinline__ int cube_case(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t c4, uint32_t c5,
@@ -432,6 +370,12 @@ long mc_segments(int X, int Y, int Z, bool vec4) {
 }
 long mc_scan_chunks(long nsegs) { return (nsegs + SCAN_CHUNK - 1) / SCAN_CHUNK; }
 
+void launch_segment_scan(int32_t* counts, long n, int32_t* chunk_sums, int32_t* total, hipStream_t s) {
+    const int chunks = (int)mc_scan_chunks(n);
+    scan_sum_kernel<<<chunks, 256, 0, s>>>(counts, n, chunk_sums);
+    scan_apply_kernel<<<chunks, 256, 0, s>>>(counts, n, counts, chunk_sums, total);
+}
+
 hipError_t launch_marching_cubes(const uint32_t* vol, int X, int Y, int Z, const float cell_size[3],
                                  const int32_t* tri_table, const int32_t* num_verts_table, float* out_points,
                                  int max_vertices, int32_t* total_vertices, int32_t* seg_off, int32_t* chunk_sums,
@@ -462,9 +406,7 @@ hipError_t launch_marching_cubes(const uint32_t* vol, int X, int Y, int Z, const
     dim3 block(64, 4), grid(a.nseg, (Y + 4 * MC_ROWS - 1) / (4 * MC_ROWS), (Z + zchunk - 1) / zchunk);
     if (vec4) mc_count_kernel<4><<<grid, block, 0, s>>>(a, seg_off);
     else mc_count_kernel<1><<<grid, block, 0, s>>>(a, seg_off);
-    const int chunks = (int)mc_scan_chunks(nsegs);
-    scan_sum_kernel<<<chunks, 256, 0, s>>>(seg_off, nsegs, chunk_sums);
-    scan_apply_kernel<<<chunks, 256, 0, s>>>(seg_off, nsegs, seg_off, chunk_sums, total_vertices);
+    launch_segment_scan(seg_off, nsegs, chunk_sums, total_vertices, s);
     if (out_points && max_vertices > 0) {
         long want = 8192;
         if (const char* e = dev_env("DFA_MC_EMIT_BLOCKS")) want = std::max(1L, atol(e));  // (development builds)

@@ -528,9 +528,10 @@ __device__ __forceinline__ float interpolate(const RaycastArgs& a, f3 cf, RayTal
     return inside ? tsdf : qnan();
 }
 
-// :320-336
+// :320-336 before the normalisation: central differences of the interpolant, each divided by its delta (the raycaster's
+// __fdividef as the correctly rounded divide); also ExtractNormals :625-660
 template <bool TALLY = false>
-__device__ __forceinline__ f3 compute_normal(const RaycastArgs& a, f3 p, RayTally* tally = nullptr) {
+__device__ __forceinline__ f3 tsdf_gradient(const RaycastArgs& a, f3 p, RayTally* tally = nullptr) {
     const f3 vi = mk3(a.vix, a.viy, a.viz);
     f3 n;
     const float Fx1 = interpolate<TALLY>(a, mk3(p.x + a.gdx, p.y, p.z) * vi, tally);
@@ -542,7 +543,13 @@ __device__ __forceinline__ f3 compute_normal(const RaycastArgs& a, f3 p, RayTall
     const float Fz1 = interpolate<TALLY>(a, mk3(p.x, p.y, p.z + a.gdz) * vi, tally);
     const float Fz2 = interpolate<TALLY>(a, mk3(p.x, p.y, p.z - a.gdz) * vi, tally);
     n.z             = (Fz1 - Fz2) / a.gdz;
-    return normalized(n);
+    return n;
+}
+
+// :320-336
+template <bool TALLY = false>
+__device__ __forceinline__ f3 compute_normal(const RaycastArgs& a, f3 p, RayTally* tally = nullptr) {
+    return normalized(tsdf_gradient<TALLY>(a, p, tally));
 }
 
 // march steps whose voxels are requested together (measured at 512^3 / VGA and 1024^3 / 720p: 1 step 0.082 / 0.219 ms,
@@ -959,6 +966,38 @@ hipError_t launch_vertex_normals(const uint32_t* vol, int X, int Y, int Z, const
     const float id12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0}, id9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     RaycastArgs a = make_raycast_args(vol, X, Y, Z, voxel_size, 1.f, id12, id9, 1.f, 1.f, 0.f, 0.f, 1.f, delta_factor, 0, 0);
     vertex_normals_kernel<<<(n + 255) / 256, 256, 0, s>>>(a, (const float4*)points, n, (float4*)normals);
+    return launch_status();
+}
+
+// TsdfVolume::fetchNormals — ExtractNormals (tsdf_volume.cu:602-680): the point is taken back into the volume frame
+// (q = Rinv (p - t), :617), its nearest voxel (round-half-even, :609-613) must lie inside [2, dim - 3] on every axis
+// (:619-620, otherwise the normal is NaN), and the gradient of the interpolant at q is rotated by R and THEN normalised
+// (:662; compute_normal normalises in the volume frame).  The voxel test compares the rounded floats with the bounds:
+// the same answer as the reference's __float2int_rn, whose saturation and NaN -> 0 keep such points outside as well.
+__global__ __launch_bounds__(256) void extract_normals_kernel(const RaycastArgs a, const Aff3 vol2world,
+                                                              const float4* __restrict__ points, int n,
+                                                              float4* __restrict__ normals) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = points[i];
+    const f3 q     = mul(a.Rinv, mk3(p.x, p.y, p.z) - mk3(vol2world.t[0], vol2world.t[1], vol2world.t[2]));
+    const float gx = rintf(q.x * a.vix), gy = rintf(q.y * a.viy), gz = rintf(q.z * a.viz);
+    f3 nn = mk3(qnan(), qnan(), qnan());
+    if (gx > 1.f && gy > 1.f && gz > 1.f && gx < (float)(a.X - 2) && gy < (float)(a.Y - 2) && gz < (float)(a.Z - 2))
+        nn = normalized(mulR(vol2world, tsdf_gradient(a, q)));
+    normals[i] = make_float4(nn.x, nn.y, nn.z, 0.f);
+}
+
+hipError_t launch_extract_normals(const uint32_t* vol, int X, int Y, int Z, const float voxel_size[3], const float vol2world[12],
+                                  const float Rinv[9], float delta_factor, const float* points, int n, float* normals,
+                                  hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const float id12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    RaycastArgs a = make_raycast_args(vol, X, Y, Z, voxel_size, 1.f, id12, Rinv, 1.f, 1.f, 0.f, 0.f, 1.f, delta_factor, 0, 0);
+    Aff3 aff;
+    for (int i = 0; i < 9; ++i) aff.m[i] = vol2world[i];
+    for (int i = 0; i < 3; ++i) aff.t[i] = vol2world[9 + i];
+    extract_normals_kernel<<<(n + 255) / 256, 256, 0, s>>>(a, aff, (const float4*)points, n, (float4*)normals);
     return launch_status();
 }
 

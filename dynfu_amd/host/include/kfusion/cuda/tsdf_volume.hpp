@@ -2,8 +2,8 @@
 // (include/kfusion/cuda/tsdf_volume.hpp:7-73; behaviour src/kfusion/tsdf_volume.cpp:18-129) on the dynfu_amd C ABI.
 //
 // Layout of this adaptor: the volume's settings live in one plain struct, trivial accessors are inline, the
-// three operations that touch the GPU (clear / integrate / raycast) are one dfa_tsdf_* call each.
-// Not provided: fetchCloud / fetchNormals / get,setGridOrigin (not on the DynFusion path).
+// operations that touch the GPU (clear / integrate / raycast / fetchCloud / fetchNormals) are one dfa_tsdf_* call each.
+// Not provided: get,setGridOrigin (not on the DynFusion path).
 #pragma once
 #include <algorithm>
 
@@ -59,6 +59,13 @@ public:
     virtual void raycast(const Affine3f& camera_pose, const Intr& intr, Depth& depth, Normals& normals);
     virtual void raycast(const Affine3f& camera_pose, const Intr& intr, Cloud& points, Normals& normals);
     virtual void applyAffine(const Affine3f& affine) { cfg_.pose = affine * cfg_.pose; }
+    // the zero crossings on the voxel edges, in the world frame (pose), as float4 {x, y, z, 0} (tsdf_volume.hpp:49,
+    // tsdf_volume.cpp:131-147): an empty buffer is created with 10 000 000 points; returns a non-owning array over the
+    // first min(points, capacity) of them.  Unlike the reference the order is defined (ascending voxel index), nothing is
+    // written past the buffer, and it reads only the boxes of the occupancy map that can hold a point when there is one.
+    dfa::DeviceArray<Point> fetchCloud(dfa::DeviceArray<Point>& cloud_buffer) const;
+    // normals of fetchCloud's points (tsdf_volume.hpp:50, tsdf_volume.cpp:149-160); NaN within 2 voxels of the border
+    void fetchNormals(const dfa::DeviceArray<Point>& cloud, dfa::DeviceArray<Normal>& normals) const;
 
     // --- settings ---------------------------------------------------------------------------------------------
     Vec3i getDims() const { return cfg_.dims; }

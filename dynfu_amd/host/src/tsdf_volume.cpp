@@ -91,3 +91,38 @@ void TsdfVolume::raycast(const Affine3f& camera_pose, const Intr& intr, Cloud& p
                                        nullptr),
                "TsdfVolume::raycast(points)");
 }
+
+dfa::DeviceArray<Point> TsdfVolume::fetchCloud(dfa::DeviceArray<Point>& cloud_buffer) const {  // :131-147
+    enum { DEFAULT_CLOUD_BUFFER_SIZE = 10 * 1000 * 1000 };
+    if (cloud_buffer.empty()) cloud_buffer.create(DEFAULT_CLOUD_BUFFER_SIZE);
+    float aff[12];
+    cfg_.pose.to12(aff);
+    const Vec3f vsz       = getVoxelSize();
+    const int cap         = (int)std::min<size_t>(cloud_buffer.size(), 0x7fffffff);
+    const uint8_t* occ    = occupancy();
+    dfa::DeviceArray<int> total(1);
+    if (occ)
+        dfa::check(dfa_tsdf_extract_cloud_occ(blob_.ptr<uint32_t>(), occ, cfg_.dims[0], cfg_.dims[1], cfg_.dims[2], vsz.v, aff,
+                                              (float*)cloud_buffer.ptr(), cap, total.ptr(), nullptr),
+                   "TsdfVolume::fetchCloud");
+    else
+        dfa::check(dfa_tsdf_extract_cloud(blob_.ptr<uint32_t>(), cfg_.dims[0], cfg_.dims[1], cfg_.dims[2], vsz.v, aff,
+                                          (float*)cloud_buffer.ptr(), cap, total.ptr(), nullptr),
+                   "TsdfVolume::fetchCloud");
+    int n = 0;
+    total.DeviceMemory::download(&n, sizeof(n));  // (the reference's extractCloud synchronises the device and reads its counter back)
+    return dfa::DeviceArray<Point>(cloud_buffer.ptr(), (size_t)std::min(n, cap));
+}
+
+void TsdfVolume::fetchNormals(const dfa::DeviceArray<Point>& cloud, dfa::DeviceArray<Normal>& normals) const {  // :149-160
+    normals.create(cloud.size());
+    float aff[12], rinv[9];
+    cfg_.pose.to12(aff);
+    cfg_.pose.inverse_rotation(rinv);
+    const Vec3f vsz = getVoxelSize();
+    dfa::check(dfa_tsdf_extract_normals(blob_.ptr<uint32_t>(), cfg_.dims[0], cfg_.dims[1], cfg_.dims[2], vsz.v, aff, rinv,
+                                        cfg_.grad_delta, (const float*)cloud.ptr(), (int)cloud.size(), (float*)normals.ptr(),
+                                        nullptr),
+               "TsdfVolume::fetchNormals");
+    dfa::device_synchronize();  // (the reference's extractNormals synchronises the device, tsdf_volume.cu:719)
+}

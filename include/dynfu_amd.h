@@ -130,6 +130,36 @@ int dfa_tsdf_vertex_normals(const uint32_t* volume, int X, int Y, int Z, const f
                             float gradient_delta_factor, const float* points, int n, float* normals,
                             dfa_stream_t stream);
 
+/* Point cloud of the surface — replaces kfusion::device::extractCloud (internal.hpp:162, tsdf_volume.cu:419-600,682-699;
+ * TsdfVolume::fetchCloud, tsdf_volume.cpp:131-147).  FullScan6's rules: a voxel with z < Z - 1, a non-zero weight and a
+ * distance F != 1 emits a point on its edge to +x (if x + 1 < X), +y (if y + 1 < Y) and +z when the far voxel has a
+ * non-zero weight, a distance Fn != 1 and the strictly opposite sign; the coordinate along the edge is
+ * (V |Fn| + (V + voxel) |F|) / (|F| + |Fn|) with V the voxel centre (i + 0.5) voxel_size, and the point is vol2world p
+ * (the volume's pose: R row-major, then t), stored as float4 {x, y, z, 0}.
+ * Deliberately NOT the reference's output contract:
+ *   - order: ascending linear voxel index z*X*Y + y*X + x, within a voxel +x, +y, +z; every run gives the same bits
+ *     (the reference appends at an atomic counter);
+ *   - out_points (device, 16-byte aligned) receives the first min(total, max_points) points and nothing past them (the
+ *     reference's last warp stores beyond the buffer); NULL with max_points = 0 counts only;
+ *   - total_points (device, optional): the points the volume has — more than max_points means truncation;
+ *   - stream-ordered, no host synchronisation, no state shared between calls on different streams (the reference keeps
+ *     its counters in static device variables and synchronises the device). */
+int dfa_tsdf_extract_cloud(const uint32_t* volume, int X, int Y, int Z, const float voxel_size[3], const float vol2world[12],
+                           float* out_points, int max_points, int32_t* total_points, dfa_stream_t stream);
+/* ... with the volume's occupancy map (see dfa_tsdf_occupancy_bytes): boxes that cannot hold a point are not read;
+ * identical output.  The map must describe the volume, as for dfa_marching_cubes_occ. */
+int dfa_tsdf_extract_cloud_occ(const uint32_t* volume, const uint8_t* occupancy, int X, int Y, int Z,
+                               const float voxel_size[3], const float vol2world[12], float* out_points, int max_points,
+                               int32_t* total_points, dfa_stream_t stream);
+/* Normals of an extracted cloud — replaces kfusion::device::extractNormals (internal.hpp:163, tsdf_volume.cu:602-680,
+ * 701-720; TsdfVolume::fetchNormals, tsdf_volume.cpp:149-160).  q = Rinv (p - t) in the volume frame; its nearest voxel
+ * (round-half-even) must be inside [2, dim - 3] on every axis, else the normal is quiet NaN; otherwise the central
+ * differences of the trilinear interpolant at q +- gradient_delta_factor voxels, rotated by R and then normalised.
+ * Rinv: the inverse of vol2world's rotation, as for the raycast.  points / normals: n float4, device, 16-byte aligned. */
+int dfa_tsdf_extract_normals(const uint32_t* volume, int X, int Y, int Z, const float voxel_size[3], const float vol2world[12],
+                             const float Rinv[9], float gradient_delta_factor, const float* points, int n, float* normals,
+                             dfa_stream_t stream);
+
 /* raycast (points variant) — internal.hpp:165-166, tsdf_volume.cu:258-318,371-386.
  * points / normals: float4 images; misses are quiet NaN. */
 int dfa_tsdf_raycast_points(const uint32_t* volume, int X, int Y, int Z, const float voxel_size[3], float trunc_dist,
