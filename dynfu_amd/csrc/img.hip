@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void normals_kernel(const uint16_t* __restrict
                                                       float* __restrict__ normals, int normals_step) {
     const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
     if (x >= cols || y >= rows) return;
-    const float qnan = __builtin_nanf("");
+    const float qnan = __uint_as_float(0x7fffffffu);  // numeric_limits<float>::quiet_NaN(), temp_utils.hpp:21
     float4 n_out = make_float4(qnan, qnan, qnan, 0.f);  // :139
     if (x < cols - 1 && y < rows - 1) {
         const float z00 = cpix(depth, depth_step, y, x) * 0.001f, z01 = cpix(depth, depth_step, y, x + 1) * 0.001f,
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void resize_depth_normals_kernel(const uint16_
                                                                    int ddst_step, float* __restrict__ ndst, int ndst_step) {
     const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
     if (x >= out_cols || y >= out_rows) return;
-    const float qnan = __builtin_nanf("");
+    const float qnan = __uint_as_float(0x7fffffffu);  // numeric_limits<float>::quiet_NaN(), temp_utils.hpp:21
     uint16_t d = 0;
     float4 n   = make_float4(qnan, qnan, qnan, qnan);
     const int xs = 2 * x, ys = 2 * y;
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256) void resize_points_normals_kernel(const float*
                                                                     int vdst_step, float* __restrict__ ndst, int ndst_step) {
     const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
     if (x >= out_cols || y >= out_rows) return;
-    const float qnan = __builtin_nanf("");
+    const float qnan = __uint_as_float(0x7fffffffu);  // numeric_limits<float>::quiet_NaN(), temp_utils.hpp:21
     float4 v = make_float4(qnan, qnan, qnan, 0.f), n = v;  // :323
     const int xs = 2 * x, ys = 2 * y;
     const float4 p00 = ld4(vsrc, vsrc_step, ys, xs), p01 = ld4(vsrc, vsrc_step, ys, xs + 1),

@@ -1750,7 +1750,7 @@ __global__ __launch_bounds__(256) void points_normals_kernel(const uint16_t* __r
                                                              float* __restrict__ normals, int normals_step) {
     const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
     if (x >= cols || y >= rows) return;
-    const float qnan = __builtin_nanf("");
+    const float qnan = __uint_as_float(0x7fffffffu);  // numeric_limits<float>::quiet_NaN(), temp_utils.hpp:21
     float4 P = make_float4(qnan, qnan, qnan, qnan), Nn = P;  // :195-196
     if (x < cols - 1 && y < rows - 1) {                      // :198
         const uint16_t* d0 = (const uint16_t*)((const char*)depth + (size_t)y * depth_step);

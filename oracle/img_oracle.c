@@ -37,6 +37,15 @@ float orc_exp_neg(float x) {
     return p * s.f;
 }
 
+/* numeric_limits<float>::quiet_NaN() of temp_utils.hpp:21, the bit pattern 0x7fffffff that imgproc.cu writes for an
+ * undefined normal or point (not the 0x7fc00000 of C's NAN) */
+static float ref_qnan(void) {
+    const uint32_t bits = 0x7fffffffu;
+    float f;
+    memcpy(&f, &bits, 4);
+    return f;
+}
+
 #define PIX(type, base, step, y, x) (((type*)((char*)(base) + (size_t)(y) * (size_t)(step)))[x])
 #define CPIX(type, base, step, y, x) (((const type*)((const char*)(base) + (size_t)(y) * (size_t)(step)))[x])
 
@@ -103,7 +112,8 @@ void orc_normals_mask_depth(uint16_t* depth, int depth_step, int cols, int rows,
     const float finvx = 1.f / fx, finvy = 1.f / fy;
     for (int y = 0; y < rows; ++y)
         for (int x = 0; x < cols; ++x) {
-            float n_out[4] = {NAN, NAN, NAN, 0.f};
+            const float q  = ref_qnan();
+            float n_out[4] = {q, q, q, 0.f};
             if (x < cols - 1 && y < rows - 1) {
                 const float z00 = PIX(uint16_t, depth, depth_step, y, x) * 0.001f;
                 const float z01 = PIX(uint16_t, depth, depth_step, y, x + 1) * 0.001f;
@@ -134,7 +144,8 @@ void orc_resize_depth_normals(const uint16_t* dsrc, int dsrc_step, const float* 
         for (int x = 0; x < cols / 2; ++x) {
             const int xs = 2 * x, ys = 2 * y;
             uint16_t d = 0;
-            float n[4] = {NAN, NAN, NAN, NAN};
+            const float q = ref_qnan();
+            float n[4]    = {q, q, q, q};
             const int d00 = CPIX(uint16_t, dsrc, dsrc_step, ys, xs), d01 = CPIX(uint16_t, dsrc, dsrc_step, ys, xs + 1);
             const int d10 = CPIX(uint16_t, dsrc, dsrc_step, ys + 1, xs), d11 = CPIX(uint16_t, dsrc, dsrc_step, ys + 1, xs + 1);
             if (d00 * d01 != 0 && d10 * d11 != 0) {
@@ -155,7 +166,8 @@ void orc_resize_points_normals(const float* vsrc, int vsrc_step, const float* ns
     for (int y = 0; y < rows / 2; ++y)
         for (int x = 0; x < cols / 2; ++x) {
             const int xs = 2 * x, ys = 2 * y;
-            float v[4] = {NAN, NAN, NAN, 0.f}, n[4] = {NAN, NAN, NAN, 0.f};
+            const float q = ref_qnan();
+            float v[4] = {q, q, q, 0.f}, n[4] = {q, q, q, 0.f};
             const float* p00 = &CPIX(float, vsrc, vsrc_step, ys, 4 * xs);
             const float* p01 = &CPIX(float, vsrc, vsrc_step, ys, 4 * (xs + 1));
             const float* p10 = &CPIX(float, vsrc, vsrc_step, ys + 1, 4 * xs);

@@ -22,9 +22,11 @@
  *                                 (oracle/_ref, built from /root/reference/include/nanoflann)
  *   warp-field solve  : pinned  — the 8 OptTest end-state assertions of
  *                                 test/opt_optimisation_test.cpp (tolerance 1e-3)
- *   TSDF / raycast / compute_dists : PARITY UNPINNED — the reference has no tests,
- *                                 golden vectors or CPU path for them and its CUDA
- *                                 sources cannot be built here.
+ *   TSDF / raycast / compute_dists, depth pre-processing, rigid ICP : not pinned to
+ *                                 reference outputs — the reference has no tests, golden
+ *                                 vectors or CPU path for them and its CUDA sources cannot
+ *                                 be built here — but cross-checked by independent numpy
+ *                                 statements (tests/tsdf_statement.py, tests/img_statement.py).
  */
 #ifndef DYNFU_ORACLE_H
 #define DYNFU_ORACLE_H
@@ -169,7 +171,8 @@ void orc_huber_weights(const float* node_pos, const float* node_dq, const float*
                        float* huber);
 
 /* -------------------------------------------------- depth pre-processing -- */
-/* src/kfusion/cuda/imgproc.cu (see img_oracle.c); PARITY UNPINNED.  Steps are in bytes. */
+/* src/kfusion/cuda/imgproc.cu (see img_oracle.c); not pinned to reference outputs, cross-checked by
+ * tests/img_statement.py.  Steps are in bytes. */
 float orc_exp_neg(float x); /* the stand-in for __expf in the bilateral weight (x <= 0) */
 void orc_bilateral(const uint16_t* src, int src_step, uint16_t* dst, int dst_step, int cols, int rows, int ksz,
                    float sigma_spatial, float sigma_depth);
@@ -183,7 +186,8 @@ void orc_resize_points_normals(const float* vsrc, int vsrc_step, const float* ns
                                float* vdst, int vdst_step, float* ndst, int ndst_step);
 
 /* ------------------------------------------------------------- rigid ICP -- */
-/* one linearisation of src/kfusion/cuda/proj_icp.cu (see icp_oracle.c); PARITY UNPINNED.
+/* one linearisation of src/kfusion/cuda/proj_icp.cu (see icp_oracle.c); not pinned to reference outputs,
+ * cross-checked by tests/img_statement.py.
  * depth_variant: curr / prev are u16 depth images; otherwise float4 vertex maps.  aff: R row-major then t. */
 void orc_icp_sums(int depth_variant, const void* curr, int curr_step, const float* ncurr, int ncurr_step, const void* prev,
                   int prev_step, const float* nprev, int nprev_step, int cols, int rows, const float aff[12], float fx,

@@ -62,7 +62,9 @@ static void reproj(int u, int v, float z, float finvx, float finvy, float cx, fl
 void orc6_points_normals(const uint16_t* depth, int depth_step, int cols, int rows, float fx, float fy, float cx,
                          float cy, float* points, int points_step, float* normals, int normals_step) {
     const float finvx = 1.f / fx, finvy = 1.f / fy; /* Reprojector ctor, precomp.cpp */
-    const float qnan = NAN;
+    const uint32_t qbits = 0x7fffffffu; /* numeric_limits<float>::quiet_NaN(), temp_utils.hpp:21 */
+    float qnan;
+    memcpy(&qnan, &qbits, 4);
     for (int y = 0; y < rows; ++y) {
         const uint16_t* d0 = (const uint16_t*)((const char*)depth + (size_t)y * depth_step);
         const uint16_t* d1 = (const uint16_t*)((const char*)depth + (size_t)(y + 1) * depth_step);

@@ -234,7 +234,8 @@ static inline float unpack_tsdf(uint32_t p) { return orc_half_to_float((uint16_t
 static inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 /* :187-193 — nearest voxel, round-half-even. The reference does no bounds check; the ray
- * is kept inside [0, size-voxel] by construction, the clamp only guards memory safety. */
+ * is kept inside [0, size-voxel] by construction, the clamp only guards memory safety (no ray
+ * reaches it: tests/test_tsdf_statement_cpu.py::test_rays_never_leave_the_volume_from_adversarial_poses). */
 static inline float fetch_tsdf(const raycaster* rc, f3 p) {
     int x = (int)lrintf(p.x * rc->voxel_inv.x);
     int y = (int)lrintf(p.y * rc->voxel_inv.y);

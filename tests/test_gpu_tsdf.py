@@ -1,8 +1,11 @@
-"""-m gpu parity tests of the TSDF seam: HIP kernels (through the C ABI) vs the CPU oracle.
+"""-m gpu parity tests of the TSDF seam: HIP kernels (through the C ABI) vs the CPU oracle, and at the edges
+(projection boundaries, camera plane, truncation band, special halves, weight saturation, 1- and 2-voxel axes,
+axis-parallel rays, cameras inside the volume) vs the independent numpy statement tests/tsdf_statement.py.
 
 Bar: BIT-EXACT — voxel indices touched, 16-bit weights and half-float tsdf bits; raycast
 outputs compared as raw float bits (misses are the 0x7fffffff NaN of the reference).
-The TSDF oracle itself is unpinned (the reference has no TSDF tests), see oracle/oracle.h.
+The oracle is cross-checked by that statement on the CPU (tests/test_tsdf_statement_cpu.py); neither is pinned to
+reference outputs, since the reference has none for the TSDF (oracle/oracle.h).
 """
 import os
 
@@ -567,3 +570,194 @@ def test_argument_errors_are_loud(A):
         A.tsdf_integrate(v, d, [0.1, 0.1, 0.1], 0.1, 70000, np.eye(4)[:3], 1, 1, 0, 0)  # weight overflow
     with pytest.raises(A.DynfuAmdError):
         A.tsdf_integrate(v.cpu(), d, [0.1, 0.1, 0.1], 0.1, 64, np.eye(4)[:3], 1, 1, 0, 0)  # host pointer
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# HIP against the independent numpy statement (tests/tsdf_statement.py) at the edges where a fast path may split from
+# the source.  Each runs at the run-classified default and at the per-voxel sweep (DFA_TSDF_LEGACY=1, development
+# library): the classified sweep's skip rules are where an edge voxel could be dropped.
+import tsdf_statement as St  # noqa: E402
+
+HALF_SPECIALS = np.array([0x0000, 0x8000, 0x0001, 0x8001, 0x03FF, 0x83FF, 0x3C00, 0xBC00, 0x3555], np.uint16)
+
+
+@pytest.fixture(params=["classified", "per_voxel"])
+def sweep(request, monkeypatch):
+    """the integrate sweep under test: the default, or the per-voxel sweep of the development library"""
+    if request.param == "classified":
+        monkeypatch.delenv("DFA_TSDF_LEGACY", raising=False)
+        yield request.param
+        return
+    from dynfu_amd import _lib
+    monkeypatch.setenv("DFA_TSDF_LEGACY", "1")
+    with _lib.use_library(_lib.dev_lib_path()):
+        yield request.param
+
+
+def _junk(shape, maxw, seed):
+    """previous volume: special halves (subnormal, +-0, +-1) and weights at 0, max_weight - 1 and max_weight"""
+    rng = np.random.default_rng(seed)
+    h = HALF_SPECIALS[rng.integers(0, len(HALF_SPECIALS), shape)].astype(np.uint32)
+    w = np.array([0, max(maxw - 1, 0), maxw], np.uint32)[rng.integers(0, 3, shape)]
+    return h | (w << 16)
+
+
+def _integrate_vs_statement(A, dims, voxel, trunc, maxw, v2c, intr, dists, seed=0):
+    """fused clear + integrate, then an integrate over a volume of special previous values: HIP == statement"""
+    import torch
+    X, Y, Z = dims
+    v = torch.full((Z, Y, X), -1, dtype=torch.int32, device="cuda")
+    A.tsdf_clear_integrate(v, dev(dists), voxel, trunc, maxw, v2c, *intr)
+    torch.cuda.synchronize()
+    want = St.integrate(St.clear((Z, Y, X)), dists, voxel, trunc, maxw, v2c, *intr)
+    got = host(v, np.uint32)
+    assert np.array_equal(got, want), int((got != want).sum())
+    junk = _junk((Z, Y, X), maxw, seed)
+    v = dev(junk)
+    A.tsdf_integrate(v, dev(dists), voxel, trunc, maxw, v2c, *intr)
+    torch.cuda.synchronize()
+    want2 = St.integrate(junk, dists, voxel, trunc, maxw, v2c, *intr)
+    got = host(v, np.uint32)
+    assert np.array_equal(got, want2), int((got != want2).sum())
+    return want, want2, junk
+
+
+# exact-arithmetic grids: voxel 0.25 m, f = 4, so that projections land exactly on texel edges, on cols, on -0
+EDGE_CASES = {
+    "integral_projections": dict(t=(-0.5, -0.25, 0.5), f=4.0, c=0.0),
+    "just_below_integral": dict(t=(-0.5, -0.25, 0.5 - 2.0 ** -22), f=4.0, c=0.0),
+    "negative_zero": dict(t=(0.0, 0.0, 0.5), f=-4.0, c=-0.0),
+    "camera_plane_at_a_slice": dict(t=(-0.5, 0.0, -1.0), f=4.0, c=0.0),
+    "slice_just_behind_the_camera": dict(t=(0.0, -0.25, -1.0 - 2.0 ** -20), f=4.0, c=0.0),
+}
+
+
+@pytest.mark.parametrize("case", sorted(EDGE_CASES))
+@pytest.mark.parametrize("dims", [(9, 7, 14), (1, 2, 12), (2, 1, 3)])
+def test_integrate_equals_statement_at_projection_and_camera_plane_edges(A, sweep, case, dims):
+    e = EDGE_CASES[case]
+    voxel = np.full(3, 0.25, np.float32)
+    v2c = aff12(np.eye(3), e["t"])
+    rows, cols = 5, 7  # voxel x = 9 projects exactly onto cols (= 7) at vc.z = 1
+    intr = (e["f"], e["f"], e["c"], e["c"])
+    rng = np.random.default_rng(len(case))
+    dists = rng.uniform(0.3, 3.0, (rows, cols)).astype(np.float16).view(np.uint16)
+    dists[0, 0] = 0x8000
+    want, _, _ = _integrate_vs_statement(A, dims, voxel, 0.3, 3, v2c, intr, dists, seed=len(case))
+    if dims == (9, 7, 14) and case != "negative_zero":
+        assert (want != 0).mean() > 0.05
+
+
+@pytest.mark.parametrize("dims", [(1, 1, 16), (2, 2, 16), (1, 3, 16)])
+def test_integrate_equals_statement_on_the_truncation_band_edges(A, sweep, dims):
+    """a column down the optical axis with a surface at 1.5 m, voxel 0.125 m, trunc 0.25 m: slices at sdf == +trunc
+    (tsdf == 1) and sdf == -trunc (the last one kept) in exact arithmetic; weights saturating at max_weight"""
+    voxel = np.full(3, 0.125, np.float32)
+    v2c = aff12(np.eye(3), [0, 0, 0.5])
+    dists = np.full((4, 4), np.float16(1.5).view(np.uint16), np.uint16)
+    want, want2, junk = _integrate_vs_statement(A, dims, voxel, 0.25, 2, v2c, (1.0, 1.0, 0.0, 0.0), dists)
+    F, W = St.unpack(want[:, 0, 0])
+    assert F[:11].tolist() == [1] * 7 + [0.5, 0, -0.5, -1] and not want[11:, 0, 0].any()
+    assert (St.unpack(want2[:11, 0, 0])[1] == np.minimum(St.unpack(junk[:11, 0, 0])[1] + 1, 2)).all()
+
+
+def test_integrate_equals_statement_rotated_camera_256(A, sweep):
+    """one full-size volume: C1's 256^3, a camera turned so that zstep has three non-zero components, two frames"""
+    import torch
+    cfg, intr, voxel, trunc, vol2cam, _, _, _ = _scene("C1")
+    dim = cfg["dim"]
+    R = rot([0.3, 1.0, 0.2], 0.25)
+    centre = 0.5 * voxel * dim
+    v2c = aff12(R, (vol2cam[9:] + centre) - (R @ centre).astype(np.float32))
+    v = torch.empty((dim, dim, dim), dtype=torch.int32, device="cuda")
+    want = St.clear((dim, dim, dim))
+    for i, frame in enumerate((0, 9)):
+        d = St.compute_dists(_scene("C1", frame=frame)[7], *intr)
+        (A.tsdf_clear_integrate if i == 0 else A.tsdf_integrate)(v, dev(d), voxel, trunc, 64, v2c, *intr)
+        want = St.integrate(want, d, voxel, trunc, 64, v2c, *intr)
+    assert np.array_equal(host(v, np.uint32), want)
+    assert float((want >> 16 == 2).mean()) > 0.02
+
+
+def test_compute_dists_equals_statement_pitched(A):
+    import torch
+    rng = np.random.default_rng(3)
+    for rows, cols in ((1, 1), (37, 53), (8, 130)):
+        depth = rng.integers(0, 65536, (rows, cols)).astype(np.uint16)
+        d_in = torch.zeros((rows, cols + 5), dtype=torch.uint16, device="cuda")
+        d_in[:, :cols] = dev(depth)
+        d_out = torch.zeros((rows, cols + 3), dtype=torch.uint16, device="cuda")
+        intr = (3.0, 2.5, cols / 2 - 0.5, rows / 2 - 0.5)
+        A.compute_dists(d_in[:, :cols], d_out[:, :cols], *intr)
+        assert np.array_equal(host(d_out)[:, :cols], St.compute_dists(depth, *intr))
+
+
+def _raycast_vs_statement(A, v, vol, voxel, trunc, c2v, ri, intr, W, H):
+    import torch
+    pts = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda")
+    nrm = torch.zeros_like(pts)
+    A.tsdf_raycast_points(v, voxel, trunc, c2v, ri, *intr, synth.RAYCAST_STEP_FACTOR, synth.GRADIENT_DELTA_FACTOR, pts, nrm)
+    P, N = St.raycast_points(vol, voxel, trunc, c2v, ri, *intr, synth.RAYCAST_STEP_FACTOR, synth.GRADIENT_DELTA_FACTOR, W, H)
+    assert np.array_equal(bits(host(pts)), bits(P)) and np.array_equal(bits(host(nrm)), bits(N))
+    dep = torch.full((H, W), 7, dtype=torch.uint16, device="cuda")
+    A.tsdf_raycast_depth(v, voxel, trunc, c2v, ri, *intr, synth.RAYCAST_STEP_FACTOR, synth.GRADIENT_DELTA_FACTOR, dep, nrm)
+    D, N2 = St.raycast_depth(vol, voxel, trunc, c2v, ri, *intr, synth.RAYCAST_STEP_FACTOR, synth.GRADIENT_DELTA_FACTOR, W, H)
+    assert np.array_equal(host(dep), D) and np.array_equal(bits(host(nrm)), bits(N2))
+    return int((~np.isnan(P[..., 0])).sum())
+
+
+def test_raycast_equals_statement_on_axis_parallel_rays_inside_and_on_faces(A, sweep):
+    """T0's sphere fused by the sweep under test, then cast from the centre of the volume, from a face, an edge and a
+    corner, with the camera axes along the volume's (the centre column of rays exactly axis-parallel, both signs) and
+    turned; image sizes that are not multiples of the 32 x 8 tile"""
+    import itertools
+    cfg, intr, voxel, trunc, vol2cam, _, _, depth = _scene("T0")
+    dim = cfg["dim"]
+    dists = St.compute_dists(depth, *intr)
+    vol, _, _ = _integrate_vs_statement(A, (dim, dim, dim), voxel, trunc, 64, vol2cam, intr, dists)
+    v = dev(vol)
+    bm = voxel * dim - voxel
+    hits = 0
+    for where, (W, H) in zip(((0.5, 0.5, 0.5), (0.5, 0.5, 0.0), (0.0, 0.5, 0.0), (1.0, 1.0, 1.0), (0.3, 0.6, 0.45)),
+                             ((33, 9), (17, 13), (1, 1), (40, 7), (9, 31))):
+        cam = (bm * np.array(where, np.float32)).astype(np.float32)
+        f = 0.6 * W + 1
+        li = (f, f, (W - 1) / 2, (H - 1) / 2)
+        for perm, sign in itertools.product(((0, 1, 2), (2, 0, 1), (1, 2, 0)), (1, -1)):
+            R = np.eye(3)[:, perm] * sign
+            hits += _raycast_vs_statement(A, v, vol, voxel, trunc, aff12(R, cam), R.T.astype(np.float32).reshape(-1),
+                                          li, W, H)
+        R = rot([0.3, -1, 0.5], 0.7)
+        hits += _raycast_vs_statement(A, v, vol, voxel, trunc, aff12(R, cam), R.T.astype(np.float32).reshape(-1), li, W, H)
+    assert hits > 100
+
+
+def test_raycast_equals_statement_when_tmin_equals_tmax(A):
+    """rays that graze an edge of the box [0, size - voxel]: tmin == tmax, no sample; and a ray along a face"""
+    vol = St.pack(np.full((4, 5, 6), 0.5, np.float32), np.ones((4, 5, 6), np.uint32))
+    vol[2:, :, :] = St.pack(np.full((2, 5, 6), -0.5, np.float32), np.ones((2, 5, 6), np.uint32))
+    voxel = np.full(3, 0.25, np.float32)
+    bm = voxel * np.array([6, 5, 4], np.float32) - voxel
+    v = dev(vol)
+    for cam in ((-0.5, -0.5, 0.3), (bm[0] + 0.5, 0.0, 0.3), (0.0, 0.0, -0.5), (bm[0], bm[1], -0.5)):
+        c = np.array(cam, np.float32)
+        R = np.eye(3)
+        if cam[2] > 0:  # looking along +x (or -x) through the edge x .. , y = 0
+            R = np.eye(3)[:, [1, 2, 0]] * (1 if cam[0] < 0 else -1)
+        _raycast_vs_statement(A, v, vol, voxel, 0.3, aff12(R, c), R.T.astype(np.float32).reshape(-1),
+                              (2.0, 2.0, 1.0, 1.0), 3, 3)
+
+
+def test_vertex_normals_equal_statement(A):
+    """dfa_tsdf_vertex_normals (the raycaster's compute_normal at given points) on the hits of a fused sphere"""
+    cfg, intr, voxel, trunc, vol2cam, cam2vol, rinv, depth = _scene("T0")
+    dim = cfg["dim"]
+    vol = St.integrate(St.clear((dim, dim, dim)), St.compute_dists(depth, *intr), voxel, trunc, 64, vol2cam, *intr)
+    P, _ = St.raycast_points(vol, voxel, trunc, cam2vol, rinv, *intr, synth.RAYCAST_STEP_FACTOR,
+                             synth.GRADIENT_DELTA_FACTOR, cfg["width"], cfg["height"])
+    pts = P[~np.isnan(P[..., 0])].copy()
+    pts[:, :3] += cam2vol[9:]
+    assert len(pts) > 1000
+    want = St.vertex_normals(vol, voxel, synth.GRADIENT_DELTA_FACTOR, pts)
+    got = host(A.tsdf_vertex_normals(dev(vol), voxel, synth.GRADIENT_DELTA_FACTOR, dev(pts)))
+    assert np.array_equal(bits(got), bits(want))
