@@ -458,7 +458,7 @@ __global__ __launch_bounds__(256) void prepare_rows_kernel(SolveView s, SolveSta
 // ------------------------------------------------------------------------------------------
 // assembly: one 256-thread workgroup per node.  Its ~128 k rows (transpose graph) are spread
 // over the 4 waves, every row contributes k (column, tau w_a w_b) pairs to an LDS hash keyed by
-// column; wave 0 then compacts the hash into the node's ELL row.  Each row is one packed record
+// column; the four waves then compact the hash into the node's ELL row, ascending by column.  Each row is one packed record
 // (k ids, k weights, e, tau) read with 16-byte loads from a single cache line.
 
 constexpr int HASH      = 512;
@@ -677,36 +677,51 @@ __global__ __launch_bounds__(256) void assemble_kernel(SolveView s, SolveState* 
 #ifdef DFA_PCG_PROFILE
     t3_ = clock64();
 #endif
-    // compact the hash into the ELL row (slot-major: entry q of row a at [q*D + a]: a slot of all rows is
-    // one contiguous 4*D-byte segment, which the sorted-row PCG prologues re-read from L1/L2); each wave owns
-    // HASH/4 consecutive hash slots, wave offsets come from a 4-entry LDS prefix
+    // compact the hash into the ELL row (slot-major: entry q of row a at [q*D + a]: a slot of all rows is one
+    // contiguous 8*D-byte segment), entries in ascending column order:
+    // the PCG gathers p[col] of 64 rows per wave instruction, and rows sorted by column spread those reads over
+    // the LDS banks (hash order: 5.38 clocks per wave instruction on the C2 tables, sorted: 3.90).  Each wave owns
+    // HASH/4 consecutive hash slots (two per lane, held in registers); the valid keys are first packed into key[0,
+    // total) in slot order, then every key's place is the number of smaller keys in the row (~15, broadcast reads).
     constexpr int PER_WAVE = HASH / 4;
-    int wcnt               = 0;
-    for (int base = 0; base < PER_WAVE; base += 64)
-        wcnt += __popcll(__ballot(key[wave * PER_WAVE + base + lane] >= 0));
+    constexpr int PER_LANE = PER_WAVE / 64;
+    int kk[PER_LANE];
+    float vv[PER_LANE];
+    int wcnt = 0;
+#pragma unroll
+    for (int i = 0; i < PER_LANE; ++i) {
+        const int hq = wave * PER_WAVE + 64 * i + lane;
+        kk[i]        = key[hq];
+        vv[i]        = (float)((double)(val[hq] - val[hq + HASH]) * fx.down);
+        wcnt += __popcll(__ballot(kk[i] >= 0));
+    }
     if (lane == 0) wave_cnt[wave] = wcnt;
-    __syncthreads();
+    __syncthreads();  // (also: every wave has read its hash slots before key[] is overwritten below)
     int pos0 = 0, total = 0;
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
         pos0 += w < wave ? wave_cnt[w] : 0;
         total += wave_cnt[w];
     }
-    float diag = 0.f;
-    for (int base = 0; base < PER_WAVE; base += 64) {
-        const int kk     = key[wave * PER_WAVE + base + lane];
-        const int hq     = wave * PER_WAVE + base + lane;
-        const float vv   = (float)((double)(val[hq] - val[hq + HASH]) * fx.down);
-        const bool valid = kk >= 0;
-        const uint64_t m = __ballot(valid);
-        const int pos    = pos0 + __popcll(m & ((1ull << lane) - 1ull));
-        if (valid) {
-            if (pos < s.ell_cap) {
-                s.ell[(size_t)pos * s.D + a] = make_float2(vv, __int_as_float(kk));
-            }
-            if (kk == a) s.diag[a] = vv, diag = 1.f;
-        }
+#pragma unroll
+    for (int i = 0; i < PER_LANE; ++i) {
+        const uint64_t m = __ballot(kk[i] >= 0);
+        if (kk[i] >= 0) key[pos0 + __popcll(m & ((1ull << lane) - 1ull))] = kk[i];
         pos0 += __popcll(m);
+    }
+    __syncthreads();
+    int rank[PER_LANE] = {};
+    for (int q = 0; q < total; ++q) {
+        const int kq = key[q];
+#pragma unroll
+        for (int i = 0; i < PER_LANE; ++i) rank[i] += kq < kk[i];
+    }
+    float diag = 0.f;
+#pragma unroll
+    for (int i = 0; i < PER_LANE; ++i) {
+        if (kk[i] < 0) continue;
+        if (rank[i] < s.ell_cap) s.ell[(size_t)rank[i] * s.D + a] = make_float2(vv[i], __int_as_float(kk[i]));
+        if (kk[i] == a) s.diag[a] = vv[i], diag = 1.f;
     }
     const bool has_diag = __syncthreads_or(diag != 0.f);
     if (threadIdx.x == 0) {
