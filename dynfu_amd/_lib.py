@@ -705,7 +705,9 @@ class Solver:
                     assemble_launches=t.assemble_launches, matrix_nnz=t.matrix_nnz, pcg_iters=t.pcg_iters, solves=t.solves)
 
     def team_pcg_info(self):
-        """dfa_solver_team_pcg_info: {launches, aborts, disabled} of the team PCG (plans of 2 049 .. ~9 300 nodes)"""
+        """dfa_solver_team_pcg_info: {launches, aborts, disabled} of the team PCG (plans of 2 049 nodes up to the team
+        form's bound, 19 584 nodes; rows longer than J x 20 entries, J = 1024 / ceil(D / 32), make the first launch give
+        up and the plan fall back to the launched form)"""
         a, b, c = C.c_int(), C.c_int(), C.c_int()
         _check(self._L.dfa_solver_team_pcg_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return dict(launches=a.value, aborts=b.value, disabled=bool(c.value))

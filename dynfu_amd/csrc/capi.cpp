@@ -163,7 +163,8 @@ struct dfa_solver {
     size_t ev_used;
     int timed_solves = 0;
     dfa::MbGraphCache mb_graphs;  // HIP graphs of the many-workgroup PCG's launch chunks
-    dfa::TeamPcg team;            // host side of the team PCG (plans of 2 049 .. ~9 300 nodes)
+    dfa::TeamPcg team;            // host side of the team PCG (plans of 2 049 nodes up to solve_team_pcg_fits: 19 584;
+                                  // rows longer than J x 20 entries make the first launch give up and the plan fall back)
     bool deterministic = false;  // order-stable variant (dfa_solver_set_deterministic), applied by the next set_problem
     bool just_reset = false;  // the unknowns and the state block were zeroed by set_problem and not touched since
     long long* iters_total = nullptr;  // device: PCG iterations of all solves since enable_timing(1)
@@ -855,7 +856,8 @@ int dfa_solver_create(int max_D, int max_N, int k, dfa_solver** out) {
     }
     // (plans of up to 2 048 nodes solve in the register-resident kernels: no team buffers for them outside development builds)
     if (rc == DFA_OK && dfa::solve_team_pcg_fits(max_D) && (max_D > 2048 || dfa::kDevAB)) {
-        // team PCG: control block (zeroed once: barrier rounds only ever grow), exchange buffer, the pinned abort count
+        // team PCG: control block and flag words (zeroed once: barrier rounds grow; the words are cleared again only where
+        // the rounds would wrap), exchange buffer, the pinned abort count
         s->v.team_stride = (max_D + 3) & ~3;
         rc = plan_alloc(s, &s->v.team_ctl, 1);
         const size_t areas = (size_t)3 * dfa::solve_team_pcg_rounds();  // an area per barrier round and coordinate (50 MB at 8 k nodes)
@@ -868,6 +870,8 @@ int dfa_solver_create(int max_D, int max_N, int k, dfa_solver** out) {
         if (rc == DFA_OK && hipHostMalloc((void**)&s->team.host_abort, sizeof(int), hipHostMallocDefault) == hipSuccess) {
             *s->team.host_abort = 0;
             s->team.ctl = s->v.team_ctl;
+            // (development builds: DFA_MB_TEAM_EPOCH = the first barrier round, e.g. just below 2^32 for the wrap's test)
+            if (const char* e0 = dfa::dev_env("DFA_MB_TEAM_EPOCH")) s->team.epoch = (unsigned)std::strtoul(e0, nullptr, 0);
         }
     }
     if (rc == DFA_OK) rc = plan_alloc(s, &s->state, 1);

@@ -2105,7 +2105,8 @@ static hipError_t launch_mb_pcg(const SolveView& s, SolveState* state, int max_i
 
 // ------------------------------------------------------------------------------------------
 // PCG by three TEAMS of persistent workgroups, one coordinate per team, every team confined to ONE XCD
-// (plans of 2 049 .. ~19 000 nodes: C3, C4, the adaptor's frames).
+// (plans of 2 049 nodes up to the bound of solve_team_pcg_fits, 19 584 nodes: C3, C4, the adaptor's frames; rows longer
+// than J x TEAM_E entries make the first launch give up and the plan fall back to the launched form).
 //
 // The launched form above pays a kernel boundary per iteration: ~5.8 us for an iteration whose arithmetic takes a fraction of
 // a microsecond, and the host has to guess how many launches to enqueue (192 launches for 105 iterations per C3 frame).
@@ -2141,14 +2142,16 @@ static hipError_t launch_mb_pcg(const SolveView& s, SolveState* state, int max_i
 // L1 and is served by that same L2.  So every barrier round of a launch has an exchange area of its own, and a flag word
 // is stored TEAM_K times: poll attempt k reads copy k, a fresh line, and only a wait that outlasts TEAM_K attempts goes on
 // with agent-scope loads.  Flag words are self-validating ({round, value} in one 64-bit store; rounds grow from launch to
-// launch, so nothing is ever reset), and the vectors are complete when the flag is stored because every wave has waited for
+// launch, and only where they would wrap are the words cleared), and the vectors are complete when the flag is stored because every wave has waited for
 // its stores' acknowledgements (vmcnt(0): stores count in vmcnt on gfx9) before the workgroup barrier in front of it.
 // What makes this enough is that writer and reader share the L2 — which the XCC_ID census guarantees and nothing else does.
-// Every spin is bounded by the wall clock (s_memrealtime): a team that cannot assemble (placement, starvation by other
-// kernels) or a row that does not fit the register slots ABORTS before it has changed anything, and the guard launch behind
-// (pcg_team_guard_kernel: one workgroup per coordinate, returns at entry otherwise) solves every coordinate nobody has dealt
-// with — a team that gave up, a team no workgroup ever joined — by itself; the host sees the count in pinned memory at its
-// next call and goes back to the launched form.
+// The team kernel writes only its exchange areas, flag words, staging x (the plan's mb_x, component c) and TeamCtl; t and
+// SolveState change only in the guard launch behind it (pcg_team_guard_kernel: one workgroup per coordinate), which runs
+// once the whole team launch has ended.  It commits a coordinate whose TEAM_W members all finished and none gave up, and
+// solves every other one by itself — a team that gave up, a team no workgroup ever joined.  Every spin is bounded by the
+// wall clock (s_memrealtime): a team that cannot assemble (placement, starvation by other kernels), a row that does not fit
+// the register slots, or a member whose wait times out gives up; the host sees the count in pinned memory at its next call
+// and goes back to the launched form.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__) && !defined(__gfx90a__)
 #error "pcg_team_kernel orders its stores with s_waitcnt vmcnt(0): gfx9 only (gfx10+ count stores in vscnt)"
 #endif
@@ -2233,7 +2236,8 @@ __device__ __forceinline__ bool team_wait(const unsigned long long* __restrict__
 // plans whose longest row fits 16 slots per thread
 template <int E, bool TREG>
 __device__ __forceinline__ void team_member(const SolveView& s, SolveState* __restrict__ st, TeamCtl* ctl, char* smem, float (&red)[3][TEAM_NT / 64],
-                                            float* bc, int c, int rank, unsigned epoch0, int max_iter, float pcg_tol, int* host_abort) {
+                                            float* bc, int c, int rank, unsigned epoch0, int max_iter, float pcg_tol, int* host_abort,
+                                            bool late_give_up) {
     const int tid = threadIdx.x, D = s.D;
     float2* mt_s = (float2*)smem;                                      // Dpad x (m, t) ...
     float* m_s   = (float*)smem;                                       // ... TREG: Dpad x m
@@ -2357,7 +2361,7 @@ __device__ __forceinline__ void team_member(const SolveView& s, SolveState* __re
 
     const float floor_ = 1e-12f;
     const float tol2   = pcg_tol * pcg_tol > floor_ ? pcg_tol * pcg_tol : floor_;
-    float target = 0.f, gamma_old = 1.f, alpha_old = 1.f, rz0 = 0.f;
+    float target = 0.f, gamma_old = 1.f, alpha_old = 1.f;
     int it = 0;
     bool gave_up = false;
     while (it < max_iter) {
@@ -2365,17 +2369,10 @@ __device__ __forceinline__ void team_member(const SolveView& s, SolveState* __re
         const unsigned round = epoch0 + (unsigned)it;
         if (it == 0) {
             if (!team_wait<true>(words_at(0), round, sm, &ctl->abort[c], TEAM_TICKS_FIRST, bc)) { gave_up = true; break; }
-            rz0 = sm[2];
-            if (st->grad_first > 0.0 && (double)rz0 <= 1e-12 * st->grad_first) {  // the same decision in every team
-                if (tid == 0 && rank == 0) {
-                    ctl->handled[c] = 1u;
-                    if (c == 0) {
-                        st->gn_iters += 1;
-                        solve_mark_at_floor(st);
-                    }
-                }
-                return;
-            }
+            const float rz0    = sm[2];
+            const bool at_floor = st->grad_first > 0.0 && (double)rz0 <= 1e-12 * st->grad_first;  // the same in every team
+            if (tid == 0 && rank == 0) ctl->rz0[c] = rz0, ctl->at_floor[c] = at_floor;
+            if (at_floor) break;  // (x = 0: nothing to solve)
             target = fmaxf(tol2 * rz0, solve_floor(st)) * (1.0f / 3.0f);  // this coordinate's share of the joint target
         } else {
 #ifdef DFA_PCG_PROFILE
@@ -2386,7 +2383,10 @@ __device__ __forceinline__ void team_member(const SolveView& s, SolveState* __re
         }
         const float gamma = sm[0], delta = sm[1];
         PROF_MARK(0);  // wait
-        if (!(gamma > target)) break;  // converged: (r, M^-1 r) of the iterate in x
+        if (!(gamma > target)) {  // converged: (r, M^-1 r) of the iterate in x
+            gave_up = late_give_up;  // (development builds: a member that gives up behind the last barrier its team passed)
+            break;
+        }
         const float beta  = it == 0 ? 0.f : gamma / gamma_old;
         const float denom = it == 0 ? delta : delta - beta * gamma / alpha_old;
         if (!(denom > 0.f)) break;
@@ -2453,23 +2453,15 @@ __device__ __forceinline__ void team_member(const SolveView& s, SolveState* __re
         st->prof[6] += pw_[0], st->prof[7] += pw_[1];
     }
 #endif
-    if (gave_up) {  // nothing of this coordinate has been written: the guard launch solves it
+    if (gave_up) {  // the guard launch solves this coordinate (t is untouched: members only stage x)
         if ((tid & 63) == 0) team_give_up(ctl, c, host_abort);
         return;
     }
-    if (owner) s.t[3 * a + c] += x;
-    if (tid == 0 && rank == 0) {
-        ctl->handled[c] = 1u;  // (every member is past the last barrier and adds its rows' x: done when the kernel is)
-        // iterations of this launch = those of its slowest coordinate; the last team (or guard workgroup) to arrive books them
-        atomicMax(&st->split_iters, it);
-        __threadfence();
-        if (atomicAdd(&st->split_ticket, 1u) == 2u) {
-            __threadfence();
-            st->pcg_iters += atomicExch(&st->split_iters, 0);
-            st->split_ticket = 0u;
-            if (st->grad_first == 0.0) st->grad_first = (double)rz0;
-            st->gn_iters += 1;
-        }
+    // staged for the guard launch, which commits it only if every member of the team gets here and none gives up
+    if (owner) ((float*)s.mb_x)[4 * a + c] = x;
+    if (tid == 0) {
+        atomicAdd(&ctl->finished[c], 1u);
+        if (rank == 0) ctl->iters[c] = it;
     }
 }
 
@@ -2479,7 +2471,7 @@ __global__ __launch_bounds__(TEAM_NT) void pcg_team_kernel(SolveView s, SolveSta
     __shared__ int rank_sh;
     __shared__ float red[3][TEAM_NT / 64];
     __shared__ float bc[4];
-    if (st->done) return;
+    if (st->done || st->converged) return;  // (converged: a no-op iteration, see SolveState::converged; the guard books it)
     const unsigned xcc = xcc_id();
     if (xcc >= 3u) return;
     const int c = (int)xcc, tid = threadIdx.x, D = s.D;
@@ -2488,119 +2480,136 @@ __global__ __launch_bounds__(TEAM_NT) void pcg_team_kernel(SolveView s, SolveSta
     __syncthreads();
     const int rank = rank_sh;
     if (rank >= TEAM_W) return;  // the team is complete without this workgroup
-    // (ctl->handled[c]: team c has dealt with its coordinate — solved it, or found there was nothing to solve.  The guard
-    // launch solves every coordinate nobody has dealt with: a team that gave up, and a team that never existed — a device
-    // whose XCC_IDs are not 0, 1, 2, a partition mode with fewer XCDs)
-    if (st->converged) {         // no-op iteration (see SolveState::converged); booked once
-        if (tid == 0 && rank == 0) {
-            ctl->handled[c] = 1u;
-            if (c == 0) st->gn_iters += 1, st->gn_noop += 1;
-        }
-        return;
-    }
-    if ((force_abort >> c) & 1) {  // (development builds: the guard launch's test; 8 + mask: leave without a word, as a team that never existed)
+    // (development builds, the guard launch's tests: the teams of the masked coordinates give up at entry; 8 + mask: they
+    // leave without a word, as a team that never existed; 32 + mask: their member TEAM_W - 1 gives up behind the barrier of
+    // the converging round while the others finish)
+    const bool masked = (force_abort >> c) & 1;
+    if (masked && !(force_abort & 32)) {
         if (tid == 0 && !(force_abort & 8)) team_give_up(ctl, c, host_abort);
         return;
     }
+    const bool late_give_up = masked && rank == TEAM_W - 1;
     // which form: the longest row of the matrix (SolveState::max_row_nnz, raised by the assembly in front of this launch: the
     // same value in every workgroup) against the 16 slots per thread of the form that keeps t's replica in registers
     const int rows_ = (D + TEAM_W - 1) / TEAM_W, j_ = TEAM_NT / rows_;
     const bool treg = st->max_row_nnz <= j_ * TEAM_E_TREG && !(force_abort & 16);  // (development builds: 16 = the (m, t) form always)
-    if (treg) team_member<TEAM_E_TREG, true>(s, st, ctl, smem, red, bc, c, rank, epoch0, max_iter, pcg_tol, host_abort);
-    else team_member<TEAM_E, false>(s, st, ctl, smem, red, bc, c, rank, epoch0, max_iter, pcg_tol, host_abort);
+    if (treg) team_member<TEAM_E_TREG, true>(s, st, ctl, smem, red, bc, c, rank, epoch0, max_iter, pcg_tol, host_abort, late_give_up);
+    else team_member<TEAM_E, false>(s, st, ctl, smem, red, bc, c, rank, epoch0, max_iter, pcg_tol, host_abort, late_give_up);
 }
 
-// The guard behind every team launch: workgroup c resets team c's arrival counter for the next launch and, if the team
-// gave up, solves coordinate c by itself — the same recurrence and stopping rules in one 1024-thread workgroup, u in LDS,
-// the matrix streamed from the ELL as assembled, the rows' vectors in the plan's mb_* buffers (component c).  Slow (tens of
-// microseconds per iteration) and rare by construction.
+// The guard behind every team launch, and for the team form the only writer of t and SolveState: it runs once the whole
+// team launch has ended.  Workgroup c commits team c's result if all TEAM_W members finished and none gave up (t += the
+// staged x; nothing but the at-floor mark if the team found the gradient at the floor); otherwise it solves coordinate c
+// by itself, which is safe because the team has not touched t — the same recurrence and stopping rules in one
+// 1024-thread workgroup, u in LDS, the matrix streamed from the ELL as assembled, the rows' vectors in the plan's mb_*
+// buffers (component c).  Slow (tens of microseconds per iteration) and rare by construction.  It resets team c's words
+// of the control block for the next launch.
 __global__ __launch_bounds__(1024) void pcg_team_guard_kernel(SolveView s, SolveState* __restrict__ st, int max_iter, float pcg_tol,
                                                               int* host_abort) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ float red0[16], red1[16];
-    __shared__ unsigned todo_sh;
+    __shared__ int todo_sh, it_sh, floor_sh;  // todo: 0 nothing, 1 commit the team's result, 2 solve here
+    __shared__ float rz0_sh;
     const int c = blockIdx.x, tid = threadIdx.x, D = s.D;
     TeamCtl* ctl = s.team_ctl;
     if (tid == 0) {
-        // the coordinate is this workgroup's if nobody has dealt with it: its team gave up (abort: counted by the team), or no
-        // workgroup of the team launch ever took it (counted here: the plan goes back to the launched form)
-        const unsigned handled = ctl->handled[c], gave_up = ctl->abort[c];
-        todo_sh = st->done ? 0u : !handled;
-        if (todo_sh && !gave_up && host_abort) atomicAdd_system(host_abort, 1);
-        ctl->abort[c] = 0u, ctl->count[c] = 0u, ctl->handled[c] = 0u;
+        // (st->done and st->converged are read here by every workgroup and written, if at all, by the last one to arrive
+        // at the ticket below: the three agree)
+        const bool gave_up = ctl->abort[c] != 0u, complete = ctl->finished[c] == (unsigned)TEAM_W && !gave_up;
+        todo_sh = 0;
+        if (!st->done && st->converged) {  // the team launch returned at entry: a no-op iteration, booked once
+            if (c == 0) st->gn_iters += 1, st->gn_noop += 1;
+        } else if (!st->done) {
+            todo_sh = complete ? 1 : 2;
+            // a team that gave up has counted itself; a team nobody joined is counted here: the plan goes back to the
+            // launched form
+            if (!complete && !gave_up && host_abort) atomicAdd_system(host_abort, 1);
+            it_sh = ctl->iters[c], rz0_sh = ctl->rz0[c], floor_sh = (int)ctl->at_floor[c];
+        }
+        ctl->count[c] = 0u, ctl->abort[c] = 0u, ctl->finished[c] = 0u, ctl->at_floor[c] = 0u, ctl->iters[c] = 0, ctl->rz0[c] = 0.f;
     }
     __syncthreads();
-    if (!todo_sh) return;
-    if (st->converged) {  // no-op iteration, booked once — by whoever deals with coordinate 0
-        if (tid == 0 && c == 0) st->gn_iters += 1, st->gn_noop += 1;
-        return;
-    }
-    float* u_s = (float*)smem;  // Dpad
-    float *xs = (float*)s.mb_x + c, *rs = (float*)s.mb_r + c, *ps = (float*)s.mb_p + c, *ss = (float*)s.mb_s + c;  // [4 a]
-    float joint_loc = 0.f;
-    for (int a = tid; a < D; a += 1024) {
-        const float d    = s.diag[a];
-        const float minv = d > FLT_EPSILON ? 1.0f / d : 1.0f;
-#pragma unroll
-        for (int cc = 0; cc < 3; ++cc) {
-            const float g = s.g[3 * a + cc];
-            joint_loc     = fmaf(g, minv * g, joint_loc);
-        }
-        const float g = s.g[3 * a + c];
-        xs[4 * a] = 0.f, rs[4 * a] = g, ps[4 * a] = 0.f, ss[4 * a] = 0.f;
-        u_s[a] = minv * g;
-    }
-    const float rz0 = block_sum_f<16>(joint_loc, red0);  // (its barrier publishes u_s)
-    if (st->grad_first > 0.0 && (double)rz0 <= 1e-12 * st->grad_first) {
-        if (tid == 0 && c == 0) {
-            st->gn_iters += 1;
-            solve_mark_at_floor(st);
-        }
-        return;
-    }
-    const float floor_ = 1e-12f;
-    const float tol2   = pcg_tol * pcg_tol > floor_ ? pcg_tol * pcg_tol : floor_;
-    const float target = fmaxf(tol2 * rz0, solve_floor(st)) * (1.0f / 3.0f);
-    float gamma_old = 1.f, alpha_old = 1.f;
-    int it = 0;
-    __syncthreads();
-    while (it < max_iter) {
-        float g_loc = 0.f, d_loc = 0.f;
-        for (int a = tid; a < D; a += 1024) {
-            const int cnt = min(s.ell_cnt[a], s.ell_cap);
-            float w = 0.f;
-            for (int q = 0; q < cnt; ++q) {
-                const float2 en = s.ell[(size_t)q * D + a];
-                w = fmaf(en.x, u_s[__float_as_int(en.y)], w);
-            }
-            ((float*)s.mb_w)[4 * a + c] = w;
-            g_loc = fmaf(rs[4 * a], u_s[a], g_loc), d_loc = fmaf(w, u_s[a], d_loc);
-        }
-        const float gw = wave_total(g_loc), dw = wave_total(d_loc);
-        if ((tid & 63) == 0) red0[tid >> 6] = gw, red1[tid >> 6] = dw;
-        __syncthreads();
-        float gamma = 0.f, delta = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) gamma += red0[i], delta += red1[i];
-        if (!(gamma > target)) break;
-        const float beta  = it == 0 ? 0.f : gamma / gamma_old;
-        const float denom = it == 0 ? delta : delta - beta * gamma / alpha_old;
-        if (!(denom > 0.f)) break;
-        const float alpha = gamma / denom;
+    if (todo_sh == 0) return;
+    int it = it_sh;
+    float rz0 = rz0_sh;
+    bool at_floor = floor_sh != 0;
+    float* xs = (float*)s.mb_x + c;  // [4 a]
+    if (todo_sh == 2) {
+        float* u_s = (float*)smem;  // Dpad
+        float *rs = (float*)s.mb_r + c, *ps = (float*)s.mb_p + c, *ss = (float*)s.mb_s + c;
+        float joint_loc = 0.f;
         for (int a = tid; a < D; a += 1024) {
             const float d    = s.diag[a];
             const float minv = d > FLT_EPSILON ? 1.0f / d : 1.0f;
-            const float p = fmaf(beta, ps[4 * a], u_s[a]), sn = fmaf(beta, ss[4 * a], ((float*)s.mb_w)[4 * a + c]);
-            const float rn = fmaf(-alpha, sn, rs[4 * a]);
-            ps[4 * a] = p, ss[4 * a] = sn, xs[4 * a] = fmaf(alpha, p, xs[4 * a]), rs[4 * a] = rn;
-            u_s[a] = minv * rn;  // (own row only; the gathers of this iteration are behind the reduction's barrier)
+#pragma unroll
+            for (int cc = 0; cc < 3; ++cc) {
+                const float g = s.g[3 * a + cc];
+                joint_loc     = fmaf(g, minv * g, joint_loc);
+            }
+            const float g = s.g[3 * a + c];
+            xs[4 * a] = 0.f, rs[4 * a] = g, ps[4 * a] = 0.f, ss[4 * a] = 0.f;
+            u_s[a] = minv * g;
         }
-        ++it;
-        gamma_old = gamma, alpha_old = alpha;
+        rz0      = block_sum_f<16>(joint_loc, red0);  // (its barrier publishes u_s)
+        at_floor = st->grad_first > 0.0 && (double)rz0 <= 1e-12 * st->grad_first;
+        it       = 0;
+        const float floor_ = 1e-12f;
+        const float tol2   = pcg_tol * pcg_tol > floor_ ? pcg_tol * pcg_tol : floor_;
+        const float target = fmaxf(tol2 * rz0, solve_floor(st)) * (1.0f / 3.0f);
+        float gamma_old = 1.f, alpha_old = 1.f;
         __syncthreads();
+        while (!at_floor && it < max_iter) {
+            float g_loc = 0.f, d_loc = 0.f;
+            for (int a = tid; a < D; a += 1024) {
+                const int cnt = min(s.ell_cnt[a], s.ell_cap);
+                float w = 0.f;
+                for (int q = 0; q < cnt; ++q) {
+                    const float2 en = s.ell[(size_t)q * D + a];
+                    w = fmaf(en.x, u_s[__float_as_int(en.y)], w);
+                }
+                ((float*)s.mb_w)[4 * a + c] = w;
+                g_loc = fmaf(rs[4 * a], u_s[a], g_loc), d_loc = fmaf(w, u_s[a], d_loc);
+            }
+            const float gw = wave_total(g_loc), dw = wave_total(d_loc);
+            if ((tid & 63) == 0) red0[tid >> 6] = gw, red1[tid >> 6] = dw;
+            __syncthreads();
+            float gamma = 0.f, delta = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) gamma += red0[i], delta += red1[i];
+            if (!(gamma > target)) break;
+            const float beta  = it == 0 ? 0.f : gamma / gamma_old;
+            const float denom = it == 0 ? delta : delta - beta * gamma / alpha_old;
+            if (!(denom > 0.f)) break;
+            const float alpha = gamma / denom;
+            for (int a = tid; a < D; a += 1024) {
+                const float d    = s.diag[a];
+                const float minv = d > FLT_EPSILON ? 1.0f / d : 1.0f;
+                const float p = fmaf(beta, ps[4 * a], u_s[a]), sn = fmaf(beta, ss[4 * a], ((float*)s.mb_w)[4 * a + c]);
+                const float rn = fmaf(-alpha, sn, rs[4 * a]);
+                ps[4 * a] = p, ss[4 * a] = sn, xs[4 * a] = fmaf(alpha, p, xs[4 * a]), rs[4 * a] = rn;
+                u_s[a] = minv * rn;  // (own row only; the gathers of this iteration are behind the reduction's barrier)
+            }
+            ++it;
+            gamma_old = gamma, alpha_old = alpha;
+            __syncthreads();
+        }
     }
-    for (int a = tid; a < D; a += 1024) s.t[3 * a + c] += xs[4 * a];
+    if (!at_floor) {  // t += x, four rows' loads in flight per thread
+        for (int a0 = tid; a0 < D; a0 += 4 * 1024) {
+            float xv[4], tv[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int a = min(a0 + q * 1024, D - 1);
+                xv[q] = xs[4 * a], tv[q] = s.t[3 * a + c];
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (a0 + q * 1024 < D) s.t[3 * (a0 + q * 1024) + c] = tv[q] + xv[q];
+        }
+    }
     if (tid == 0) {
+        // iterations of this launch = those of its slowest coordinate; the last workgroup to arrive books them (at the
+        // floor: no iterations, and the mark — the same decision in every coordinate)
         atomicMax(&st->split_iters, it);
         __threadfence();
         if (atomicAdd(&st->split_ticket, 1u) == 2u) {
@@ -2609,12 +2618,13 @@ __global__ __launch_bounds__(1024) void pcg_team_guard_kernel(SolveView s, Solve
             st->split_ticket = 0u;
             if (st->grad_first == 0.0) st->grad_first = (double)rz0;
             st->gn_iters += 1;
+            if (at_floor) solve_mark_at_floor(st);
         }
     }
 }
 
-// plans the team form can serve: (m, t) of every row + the partial sums in one CU's LDS, a member's rows on its threads (it
-// is USED above the register-resident kernels: more than 2 048 nodes)
+// plans the team form can serve: (m, t) of every row + the partial sums in one CU's LDS (Dpad <= 19 584), a member's rows on
+// its threads (it is USED above the register-resident kernels: more than 2 048 nodes)
 bool solve_team_pcg_fits(int D) {
     return sizeof(float2) * (size_t)((D + 3) & ~3) + sizeof(float) * TEAM_NT + 1024 <= 158 * 1024 && (D + TEAM_W - 1) / TEAM_W <= TEAM_NT;
 }
@@ -2627,9 +2637,6 @@ static hipError_t launch_team_pcg(const SolveView& s, SolveState* state, int max
     hipError_t e = allow_big_lds(pcg_team_kernel);
     if (e == hipSuccess) e = allow_big_lds(pcg_team_guard_kernel);
     if (e != hipSuccess) return e;
-    const unsigned epoch0 = tp->epoch;
-    tp->epoch += (unsigned)max_iter + 8u;
-    if (tp->epoch < epoch0 || tp->epoch == 0u) tp->epoch = 1u;  // (wrapped: never round 0, the value of a word nobody has written)
     const size_t lds = std::max(sizeof(float2) * (size_t)s.Dpad + sizeof(float) * TEAM_NT, TEAM_MIN_LDS);
     if (max_iter + 1 > TEAM_ROUNDS) return hipErrorInvalidValue;  // (route_pcg asks solve_team_pcg_fits first)
     {   // The barrier rounds of a launch are numbered from `epoch0`, a kernel ARGUMENT: a captured launch replayed from a HIP
@@ -2665,6 +2672,15 @@ static hipError_t launch_team_pcg(const SolveView& s, SolveState* state, int max
             return e;
         }
     }
+    // rounds epoch0 .. epoch0 + max_iter of this launch.  Where they would wrap or reach 0 (the value of a word nobody has
+    // written), the flag words are cleared behind the plan's earlier launches and the rounds start again at 1.
+    unsigned epoch0     = tp->epoch;
+    const unsigned span = (unsigned)max_iter + 8u;
+    if (epoch0 == 0u || epoch0 > ~0u - span) {
+        if ((e = hipMemsetAsync(s.team_words, 0, sizeof(unsigned long long) * solve_team_pcg_words(), st)) != hipSuccess) return e;
+        epoch0 = 1u;
+    }
+    tp->epoch = epoch0 + span;
     pcg_team_kernel<<<8 * TEAM_W, TEAM_NT, lds, st>>>(s, state, epoch0, max_iter, pcg_tol, tp->host_abort,
                                                              dev_env_int("DFA_MB_TEAM_ABORT", 0));
     pcg_team_guard_kernel<<<3, 1024, sizeof(float) * (size_t)s.Dpad, st>>>(s, state, max_iter, pcg_tol, tp->host_abort);

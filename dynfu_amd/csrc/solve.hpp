@@ -18,7 +18,7 @@ struct SolveState {
     int max_row_nnz;
     int overflow;       // a row of the normal matrix did not fit the plan's ELL capacity
     int pcg_fallback;   // (unused since the streaming path runs inside the register-resident launch; keeps the layout)
-    int split_iters;    // per-coordinate PCG: most iterations any coordinate took in the launch in flight
+    int split_iters;    // per-coordinate PCG (and the team PCG's guard): most iterations any coordinate took in the launch in flight
     unsigned int split_ticket;  // ... and how many of its three workgroups have finished
     // multi-workgroup PCG: flags and scalars carried from one launch to the next
     int mb_done;
@@ -54,11 +54,15 @@ __device__ __forceinline__ void solve_mark_at_floor(SolveState* st) {
     else if (!st->converged) st->converged = 2;
 }
 
-// control block of the team PCG (pcg_team_kernel): device memory of the plan, zeroed once
+// control block of the team PCG (pcg_team_kernel): device memory of the plan, zeroed once.  The team kernel writes it, the
+// guard launch behind it reads it, decides and resets every field for the next launch.
 struct TeamCtl {
-    unsigned int count[3];                  // workgroups of team c that have arrived in the launch in flight (zeroed by the guard launch)
-    unsigned int abort[3];                  // team c gave up in the launch in flight: the guard launch solves its coordinate
-    unsigned int handled[3];                // team c has dealt with its coordinate in the launch in flight (the guard launch takes what nobody has)
+    unsigned int count[3];     // workgroups of team c that have arrived in the launch in flight
+    unsigned int abort[3];     // a member of team c gave up in the launch in flight: the guard launch solves its coordinate
+    unsigned int finished[3];  // members of team c that left the iteration normally (x of their rows in mb_x, component c)
+    int iters[3];              // team c's iterations ...
+    float rz0[3];              // ... its joint (r0, z0) ...
+    unsigned int at_floor[3];  // ... and whether it found the gradient at the floor (nothing to solve: the guard only marks it)
 };
 
 struct SolveView {
@@ -166,7 +170,7 @@ struct MbGraphCache {
 struct TeamPcg {
     TeamCtl* ctl    = nullptr;  // == SolveView::team_ctl (null: no team PCG for this plan)
     int* host_abort = nullptr;  // pinned: teams that have given up so far, written by the device
-    unsigned epoch  = 1;        // first barrier round of the next launch (rounds only ever grow: no flag is ever reset)
+    unsigned epoch  = 1;        // first barrier round of the next launch (rounds grow; where they would wrap, the flags are cleared)
     long launches   = 0;
     bool disabled   = false;    // a team has given up before: the launched form from now on
 };

@@ -396,8 +396,10 @@ int dfa_solver_set_problem(dfa_solver* s, const float* node_pos, const float* no
  * the outer iteration's first linearisation and restart the PCG on g - A (t - t_0) when lambda > 0 and gn_tol = 0; the
  * call reads the plan's `converged` flag back every 4th iteration of an outer iteration and stops launching its
  * remaining (or all remaining) iterations once it is set (the iterations not launched are booked as no-ops, like those
- * whose kernels return at entry).  Plans of 2 049 .. ~19 000 nodes run their PCG as three teams of persistent workgroups
- * (a coordinate per XCD, one barrier per iteration through that XCD's L2: DESIGN.md 4.3) — also without any host
+ * whose kernels return at entry).  Plans of 2 049 nodes up to the team form's bound (19 584 nodes: the (m, t) pair of
+ * every row in one CU's LDS) run their PCG as three teams of persistent workgroups (a coordinate per XCD, one barrier per
+ * iteration through that XCD's L2: DESIGN.md 4.3; rows longer than J x 20 entries, J = 1024 / ceil(D / 32) threads per
+ * row, make the first team launch give up and the plan fall back to the launched form) — also without any host
  * synchronisation up to 8 Gauss-Newton iterations, with the same read-back every 4th iteration beyond —; a plan whose
  * team has given up once (dfa_solver_team_pcg_info), larger plans, and linear_iter > 256 use a many-workgroup PCG whose
  * launches go out in chunks, and the call then waits for `stream` about once per Gauss-Newton iteration to read the stop
@@ -481,10 +483,12 @@ typedef void (*dfa_overlap_fn)(void* user, dfa_stream_t solve_stream, int gn_ite
 int dfa_solver_set_overlap_callback(dfa_solver* s, dfa_overlap_fn fn, void* user);
 int dfa_solver_get_timing(dfa_solver* s, dfa_solve_timing* host_out, dfa_stream_t stream);
 
-/* The PCG of plans with 2 049 .. ~9 300 nodes runs as three teams of persistent workgroups (one coordinate each, each team
- * on one XCD: no kernel boundary per iteration).  A team that cannot assemble, or meets a row of the normal
- * matrix too long for its register slots, gives up before it has changed anything; the guard launch behind it solves that
- * coordinate and the plan takes the launch-per-iteration form from its next PCG on.  This reports what has happened so far
+/* The PCG of plans of 2 049 nodes up to the team form's bound (19 584 nodes: the (m, t) pair of every row in one CU's LDS)
+ * runs as three teams of persistent workgroups (one coordinate each, each team on one XCD: no kernel boundary per
+ * iteration).  A team that cannot assemble, or meets a row of the normal matrix longer than its register
+ * slots (J x 20 entries, J = 1024 / ceil(D / 32) threads per row), gives up; the team changes neither the translations nor
+ * the solve's state, the guard launch behind it solves that coordinate, and the plan falls back to the launch-per-iteration
+ * form from its next PCG on.  This reports what has happened so far
  * (no synchronisation; counts of the calling thread's view): team launches enqueued, teams that gave up, whether the plan
  * has gone back to the launched form (1 also for plans the team form does not serve).  Replaces nothing in the reference:
  * Opt's solver (src/dynfu/utils/opt_solver.cpp:107-147) reports no such thing. */

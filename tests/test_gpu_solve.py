@@ -743,14 +743,15 @@ def test_team_pcg_of_two_plans_on_two_streams(A):
         s.close()
 
 
-@pytest.mark.parametrize("mask", [2, 7, 8 + 4, 8 + 7])
+@pytest.mark.parametrize("mask", [2, 7, 8 + 4, 8 + 7, 32 + 2, 32 + 7])
 def test_team_pcg_guard_solves_what_a_team_gave_up(A, devlib, monkeypatch, mask):
     """DFA_MB_TEAM_ABORT (development builds) makes the teams of the masked coordinates give up at entry, as a team does
     that cannot assemble on its XCD or meets a row too long for its register slots — with 8 added they leave without a word,
-    as on a device where no workgroup ever lands on that team's XCD (another partition mode, other XCC_IDs): the guard launch
-    behind solves every coordinate nobody has dealt with (same recurrence, one workgroup), the answer is the team's, the event
-    is counted in pinned memory and the plan takes a launch per iteration from its next solve on — and still gives the same
-    answer."""
+    as on a device where no workgroup ever lands on that team's XCD (another partition mode, other XCC_IDs); with 32 added
+    one member gives up late, behind the barrier of the round where its team converges, while the other 31 finish (a
+    member whose wait timed out on a stall): the guard launch behind solves every coordinate its team did not complete
+    (same recurrence, one workgroup) on a t no member has touched, the answer is the team's, the event is counted in pinned
+    memory and the plan takes a launch per iteration from its next solve on — and still gives the same answer."""
     cfg, prob, kw = _c3_problem(A, frame=4)
     s = A.Solver(cfg["D"], prob[3].shape[0], cfg["k"])
     s.set_problem(*prob)
@@ -772,6 +773,36 @@ def test_team_pcg_guard_solves_what_a_team_gave_up(A, devlib, monkeypatch, mask)
     assert info["disabled"] and info["launches"] == launches
     assert np.abs(host(s.translations()) - t_team).max() <= 1e-6
     s.close()
+
+
+def test_team_pcg_rounds_that_wrap_around_32_bits(A, devlib, monkeypatch):
+    """The barrier rounds of the team PCG are 32-bit tags that grow from launch to launch.  DFA_MB_TEAM_EPOCH (development
+    builds) starts a plan's rounds just below 2^32: the launch whose rounds would wrap clears the plan's flag words and
+    starts again at 1.  Every solve of that plan, before and after the wrap, gives the bits of a plan started at 1, and no
+    team gives up (a stale or zero round tag would let a team pass a barrier early, or wait until it times out)."""
+    cfg, prob, kw = _c3_problem(A, frame=6)
+    span = kw["linear_iter"] + 8  # rounds a launch takes
+    start = 2**32 - 3 * span - 100  # the fourth launch wraps
+    plans = []
+    for epoch in (None, start):
+        if epoch is not None:
+            monkeypatch.setenv("DFA_MB_TEAM_EPOCH", str(epoch))
+        s = A.Solver(cfg["D"], prob[3].shape[0], cfg["k"])
+        monkeypatch.delenv("DFA_MB_TEAM_EPOCH", raising=False)
+        s.set_deterministic(True)  # (the same bits from the same inputs in two plans)
+        s.set_problem(*prob)
+        plans.append(s)
+    for _ in range(3):
+        t = []
+        for s in plans:
+            s.solve(_params(A, **kw))
+            t.append(host(s.translations()))
+        assert np.array_equal(t[0], t[1])
+    for s in plans:
+        info = s.team_pcg_info()
+        assert info["aborts"] == 0 and not info["disabled"], info
+        s.close()
+    assert info["launches"] * span > 2**32 - start  # (the second plan's rounds did wrap)
 
 
 @pytest.mark.parametrize("name,k", [("T0", 4), ("T1", 4), ("T1", 8)])
