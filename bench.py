@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — frames/sec of the warp-solve + TSDF-fuse hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the headline figure, the
+roofline of the kernels timed inside those steps and the last frame's error against ground truth.  Everything else it can
+measure or check (CPU baselines, the other configurations and modes, per-frame latency, raycast / sweep variants, the
+pipelined and multi-sequence figures, the DynFusion::operator() sequence, the collective timings) takes runs of its own and
+comes with --full; the --no-* options leave single parts of that out.
 
 One "step" = one frame of BASELINE.json's metric: compute_dists + clear+integrate (fused sweep)
 of the 512^3 volume, graph build (k-NN of 262 144 canonical vertices among 2 048 nodes + the
@@ -65,8 +71,11 @@ def parse():
     ap.add_argument("--fuse-after-build", action="store_true",
                     help="launch the TSDF sweep behind the graph build (A/B; default up to 2048 nodes: in the shadow of the "
                          "first PCG, behind the solver's overlap event)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline figure (CPU baselines, "
+                         "other configurations and modes, latency, raycast, pipelined / multi-sequence, end-to-end sequence)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-northstar", action="store_true", help="skip the short north-star-mode measurement of the default run")
+    ap.add_argument("--no-northstar", action="store_true", help="skip the short north-star-mode measurement of --full")
     ap.add_argument("--no-pipelined-probe", action="store_true", help="skip the short pipelined-throughput measurement")
     ap.add_argument("--sequences-per-gpu", type=int, nargs="*", default=[1, 2, 4],
                     help="the multi_sequence figure: S independent sequences on this GPU, each on streams of its own (default 1 2 4)")
@@ -80,7 +89,7 @@ def parse():
                          "reference's data flow — noisy depth, marching-cubes live cloud, nearest-vertex correspondence "
                          "(prints the line of that workload alone)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short C3 / C4 measurements (both modes) of the default run")
+                    help="skip the short C3 / C4 measurements (both modes) of --full")
     ap.add_argument("--no-raycast", action="store_true", help="skip the raycast figures (SURVEY 8d: reported separately)")
     ap.add_argument("--no-end-to-end", action="store_true",
                     help="skip the DynFusion::operator() sequence (the reference's own timed region, C++ adaptor classes)")
@@ -586,23 +595,28 @@ def live_depth_probe(cfg_name, device, steps=30, warmup=5, seq=None):
         seq.frame(warmup + f)
     torch.cuda.synchronize(device)
     dt = time.perf_counter() - t0
+    return dict(value=round(steps / dt, 2), unit="frames/s", steps=steps, warmup=warmup, ms_per_step=round(dt / steps * 1e3, 4),
+                **live_depth_fields(seq, cfg_name),
+                note="secondary figure: SURVEY 8(d)'s index-aligned zero-residual targets are the headline workload")
+
+
+def live_depth_fields(seq, cfg_name):
+    """the workload of a SequenceLive and what the solve of its last frame went through: PCG iterations, the share of rows
+    the Tukey weight rejects, energies, the residual after the warp"""
     st = seq.solver.stats()
     tw = seq.solver.tukey_weights()
     resid = (seq.warped - seq.live_last).norm(dim=1)
-    out = dict(value=round(steps / dt, 2), unit="frames/s", steps=steps, warmup=warmup, ms_per_step=round(dt / steps * 1e3, 4),
-               workload="%s, reference-parity energy on the reference's data flow: depth with sigma = 1 mm noise -> fused %d^3 "
-                        "volume -> marching cubes (%d vertices, %d of them on the object, every %dth of those kept: %d rows) -> "
-                        "nearest canonical vertex of every live vertex (dfa_correspond, %d canonical vertices) -> graph build "
-                        "(%d nodes, k=%d) -> %d GN x PCG<=256 -> warp; one stream"
-                        % (cfg_name, seq.cfg["dim"], seq.mc_total, seq.mc_object, seq.stride, seq.rows, seq.N, seq.D, seq.k,
-                           seq.cfg["gn_iters"]),
-               pcg_iterations_last_frame=st["pcg_iters"], gn_iterations_last_frame=st["gn_iters"],
-               gn_iterations_noop_last_frame=st["gn_noop"], cost_first=st["initial_cost"], cost_last=st["final_cost"],
-               tukey_rejected_fraction=round(float((tw == 0).float().mean()), 5),
-               tukey_mean_weight=round(float(tw.mean()), 5),
-               residual_after_warp_mm=dict(median=round(float(resid.median()) * 1e3, 3), p95=round(float(resid.quantile(0.95)) * 1e3, 3)),
-               note="secondary figure: SURVEY 8(d)'s index-aligned zero-residual targets are the headline workload")
-    return out
+    return dict(workload="%s, reference-parity energy on the reference's data flow: depth with sigma = 1 mm noise -> fused %d^3 "
+                         "volume -> marching cubes (%d vertices, %d of them on the object, every %dth of those kept: %d rows) -> "
+                         "nearest canonical vertex of every live vertex (dfa_correspond, %d canonical vertices) -> graph build "
+                         "(%d nodes, k=%d) -> %d GN x PCG<=256 -> warp; one stream"
+                         % (cfg_name, seq.cfg["dim"], seq.mc_total, seq.mc_object, seq.stride, seq.rows, seq.N, seq.D, seq.k,
+                            seq.cfg["gn_iters"]),
+                pcg_iterations_last_frame=st["pcg_iters"], gn_iterations_last_frame=st["gn_iters"],
+                gn_iterations_noop_last_frame=st["gn_noop"], cost_first=st["initial_cost"], cost_last=st["final_cost"],
+                tukey_rejected_fraction=round(float((tw == 0).float().mean()), 5),
+                tukey_mean_weight=round(float(tw.mean()), 5),
+                residual_after_warp_mm=dict(median=round(float(resid.median()) * 1e3, 3), p95=round(float(resid.quantile(0.95)) * 1e3, 3)))
 
 
 def cpu_quota():
@@ -913,13 +927,13 @@ def main_northstar(args, torch, replicas, rank, world, device):
                            workload_detail="inexact Newton: %s; DQ blend of k-NN nodes, projective association, lambda=200"
                                            % northstar_fields(seq, st)["pcg_tolerance_schedule"],
                            parallelism="replicas x%d (one sequence per GPU, no collective)" % n_gpus, ranks_seen=n_gpus,
-                           rccl_selfcheck=rccl_selfcheck(), repeats=len(regions), launcher=launcher_mark(),
+                           rccl_selfcheck=rccl_selfcheck(args.full), repeats=len(regions), launcher=launcher_mark(),
                            streams="one HIP stream (every kernel of this mode fills the chip: a second stream for the sweep costs 6-8 %)"
                                    if not seq.overlap or args.serial else ("fuse || graph build + solve on two HIP streams" if args.fuse_first else
                                                                            "graph build, then fuse || solve on two HIP streams"),
                            last_frame=northstar_fields(seq, st)),
                region_ms=[round(r * 1e3, 4) for r in regions], region_steps=counts, roofline=rl[0], roofline_other=rl[1:])
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         params = seq.params
         del seq
         torch.cuda.empty_cache()
@@ -1457,10 +1471,11 @@ def ranks_seen(device=None):
     return replicas.count_ranks(device)
 
 
-def rccl_selfcheck():
-    """what the one-rank process group of an N = 1 run found (dynfu_amd/replicas.py: init(single_rank_group=True))"""
+def rccl_selfcheck(timing=False):
+    """what the one-rank process group of an N = 1 run found (dynfu_amd/replicas.py: init(single_rank_group=True)); with
+    `timing` (--full) also the host time of its barrier and all-reduce"""
     from dynfu_amd import replicas
-    if replicas.selfcheck is not None and "collective_host_ms" not in replicas.selfcheck:
+    if timing and replicas.selfcheck is not None and "collective_host_ms" not in replicas.selfcheck:
         import torch
         dev = torch.device("cuda", torch.cuda.current_device()) if replicas.selfcheck.get("backend") == "nccl" and torch.cuda.is_available() else None
         replicas.selfcheck["collective_host_ms"] = replicas.time_collectives(dev)
@@ -1489,7 +1504,7 @@ def main_dry_run(args):
                               ms_per_step=round(step_s * 1e3, 4), higher_is_better=True, scaling="weak", vs_baseline=None,
                               dtype="f32", data="none (dry run: sleeps)",
                               config=dict(workload="dry run of the rank launcher (no GPU work)", ranks_seen=seen,
-                                          rccl_selfcheck=rccl_selfcheck(), repeats=len(regions), launcher=launcher_mark(),
+                                          rccl_selfcheck=rccl_selfcheck(args.full), repeats=len(regions), launcher=launcher_mark(),
                                           parallelism="replicas x%d (no collective; counted by all-reduce, %s)" % (seen, args.backend)),
                               region_ms=[round(r * 1e3, 4) for r in regions], region_steps=counts), args)
     replicas.shutdown()
@@ -1518,9 +1533,10 @@ def main():
     # process has made its first GPU call (torch.cuda.is_available() below is one), and has finished before the timed
     # region starts: nothing of it overlaps the measurement.
     e2e = None
-    if world == 1 and args.mode == "ref" and args.live == "targets" and not args.no_end_to_end and under_profiler():
+    wants_e2e = args.full and world == 1 and args.mode == "ref" and args.live == "targets" and not args.no_end_to_end
+    if wants_e2e and under_profiler():
         e2e = dict(skipped="running under rocprofv3: no child process is started from a profiled process")
-    elif world == 1 and args.mode == "ref" and args.live == "targets" and not args.no_end_to_end:
+    elif wants_e2e:
         if not os.path.exists("/dev/kfd"):  # (a file probe: nothing here may touch the GPU before the child has run)
             raise SystemExit("bench.py needs a GPU: the hot path has no CPU fallback")
         try:
@@ -1548,11 +1564,15 @@ def main():
         if rank == 0:
             if args.dump_outputs:
                 dump_outputs(seq, args.dump_outputs)
-            rec = live_depth_probe(args.config, device, steps=min(K, 30), warmup=0, seq=seq)
+            if args.full:
+                rec = live_depth_probe(args.config, device, steps=min(K, 30), warmup=0, seq=seq)
+            else:
+                rec = dict(unit="frames/s", **live_depth_fields(seq, args.config))
             rec.update(metric="frames/sec (warp-solve + TSDF fuse), 512^3 vol / 2k nodes / VGA depth", value=round(n_gpus / step_s, 2),
                        n_gpus=n_gpus, steps=K, warmup=args.warmup, ms_per_step=round(step_s * 1e3, 4), higher_is_better=True,
                        scaling="weak", vs_baseline=None, dtype="f32", data="synthetic",
-                       config=dict(workload=rec.pop("workload"), ranks_seen=n_gpus, repeats=len(regions), rccl_selfcheck=rccl_selfcheck(),
+                       config=dict(workload=rec.pop("workload"), ranks_seen=n_gpus, repeats=len(regions),
+                                   rccl_selfcheck=rccl_selfcheck(args.full),
                                    parallelism="replicas x%d (one sequence per GPU, no collective)" % n_gpus),
                        region_ms=[round(r * 1e3, 4) for r in regions], region_steps=counts)
             finish(rec, args)
@@ -1601,17 +1621,18 @@ def main():
     if args.dump_outputs:
         dump_outputs(seq, args.dump_outputs)
 
-    # ---- per-frame latency (SURVEY.md §8d asks for median and p95): a separate pass OUTSIDE the timed region, every
+    # ---- per-frame latency (SURVEY.md §8d asks for median and p95, --full): a separate pass OUTSIDE the timed region, every
     # frame bracketed by two events and synchronised, so that a frame cannot hide behind the launches of the next
     lat = []
-    for f in range(min(K, 50)):
-        e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
-        e0.record()
-        seq.frame(Wm + f, args.serial)
-        e1.record()
-        e1.synchronize()
-        lat.append(e0.elapsed_time(e1))
-    lat.sort()
+    if args.full:
+        for f in range(min(K, 50)):
+            e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+            e0.record()
+            seq.frame(Wm + f, args.serial)
+            e1.record()
+            e1.synchronize()
+            lat.append(e0.elapsed_time(e1))
+        lat.sort()
 
     # ---- roofline of the kernels measured live with HIP events on their launch streams
     dim, Wd, Hd = cfg["dim"], cfg["width"], cfg["height"]
@@ -1688,7 +1709,7 @@ def main():
                                            "return at entry; PCG tolerance 1e-6 per linearisation, never below 1e-12 of the solve's "
                                            "first gradient",
                            parallelism="replicas x%d (one sequence per GPU, no collective)" % n_gpus, ranks_seen=n_gpus,
-                           rccl_selfcheck=rccl_selfcheck(), streams_probe=STREAM_PROBES[:1], repeats=len(regions),
+                           rccl_selfcheck=rccl_selfcheck(args.full), streams_probe=STREAM_PROBES[:1], repeats=len(regions),
                            launcher=launcher_mark(),
                            streams="serial" if args.serial else ("fuse || graph build of frame f+1 || solve of frame f on three "
                                                                  "HIP streams, two solver plans" if args.pipeline else
@@ -1699,12 +1720,13 @@ def main():
                            pcg_iterations_last_frame=st["pcg_iters"], gn_iterations_last_frame=st["gn_iters"],
                            gn_iterations_noop_last_frame=st["gn_noop"],
                            max_abs_translation_error_vs_ground_truth_m=round(t_err, 6)),
-               frame_latency_ms=dict(median=round(lat[len(lat) // 2], 4), p95=round(lat[min(len(lat) - 1, int(0.95 * len(lat)))], 4),
-                                     frames=len(lat), note="each frame synchronised, measured after the timed region"),
                region_ms=[round(r * 1e3, 4) for r in regions], region_steps=counts,
                roofline=dominant, roofline_other=[other],
                solve_kernels_ms_per_frame=dict(pcg=round(pcg_total_ms, 4), assemble=round(tm["assemble_ms"] / frames_timed, 4)))
-    if world == 1:
+    if lat:
+        out["frame_latency_ms"] = dict(median=round(lat[len(lat) // 2], 4), p95=round(lat[min(len(lat) - 1, int(0.95 * len(lat)))], 4),
+                                       frames=len(lat), note="each frame synchronised, measured after the timed region")
+    if world == 1 and args.full:
         # secondary figures: a failure in one of them must not cost the line its contract fields
         if not args.no_raycast:
             try:

@@ -221,9 +221,36 @@ def test_world_size_must_match_gpus():
     assert r.returncode == 0 and json.loads(r.stdout.strip().splitlines()[-1])["n_gpus"] == 1
 
 
+def test_full_adds_the_collective_timings_to_the_self_check():
+    """the host time of the one-rank group's barrier and all-reduce is a measurement of its own: --full only"""
+    r = _bench("--gpus", "1", "--backend", "gloo", "--dry-run", "--steps", "2", "--warmup", "0")
+    assert r.returncode == 0, r.stderr[-2000:]
+    sc = _detail()["config"]["rccl_selfcheck"]
+    assert sc["ok"] is True and "collective_host_ms" not in sc
+    r = _bench("--gpus", "1", "--backend", "gloo", "--dry-run", "--steps", "2", "--warmup", "0", "--full")
+    assert r.returncode == 0, r.stderr[-2000:]
+    sc = _detail()["config"]["rccl_selfcheck"]
+    assert sc["ok"] is True and len(sc["collective_host_ms"]["barrier_ms"]) == 5
+
+
+@pytest.mark.gpu
+def test_plain_run_leaves_the_secondary_figures_to_full():
+    """without --full a run does what its headline figure needs: the timed steps, the roofline of the kernels timed inside
+    them and the last frame's error against ground truth; no CPU baseline, other configuration, latency pass or probe"""
+    r = _bench("--steps", "5", "--warmup", "2", timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line, d = _line(r.stdout), _detail()
+    assert line["steps"] == 5 and line["value"] == d["value"] > 30.0 and sum(d["region_steps"]) == 5
+    assert line["roofline"]["bound"] == "hbm" and d["config"]["max_abs_translation_error_vs_ground_truth_m"] < 1e-4
+    for key in ("cpu_baseline", "other_configs", "northstar_mode", "live_depth_mode", "pipelined", "multi_sequence", "raycast",
+                "fuse_variants", "end_to_end", "frame_latency_ms"):
+        assert key not in d, key
+    assert "cpu_baseline" not in line and "secondary" not in line
+
+
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_fields():
-    r = _bench("--steps", "5", "--warmup", "2", "--cpu-frames", "1", timeout=1500)
+    r = _bench("--steps", "5", "--warmup", "2", "--cpu-frames", "1", "--full", timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     # ONE line on stdout, the JSON one, under 4 KB with no long strings — RCCL's version block and every other library's
     # chatter go to stderr (claim_stdout); everything beyond the contract's fields is in the detail file

@@ -9,7 +9,7 @@ lite="--no-cpu-baseline --no-northstar --no-pipelined-probe --no-live-depth --no
 for c in C1 C3 C4; do python bench.py --config $c $lite --steps 50 2>/dev/null | tail -1 >> $out; done
 for c in C1 C2 C3 C4; do python bench.py --mode northstar --config $c --no-cpu-baseline --steps 40 2>/dev/null | tail -1 >> $out; done
 python bench.py --live depth --steps 60 2>/dev/null | tail -1 >> $out
-python bench.py 2>/dev/null | tail -1 > gpurun_out/${tag}_default.json
+python bench.py --full 2>/dev/null | tail -1 > ${out%_configs.jsonl}_default.json
 wc -l $out; python3 - <<PY
 import json
 for ln in open("$out"):

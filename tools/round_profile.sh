@@ -5,7 +5,7 @@ tag=${1:-prof}
 out=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $out
 timeout 1100 python -m pytest tests -x -q -m gpu 2>&1 | tail -4
-timeout 600 python bench.py > $out/bench_default_$tag.json 2> $out/bench_default_$tag.err; tail -c 600 $out/bench_default_$tag.json
+timeout 600 python bench.py --full > $out/bench_default_$tag.json 2> $out/bench_default_$tag.err; tail -c 600 $out/bench_default_$tag.json
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$tag -o c2 -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-northstar --no-pipelined-probe > $out/prof_$tag.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
