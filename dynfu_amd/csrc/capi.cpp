@@ -181,7 +181,6 @@ struct dfa_solver6 {
     float* raw_w;       // N x k un-normalised weights of the k-NN pass
     int32_t* raw_reg;   // D x (k + 1)
     const float* node_dq;  // borrowed: transforms at set_problem time
-    int32_t* xcd_perm = nullptr;  // (development builds, DFA_XCD_MAP=2: Morton order of the nodes — an experiment's scratch)
     std::vector<void*> blocks;
     GridScratch grid;
     bool has_problem;
@@ -1249,7 +1248,6 @@ void dfa_solver6_destroy(dfa_solver6* s) {
     if (s->capture_stream) (void)hipStreamDestroy(s->capture_stream);
     for (hipEvent_t e : s->events) (void)hipEventDestroy(e);
     for (void* p : s->blocks) (void)hipFree(p);
-    if (s->xcd_perm) (void)hipFree(s->xcd_perm);
     s->grid.release();
     delete s;
 }
@@ -1274,37 +1272,6 @@ int dfa_solver6_set_problem(dfa_solver6* s, const float* node_pos, const float* 
     const int kreg = s->k + 1;
     HIP_TRY(dfa::launch_knn(node_pos, node_w, D, node_pos, D, kreg, s->raw_reg, nullptr, grid, S(stream)));
     HIP_TRY(dfa::s6_build_graph(v, s->state, canon_vertices, canon_normals, s->raw_w, s->raw_reg, kreg, S(stream)));
-    v.xcd_perm = nullptr;
-    if (dfa::kDevAB && dfa::dev_env_int("DFA_XCD_MAP", 0) == 2) {
-        // (experiment only, profiles/r06_xcd_map.md: the nodes along a Morton curve of their positions, sorted on the host —
-        // a synchronisation per graph build that a product form would replace by a device sort)
-        std::vector<float> pos((size_t)3 * D);
-        HIP_TRY(hipMemcpyAsync(pos.data(), node_pos, sizeof(float) * pos.size(), hipMemcpyDeviceToHost, S(stream)));
-        HIP_TRY(hipStreamSynchronize(S(stream)));
-        float lo[3] = {pos[0], pos[1], pos[2]}, hi[3] = {pos[0], pos[1], pos[2]};
-        for (int i = 0; i < D; ++i)
-            for (int a = 0; a < 3; ++a) lo[a] = std::min(lo[a], pos[3 * i + a]), hi[a] = std::max(hi[a], pos[3 * i + a]);
-        auto spread = [](uint64_t x) {  // 21 bits -> every third bit
-            x &= 0x1fffff, x = (x | x << 32) & 0x1f00000000ffffull, x = (x | x << 16) & 0x1f0000ff0000ffull;
-            x = (x | x << 8) & 0x100f00f00f00f00full, x = (x | x << 4) & 0x10c30c30c30c30c3ull, x = (x | x << 2) & 0x1249249249249249ull;
-            return x;
-        };
-        std::vector<std::pair<uint64_t, int32_t>> key((size_t)D);
-        for (int i = 0; i < D; ++i) {
-            uint64_t m = 0;
-            for (int a = 0; a < 3; ++a) {
-                const float u = (pos[3 * i + a] - lo[a]) / std::max(hi[a] - lo[a], 1e-12f);
-                m |= spread((uint64_t)(u * 1048575.f)) << a;
-            }
-            key[i] = {m, i};
-        }
-        std::sort(key.begin(), key.end());
-        std::vector<int32_t> perm((size_t)D);
-        for (int i = 0; i < D; ++i) perm[i] = key[i].second;
-        if (!s->xcd_perm) HIP_TRY(hipMalloc((void**)&s->xcd_perm, sizeof(int32_t) * (size_t)s->max_D));
-        HIP_TRY(hipMemcpy(s->xcd_perm, perm.data(), sizeof(int32_t) * perm.size(), hipMemcpyHostToDevice));
-        v.xcd_perm = s->xcd_perm;
-    }
     s->has_problem = true;
     return DFA_OK;
 }
@@ -1339,7 +1306,6 @@ int dfa_solver6_solve(dfa_solver6* s, const float* live_vertex_map, int vertex_s
     s->ev_used = 0;
     HIP_TRY(dfa::s6_begin(s->v, s->state, s->node_dq, early ? p.num_iter * p.gn_iter : 0, st));
     s->last_launches = 0;
-    const bool no_graph = dfa::dev_env("DFA_S6_NO_GRAPH") != nullptr;  // (development builds: launches issued one by one)
     // ---- launch budget: fold the solves up to n - 2 into the history (in order, each behind its completion event)
     const bool adaptive = prm->adaptive_launch && s->mirror;
     const unsigned long long n = s->solve_seq++;
@@ -1423,7 +1389,7 @@ int dfa_solver6_solve(dfa_solver6* s, const float* live_vertex_map, int vertex_s
             // the PCG launches of one Gauss-Newton iteration are replayed as a HIP graph (one per launch count); if capture
             // is not possible here (it never is on some stream configurations) the launches are issued one by one
             bool replayed = false;
-            if (!s->graph_disabled && !no_graph) {
+            if (!s->graph_disabled) {
                 auto it = s->pcg_graphs.find(launches);
                 if (it == s->pcg_graphs.end()) {
                     hipGraph_t g = nullptr;

@@ -27,7 +27,6 @@
 #include <cstring>
 
 #include "device_math.hpp"
-#include "dev_switch.hpp"
 #include "kernels.hpp"
 #include "vol_rows.hpp"
 
@@ -408,9 +407,7 @@ hipError_t launch_marching_cubes(const uint32_t* vol, int X, int Y, int Z, const
     else mc_count_kernel<1><<<grid, block, 0, s>>>(a, seg_off);
     launch_segment_scan(seg_off, nsegs, chunk_sums, total_vertices, s);
     if (out_points && max_vertices > 0) {
-        long want = 8192;
-        if (const char* e = dev_env("DFA_MC_EMIT_BLOCKS")) want = std::max(1L, atol(e));  // (development builds)
-        const unsigned eblocks = (unsigned)std::min<long>((nsegs + 3) / 4, want);
+        const unsigned eblocks = (unsigned)std::min<long>((nsegs + 3) / 4, 8192);
         if (vec4) mc_emit_kernel<4><<<eblocks, block, 0, s>>>(a, seg_off, (float4*)out_points, max_vertices, nsegs);
         else mc_emit_kernel<1><<<eblocks, block, 0, s>>>(a, seg_off, (float4*)out_points, max_vertices, nsegs);
     }

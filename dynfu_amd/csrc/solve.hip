@@ -567,8 +567,7 @@ extern "C" __attribute__((visibility("default"))) int dfa_dev_asm_timing(unsigne
 #endif
 
 template <int K>
-__global__ __launch_bounds__(256) void assemble_kernel(SolveView s, SolveState* __restrict__ st, int save_base, int xcd_map,
-                                                       float amax_unset) {
+__global__ __launch_bounds__(256) void assemble_kernel(SolveView s, SolveState* __restrict__ st, int save_base, float amax_unset) {
     __shared__ int key[HASH];
     __shared__ long long val[2 * HASH];  // [0, HASH): sums of the non-negative addends, [HASH, 2 HASH): of the negative ones' magnitudes
     __shared__ float gpart[4][3];
@@ -577,11 +576,8 @@ __global__ __launch_bounds__(256) void assemble_kernel(SolveView s, SolveState* 
     if (st->done || st->converged) return;
     // (workgroup -> node in launch order.  A contiguous node range per XCD — so that the rows a node shares with its
     // neighbours are fetched into one L2 instead of up to eight — left the launch at 345 us at C4: it was never bound by
-    // the fetches.)
-    int a = blockIdx.x;
-#ifdef DFA_DEV_AB  // DFA_XCD_MAP=1: the experiment above, kept for its counters (profiles/r06_xcd_map.md)
-    if (xcd_map && (s.D & 7) == 0) a = (a & 7) * (s.D >> 3) + (a >> 3);
-#endif
+    // the fetches; profiles/r06_xcd_map.md.)
+    const int a = blockIdx.x;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #ifdef DFA_PCG_PROFILE
     long long t0_ = clock64(), t1_, t2_, t3_, t4_;
@@ -935,11 +931,8 @@ __device__ __forceinline__ double block_sum(float v, float* red) {
 // PCG targets never go below the round-off floor of the SOLVE: 1e-12 of the first linearisation's (r0, z0), the level
 // at which a whole linearisation is skipped.  A late Gauss-Newton iteration starts from a small gradient, and 1e-12 of
 // THAT is out of float's reach — its PCG would polish noise until the iteration cap (C2: the third iteration spent 108
-// PCG iterations to move the translations by 2e-7 m).  DFA_PCG_NO_SOLVE_FLOOR=1 (A/B): per-linearisation targets only.
-__device__ int g_floor_off = 0;
-__device__ __forceinline__ float solve_floor(const SolveState* st) {
-    return g_floor_off ? 0.f : (float)(1e-12 * st->grad_first);
-}
+// PCG iterations to move the translations by 2e-7 m).
+__device__ __forceinline__ float solve_floor(const SolveState* st) { return (float)(1e-12 * st->grad_first); }
 
 // DFA_PCG_PROFILE builds accumulate shader cycles per PCG phase (thread 0) into SolveState::prof
 #ifdef DFA_PCG_PROFILE
@@ -971,9 +964,9 @@ __device__ __forceinline__ float block_sum_f(float v, float* red) {
 // are what matters: the prologue counting-sorts the rows by length (wave-uniform loop bounds with
 // almost no padding) and repacks the ELL image rank-major with 16-bit columns — 6 B per non-zero,
 // fully coalesced — into the plan's workspace.
-// The whole workgroup (NT threads, NT * RPT >= D) runs this: the body of pcg_kernel below, and the way out of the
-// register-resident kernel when a row pair does not fit its slots (it used to be a second launch behind every
-// register-resident one, which returned at once in the common case: 5 launches per C2 frame).
+// The whole workgroup (NT threads, NT * RPT >= D) runs this: the way out of the register-resident kernel when a row pair
+// does not fit its slots (it used to be a launch of its own behind every register-resident one, which returned at once
+// in the common case: 5 launches per C2 frame).
 template <int NT, int RPT>
 __device__ __forceinline__ void pcg_stream_body(const SolveView& s, SolveState* __restrict__ st, int max_iter, float pcg_tol,
                                                 char* smem) {
@@ -1155,20 +1148,6 @@ __device__ __forceinline__ void pcg_stream_body(const SolveView& s, SolveState* 
         if (skip) solve_mark_at_floor(st);
     }
 }
-
-#ifdef DFA_DEV_AB  // the streaming kernel as a launch of its own (DFA_PCG_VARIANT=0 / 4): development builds only
-template <int NT, int RPT>
-__global__ __launch_bounds__(NT) void pcg_kernel(SolveView s, SolveState* __restrict__ st, int max_iter,
-                                                   float pcg_tol) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (st->done) return;
-    if (st->converged) {  // no-op iteration (see SolveState::converged)
-        if (threadIdx.x == 0) st->gn_iters += 1, st->gn_noop += 1;
-        return;
-    }
-    pcg_stream_body<NT, RPT>(s, st, max_iter, pcg_tol, smem);
-}
-#endif  // DFA_DEV_AB
 
 // ------------------------------------------------------------------------------------------
 // PCG with the WHOLE matrix in registers (D <= 2 * NT rows).
@@ -1677,7 +1656,7 @@ hipError_t solve_assemble(const SolveView& s, SolveState* state, int save_base, 
     // max(1, w_reg^2), instead of a grid for addends of 1e-30 that the first real one would overflow.
     const float amax_unset = std::max(1.0f, w_reg_sq);
     if (s.deterministic) KDISPATCH(assemble_det_kernel, s.k, <<<s.D, 256, 0, st>>>(s, state, save_base, amax_unset));
-    else KDISPATCH(assemble_kernel, s.k, <<<s.D, 256, 0, st>>>(s, state, save_base, dev_env_int("DFA_XCD_MAP", 0), amax_unset));
+    else KDISPATCH(assemble_kernel, s.k, <<<s.D, 256, 0, st>>>(s, state, save_base, amax_unset));
     return hipGetLastError();
 }
 
@@ -1707,15 +1686,10 @@ hipError_t solve_regradient(const SolveView& s, SolveState* state, hipStream_t s
 // ------------------------------------------------------------------------------------------
 // PCG across many workgroups, for plans with more than 2048 nodes (above 8192 the single-workgroup kernels cannot
 // hold p in one CU's LDS at all; between 2048 and 8192 they spend ~1 ms per launch sorting and repacking the matrix).
-// Textbook preconditioned CG, same stopping rules as the kernels above, two launches per iteration — kernel
-// boundaries are the grid barriers (a software barrier over 512 workgroups costs 9 - 41 us on this part, a boundary
-// ~4 us: tools/microbench_gridbarrier.hip):
-//   A(it)  beta from the partial r.z sums of the two previous updates; q = A p with p = z + beta p_old formed in the
-//          gather (16 lanes per row over the slot-major ELL as assembled, no repacking); partial p.q
-//   B(it)  alpha; x += alpha p; r -= alpha q; z = M^-1 r; partial r.z
-// (The one-launch Chronopoulos-Gear form used for the 6x6-block system in solve6.hip was tried here first: in fp32 its
-// recurrences stall just above the 1e-6 residual target and it took ~30 iterations where this form takes ~11.)
-// Vector roles in the plan's mb_* buffers: x, r, z = mb_u[0], q = mb_w, p ping-pong = mb_p / mb_s.
+// Preconditioned CG, same stopping rules as the kernels above, one launch per iteration — kernel boundaries are the grid
+// barriers (a software barrier over 512 workgroups costs 9 - 41 us on this part, a boundary ~4 us:
+// tools/microbench_gridbarrier.hip).  16 lanes per row over the slot-major ELL as assembled, no repacking.  (The first
+// form, textbook PCG with two launches per iteration, was replaced by the one below: DESIGN_NOTES.md.)
 constexpr int MB_LPR = 16;  // lanes per row
 
 __device__ __forceinline__ float sum_partials_mb(const float* __restrict__ part, int n) {
@@ -1754,104 +1728,8 @@ __device__ __forceinline__ float group16_sum(float v) {
     return v;
 }
 
-#ifdef DFA_DEV_AB  // the textbook form (two launches per iteration, DFA_MB_FORM=2): development builds only
-__global__ __launch_bounds__(256) void pcg_mb_matvec_kernel(SolveView s, SolveState* __restrict__ st, int it, float pcg_tol) {
-    __shared__ float sh[4];
-    if (st->mb_done) return;
-    const int nbu = (s.D + 255) / 256;  // workgroups of the init / update kernels
-    const float rz_cur = sum_partials_mb(s.mb_gpart[it & 1], nbu);
-    const float floor_ = 1e-12f;
-    const float tol2   = pcg_tol * pcg_tol > floor_ ? pcg_tol * pcg_tol : floor_;
-    float beta = 0.f;
-    bool stop  = !(rz_cur > 0.f);
-    if (it == 0) {
-        const bool at_floor = st->grad_first > 0.0 && (double)rz_cur <= (double)floor_ * st->grad_first;
-        stop                = stop || at_floor;  // nothing left to solve
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            st->mb_rz0 = rz_cur;
-            if (at_floor) solve_mark_at_floor(st);
-        }
-    } else {
-        const float rz_prev = sum_partials_mb(s.mb_gpart[(it + 1) & 1], nbu);
-        beta                = rz_cur / rz_prev;
-        stop                = stop || rz_cur <= fmaxf(tol2 * st->mb_rz0, solve_floor(st));
-    }
-    if (stop) {  // the same decision in every workgroup
-        if (blockIdx.x == 0 && threadIdx.x == 0) st->mb_done = 1;
-        return;
-    }
-    const int lane16 = threadIdx.x & (MB_LPR - 1);
-    const int a      = (blockIdx.x * 256 + threadIdx.x) / MB_LPR;
-    const float4* z    = s.mb_u[0];
-    const float4* pold = (it & 1) ? s.mb_p : s.mb_s;  // written by launch it - 1
-    float4* pnew       = (it & 1) ? s.mb_s : s.mb_p;
-    float ax = 0.f, ay = 0.f, az = 0.f;
-    const bool row_ok = a < s.D;
-    const int cnt     = row_ok ? s.ell_cnt[a] : 0;
-    for (int q = lane16; q < cnt; q += MB_LPR) {
-        const float2 e  = s.ell[(size_t)q * s.D + a];
-        const int col   = __float_as_int(e.y);
-        const float val = e.x;
-        float4 pv       = z[col];
-        if (it > 0) {
-            const float4 po = pold[col];
-            pv.x = fmaf(beta, po.x, pv.x), pv.y = fmaf(beta, po.y, pv.y), pv.z = fmaf(beta, po.z, pv.z);
-        }
-        ax = fmaf(val, pv.x, ax), ay = fmaf(val, pv.y, ay), az = fmaf(val, pv.z, az);
-    }
-    ax = group16_sum(ax), ay = group16_sum(ay), az = group16_sum(az);
-    float pq = 0.f;
-    if (row_ok && lane16 == 0) {
-        float4 pv = z[a];
-        if (it > 0) {
-            const float4 po = pold[a];
-            pv.x = fmaf(beta, po.x, pv.x), pv.y = fmaf(beta, po.y, pv.y), pv.z = fmaf(beta, po.z, pv.z);
-        }
-        pnew[a]   = pv;
-        s.mb_w[a] = make_float4(ax, ay, az, 0.f);
-        pq        = fmaf(pv.z, az, fmaf(pv.y, ay, pv.x * ax));
-    }
-    pq = wave_sum_all(pq);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = pq;
-    __syncthreads();
-    if (threadIdx.x == 0) s.mb_dpart[0][blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-__global__ __launch_bounds__(256) void pcg_mb_update_kernel(SolveView s, SolveState* __restrict__ st, int it) {
-    __shared__ float sh[4];
-    if (st->mb_done) return;
-    const float rz_cur = sum_partials_mb(s.mb_gpart[it & 1], (s.D + 255) / 256);
-    const float pq     = sum_partials_mb(s.mb_dpart[0], solve_mb_blocks(s.D));
-    if (!(pq > 0.f)) {  // breakdown: keep x
-        if (blockIdx.x == 0 && threadIdx.x == 0) st->mb_done = 1;
-        return;
-    }
-    const float alpha = rz_cur / pq;
-    const int a       = blockIdx.x * blockDim.x + threadIdx.x;
-    float rz          = 0.f;
-    if (a < s.D) {
-        const float4 p = ((it & 1) ? s.mb_s : s.mb_p)[a], q = s.mb_w[a];
-        float4 x = s.mb_x[a], r = s.mb_r[a];
-        x.x = fmaf(alpha, p.x, x.x), x.y = fmaf(alpha, p.y, x.y), x.z = fmaf(alpha, p.z, x.z);
-        r.x = fmaf(-alpha, q.x, r.x), r.y = fmaf(-alpha, q.y, r.y), r.z = fmaf(-alpha, q.z, r.z);
-        const float d    = s.diag[a];
-        const float minv = d > FLT_EPSILON ? 1.0f / d : 1.0f;
-        const float4 z   = make_float4(minv * r.x, minv * r.y, minv * r.z, 0.f);
-        s.mb_x[a] = x, s.mb_r[a] = r, s.mb_u[0][a] = z;
-        rz = fmaf(r.z, z.z, fmaf(r.y, z.y, r.x * z.x));
-    }
-    rz = wave_sum_all(rz);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = rz;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        s.mb_gpart[(it + 1) & 1][blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-        if (blockIdx.x == 0) st->mb_iters += 1;
-    }
-}
-#endif  // DFA_DEV_AB
-
 // ---- Chronopoulos-Gear form: ONE launch per iteration (the two inner products are taken together after the matrix
-// product, so an iteration needs one grid-wide synchronisation; the textbook form above needs two).  As in
+// product, so an iteration needs one grid-wide synchronisation; the textbook form needs two).  As in
 // s6_pcg_step_kernel:  u = M^-1 r, w = A u, m = M^-1 w, t kept by t_i = m_i + beta_i t_(i-1);
 //   p_i = u_i + beta_i p_(i-1);  s_i = w_i + beta_i s_(i-1);  x += alpha_i p_i;  r -= alpha_i s_i;  u_(i+1) = u_i - alpha_i t_i;
 //   w_(i+1) = A u_(i+1) = A u_i - alpha_i (A m_i + beta_i A t_(i-1))  — gathered from the vectors of launch i - 1;
@@ -1996,31 +1874,15 @@ void MbGraphCache::release() {
     if (capture) (void)hipStreamDestroy(capture), capture = nullptr;
 }
 
-// development builds: DFA_MB_FORM=2 is the textbook form, two launches per iteration
-static bool mb_one_launch() { return dev_env_int("DFA_MB_FORM", 1) != 2; }
-
 // iterations [it0, it1): from the cache's graph of that range when there is (or can be) one, else launch by launch
 static hipError_t launch_mb_range(const SolveView& s, SolveState* state, int it0, int it1, float pcg_tol,
                                   MbGraphCache* gc, hipStream_t st) {
     const int nb = solve_mb_blocks(s.D);
-#ifdef DFA_DEV_AB
-    const int nbu = (s.D + 255) / 256;
-#endif
     auto direct = [&](hipStream_t q) {
-        for (int it = it0; it < it1; ++it) {
-#ifdef DFA_DEV_AB
-            if (!mb_one_launch()) {
-                pcg_mb_matvec_kernel<<<nb, 256, 0, q>>>(s, state, it, pcg_tol);
-                pcg_mb_update_kernel<<<nbu, 256, 0, q>>>(s, state, it);
-                continue;
-            }
-#endif
-            pcg_mb_step_kernel<<<nb, 256, 0, q>>>(s, state, it, pcg_tol);
-        }
+        for (int it = it0; it < it1; ++it) pcg_mb_step_kernel<<<nb, 256, 0, q>>>(s, state, it, pcg_tol);
         return hipGetLastError();
     };
-    const bool no_graph = dev_env("DFA_MB_NO_GRAPH") != nullptr;  // A/B (development builds)
-    if (!gc || gc->disabled || no_graph || it1 - it0 < 4) return direct(st);
+    if (!gc || gc->disabled || it1 - it0 < 4) return direct(st);
     MbGraphCache::Entry* hit = nullptr;
     for (int i = 0; i < gc->used && !hit; ++i) {
         MbGraphCache::Entry& c = gc->e[i];
@@ -2060,10 +1922,10 @@ static hipError_t launch_mb_pcg(const SolveView& s, SolveState* state, int max_i
                                 MbGraphCache* gc, hipStream_t st) {
     const int nb = solve_mb_blocks(s.D), nbu = (s.D + 255) / 256;
     pcg_mb_init_kernel<<<nbu, 256, 0, st>>>(s, state);
-    if (mb_one_launch()) pcg_mb_step_kernel<<<nb, 256, 0, st>>>(s, state, -1, pcg_tol);
+    pcg_mb_step_kernel<<<nb, 256, 0, st>>>(s, state, -1, pcg_tol);
     int chunk = 16;
     const int ci = gc ? std::min(gc->call++, 63) : 0;
-    if (mb_one_launch() && gc && host_flag && gc->pred[ci] > 0) chunk = std::max(8, (gc->pred[ci] + 4 + 7) & ~7);
+    if (gc && host_flag && gc->pred[ci] > 0) chunk = std::max(8, (gc->pred[ci] + 4 + 7) & ~7);
     for (int it = 0; it < max_iter;) {
         const int end = host_flag ? std::min(max_iter, it + chunk) : max_iter;
         {
@@ -2071,7 +1933,7 @@ static hipError_t launch_mb_pcg(const SolveView& s, SolveState* state, int max_i
             if (e != hipSuccess) return e;
             it = end;
         }
-        if (mb_one_launch() && host_flag && it < max_iter) {
+        if (host_flag && it < max_iter) {
             // step `it` first evaluates the stopping rule on the residual the chunk left, then iterates
             pcg_mb_step_kernel<<<nb, 256, 0, st>>>(s, state, it, pcg_tol);
             // mb_done, converged, mb_skip, mb_iters
@@ -2082,22 +1944,7 @@ static hipError_t launch_mb_pcg(const SolveView& s, SolveState* state, int max_i
             if (*host_flag) break;
             ++it;
             chunk = 16;  // the prediction fell short: go on in small chunks
-            continue;
         }
-#ifdef DFA_DEV_AB
-        if (host_flag && it < max_iter) {
-            // one more matvec launch evaluates the stopping rule on the last update's residual
-            pcg_mb_matvec_kernel<<<nb, 256, 0, st>>>(s, state, it, pcg_tol);
-            // mb_done and, directly behind it, converged (the caller stops launching Gauss-Newton iterations on it)
-            hipError_t e = hipMemcpyAsync(host_flag, &state->mb_done, 2 * sizeof(int), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return e;
-            if (*host_flag) break;
-            pcg_mb_update_kernel<<<nbu, 256, 0, st>>>(s, state, it);  // the matvec above was iteration `it`
-            ++it;
-            chunk *= 2;
-        }
-#endif
     }
     pcg_mb_finish_kernel<<<nbu, 256, 0, st>>>(s, state);
     return hipGetLastError();
@@ -2698,19 +2545,6 @@ static hipError_t allow_big_lds(Kernel* k) {
     return allow_dynamic_lds((const void*)k, 160 * 1024 - 1024);  // once per (device, kernel)
 }
 
-#ifdef DFA_DEV_AB
-// streaming kernel (matrix re-read from L2 every iteration): 1024 threads, RPT rows per thread
-template <int RPT>
-static hipError_t launch_streaming_pcg(const SolveView& s, SolveState* state, int max_iter, float pcg_tol,
-                                       hipStream_t st) {
-    hipError_t e = allow_big_lds(pcg_kernel<1024, RPT>);
-    if (e != hipSuccess) return e;
-    const size_t shmem = sizeof(float4) * (size_t)s.Dpad + 32 * sizeof(float) + 260 * sizeof(int);
-    pcg_kernel<1024, RPT><<<1, 1024, shmem, st>>>(s, state, max_iter, pcg_tol);
-    return hipGetLastError();
-}
-#endif  // DFA_DEV_AB
-
 // register-resident kernel: NT threads own 2*P*NT rows, P pairs of E matrix slots per thread
 // (NC = 3: one workgroup for the joint system; NC = 1: three workgroups, one coordinate each)
 template <int NT, int P, int E, int NC>
@@ -2723,53 +2557,28 @@ static hipError_t launch_paired_pcg(const SolveView& s, SolveState* state, int m
     return hipGetLastError();
 }
 
-#ifdef DFA_DEV_AB
-static void sync_floor_switch() {
-    static int done = -1;
-    const int want = dev_env("DFA_PCG_NO_SOLVE_FLOOR") ? 1 : 0;
-    if (done != want) {
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_floor_off), &want, sizeof(int));
-        done = want;
-    }
-}
-#endif
-
 // The PCG of one linearisation.  Up to 2 048 nodes: the register-resident kernel, one workgroup per coordinate (a system
 // that does not fit the registers is streamed inside the same launch); above: the many-workgroup PCG, which reads the
 // assembled ELL directly (the single-workgroup streaming kernel spends ~1 ms per launch sorting and repacking the matrix
 // by itself at 8 k nodes).
-// Development builds (-DDFA_DEV_AB) also hold the kernels this routing was measured against, selected by
-// DFA_PCG_VARIANT (read at every call: the tests switch it): 0 streaming, 1 register-resident with the three coordinates
-// in ONE workgroup (shared CG scalars, as the oracle), 2 / 5 its 512-thread flavours, 3 many-workgroup at any size,
-// 4 streaming up to 8 192 nodes.
+// Development builds (-DDFA_DEV_AB) also hold the forms the tests compare against, selected by DFA_PCG_VARIANT (read at
+// every call: the tests switch it): 1 register-resident with the three coordinates in ONE workgroup (shared CG scalars,
+// as the oracle), 3 many-workgroup at any size.
 static hipError_t route_pcg(const SolveView& s, SolveState* state, int max_iter, float pcg_tol, int* host_flag, MbGraphCache* gc,
                             TeamPcg* team, hipEvent_t& main_done, hipStream_t st) {
     const int D = s.D;
 #ifdef DFA_DEV_AB
-    sync_floor_switch();
     const int v2 = dev_env_int("DFA_PCG_VARIANT", -1);
     if (dev_env_int("DFA_MB_TEAM", 1) == 2 && team && team->ctl && !team->disabled && solve_team_pcg_fits(D) && max_iter < TEAM_ROUNDS &&
         !(team->host_abort && *(volatile int*)team->host_abort != 0))
         return launch_team_pcg(s, state, max_iter, pcg_tol, team, st);
     if (v2 == 3) return launch_mb_pcg(s, state, max_iter, pcg_tol, host_flag, gc, st);
-    if (D <= 2048 && v2 != 0) {
-        // 512 threads leave 256 VGPRs per lane (64 slots per row pair: k = 8 rows fit), 1024 threads 128 VGPRs (32 slots: k = 4)
-        if (D <= 1024 && v2 == 1) return launch_paired_pcg<512, 1, 64, 3>(s, state, max_iter, pcg_tol, st);
-        if (D <= 1024) return launch_paired_pcg<512, 1, 64, 1>(s, state, max_iter, pcg_tol, st);
-        if (v2 == 2) return launch_paired_pcg<512, 2, 32, 3>(s, state, max_iter, pcg_tol, st);
-        if (v2 == 1) return launch_paired_pcg<1024, 1, 32, 3>(s, state, max_iter, pcg_tol, st);
-        if (v2 == 5) return launch_paired_pcg<512, 2, 32, 1>(s, state, max_iter, pcg_tol, st);
-        return launch_paired_pcg<1024, 1, 32, 1>(s, state, max_iter, pcg_tol, st);
-    }
-    if (D <= 1024) return launch_streaming_pcg<1>(s, state, max_iter, pcg_tol, st);
-    if (D <= 2048) return launch_streaming_pcg<2>(s, state, max_iter, pcg_tol, st);
-    if (v2 == 4 && D <= 4096) return launch_streaming_pcg<4>(s, state, max_iter, pcg_tol, st);
-    if (v2 == 4 && D <= 8192) return launch_streaming_pcg<8>(s, state, max_iter, pcg_tol, st);
-#else
+    if (v2 == 1 && D <= 1024) return launch_paired_pcg<512, 1, 64, 3>(s, state, max_iter, pcg_tol, st);
+    if (v2 == 1 && D <= 2048) return launch_paired_pcg<1024, 1, 32, 3>(s, state, max_iter, pcg_tol, st);
+#endif
     // 512 threads leave 256 VGPRs per lane (64 slots per row pair: k = 8 rows fit), 1024 threads 128 VGPRs (32 slots: k = 4)
     if (D <= 1024) return launch_paired_pcg<512, 1, 64, 1>(s, state, max_iter, pcg_tol, st);
     if (D <= 2048) return launch_paired_pcg<1024, 1, 32, 1>(s, state, max_iter, pcg_tol, st);
-#endif
     // (development builds: DFA_MB_TEAM=0 the launched form, =2 the team form at any size)
     if (team && team->ctl && !team->disabled && solve_team_pcg_fits(D) && max_iter < TEAM_ROUNDS && dev_env_int("DFA_MB_TEAM", 1) != 0) {
         // a team that gave up in an earlier launch (placement, starvation, a row too long) has said so in pinned memory: from

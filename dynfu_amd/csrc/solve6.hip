@@ -30,7 +30,6 @@
 #include <cstdlib>
 
 #include "dq_device.hpp"
-#include "dev_switch.hpp"
 #include "kernels.hpp"
 #include "solve.hpp"
 #include "solve6.hpp"
@@ -913,9 +912,6 @@ __global__ __launch_bounds__(256) void s6_rslot_kernel(Solve6View s) {
 constexpr int S6_MAXSLOT = S6_MAXSLOT_PATTERN;  // = plan capacity of a block row
 
 typedef float v2f __attribute__((ext_vector_type(2)));
-#ifndef DFA_S6_ABLATE
-#define DFA_S6_ABLATE 0  // development builds only (-DDFA_S6_ABLATE=mask): 1 no record walk, 4 no off-diagonal epilogue, 8 contiguous rows
-#endif
 
 // Fourth form (round 3).  The third form (a quad of lanes owned a unit's 8 x 8 moment, 16 records per wave instruction) was
 // bound by instruction ISSUE, not by memory or LDS: SQ counters at C3 gave 22 k vector instructions per workgroup of which
@@ -947,9 +943,7 @@ __host__ __device__ constexpr int s6_sym(int i, int j) {
     return 20 + 2 * (t == 0 ? 0 : t == 1 ? 3 : 5) + (j - i - 1);
 }
 
-#ifndef DFA_S6_WAVES
-#define DFA_S6_WAVES 4  // waves per SIMD the register allocation aims at (four workgroups per CU by LDS: <= 128 VGPRs, 3-4 spilled)
-#endif
+constexpr int S6_ASM_WAVES = 4;  // waves per SIMD the register allocation aims at (four workgroups per CU by LDS: <= 128 VGPRs, 3-4 spilled)
 #ifdef DFA_S6_DEBUG
 __device__ float s6_dbg[256 * (S6_MAXSLOT * 36 + 8)];
 extern "C" __attribute__((visibility("default"))) int dfa_dev_s6_moments(float* out) {
@@ -967,8 +961,8 @@ constexpr size_t s6_assemble_lds(int K, int RC) {  // dynamic segment: the stage
     return rows > closing ? rows : closing;
 }
 template <int K, int S6_RC, bool KEXACT>  // KEXACT: k == K (the common case: divisions by k are shifts)
-__global__ __launch_bounds__(256, DFA_S6_WAVES) void s6_assemble2_kernel(Solve6View s, Solve6State* st, float wreg2, float damping,
-                                                                         const S6Forcing forcing, int xcd_map) {
+__global__ __launch_bounds__(256, S6_ASM_WAVES) void s6_assemble2_kernel(Solve6View s, Solve6State* st, float wreg2, float damping,
+                                                                         const S6Forcing forcing) {
     extern __shared__ __attribute__((aligned(16))) char s6_dyn[];
     // a staged row = the vertex's record as s6_linearise wrote it: l = (lW, lD) (32 bytes) | h_j = sqrt(rho) f_j, j < K |
     // sqrt(rho) r, -, -, - : RS bytes, in the order of the 16-byte chunks the row is fetched in (the LDS-DMA writes a wave's 64
@@ -989,15 +983,9 @@ __global__ __launch_bounds__(256, DFA_S6_WAVES) void s6_assemble2_kernel(Solve6V
     __shared__ uint32_t bfirst[S6_MAXSLOT];  // first unit | units << 16 of every block that has units
     // (workgroup -> node in launch order.  Consecutive nodes on one XCD — node (b mod 8) D / 8 + b / 8 for workgroup b, so that
     // a vertex record is fetched into one L2 instead of up to k — measured 0.048 against 0.050 ms at C2 and 0.156 against
-    // 0.150 at C3: not kept.)
-    int a = blockIdx.x;
+    // 0.150 at C3: not kept, profiles/r06_xcd_map.md.)
+    const int a = blockIdx.x;
     const int tid = threadIdx.x, k = s.k;
-#ifdef DFA_DEV_AB  // DFA_XCD_MAP=1: the experiment above, kept for its counters (profiles/r06_xcd_map.md)
-    if (xcd_map && a < s.D && (s.D & 7) == 0) {
-        a = (a & 7) * (s.D >> 3) + (a >> 3);           // a contiguous eighth of the order per XCD ...
-        if (xcd_map == 2 && s.xcd_perm) a = s.xcd_perm[a];  // ... of the Morton order of the node positions
-    }
-#endif
     if (a == s.D) {  // one workgroup more than nodes: the energy of the linearisation this launch follows, the state block's bookkeeping
         if (forcing.decided) return;  // (the linearisation's last workgroup has done both)
         s6_cost_total(s, st);
@@ -1108,11 +1096,7 @@ __global__ __launch_bounds__(256, DFA_S6_WAVES) void s6_assemble2_kernel(Solve6V
 #pragma unroll
         for (int q = 0; q < NCH; ++q) {
             const unsigned i = tl + 256u * q, r = i / (unsigned)RS4, c = i - (unsigned)RS4 * r;
-#if DFA_S6_ABLATE & 8
-            const size_t v = (e0 + r) % (size_t)s.N + 0 * ens[q];  // (timing only: contiguous rows instead of the gather)
-#else
             const size_t v = KEXACT ? ens[q] / (unsigned)K : ens[q] / (unsigned)k;  // (K: a shift)
-#endif
             const float4* src = reinterpret_cast<const float4*>(s.rec + (12 + K) * v) + c;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)(s6_dyn + 16 * (256 * q + 64 * wave)), 16, 0, 0);
@@ -1123,7 +1107,6 @@ __global__ __launch_bounds__(256, DFA_S6_WAVES) void s6_assemble2_kernel(Solve6V
         S6_TICK(tp1);
         S6_TICK(tp2);
         // ---- the records of this pass: a lane takes its unit's records while their rows are staged (the lists ascend)
-#if !(DFA_S6_ABLATE & 1)
         {
             bool act       = uhas && ucur < uend;
             const bool gw  = __any(uown);  // (this wave has units of slot 0)
@@ -1176,7 +1159,6 @@ __global__ __launch_bounds__(256, DFA_S6_WAVES) void s6_assemble2_kernel(Solve6V
                 walk_batch();
             }
         }
-#endif
 #pragma unroll
         for (int q = 0; q < EPT; ++q) {
             const int r = tid + 256 * q;
@@ -1302,11 +1284,7 @@ __global__ __launch_bounds__(256, DFA_S6_WAVES) void s6_assemble2_kernel(Solve6V
     // A QUAD of lanes per (block, row), ten blocks (240 threads) per round: lane z takes columns 2 z, 2 z + 1 of M_a S and every
     // fourth regularisation edge, the four partial rows are added by DPP.  (One thread per (block, row) — 102 of the 256 at C3 —
     // walked 112 FMAs, ~90 LDS reads and both edge loops alone: 7 of the workgroup's 42 us.)
-#if DFA_S6_ABLATE & 4
-    const int nfin = 1;
-#else
     const int nfin = 1 + nup;
-#endif
     constexpr int BPR = 10;
     float* ttile = reinterpret_cast<float*>(s6_dyn) + S6_MAXSLOT * 48;  // BPR x 36 floats behind M (the units' moments are dead)
     auto quad_sum = [](float x) __attribute__((always_inline)) {
@@ -1449,10 +1427,8 @@ __global__ __launch_bounds__(256, DFA_S6_WAVES) void s6_assemble2_kernel(Solve6V
 // the same launch: the gather rebuilds it from u_i, m_i, t_{i-1} and the two scalars (18 floats per
 // neighbour block next to the block's own 36).  Same iterates as textbook PCG in exact arithmetic.
 // launch `it` = -1: w_0 = A u_0, m_0, gamma_0, delta_0.   launch it >= 0: iteration `it` as above.
-#ifndef DFA_S6_PCG_WAVES
-#define DFA_S6_PCG_WAVES 5
-#endif
-__global__ __launch_bounds__(64 * S6_NODES_PER_BLOCK, DFA_S6_PCG_WAVES) void s6_pcg_step_kernel(Solve6View s, Solve6State* st, int it) {
+constexpr int S6_PCG_WAVES = 5;  // waves per SIMD the register allocation aims at
+__global__ __launch_bounds__(64 * S6_NODES_PER_BLOCK, S6_PCG_WAVES) void s6_pcg_step_kernel(Solve6View s, Solve6State* st, int it) {
     __shared__ float stage[S6_NODES_PER_BLOCK][3][64];
     __shared__ float gd_sh[S6_NODES_PER_BLOCK][2];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1843,10 +1819,7 @@ hipError_t s6_assemble(const Solve6View& s, Solve6State* state, const Solve6Para
     const float wreg2 = p.lambda / ((float)s.D * (float)s.k);
     const S6Forcing f = s6_forcing(p, gn_in_outer);
     {
-        // rows staged per pass (development builds: DFA_S6_RC for A/B): what fits in 28 KiB — with the static arrays 36 KiB,
-        // four workgroups per CU
-        static const int rc_env = dev_env_int("DFA_S6_RC", 0);
-        const int rc = rc_env ? rc_env : (s.k <= 4 ? 448 : 352);
+        // rows staged per pass: what fits in 28 KiB — with the static arrays 36 KiB, four workgroups per CU
 #define S6A2(KK, RC)                                                                                              \
     do {                                                                                                          \
         if (s.k == (KK)) S6A2X(KK, RC, true);                                                                     \
@@ -1859,15 +1832,10 @@ hipError_t s6_assemble(const Solve6View& s, Solve6State* state, const Solve6Para
             const hipError_t ae = allow_dynamic_lds((const void*)s6_assemble2_kernel<KK, RC, EX>, (int)sh);         \
             if (ae != hipSuccess) return ae;                                                                      \
         }                                                                                                         \
-        s6_assemble2_kernel<KK, RC, EX><<<s.D + 1, 256, sh, st>>>(s, state, wreg2, p.damping, f, dev_env_int("DFA_XCD_MAP", 0)); \
+        s6_assemble2_kernel<KK, RC, EX><<<s.D + 1, 256, sh, st>>>(s, state, wreg2, p.damping, f);                         \
     } while (0)
-        if (s.k <= 4) {
-            if (rc <= 320) S6A2(4, 320);
-            else S6A2(4, 448);
-        } else {
-            if (rc <= 256) S6A2(8, 256);
-            else S6A2(8, 352);
-        }
+        if (s.k <= 4) S6A2(4, 448);
+        else S6A2(8, 352);
 #undef S6A2
 #undef S6A2X
     }

@@ -85,9 +85,6 @@ struct IntegrateArgs {
     uint8_t* occ;  // occupancy map (kernels.hpp: OccDims) or null
     int ox, oy;
     int occ_known;  // fused sweep: the map describes the volume as it is NOW — a box without weights that gets none is not written
-    int chunk_rule;  // 1: a wave first asks whether its whole z chunk is skipped (tsdf_classify.hpp: chunk_skipped)
-    int nt;      // DFA_TSDF_NT=1 (A/B): non-temporal stores in the fused sweep
-    int ablate;  // -DDFA_DEV_ABLATE builds only (DFA_TSDF_ABLATE): 1 every run SKIP, 2 FULL runs filled like FRONT, 3 no classification
 };
 
 // x / z and y / z, correctly rounded.  hipcc expands an fp32 division into
@@ -170,90 +167,45 @@ __device__ __forceinline__ uint32_t integrate_voxel(const IntegrateArgs& a, f3 v
     return voxel_update<FUSED_CLEAR>(a, old, tsdf);
 }
 
-template <int VX>
-struct VoxVec;
-template <>
-struct VoxVec<4> {
-    uint4 v;
-    __device__ __forceinline__ uint32_t get(int i) const { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
-    __device__ __forceinline__ void set(int i, uint32_t x) {
-        if (i == 0) v.x = x;
-        else if (i == 1) v.y = x;
-        else if (i == 2) v.z = x;
-        else v.w = x;
-    }
-    __device__ __forceinline__ void load(const uint32_t* p) { v = *(const uint4*)p; }
-    __device__ __forceinline__ void store(uint32_t* p) const { *(uint4*)p = v; }
-    __device__ __forceinline__ void zero() { v = make_uint4(0u, 0u, 0u, 0u); }
-};
-template <>
-struct VoxVec<1> {
-    uint32_t v;
-    __device__ __forceinline__ uint32_t get(int) const { return v; }
-    __device__ __forceinline__ void set(int, uint32_t x) { v = x; }
-    __device__ __forceinline__ void load(const uint32_t* p) { v = *p; }
-    __device__ __forceinline__ void store(uint32_t* p) const { *p = v; }
-    __device__ __forceinline__ void zero() { v = 0u; }
-};
-
-// block = (64, 4): a wave spans 64*VX voxels in x, the block 4 rows in y; grid.z = z chunks.
-template <bool FUSED_CLEAR, int VX>
+// block = (64, 4): a wave spans 64 voxels in x, the block 4 rows in y; grid.z = z chunks.
+template <bool FUSED_CLEAR>
 __global__ __launch_bounds__(256) void integrate_kernel(const IntegrateArgs a) {
-    const int x0 = (blockIdx.x * 64 + threadIdx.x) * VX;
-    const int y  = blockIdx.y * 4 + threadIdx.y;
-    if (x0 >= a.X || y >= a.Y) return;
+    const int x = blockIdx.x * 64 + threadIdx.x;
+    const int y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= a.X || y >= a.Y) return;
     const int z0 = blockIdx.z * a.zchunk;
     const int z1 = min(z0 + a.zchunk, a.Z);
 
     // :58
     const f3 zstep = mk3(a.vol2cam.m[2], a.vol2cam.m[5], a.vol2cam.m[8]) * a.vsz;
     const f3 t     = mk3(a.vol2cam.t[0], a.vol2cam.t[1], a.vol2cam.t[2]);
-    f3 vc[VX];
-#pragma unroll
-    for (int v = 0; v < VX; ++v) {
-        const f3 vx = mk3((float)(x0 + v) * a.vsx, (float)y * a.vsy, 0.f);  // :60
-        vc[v]       = mulR(a.vol2cam, vx) + t;                              // :61
-    }
+    const f3 vx    = mk3((float)x * a.vsx, (float)y * a.vsy, 0.f);  // :60
+    f3 vc          = mulR(a.vol2cam, vx) + t;                        // :61
     // replay the z0 running additions of :64 so the chunk starts on the reference's value
-    for (int i = 0; i < z0; ++i) {
-#pragma unroll
-        for (int v = 0; v < VX; ++v) vc[v] = vc[v] + zstep;
-    }
+    for (int i = 0; i < z0; ++i) vc = vc + zstep;
 
     const size_t slice = (size_t)a.X * a.Y;
-    uint32_t* ptr      = a.vol + (size_t)x0 + (size_t)a.X * y + slice * z0;
+    uint32_t* ptr      = a.vol + (size_t)x + (size_t)a.X * y + slice * z0;
 
     constexpr int U = 4;  // slices in flight per lane
     int z           = z0;
     for (; z + U <= z1; z += U, ptr += slice * U) {
-        VoxVec<VX> cur[U];
+        uint32_t cur[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (FUSED_CLEAR) cur[u].zero();
-            else cur[u].load(ptr + slice * u);
-        }
+        for (int u = 0; u < U; ++u) cur[u] = FUSED_CLEAR ? 0u : ptr[slice * u];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             bool changed = FUSED_CLEAR;  // the fused sweep writes every voxel
-#pragma unroll
-            for (int v = 0; v < VX; ++v) {
-                cur[u].set(v, integrate_voxel<FUSED_CLEAR>(a, vc[v], cur[u].get(v), changed));
-                vc[v] = vc[v] + zstep;  // :64, also for skipped voxels
-            }
-            if (changed) cur[u].store(ptr + slice * u);
+            cur[u]       = integrate_voxel<FUSED_CLEAR>(a, vc, cur[u], changed);
+            vc           = vc + zstep;  // :64, also for skipped voxels
+            if (changed) ptr[slice * u] = cur[u];
         }
     }
     for (; z < z1; ++z, ptr += slice) {
-        VoxVec<VX> cur;
-        if (FUSED_CLEAR) cur.zero();
-        else cur.load(ptr);
-        bool changed = FUSED_CLEAR;
-#pragma unroll
-        for (int v = 0; v < VX; ++v) {
-            cur.set(v, integrate_voxel<FUSED_CLEAR>(a, vc[v], cur.get(v), changed));
-            vc[v] = vc[v] + zstep;
-        }
-        if (changed) cur.store(ptr);
+        bool changed     = FUSED_CLEAR;
+        const uint32_t v = integrate_voxel<FUSED_CLEAR>(a, vc, FUSED_CLEAR ? 0u : *ptr, changed);
+        vc               = vc + zstep;
+        if (changed) *ptr = v;
     }
 }
 
@@ -265,7 +217,7 @@ __global__ __launch_bounds__(256) void integrate_kernel(const IntegrateArgs a) {
 // skipped, 10 % are in front of the surface, 7 % take the per-voxel path; a wave does when one of its lanes does.
 //   * fused clear + integrate: skipped runs store zeros, front runs a constant — the sweep becomes a store stream;
 //   * read + write sweep: skipped runs touch no memory at all.
-// A wave covers WX x (64 / WX) columns, a block 64 x 4.  Measured (tools/tsdf_sweep.py, fused sweep, 512^3 / 1024^3):
+// A wave covers 32 x 2 columns, a block 64 x 4.  Measured (wave shapes and run lengths of earlier trees, fused sweep, 512^3 / 1024^3):
 //   per-voxel kernel 0.222 / 1.174 ms; U = 4, WX = 64: 0.157 / 0.883; U = 8, WX = 64: 0.137 / 0.825;
 //   U = 8, WX = 32: 0.117 / 0.721 (128-byte row segments, and lanes that agree more often: 14 % instead of 19 % of
 //   the wave runs hold a lane on the per-voxel path); U = 8, WX = 16: 0.161 / 1.236 (64-byte segments: half cache
@@ -296,9 +248,10 @@ __global__ __launch_bounds__(256) void dists_tiles_kernel(const uint16_t* __rest
     if (lane == 0) tiles[tile] = lo | (hi << 16);
 }
 
-template <bool FUSED_CLEAR, int WX, int U>
+template <bool FUSED_CLEAR>
 __global__ __launch_bounds__(256) void integrate_runs_kernel(const IntegrateArgs a, const RunConsts rc, const RunConsts rcc,
                                                              const uint32_t front_const) {
+    constexpr int WX = 32, U = RUN_U;  // a wave = 32 x 2 voxel columns, runs of RUN_U voxels
     const int lane  = threadIdx.x, wave = threadIdx.y;  // block (64, 4)
     // the block's 64 x 4 columns, WX x (64 / WX) per wave: waves side by side in x, then stacked in y
     constexpr int WAVES_X = 64 / WX, WAVE_ROWS = 64 / WX;
@@ -312,14 +265,13 @@ __global__ __launch_bounds__(256) void integrate_runs_kernel(const IntegrateArgs
     const f3 vx    = mk3((float)x * a.vsx, (float)y * a.vsy, 0.f);                                   // :60
     f3 vc          = mulR(a.vol2cam, vx) + mk3(a.vol2cam.t[0], a.vol2cam.t[1], a.vol2cam.t[2]);      // :61
     // (all of a chunk's map bytes up front, as a bit mask: a load per run in front of the decision is a memory round trip per run)
-    constexpr int WAVE_ROWS_ = 64 / WX;
     const size_t occ_layer = (size_t)a.ox * a.oy;
     // bit r of (clean_hi : clean): the box of the chunk's r-th run held zeros on entry (fused sweep over a known map); 128 runs
     // are a whole column of a 1024^3 volume, runs beyond are not known to be clean
     unsigned long long clean = 0ull, clean_hi = 0ull;
     const int nruns          = (z1 - z0) / U;
     if (FUSED_CLEAR && a.occ && a.occ_known) {
-        const uint8_t* occ_old = a.occ + (size_t)(x / WX) + (size_t)a.ox * ((size_t)(y / WAVE_ROWS_) + (size_t)a.oy * (size_t)(z0 / U));
+        const uint8_t* occ_old = a.occ + (size_t)(x / WX) + (size_t)a.ox * ((size_t)(y / WAVE_ROWS) + (size_t)a.oy * (size_t)(z0 / U));
 #pragma unroll 8
         for (int r = 0; r < min(nruns, 64); ++r) clean |= (unsigned long long)(occ_old[(size_t)r * occ_layer] == 0) << r;
 #pragma unroll 8
@@ -329,8 +281,7 @@ __global__ __launch_bounds__(256) void integrate_runs_kernel(const IntegrateArgs
     // half of a volume lies outside the frustum — there is nothing to classify or replay; the accumulating sweep leaves such
     // voxels alone anyway, the fused sweep may when the map says they are zeros already (and the chunk has no tail).
     auto ones = [](int n) { return n >= 64 ? ~0ull : n <= 0 ? 0ull : (1ull << n) - 1ull; };
-    if (a.chunk_rule && (!FUSED_CLEAR || (a.occ && a.occ_known && nruns <= 128 && nruns * U == z1 - z0 && clean == ones(nruns) &&
-                                          clean_hi == ones(nruns - 64)))) {
+    if (!FUSED_CLEAR || (a.occ && a.occ_known && nruns <= 128 && nruns * U == z1 - z0 && clean == ones(nruns) && clean_hi == ones(nruns - 64))) {
         const float zs[3] = {zstep.x, zstep.y, zstep.z};
         const bool skip   = chunk_skipped(vc.x, vc.y, vc.z, zs, z0, z1, rcc, rcp_approx, half_bits_to_float_u);
         if (__ballot(!skip) == 0ull) return;  // (a skipped chunk leaves the map's bytes as they are: nothing gained a weight)
@@ -344,7 +295,7 @@ __global__ __launch_bounds__(256) void integrate_runs_kernel(const IntegrateArgs
     int z      = z0;
     RunEnd end = run_end(vc.x, vc.y, vc.z, rc, rcp_approx);
     // occupancy map: a byte per (this wave's WX x (64 / WX) columns) x (run of 8 slices) — the launcher passes it only for
-    // WX = 32, U = 8 and chunks that start on a multiple of 8.  Written by the first live lane of the wave.
+    // chunks that start on a multiple of 8.  Written by the first live lane of the wave.
     uint8_t* occ_cell = nullptr;
     if (a.occ) {
         const unsigned long long live = __ballot(1);
@@ -358,22 +309,9 @@ __global__ __launch_bounds__(256) void integrate_runs_kernel(const IntegrateArgs
         const bool was_clean = (clean & 1ull) != 0ull;
         clean = (clean >> 1) | (clean_hi << 63), clean_hi >>= 1;
         const f3 far     = vc + stepU;
-        int cls          = RUN_SKIP;
-#ifdef DFA_DEV_ABLATE
-        if (a.ablate != 3) {
-            const RunEnd nxt = run_end(far.x, far.y, far.z, rc, rcp_approx);
-            cls              = classify_run(end, nxt, rc, half_bits_to_float_u);
-            end              = nxt;
-            if (a.ablate == 1) cls = RUN_SKIP;
-            if (a.ablate == 2 && cls == RUN_FULL) cls = RUN_FRONT;
-        }
-#else
-        {
-            const RunEnd nxt = run_end(far.x, far.y, far.z, rc, rcp_approx);
-            cls              = classify_run(end, nxt, rc, half_bits_to_float_u);
-            end              = nxt;
-        }
-#endif
+        const RunEnd nxt = run_end(far.x, far.y, far.z, rc, rcp_approx);
+        const int cls    = classify_run(end, nxt, rc, half_bits_to_float_u);
+        end              = nxt;
         bool untouched = false;  // (wave-uniform) a box of zeros that stays one
         if (a.occ) {  // (uniform) bit 0: a run of the box was not SKIP (SKIP runs are the only ones that leave, or find, no
                       // weight); bit 1: a run was FULL — the only runs that can leave a NEGATIVE distance (FRONT runs write +1)
@@ -402,13 +340,8 @@ __global__ __launch_bounds__(256) void integrate_runs_kernel(const IntegrateArgs
                     out[u] = integrate_voxel<true>(a, p[u], 0u, changed);
                 }
             }
-            if (a.nt) {
 #pragma unroll
-                for (int u = 0; u < U; ++u) __builtin_nontemporal_store(out[u], ptr + slice * u);
-            } else {
-#pragma unroll
-                for (int u = 0; u < U; ++u) ptr[slice * u] = out[u];
-            }
+            for (int u = 0; u < U; ++u) ptr[slice * u] = out[u];
         } else if (cls != RUN_SKIP) {
             uint32_t cur[U];
 #pragma unroll
@@ -554,10 +487,7 @@ __device__ __forceinline__ f3 compute_normal(const RaycastArgs& a, f3 p, RayTall
 
 // march steps whose voxels are requested together (measured at 512^3 / VGA and 1024^3 / 720p: 1 step 0.082 / 0.219 ms,
 // 2: 0.063 / 0.158, 4: 0.057 / 0.140, 6: 0.060 / 0.143, 8: 0.062 / 0.148 in the first batched form)
-#ifndef DFA_RAY_BATCH  // (compile-time A/B: tools/ab_variant.sh rb8 tsdf.hip -DDFA_RAY_BATCH=8)
-#define DFA_RAY_BATCH 4
-#endif
-constexpr int RAY_BATCH = DFA_RAY_BATCH;
+constexpr int RAY_BATCH = 4;
 
 // shared body of the two TsdfRaycaster::operator() overloads (:195-318)
 template <bool TALLY = false, bool IDX32 = false>
@@ -740,13 +670,12 @@ hipError_t launch_compute_dists(const uint16_t* depth, int depth_step, uint16_t*
     return launch_status();
 }
 
-static int pick_zchunk(int X, int Y, int Z, int vx, bool fused_clear);
+static int pick_zchunk(int X, int Y, int Z, bool fused_clear);
 
 hipError_t launch_tsdf_clear(uint32_t* vol, int X, int Y, int Z, hipStream_t s) {
     const size_t n = (size_t)X * Y * Z;
-    const bool linear = dev_env("DFA_TSDF_CLEAR_LINEAR") != nullptr;  // A/B (development builds): the grid-stride 16-byte stores
-    if (!linear && X % 64 == 0 && Z >= 32 && (((uintptr_t)vol & 255) == 0)) {
-        const int zchunk = pick_zchunk(X, Y, Z, 1, true);
+    if (X % 64 == 0 && Z >= 32 && (((uintptr_t)vol & 255) == 0)) {
+        const int zchunk = pick_zchunk(X, Y, Z, true);
         dim3 block(64, 4), grid(X / 64, (Y + 3) / 4, (Z + zchunk - 1) / zchunk);
         clear_columns_kernel<<<grid, block, 0, s>>>(vol, X, Y, Z, zchunk);
         return launch_status();
@@ -798,8 +727,8 @@ static hipError_t tile_scratch(hipStream_t s, size_t bytes, uint32_t** out) {
 
 // z-chunk heuristic: enough workgroups to fill 256 CUs several times over, while keeping the
 // replayed-additions prologue (z0 adds per chunk) a small fraction of a chunk's work.
-static int pick_zchunk(int X, int Y, int Z, int vx, bool fused_clear) {
-    const long columns_wg = (long)((X + 64 * vx - 1) / (64 * vx)) * ((Y + 3) / 4);
+static int pick_zchunk(int X, int Y, int Z, bool fused_clear) {
+    const long columns_wg = (long)((X + 63) / 64) * ((Y + 3) / 4);
     int zchunk            = Z;
     // Chunks no shorter than 32 slices.  Measured with one voxel per lane (tools/tsdf_kernels.py): the read+write sweep
     // wants >= 16 workgroups per CU (512^3: 0.265 ms with 4 chunks, 0.386 unsplit); the fused sweep has no loads to hide
@@ -822,14 +751,10 @@ hipError_t launch_tsdf_integrate(bool fused_clear, const uint16_t* dists, int di
                                  uint8_t* occ, bool occ_known, hipStream_t s) {
     IntegrateArgs a;
     a.occ_known = occ && occ_known && fused_clear ? 1 : 0;
-    a.chunk_rule = 0;
     a.dists = dists, a.dists_step = dists_step, a.cols = cols, a.rows = rows;
     a.vol = vol, a.X = X, a.Y = Y, a.Z = Z;
     const OccDims od = occ_dims(X, Y, Z);
     a.occ = nullptr, a.ox = od.ox, a.oy = od.oy;
-    // a sweep that does not keep the map (the per-voxel sweeps below, other wave shapes / run lengths of development builds)
-    // marks everything: the map stays a superset of the voxels with a weight
-    auto occ_all = [&]() -> hipError_t { return occ ? hipMemsetAsync(occ, 3, od.bytes(), s) : hipSuccess; };
     a.vsx = voxel_size[0], a.vsy = voxel_size[1], a.vsz = voxel_size[2];
     a.trunc      = trunc_dist;
     a.trunc_inv  = 1.f / trunc_dist;  // tsdf_volume.cu:106
@@ -837,14 +762,8 @@ hipError_t launch_tsdf_integrate(bool fused_clear, const uint16_t* dists, int di
     for (int i = 0; i < 9; ++i) a.vol2cam.m[i] = vol2cam[i];
     for (int i = 0; i < 3; ++i) a.vol2cam.t[i] = vol2cam[9 + i];
     a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy;
-#ifdef DFA_DEV_ABLATE  // development builds only (-DDFA_DEV_ABLATE): values 1 / 2 write WRONG volumes by design
-    a.ablate = dev_env_int("DFA_TSDF_ABLATE", 0);
-#else
-    a.ablate = 0;
-#endif
-    a.nt     = dev_env_int("DFA_TSDF_NT", 0);
     // The run-classified sweep.  Development builds (-DDFA_DEV_AB): DFA_TSDF_LEGACY=1 runs the per-voxel sweep (every voxel
-    // through the projection; the round-1 kernel) for A/B timings, DFA_TSDF_WAVE=16 gives a wave a 16 x 4 patch of columns.
+    // through the projection; the round-1 kernel) for A/B timings.
     const bool legacy = dev_env("DFA_TSDF_LEGACY") != nullptr;
     if (!legacy) {
         const int tcols = (cols + 7) >> TSDF_TILE_SHIFT, trows = (rows + 7) >> TSDF_TILE_SHIFT;
@@ -861,70 +780,34 @@ hipError_t launch_tsdf_integrate(bool fused_clear, const uint16_t* dists, int di
         }
         const float zstep[3] = {vol2cam[2] * a.vsz, vol2cam[5] * a.vsz, vol2cam[8] * a.vsz};
         if (extent == extent && extent < 1e30f) {  // finite poses only; anything else takes the per-voxel sweep
-            const int run_u = dev_env_int("DFA_TSDF_RUN", RUN_U);
-            const RunConsts rc = make_run_consts(tiles, cols, rows, fx, fy, cx, cy, trunc_dist, zstep, run_u == 8 ? 8 : 4, extent);
+            const RunConsts rc = make_run_consts(tiles, cols, rows, fx, fy, cx, cy, trunc_dist, zstep, RUN_U, extent);
             const uint32_t front_const = 0x3c00u | ((uint32_t)(max_weight < 1 ? max_weight : 1) << 16);  // (1.0h, min(1, max_weight))
             // >= 4 096 workgroups for either sweep: the tile look-ups of a run are dependent loads that only occupancy
             // hides (512^3 fused: 0.147 ms unsplit = 1 024 workgroups, 0.117 ms with z-chunks of 128 slices)
-            a.zchunk = pick_zchunk(X, Y, Z, 1, false);
+            a.zchunk = pick_zchunk(X, Y, Z, false);
             if (occ) a.zchunk = (a.zchunk + 7) & ~7;  // chunks of whole runs: a byte of the map has one writer
+            a.occ = occ;
             dim3 block(64, 4), grid((X + 63) / 64, (Y + 3) / 4, (Z + a.zchunk - 1) / a.zchunk);
-#ifdef DFA_DEV_AB
-            if (occ && (dev_env_int("DFA_TSDF_WAVE", 32) != 32 || run_u != 8)) {
-                const hipError_t oe = occ_all();
-                if (oe != hipSuccess) return oe;
-            } else
-#endif
-                a.occ = occ;
-            // the chunk-level rule: margins of Z running additions (DFA_TSDF_NO_CHUNK_RULE=1 in development builds: A/B)
+            // the chunk-level rule: margins of Z running additions
             const RunConsts rcc = make_run_consts(tiles, cols, rows, fx, fy, cx, cy, trunc_dist, zstep, Z, extent);
-            a.chunk_rule = dev_env("DFA_TSDF_NO_CHUNK_RULE") ? 0 : 1;
-#define DFA_RUNS(F, W, UU) integrate_runs_kernel<F, W, UU><<<grid, block, 0, s>>>(a, rc, rcc, front_const)
-#ifdef DFA_DEV_AB
-            const int wave_x = dev_env_int("DFA_TSDF_WAVE", 32);
-#define DFA_RUNS_W(F, UU) (wave_x == 16 ? DFA_RUNS(F, 16, UU) : wave_x == 32 ? DFA_RUNS(F, 32, UU) : DFA_RUNS(F, 64, UU))
-            if (run_u != RUN_U) {
-                if (fused_clear) DFA_RUNS_W(true, RUN_U == 8 ? 4 : 8);
-                else DFA_RUNS_W(false, RUN_U == 8 ? 4 : 8);
-            } else {
-                if (fused_clear) DFA_RUNS_W(true, RUN_U);
-                else DFA_RUNS_W(false, RUN_U);
-            }
-#undef DFA_RUNS_W
-#else
-            static_assert(RUN_U == 8 || RUN_U == 4, "run length of the classified sweep");
-            if (fused_clear) DFA_RUNS(true, 32, RUN_U);  // a wave = 32 x 2 voxel columns, runs of RUN_U voxels
-            else DFA_RUNS(false, 32, RUN_U);
-#endif
-#undef DFA_RUNS
+            if (fused_clear) integrate_runs_kernel<true><<<grid, block, 0, s>>>(a, rc, rcc, front_const);
+            else integrate_runs_kernel<false><<<grid, block, 0, s>>>(a, rc, rcc, front_const);
             return launch_status();
         }
     }
-    // One voxel per lane.  Four consecutive voxels per lane (16-byte accesses; DFA_TSDF_VX4=1, the first design) lose
-    // everywhere: a lane then walks its four voxels one after the other, each with its own early exits, and a wave
-    // waits for its slowest lane four times per slice (fused sweep 0.289 -> 0.229 ms at 512^3, 1.49 -> 1.38 ms at
-    // 1024^3, 0.061 -> 0.044 ms at 256^3); a wave's 256-byte stores are wide enough for HBM.
-#ifdef DFA_DEV_AB
-    const bool vec4 = dev_env("DFA_TSDF_VX4") && (X % 4 == 0) && (((uintptr_t)vol & 15) == 0);
-#else
-    constexpr bool vec4 = false;
-#endif
-    const int vx    = vec4 ? 4 : 1;
-    {
-        const hipError_t oe = occ_all();
+    // One voxel per lane.  Four consecutive voxels per lane (16-byte accesses, the first design) lost everywhere: a lane
+    // then walks its four voxels one after the other, each with its own early exits, and a wave waits for its slowest
+    // lane four times per slice (fused sweep 0.289 -> 0.229 ms at 512^3, 1.49 -> 1.38 ms at 1024^3, 0.061 -> 0.044 ms
+    // at 256^3); a wave's 256-byte stores are wide enough for HBM.
+    // This sweep does not keep the occupancy map: it marks everything, so the map stays a superset of the voxels with a weight.
+    if (occ) {
+        const hipError_t oe = hipMemsetAsync(occ, 3, od.bytes(), s);
         if (oe != hipSuccess) return oe;
     }
-    a.zchunk        = pick_zchunk(X, Y, Z, vx, fused_clear);
-    dim3 block(64, 4), grid((X + 64 * vx - 1) / (64 * vx), (Y + 3) / 4, (Z + a.zchunk - 1) / a.zchunk);
-#ifdef DFA_DEV_AB
-    if (vec4) {
-        if (fused_clear) integrate_kernel<true, 4><<<grid, block, 0, s>>>(a);
-        else integrate_kernel<false, 4><<<grid, block, 0, s>>>(a);
-        return launch_status();
-    }
-#endif
-    if (fused_clear) integrate_kernel<true, 1><<<grid, block, 0, s>>>(a);
-    else integrate_kernel<false, 1><<<grid, block, 0, s>>>(a);
+    a.zchunk = pick_zchunk(X, Y, Z, fused_clear);
+    dim3 block(64, 4), grid((X + 63) / 64, (Y + 3) / 4, (Z + a.zchunk - 1) / a.zchunk);
+    if (fused_clear) integrate_kernel<true><<<grid, block, 0, s>>>(a);
+    else integrate_kernel<false><<<grid, block, 0, s>>>(a);
     return launch_status();
 }
 

@@ -1003,8 +1003,7 @@ hipError_t point_grid_build(const PointGridView& pg, const float* pts, int n, hi
 }
 
 hipError_t knn_grid_build(const KnnGridView& g, const float* node_pos, int D, hipStream_t s) {
-    const bool four = dev_env("DFA_GRID_FOUR_KERNELS") != nullptr;  // A/B (development builds): the four-kernel build below 2 048 nodes
-    if (D <= GRID_ONE_MAX && !four) {
+    if (D <= GRID_ONE_MAX) {
         constexpr size_t lds = sizeof(int32_t) * KNN_GRID_MAX_CELLS;
         // 128 KiB of dynamic LDS needs the opt-in, once per device
         hipError_t e = allow_dynamic_lds((const void*)grid_build_one_kernel, (int)lds);

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds dynfu_amd/build/libdynfu_amd_<tag>.so with one source (or `all`) recompiled under extra flags (compile-time A/B):
-#   bash tools/ab_variant.sh rb8 tsdf.hip -DDFA_RAY_BATCH=8      then      DFA_LIB_PATH=dynfu_amd/build/libdynfu_amd_rb8.so python ...
+#   bash tools/ab_variant.sh s6t solve6.hip -DDFA_S6_TIMING      then      DFA_LIB_PATH=dynfu_amd/build/libdynfu_amd_s6t.so python ...
 #   bash tools/ab_variant.sh prof all -DDFA_PCG_PROFILE -DDFA_DEV_AB
 # Sources and flags come from dynfu_amd/build.py (one owner).
 set -e

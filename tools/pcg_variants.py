@@ -15,7 +15,7 @@ nodes, nw, ndq, verts = map(dev, (c["node_pos"], c["node_w"], c["node_dq"], c["v
 idx, w = A.knn(nodes, nw, verts, k)
 t_true = synth.true_translations(c["node_pos"], 3, k)
 live = dev(synth.live_vertices(c["verts"], idx.cpu().numpy(), w.cpu().numpy(), t_true))
-for variant in (None, "1", "3", "0"):
+for variant in (None, "1", "3"):
     if variant is None:
         os.environ.pop("DFA_PCG_VARIANT", None)
     else:

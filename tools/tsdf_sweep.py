@@ -1,5 +1,5 @@
 """dev tool: times the fused and the read+write TSDF sweep over the A/B switches of tsdf.hip in ONE process
-(DFA_TSDF_RUN / DFA_TSDF_WAVE / DFA_TSDF_ZCHUNK / DFA_TSDF_LEGACY / DFA_TSDF_ABLATE are read per call)."""
+(DFA_TSDF_LEGACY / DFA_TSDF_ZCHUNK are read per call): the per-voxel and the run-classified sweep, chunk lengths."""
 import os as _os
 _os.environ.setdefault("DFA_LIB_PATH", _os.path.join(_os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))), "dynfu_amd", "libdynfu_amd_dev.so"))  # the DFA_* switches exist in the development flavour only
 import itertools, os, sys
@@ -30,7 +30,7 @@ def timeit(fn):
 
 
 def variant(env):
-    for k in ("DFA_TSDF_RUN", "DFA_TSDF_WAVE", "DFA_TSDF_ZCHUNK", "DFA_TSDF_LEGACY", "DFA_TSDF_ABLATE"):
+    for k in ("DFA_TSDF_ZCHUNK", "DFA_TSDF_LEGACY"):
         os.environ.pop(k, None)
     os.environ.update({k: str(v) for k, v in env.items() if v is not None})
     f = timeit(lambda: A.tsdf_clear_integrate(vol, dists, voxel, trunc, 64, vol2cam, *intr))
@@ -39,9 +39,5 @@ def variant(env):
     print("%-60s fused %.4f ms (%.0f GB/s)   read+write %.4f ms" % (env, f, 4 * dim ** 3 / f / 1e6, r), flush=True)
 
 
-variant({"DFA_TSDF_LEGACY": 1})
-variant({"DFA_TSDF_LEGACY": 1, "DFA_TSDF_ZCHUNK": 128})
-variant({"DFA_TSDF_ABLATE": 3})
-variant({"DFA_TSDF_ABLATE": 3, "DFA_TSDF_ZCHUNK": 128})
-for u, w, zc in itertools.product((4, 8), (64, 32, 16), (None, 256, 128, 64)):
-    variant({"DFA_TSDF_RUN": u, "DFA_TSDF_WAVE": w, "DFA_TSDF_ZCHUNK": zc})
+for legacy, zc in itertools.product((1, None), (None, 256, 128, 64)):
+    variant({"DFA_TSDF_LEGACY": legacy, "DFA_TSDF_ZCHUNK": zc})
