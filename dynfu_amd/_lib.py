@@ -17,7 +17,8 @@ SYMBOLS = [
     "dfa_resize_depth_normals", "dfa_resize_points_normals",
     "dfa_compute_points_normals", "dfa_solver6_create", "dfa_solver6_destroy", "dfa_solver6_set_problem",
     "dfa_solver6_solve", "dfa_solver6_set_node_transforms", "dfa_solver6_node_dq", "dfa_solver6_warp", "dfa_solver6_get_stats",
-    "dfa_solver6_enable_timing", "dfa_solver6_get_timing",
+    "dfa_solver6_enable_timing", "dfa_solver6_get_timing", "dfa_solver6_matrix_blocks", "dfa_solver6_matrix_columns",
+    "dfa_solver6_matrix_row_blocks", "dfa_solver6_gradient", "dfa_solver6_step", "dfa_solver6_data_graph", "dfa_solver6_reg_graph",
     "dfa_solver_create", "dfa_solver_destroy", "dfa_solver_set_problem", "dfa_solver_solve", "dfa_solver_set_deterministic", "dfa_solver_matrix_entries", "dfa_solver_matrix_row_lengths", "dfa_solver_gradient",
     "dfa_solver_translations", "dfa_solver_node_dq", "dfa_solver_tukey_weights", "dfa_solver_huber_weights",
     "dfa_solver_data_graph", "dfa_solver_reg_graph", "dfa_solver_get_stats", "dfa_solver_enable_timing",
@@ -46,6 +47,7 @@ class Solve6Params(C.Structure):
 
 
 SOLVE6_HIST = 32  # DFA_SOLVE6_HIST
+SOLVE6_ROW_BLOCKS = 48  # DFA_SOLVE6_ROW_BLOCKS
 ABI_VERSION = 6   # DFA_ABI_VERSION
 
 
@@ -190,6 +192,10 @@ def load(path=None):
     L.dfa_solver6_get_stats.argtypes = [vp, C.POINTER(_Solve6Stats), vp]
     L.dfa_solver6_enable_timing.argtypes = [vp, i]
     L.dfa_solver6_get_timing.argtypes = [vp, C.POINTER(_Solve6Timing), vp]
+    for n in ("matrix_blocks", "matrix_columns", "matrix_row_blocks", "gradient", "step", "data_graph", "reg_graph"):
+        fn = getattr(L, "dfa_solver6_" + n)
+        fn.argtypes = [vp]
+        fn.restype = vp
     L.dfa_marching_cubes.argtypes = [vp, i, i, i, vp, vp, vp, vp, i, vp, vp]
     L.dfa_marching_cubes_occ.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, i, vp, vp]
     L.dfa_mc_default_tables.argtypes = [vp, vp]
@@ -777,6 +783,40 @@ class Solver6:
             __cuda_array_interface__ = dict(shape=(self.D, 8), typestr="<f4", data=(int(ptr), False), version=2)
 
         return torch.as_tensor(_Holder(), device="cuda").clone()
+
+    def _view(self, name, shape, dtype):
+        """Copy of a plan-owned device array as a torch tensor (zero-copy view, then clone)."""
+        torch = _torch()
+        n = 1
+        for d in shape:
+            n *= d
+        if n == 0:
+            return torch.empty(shape, dtype=dtype, device="cuda")
+        ptr = getattr(self._L, "dfa_solver6_" + name)(self._h)
+        typestr = {torch.float32: "<f4", torch.int32: "<i4"}[dtype]
+
+        class _Holder:
+            __cuda_array_interface__ = dict(shape=tuple(shape), typestr=typestr, data=(int(ptr), False), version=2)
+
+        return torch.as_tensor(_Holder(), device="cuda").clone()
+
+    def matrix(self):
+        """normal equations of the last Gauss-Newton iteration: (blocks (D, 48, 6, 6) float32 — slot 0 the damped diagonal,
+        then ascending columns —, columns (D, 48) int32, row blocks (D,) int32, gradient (D, 6) float32); slots past a row's
+        count are undefined"""
+        torch = _torch()
+        return (self._view("matrix_blocks", (self.D, SOLVE6_ROW_BLOCKS, 6, 6), torch.float32),
+                self._view("matrix_columns", (self.D, SOLVE6_ROW_BLOCKS), torch.int32),
+                self._view("matrix_row_blocks", (self.D,), torch.int32), self._view("gradient", (self.D, 6), torch.float32))
+
+    def step(self):
+        """(D, 6) twists (omega, v) the last PCG returned"""
+        return self._view("step", (self.D, 6), _torch().float32)
+
+    def graphs(self):
+        """(data graph (N, k) in the caller's vertex order, regularisation graph (D, k)), int32, -1 where empty"""
+        torch = _torch()
+        return self._view("data_graph", (self.N, self.k), torch.int32), self._view("reg_graph", (self.D, self.k), torch.int32)
 
     def warp(self, want_normals=True):
         torch = _torch()

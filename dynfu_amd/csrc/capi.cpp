@@ -1154,7 +1154,7 @@ int dfa_solver6_create(int max_D, int max_N, int k, dfa_solver6** out) {
     REQUIRE(s, "out of host memory");
     s->max_D = max_D, s->max_N = max_N, s->k = k, s->has_problem = false, s->node_dq = nullptr;
     std::memset(&s->v, 0, sizeof(s->v));
-    s->v.cap = 48;  // = S6_MAXSLOT of solve6.hip
+    s->v.cap = DFA_SOLVE6_ROW_BLOCKS;  // = S6_MAXSLOT of solve6.hip
     const size_t N = (size_t)max_N, D = (size_t)max_D, cap = (size_t)s->v.cap;
     int rc = DFA_OK;
 #define A(field, count) \
@@ -1456,6 +1456,14 @@ int dfa_solver6_get_timing(dfa_solver6* s, dfa_solve6_timing* out, dfa_stream_t 
 }
 
 const float* dfa_solver6_node_dq(const dfa_solver6* s) { return s ? s->v.dq : nullptr; }
+static_assert(DFA_SOLVE6_ROW_BLOCKS == dfa::S6_ROW_BLOCKS, "row capacity of the C ABI and of the plan (S6_MAXSLOT of solve6.hip)");
+const float* dfa_solver6_matrix_blocks(const dfa_solver6* s) { return s ? s->v.bvals : nullptr; }
+const int32_t* dfa_solver6_matrix_columns(const dfa_solver6* s) { return s ? s->v.bcols : nullptr; }
+const int32_t* dfa_solver6_matrix_row_blocks(const dfa_solver6* s) { return s ? s->v.bcnt : nullptr; }
+const float* dfa_solver6_gradient(const dfa_solver6* s) { return s ? s->v.g : nullptr; }
+const float* dfa_solver6_step(const dfa_solver6* s) { return s ? s->v.x : nullptr; }
+const int32_t* dfa_solver6_data_graph(const dfa_solver6* s) { return s ? s->v.idx_nat : nullptr; }
+const int32_t* dfa_solver6_reg_graph(const dfa_solver6* s) { return s ? s->v.reg_idx : nullptr; }
 
 int dfa_solver6_warp(dfa_solver6* s, float* out_vertices, float* out_normals, dfa_stream_t stream) {
     REQUIRE(s && s->has_problem, "no problem set");

@@ -619,7 +619,7 @@ __device__ __forceinline__ void inv6_column(const float* M, float* out, int c, f
 // Sparsity pattern of block row a (fixed by the graphs of the frame, built once per set_problem):
 // the diagonal first, then every node that shares a vertex with a or is joined to it by a
 // regularisation edge, ascending.
-constexpr int S6_MAXSLOT_PATTERN = 48;  // = S6_MAXSLOT (declared below), the plan capacity of a block row
+constexpr int S6_MAXSLOT_PATTERN = S6_ROW_BLOCKS;  // = S6_MAXSLOT (declared below), the plan capacity of a block row
 constexpr int S6_UNITS = 256;           // work units of a node's assembly = threads of its workgroup
 constexpr int S6_DEAL  = 8;             // a node's sorted rows are dealt out in this many interleaved runs (s6_pattern_kernel)
 
@@ -1543,6 +1543,11 @@ __global__ __launch_bounds__(64 * S6_NODES_PER_BLOCK, S6_PCG_WAVES) void s6_pcg_
                 }
             }
         }
+        // p^T H p, which the recurrence carries as denom, is positive in exact arithmetic; on an ill-conditioned system
+        // (lambda = 0: the nearly free sliding modes) the float32 recurrence can drive it to <= 0 long before the
+        // tolerance.  Such a PCG used to stop there (at T0 / C2 / C3 with lambda = 0 at a relative residual of 4e-3 to 3e-2,
+        // asked for 1e-4); it now restarts its directions from the current residual: beta = 0, denominator (w, u) = u^T H u.
+        if (gamma > tol2 * rz0 && !(denom > 0.f)) beta = 0.f, denom = delta;
         // converged, or breakdown: the same decision in every workgroup
         if (!(gamma > 0.f) || gamma <= tol2 * rz0 || !(denom > 0.f)) {
             if (blockIdx.x == 0 && threadIdx.x == 0) {

@@ -22,6 +22,7 @@ struct Solve6Params {
 };
 
 constexpr int S6_HIST = 32;  // = DFA_SOLVE6_HIST of include/dynfu_amd.h
+constexpr int S6_ROW_BLOCKS = 48;  // 6x6 blocks per block row of the normal matrix (= DFA_SOLVE6_ROW_BLOCKS of include/dynfu_amd.h)
 constexpr int S6_LIN_SHARDS = 32;  // arrival counters of the linearisation (one word would serialise ~2 000 atomics at ~11 ns)
 constexpr int S6_MIRROR_SKIPPED = -(1 << 30);  // launch-budget mirror: the Gauss-Newton iteration ran no PCG (its outer iteration had ended)
 

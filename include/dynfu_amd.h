@@ -612,6 +612,30 @@ const float* dfa_solver6_node_dq(const dfa_solver6* s); /* device, D x 8: solved
 int dfa_solver6_warp(dfa_solver6* s, float* out_vertices, float* out_normals, dfa_stream_t stream);
 int dfa_solver6_get_stats(dfa_solver6* s, dfa_solve6_stats* out, dfa_stream_t stream);
 
+/* The normal equations H x = g of the LAST Gauss-Newton iteration of the last solve, and what came of them (for inspection
+ * and the tests; read-only device pointers, valid until the next dfa_solver6_set_problem / dfa_solver6_solve on this plan).
+ * Unknowns are ordered per node as the twist (omega, v) of DESIGN.md §4.5, six per node.
+ *   matrix_blocks     : D x DFA_SOLVE6_ROW_BLOCKS x 36 floats — block (row a, slot q) at [(a * DFA_SOLVE6_ROW_BLOCKS + q) * 36],
+ *                       a row-major 6 x 6 block H_(a, columns[a][q]); slot 0 is the diagonal block, damping included, slots
+ *                       1 .. row_blocks[a] - 1 hold the other columns of the row in ascending order; H_ba is H_ab transposed
+ *                       bit for bit; slots past row_blocks[a] are undefined
+ *   matrix_columns    : D x DFA_SOLVE6_ROW_BLOCKS int32, the node of every slot (slot 0: a itself)
+ *   matrix_row_blocks : D int32, blocks in use per row (the pattern of the graphs: every pair of nodes in one vertex's k-NN
+ *                       list or joined by a regularisation edge, whether or not that iteration associated any row)
+ *   gradient          : D x 6 floats, g = -J^T W r
+ *   step              : D x 6 floats, the twist x the PCG returned, the step that iteration applied (the update reads it and
+ *                       does not overwrite it; a step undone by the Gauss-Newton rule is still here)
+ *   data_graph        : N x k int32, the k nearest nodes of every canonical vertex, in the caller's vertex order (-1: none)
+ *   reg_graph         : D x k int32, the k nearest OTHER nodes of every node (-1: none) */
+#define DFA_SOLVE6_ROW_BLOCKS 48
+const float* dfa_solver6_matrix_blocks(const dfa_solver6* s);
+const int32_t* dfa_solver6_matrix_columns(const dfa_solver6* s);
+const int32_t* dfa_solver6_matrix_row_blocks(const dfa_solver6* s);
+const float* dfa_solver6_gradient(const dfa_solver6* s);
+const float* dfa_solver6_step(const dfa_solver6* s);
+const int32_t* dfa_solver6_data_graph(const dfa_solver6* s);
+const int32_t* dfa_solver6_reg_graph(const dfa_solver6* s);
+
 /* hipEvent timings of the LAST solve, summed over its Gauss-Newton iterations (for bench.py's roofline) */
 typedef struct dfa_solve6_timing {
     float linearise_ms, assemble_ms, pcg_ms;

@@ -431,6 +431,8 @@ def _declare6(L):
     L.orc6_solve.argtypes = sig + [vp, C.POINTER(Solve6Stats)]
     L.orc6_cost.argtypes = sig + [vp]
     L.orc6_cost.restype = C.c_double
+    L.orc6_set_dump.argtypes = [i, vp, vp, vp, vp, C.c_long, C.POINTER(C.c_long)]
+    L.orc6_set_dump.restype = None
     L._six = True
 
 
@@ -509,6 +511,28 @@ def solve6(node_pos, node_dq, node_w, k, canon, canon_n, vmap, nmap, intr, **par
     for name in ("cost_hist", "pcg_rel_hist", "pcg_it_hist", "pcg_tol_hist", "valid_hist", "stop_hist"):
         d[name] = list(d[name])[:n]
     return out, d
+
+
+def solve6_dump(node_pos, node_dq, node_w, k, canon, canon_n, vmap, nmap, intr, gn=0, **params):
+    """orc6_solve with the normal equations of Gauss-Newton iteration `gn` copied out (orc6_set_dump).  Returns
+    (row_ptr (D + 1), cols, blocks (nblk, 6, 6), g (D, 6)) in float64 — each row's columns in the order the oracle met them
+    — and (node_dq_out, stats) of the solve."""
+    D = len(node_pos)
+    cap = D * (8 * k + 1) + 64  # (a row's columns: the nodes sharing a vertex with it, its k edges and the ones arriving)
+    for _ in range(4):
+        row_ptr, cols = np.zeros(D + 1, np.int32), np.zeros(cap, np.int32)
+        blk, g, nb = np.zeros((cap, 6, 6)), np.zeros((D, 6)), C.c_long(-1)
+        lib6().orc6_set_dump(gn, _p(row_ptr), _p(cols), _p(blk), _p(g), cap, C.byref(nb))
+        try:
+            out = solve6(node_pos, node_dq, node_w, k, canon, canon_n, vmap, nmap, intr, **params)
+        finally:
+            lib6().orc6_set_dump(-1, None, None, None, None, 0, C.byref(C.c_long(0)))
+        if nb.value < 0:
+            raise ValueError("the solve ran no assembly at Gauss-Newton iteration %d" % gn)
+        if nb.value < cap:
+            return (row_ptr, cols[:nb.value].copy(), blk[:nb.value].copy(), g), out
+        cap *= 4
+    raise ValueError("dump capacity")
 
 
 def cost6(node_pos, node_dq, node_w, k, canon, canon_n, vmap, nmap, intr, **params):

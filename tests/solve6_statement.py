@@ -1,0 +1,530 @@
+"""Independent float64 statement of ONE linearisation of the north-star (6-DoF) solve: the block normal matrix H, the
+right-hand side g, the energy, the association of every vertex, per-entry error budgets, and the statement's own solution
+x* of H x = g.  Written from the formulas of DESIGN_NOTES.md §4.5 ("Energy") and include/dynfu_amd.h, not from
+dynfu_amd/csrc/solve6.hip or oracle/solve6_oracle.c:
+
+* unknown: per node i a twist xi_i = (omega, v) about the node's current position g^_i = T_i(g_i), applied on the left:
+  r <- q(omega) r, t <- Exp(omega)(t - g^) + g^ + v.  To first order r gains 1/2 omega^ r and the dual part d = 1/2 t^ r gains
+  1/2 (omega^ d + v0^ r) with v0 = v - omega x g^ (`node_increments`: the 8 x 6 matrix of that map per node);
+* blend: a = sum_j w~_j s_j r_j, b = sum_j w~_j s_j d_j over the vertex's k nodes with non-zero weight, w~ the RBF weights
+  exp(-|c - g_j|^2 / (2 w_j^2)) divided by their sum, s_j the sign of r_j . r_0 against the first (nearest) such node;
+  p = (vec(a c a*) + 2 vec(b a*)) / |a|^2, n' = vec(a n a*) / |a|^2;
+* data term: pixel (rint(fx p_x / p_z + cx), rint(fy p_y / p_z + cy)) inside the image, p_z > 0, live vertex l and normal n
+  defined there, |p - l| <= dist_thresh, n' . n >= cos_thresh (when the canonical normals are given); residual
+  r = n . (p - l), weight rho = Tukey(|r| / tukey_offset; psi_data) — frozen at the outer iteration's first linearisation;
+  the row's 6-vector for node j is n . dp/dxi_j, by the chain rule through (a, b) (`vertex_functional` l_v, 8 numbers);
+* regulariser: per node n and each of its k nearest other nodes m, e = T_n(g_m) - g^_m (3 rows),
+  de/dxi_n = [-[T_n(g_m) - g^_n]x | I], de/dxi_m = [0 | -I], weight lambda / (D k) x Huber(|e|; psi_reg) (frozen);
+* H = J^T W J + damping I, g = -J^T W r, energy = sum W r^2.  The block pattern is the graphs': every pair of nodes in
+  one vertex's k-NN list (pattern="weights": only where both weights are non-zero in float32), every regularisation edge
+  both ways, every diagonal block — whether or not any row was associated.  Block rows in the device's layout: diagonal
+  first, then ascending columns.
+
+J is one scipy sparse matrix (data rows, then 3 rows per regularisation edge); H is a sparse product.  No Python loop over
+vertices.
+
+Budgets (`bud` per entry, `g_bud` per component, `cost_bud`) follow the device's arithmetic as DESIGN_NOTES.md §4.5 documents it,
+u = 2^-24.  The device forms every row's 6-vector as f_j M_j l in float32 — M_j the node's twist map, l the vertex
+functional, f_j = w~ s — and sums the moments S_ab = sum_v rho f_a f_b l l^T in float32 over each block's pair list, split
+into n_u work units (a block with c of its node's T records gets n_u = 2 (1 + floor((128 - B) c / T)) units, B the blocks
+the node's workgroup computes), then forms M_a S_ab M_b^T (16 products deep), writes the mirror block exactly, adds the
+regulariser's edges in float32 and the damping once.  So, per entry, with J-bar the magnitude form of J (every sum and
+product of the formulas above evaluated on absolute values, |n_i| <= 1 where the association is ambiguous):
+    |dH| <= [J-bar^T diag(kappa W + dW) J-bar]                       per-row input errors: kappa = 2 eps_J + 24 u
+          + u (ceil(c_ab / n_u) + n_u + e_ab + 20) [J-bar^T W J-bar]  summation depth of the block (e_ab its edges)
+          + u |H| + 2 [J-bar_amb^T J-bar_amb]                         final rounding; ambiguous vertices, see below
+eps_J = u (64 + 4 k + 4 x_max) / min(1, |a|^2) bounds the relative error of a data row's 6-vector (blend of k quaternions,
+three quaternion products, the RBF exponent's argument x of float32 rounding and the normalisation); 40 u (|y| + |g^|)
+bounds a regularisation row's lever arm.  dW is the weight's own error: the Tukey weight's derivative times the float32
+error of r (|drho| <= 4 (e + de) de / psi^2, de = dr / tukey_offset), and lambda / (D k) Huber's for |e| in float32.
+g and the energy follow the same way with |r| and dr in place of the second J-bar.
+
+Ambiguity: a vertex whose fp64 pixel coordinate lies within 1e-3 px (+ 8 u of the coordinate) of a rounding boundary, whose
+z, distance or normal gate quantity lies within max(1e-5 relative, its float32 error) of the threshold, or whose
+hemisphere dot product is within 1e-4 of 0, may be associated (or blended) differently in float32.  Its contribution on
+either side is at most rho <= 1 times J-bar with |n_i| <= 1 and |r| <= min(dist_thresh, psi_data tukey_offset): twice
+that goes into the budget of every entry it touches, and +-1 into the valid count.  Its energy on the other side is
+evaluated: the largest change to any of the four pixels around its coordinate, or to no association at all.
+"""
+import numpy as np
+import scipy.sparse as sp
+
+U32 = 2.0 ** -24
+
+
+# ------------------------------------------------------------------------------------------------ quaternions (w, x, y, z)
+def qmul(a, b):
+    aw, ax, ay, az = np.moveaxis(a, -1, 0)
+    bw, bx, by, bz = np.moveaxis(b, -1, 0)
+    return np.stack([aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                     aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw], -1)
+
+
+def qmul_abs(a, b):
+    """the magnitude form of qmul: every product of |a_i| |b_j| that enters a component"""
+    a, b = np.broadcast_arrays(np.abs(a), np.abs(b))
+    aw, ax, ay, az = np.moveaxis(a, -1, 0)
+    bw, bx, by, bz = np.moveaxis(b, -1, 0)
+    return np.stack([aw * bw + ax * bx + ay * by + az * bz, aw * bx + ax * bw + ay * bz + az * by,
+                     aw * by + ax * bz + ay * bw + az * bx, aw * bz + ax * by + ay * bx + az * bw], -1)
+
+
+def conj(a):
+    return a * np.array([1.0, -1.0, -1.0, -1.0])
+
+
+def pure(v):
+    return np.concatenate([np.zeros(v.shape[:-1] + (1,)), v], -1)
+
+
+def dq_point(dq, c):
+    """T(c) of unit dual quaternions (..., 8) at points (..., 3): vec(r c r*) + 2 vec(d r*)"""
+    r, d = dq[..., :4], dq[..., 4:]
+    return qmul(qmul(r, pure(c)), conj(r))[..., 1:] + 2.0 * qmul(d, conj(r))[..., 1:]
+
+
+def apply_twist(node_pos, dq, twist):
+    """node transforms after the twists (D, 6) = (omega, v), applied on the left about g^_i = T_i(g_i), in float64:
+    r' = q(omega) r (normalised), t' = Exp(omega)(t - g^) + g^ + v, d' = 1/2 t' r'"""
+    dq = np.asarray(dq, np.float64)
+    tw = np.asarray(twist, np.float64)
+    gh = dq_point(dq, np.asarray(node_pos, np.float64))
+    th = np.linalg.norm(tw[:, :3], axis=1)
+    sc = np.where(th > 1e-12, np.sin(0.5 * th) / np.where(th > 1e-12, th, 1.0), 0.5)
+    qo = np.concatenate([np.cos(0.5 * th)[:, None], sc[:, None] * tw[:, :3]], 1)
+    r, d = dq[:, :4], dq[:, 4:]
+    t = 2.0 * qmul(d, conj(r))[:, 1:]
+    tr = qmul(qmul(qo, pure(t - gh)), conj(qo))[:, 1:] + gh + tw[:, 3:]
+    rn = qmul(qo, r)
+    rn = rn / np.linalg.norm(rn, axis=1, keepdims=True)
+    return np.concatenate([rn, 0.5 * qmul(pure(tr), rn)], 1)
+
+
+# --------------------------------------------------------------------------------------------------------------- graphs
+def knn_distances(node_pos, query, k, exclude_self=False):
+    """(D or N, k) sorted float64 distances of the k nearest nodes (the k nearest OTHER nodes when exclude_self), inf past D"""
+    from scipy.spatial import cKDTree
+    p = np.asarray(node_pos, np.float64)
+    q = np.asarray(query, np.float64)
+    kk = min(k + (1 if exclude_self else 0), len(p))
+    d, i = cKDTree(p).query(q, k=kk)
+    d, i = d.reshape(len(q), kk), i.reshape(len(q), kk)
+    if exclude_self:  # drop the query node itself (the first hit at distance 0 with its own index, else the last)
+        own = i == np.arange(len(q))[:, None]
+        drop = np.where(own.any(1), own.argmax(1), kk - 1)
+        keep = np.ones_like(own)
+        keep[np.arange(len(q)), drop] = False
+        d = d[keep].reshape(len(q), kk - 1)
+    out = np.full((len(q), k), np.inf)
+    out[:, :d.shape[1]] = d[:, :k]
+    return out
+
+
+def check_graph(node_pos, query, graph, exclude_self=False, tie=1e-6):
+    """a device graph against the float64 brute force: slot j holds a node at the j-th smallest distance (ties within
+    `tie` relative may be in either order, and the k-th may be any node tied with it), -1 exactly past the nodes there are,
+    no node twice.  Returns the number of rows decided by a tie."""
+    graph = np.asarray(graph)
+    k = graph.shape[1]
+    ref = knn_distances(node_pos, query, k, exclude_self)
+    has = graph >= 0
+    assert np.array_equal(has, np.isfinite(ref)), "empty slots differ"
+    p = np.asarray(node_pos, np.float64)
+    q = np.asarray(query, np.float64)
+    d = np.where(has, np.linalg.norm(q[:, None, :] - p[np.maximum(graph, 0)], axis=2), np.inf)
+    ok = np.where(has, np.abs(d - ref) <= tie * np.maximum(ref, 1e-300) + 1e-12, True)
+    assert ok.all(), np.argwhere(~ok)[:5]
+    srt = np.sort(np.where(has, graph, -1 - np.arange(k)), 1)
+    assert (np.diff(srt, axis=1) != 0).all(), "a node twice in one row"
+    if exclude_self:
+        assert not (graph == np.arange(len(q))[:, None]).any()
+    nxt = knn_distances(node_pos, query, k + 1, exclude_self)[:, k] if k + 1 <= len(p) - exclude_self else np.full(len(q), np.inf)
+    return int((np.abs(nxt - ref[:, -1]) <= tie * np.maximum(ref[:, -1], 1e-300)).sum())
+
+
+def rbf(node_pos, node_w, canon, idx):
+    """(un-normalised weights in float64, the float32 rounding's zero pattern, the exponent's argument x)"""
+    p = np.asarray(node_pos, np.float64)
+    c = np.asarray(canon, np.float64)
+    w = np.asarray(node_w, np.float64)
+    ii = np.maximum(idx, 0)
+    d2 = ((c[:, None, :] - p[ii]) ** 2).sum(-1)
+    x = d2 / (2.0 * w[ii] ** 2)
+    e = np.where(idx >= 0, np.exp(-x), 0.0)
+    return e, (idx >= 0) & (e.astype(np.float32) > 0), np.where(idx >= 0, x, 0.0)
+
+
+# ------------------------------------------------------------------------------------------------- the twist's map M_j
+def node_increments(dq, gh):
+    """(D, 8, 6) d(r, d)/dxi of every node and its magnitude form"""
+    D = len(dq)
+    r, d = dq[:, :4], dq[:, 4:]
+    M = np.zeros((D, 8, 6))
+    Mb = np.zeros((D, 8, 6))
+    for c in range(6):
+        om = np.zeros((D, 3))
+        v = np.zeros((D, 3))
+        if c < 3:
+            om[:, c] = 1.0
+        else:
+            v[:, c - 3] = 1.0
+        v0 = v - np.cross(om, gh)
+        v0b = v
+        if c < 3:  # |omega x g^| <= |omega| x |g^| componentwise (both terms of each component)
+            a_, b_ = np.abs(om), np.abs(gh)
+            v0b = np.stack([a_[:, 1] * b_[:, 2] + a_[:, 2] * b_[:, 1], a_[:, 2] * b_[:, 0] + a_[:, 0] * b_[:, 2],
+                            a_[:, 0] * b_[:, 1] + a_[:, 1] * b_[:, 0]], 1)
+        M[:, :4, c] = 0.5 * qmul(pure(om), r)
+        M[:, 4:, c] = 0.5 * (qmul(pure(om), d) + qmul(pure(v0), r))
+        Mb[:, :4, c] = 0.5 * qmul_abs(pure(om), r)
+        Mb[:, 4:, c] = 0.5 * (qmul_abs(pure(om), d) + qmul_abs(pure(v0b), r))
+    return M, Mb
+
+
+def vertex_functional(a, b, m, c, n, p, nb=None):
+    """l (N, 8): n . dp for the increments (da, db) = basis vectors, and its magnitude form (nb: |n| to use)"""
+    N = len(a)
+    ac = conj(a)
+    cq = pure(c)
+    nb = np.abs(n) if nb is None else nb
+    l = np.zeros((N, 8))
+    lb = np.zeros((N, 8))
+    np_ = (n * p).sum(1)
+    npb = (nb * np.abs(p)).sum(1)
+    for i in range(4):
+        e = np.zeros((N, 4))
+        e[:, i] = 1.0
+        ec = conj(e)
+        # da = e: vec(e c a* + a c e*) - 2 p (a . e)     db = e: 2 vec(e a*)
+        u = qmul(qmul(e, cq), ac)[:, 1:] + qmul(qmul(a, cq), ec)[:, 1:] + 2.0 * qmul(b, ec)[:, 1:]
+        ub = qmul_abs(qmul_abs(e, cq), a)[:, 1:] + qmul_abs(qmul_abs(a, cq), e)[:, 1:] + 2.0 * qmul_abs(b, e)[:, 1:]
+        l[:, i] = ((n * u).sum(1) - 2.0 * np_ * a[:, i]) / m
+        lb[:, i] = ((nb * ub).sum(1) + 2.0 * npb * np.abs(a[:, i])) / m
+        ud = 2.0 * qmul(e, ac)[:, 1:]
+        udb = 2.0 * qmul_abs(e, a)[:, 1:]
+        l[:, 4 + i] = (n * ud).sum(1) / m
+        lb[:, 4 + i] = (nb * udb).sum(1) / m
+    return l, lb
+
+
+def tukey(e, c):
+    return np.where(e < c, (1.0 - (e / c) ** 2) ** 2, 0.0)
+
+
+def huber(e, kk):
+    return np.where(e <= kk, 1.0, kk / np.maximum(e, 1e-300))
+
+
+class Statement6:
+    """One linearisation at node transforms `node_dq`.  `data_idx` (N, k) / `reg_idx` (D, k): the graphs (-1 = empty);
+    `frozen`: the `weights()` of an earlier linearisation of the same outer iteration (None: this one sets them); `wn`:
+    normalised weights (N, k) to use instead of the float64 RBF weights of the graph; `pattern`: "graph" — the device's
+    block pattern, every pair of nodes in one vertex's k-NN list whatever their weights — or "weights", only pairs whose
+    weights are both non-zero.
+
+    Attributes: D, k, N; cols / row_ptr (block CSR in the device's layout: diagonal, then ascending), blocks (nb, 6, 6),
+    bud (nb, 6, 6); g (D, 6), g_bud; cost, cost_bud; valid (vertices with an association and rho > 0), n_amb (ambiguous
+    vertices), amb (N,) bool; pixel (N, 2) int (-1: none), assoc (N,) bool; counts: pairs (c_ab per block), T (records
+    per node), edges_in (regularisation edges arriving per node), H (scipy csr 6D x 6D)."""
+
+    def __init__(self, node_pos, node_dq, node_w, canon, canon_n, vmap, nmap, intr, params, data_idx, reg_idx,
+                 frozen=None, wn=None, pattern="graph"):
+        P = {key: float(np.float32(val)) for key, val in dict(params).items()}  # (the parameters are float32 on every side)
+        lam = P.get("lambda_", P.get("lambda"))
+        node_pos = np.asarray(node_pos, np.float64)
+        dq = np.asarray(node_dq, np.float64)
+        D = len(node_pos)
+        idx = np.asarray(data_idx, np.int64)
+        N, k = idx.shape
+        ridx = np.asarray(reg_idx, np.int64).reshape(D, k)
+        c = np.asarray(canon, np.float64).reshape(N, 3)
+        self.D, self.k, self.N = D, k, N
+        fx, fy, cx, cy = (float(v) for v in intr)
+
+        # ---- blend
+        w_raw, nz, xarg = rbf(node_pos, node_w, canon, idx)
+        wsum = w_raw.sum(1)
+        if wn is None:
+            wn = np.where(nz, w_raw / np.where(wsum > 0, wsum, 1.0)[:, None], 0.0)
+        else:  # normalised weights given (another statement's float32 ones): the same zeros
+            wn = np.asarray(wn, np.float64).reshape(N, k)
+            nz = (idx >= 0) & (wn != 0)
+        q = dq[np.maximum(idx, 0)]  # (N, k, 8)
+        first = np.where(nz.any(1), nz.argmax(1), 0)
+        r0 = q[np.arange(N), first, :4]
+        dots = (q[..., :4] * r0[:, None, :]).sum(-1)
+        s = np.where(dots < 0, -1.0, 1.0)
+        hemi_amb = (nz & (np.abs(dots) < 1e-4)).any(1)
+        f = wn * s  # (N, k)
+        a = (f[..., None] * q[..., :4]).sum(1)
+        b = (f[..., None] * q[..., 4:]).sum(1)
+        bmag = (wn[..., None] * np.abs(q[..., 4:])).sum(1)
+        m = (a * a).sum(1)
+        sup = nz.any(1) & (m > 0)
+        ms = np.where(sup, m, 1.0)
+        p = (qmul(qmul(a, pure(c)), conj(a))[:, 1:] + 2.0 * qmul(b, conj(a))[:, 1:]) / ms[:, None]
+        p = np.where(sup[:, None], p, c)
+        gh = dq_point(dq, node_pos)  # (D, 3)
+        self.ghat = gh
+        # float32 error of p, r (see the module docstring)
+        pmag = np.linalg.norm(c, axis=1) + 2.0 * np.linalg.norm(bmag, axis=1) + np.linalg.norm(p, axis=1)
+        dp = (40 + 2 * k) * U32 * pmag / np.minimum(1.0, ms)
+
+        # ---- association
+        H_, W_ = vmap.shape[:2]
+        z = p[:, 2]
+        zs = np.where(z > 0, z, 1.0)
+        uf = fx * (p[:, 0] / zs) + cx
+        vf = fy * (p[:, 1] / zs) + cy
+        duf = 8 * U32 * np.abs(uf) + 1e-3  # (1e-3 px: 2e-6 relative to p at 1.5 m and f = 525, some 32 u)
+        dvf = 8 * U32 * np.abs(vf) + 1e-3
+        ok = sup & (z > 0)
+        amb = sup & (np.abs(z) <= np.maximum(1e-5 * np.abs(z), dp))
+        u = np.where(ok, np.rint(uf), -1).astype(np.int64)
+        v = np.where(ok, np.rint(vf), -1).astype(np.int64)
+        amb |= ok & ((np.abs(np.abs(uf - np.floor(uf)) - 0.5) <= duf) | (np.abs(np.abs(vf - np.floor(vf)) - 0.5) <= dvf))
+        ok &= (u >= 0) & (v >= 0) & (u < W_) & (v < H_)
+        L = np.asarray(vmap, np.float64)[np.where(ok, v, 0), np.where(ok, u, 0), :3]
+        Ln = np.asarray(nmap, np.float64)[np.where(ok, v, 0), np.where(ok, u, 0), :3]
+        ok &= ~np.isnan(L[:, 0]) & ~np.isnan(Ln[:, 0])
+        L = np.where(ok[:, None], L, 0.0)
+        Ln = np.where(ok[:, None], Ln, 0.0)
+        dl = p - L
+        dist = np.linalg.norm(dl, axis=1)
+        dth = float(P["dist_thresh"])
+        gamb = ok & (np.abs(dist - dth) <= np.maximum(1e-5 * dth, 2 * dp))
+        amb |= gamb
+        ok &= dist <= dth
+        if canon_n is not None:
+            cn = np.asarray(canon_n, np.float64).reshape(N, 3)
+            nw = qmul(qmul(a, pure(cn)), conj(a))[:, 1:] / ms[:, None]
+            cosv = (nw * Ln).sum(1)
+            cth = float(P["cos_thresh"])
+            gc = ok & (np.abs(cosv - cth) <= np.maximum(1e-5 * abs(cth), (24 + 2 * k) * U32 / np.minimum(1.0, ms)))
+            gamb |= gc
+            amb |= gc
+            ok &= cosv >= cth
+        amb |= sup & hemi_amb
+        res = np.where(ok, (Ln * dl).sum(1), 0.0)
+        dres = np.where(ok, dp + 4 * U32 * (np.abs(p) + np.abs(L)).sum(1), 0.0)
+        off, psi = float(P["tukey_offset"]), float(P["psi_data"])
+        e = np.abs(res) / off
+        de = dres / off
+        if frozen is None:
+            rho = np.where(ok, tukey(e, psi), 0.0)
+            drho = np.where(ok, np.minimum(1.0, 4.0 * (e + de) * de / psi ** 2) * (e - de < psi), 0.0)
+            count_amb = ok & (np.abs(e - psi) <= de)
+        else:
+            rho, drho, hub_f, dhub_f, amb_f = frozen["rho"], frozen["drho"], frozen["hub"], frozen["dhub"], frozen["amb"]
+            amb |= amb_f
+            count_amb = np.zeros(N, bool)
+        self.assoc = ok
+        self.pixel = np.where(ok[:, None], np.stack([u, v], 1), -1)
+        self.rho, self.drho = rho, drho
+        self.amb = amb
+        self.n_amb = int(amb.sum())
+        self.valid = int((ok & (rho > 0)).sum())
+        self.valid_amb = int((amb | count_amb).sum())
+
+        # ---- data rows: a_j = f_j M_j^T l   (M_j: 8 x 6)
+        M, Mb = node_increments(dq, gh)
+        self.M = M
+        Ln = np.where(ok[:, None], Ln, 0.0)  # (a row the gates rejected is empty)
+        lfun, lb = vertex_functional(a, b, ms, c, Ln, p)
+        _, lb1 = vertex_functional(a, b, ms, c, Ln, p, nb=np.ones_like(Ln))  # |n_i| <= 1: any pixel
+        lb = np.where(amb[:, None], lb1, lb)
+        ii = np.maximum(idx, 0)
+        arow = f[..., None] * np.einsum("vi,vkic->vkc", lfun, M[ii])  # (N, k, 6)
+        abar = np.abs(f)[..., None] * np.einsum("vi,vkic->vkc", lb, Mb[ii])
+        eps_j = U32 * (64 + 4 * k + 4 * xarg.max(1)) / np.minimum(1.0, ms)
+        live = nz & sup[:, None]
+        data_cols = (6 * ii[..., None] + np.arange(6)).reshape(N, 6 * k)
+        keep = np.repeat(live, 6, axis=1)
+
+        # ---- regularisation rows: edge (n, s) -> m
+        wreg2 = lam / (D * k)
+        n_of = np.repeat(np.arange(D), k)
+        m_of = ridx.reshape(-1)
+        ek = m_of >= 0
+        n_e, m_e = n_of[ek], m_of[ek]
+        y = dq_point(dq[n_e], node_pos[m_e])
+        ee = y - gh[m_e]
+        en = np.linalg.norm(ee, axis=1)
+        den = 40 * U32 * (np.linalg.norm(y, axis=1) + np.linalg.norm(gh[m_e], axis=1))
+        psr = float(P["psi_reg"])
+        if frozen is None:
+            hub = huber(en, psr)
+            dhub = np.where(en + den > psr, hub * den / np.maximum(en - den, psr), 0.0)
+        else:
+            hub, dhub = hub_f, dhub_f
+        self.hub, self.dhub = hub, dhub
+        lev = y - gh[n_e]
+        dlev = 40 * U32 * (np.linalg.norm(y, axis=1) + np.linalg.norm(gh[n_e], axis=1))
+        E = len(n_e)
+        # rows c = 0..2 of edge e: columns 6 n + (0..5) then 6 m + 3 + c
+        skew = np.zeros((E, 3, 3))
+        skew[:, 0, 1], skew[:, 0, 2] = lev[:, 2], -lev[:, 1]
+        skew[:, 1, 0], skew[:, 1, 2] = -lev[:, 2], lev[:, 0]
+        skew[:, 2, 0], skew[:, 2, 1] = lev[:, 1], -lev[:, 0]
+        rvals = np.concatenate([skew, np.broadcast_to(np.eye(3), (E, 3, 3)), -np.ones((E, 3, 1))], 2)
+        rbar = np.abs(rvals) + np.concatenate([np.where(np.abs(skew) > 0, dlev[:, None, None], 0.0),
+                                               np.zeros((E, 3, 4))], 2)
+        rcols = np.concatenate([np.broadcast_to(6 * n_e[:, None, None] + np.arange(6), (E, 3, 6)),
+                                (6 * m_e[:, None] + 3 + np.arange(3))[:, :, None]], 2)
+
+        # ---- J, W, r as sparse rows (data: 6k entries per vertex; regulariser: 7 per row)
+        nd = N
+        data_ptr = np.concatenate([[0], np.cumsum(keep.sum(1))])
+        Jd = sp.csr_matrix((arow.reshape(N, 6 * k)[keep], data_cols[keep], data_ptr), shape=(nd, 6 * D))
+        Jdb = sp.csr_matrix((abar.reshape(N, 6 * k)[keep], data_cols[keep], data_ptr), shape=(nd, 6 * D))
+        rptr = np.arange(0, 3 * E * 7 + 1, 7)
+        Jr = sp.csr_matrix((rvals.reshape(-1), rcols.reshape(-1), rptr), shape=(3 * E, 6 * D))
+        Jrb = sp.csr_matrix((rbar.reshape(-1), rcols.reshape(-1), rptr), shape=(3 * E, 6 * D))
+        J = sp.vstack([Jd, Jr]).tocsr()
+        Jb = sp.vstack([Jdb, Jrb]).tocsr()
+        W = np.concatenate([np.where(ok, rho, 0.0), np.repeat(wreg2 * hub, 3)])
+        dW = np.concatenate([np.where(ok, drho, 0.0), np.repeat(wreg2 * (dhub + 3 * U32 * hub), 3)])
+        kap = np.concatenate([2 * eps_j + 24 * U32, np.full(3 * E, 24 * U32)])
+        rr = np.concatenate([res, ee.reshape(-1)])
+        dr = np.concatenate([dres + eps_j * np.abs(res), np.repeat(den, 3)])
+        amb_rows = np.concatenate([amb & sup, np.zeros(3 * E, bool)])
+        self.J, self.W, self.r = J, W, rr
+        self._keep = (node_pos, idx, wn, nz, c, L, Ln, ok, n_e, m_e)
+
+        damping = float(P["damping"])
+        H = (J.T @ sp.diags(W) @ J).tocsr() + damping * sp.identity(6 * D, format="csr")
+        Hb = (Jb.T @ sp.diags(kap * W + dW) @ Jb).tocsr()
+        Hw = (Jb.T @ sp.diags(W) @ Jb).tocsr()
+        Ja = Jb[np.flatnonzero(amb_rows)]
+        Ha = (Ja.T @ Ja).tocsr() * 2.0
+        self.H = H
+        self.g = -(J.T @ (W * rr)).reshape(D, 6)
+        rmax = min(dth, psi * off)
+        self.cost = float((W * rr * rr).sum())
+        namb = amb & sup
+        # an ambiguous vertex's energy on the other side: any of the (up to) four pixels around its coordinate, or none
+        av = np.flatnonzero(namb)
+        mine = (W[:N] * res * res)[av]
+        worst = mine.copy()
+        vm, nm = np.asarray(vmap, np.float64), np.asarray(nmap, np.float64)
+        for uu in (np.floor(uf[av]), np.floor(uf[av]) + 1):
+            for vv in (np.floor(vf[av]), np.floor(vf[av]) + 1):
+                inside = (z[av] > 0) & (uu >= 0) & (vv >= 0) & (uu < W_) & (vv < H_)
+                ui, vi = np.where(inside, uu, 0).astype(np.int64), np.where(inside, vv, 0).astype(np.int64)
+                L2, N2 = vm[vi, ui, :3], nm[vi, ui, :3]
+                ok2 = inside & ~np.isnan(L2[:, 0]) & ~np.isnan(N2[:, 0])
+                d2 = p[av] - np.where(ok2[:, None], L2, 0.0)
+                ok2 &= np.linalg.norm(d2, axis=1) <= dth * (1 + 1e-5)
+                if canon_n is not None:
+                    ok2 &= (nw[av] * np.where(ok2[:, None], N2, 0.0)).sum(1) >= cth - 1e-5
+                r2 = np.where(ok2, (np.where(ok2[:, None], N2, 0.0) * d2).sum(1), 0.0)
+                w2 = tukey(np.abs(r2) / off, psi) if frozen is None else rho[av]
+                worst = np.maximum(worst, np.abs(np.where(ok2, w2 * r2 * r2, 0.0) - mine))
+        worst = np.where(gamb[av] | (np.abs(z[av]) <= np.maximum(1e-5 * np.abs(z[av]), dp[av])), np.maximum(worst, mine),
+                         worst)  # (a gate quantity at its threshold: or not associated at all)
+        self.cost_bud = float((dW * rr * rr + 2 * W * np.abs(rr) * dr + 80 * U32 * W * rr * rr).sum() + worst.sum()
+                              + hemi_amb[av].sum() * rmax ** 2)
+
+        # ---- block pattern (the graphs') and per-block counts
+        on = (idx >= 0) if pattern == "graph" else nz
+        B = sp.csr_matrix((np.ones(int(on.sum())), idx[on], np.concatenate([[0], np.cumsum(on.sum(1))])), shape=(N, D))
+        C = (B.T @ B).tocoo()  # c_ab: vertices that have both a and b
+        R = sp.coo_matrix((np.ones(E), (n_e, m_e)), shape=(D, D))
+        keys = np.unique(np.concatenate([C.row.astype(np.int64) * D + C.col, n_e * D + m_e, m_e * D + n_e,
+                                         np.arange(D, dtype=np.int64) * (D + 1)]))
+        ra, cb = keys // D, keys % D
+        order = np.lexsort((cb, cb != ra, ra))
+        keys, ra, cb = keys[order], ra[order], cb[order]
+        self.keys = keys
+        self.cols = cb.astype(np.int32)
+        self.row_ptr = np.concatenate([[0], np.cumsum(np.bincount(ra, minlength=D))])
+        self.row_blocks = np.diff(self.row_ptr)
+        nb = len(keys)
+        skey = np.argsort(keys)
+
+        def blockify(Mx):
+            Mx = Mx.tocoo()
+            bk = (Mx.row // 6).astype(np.int64) * D + Mx.col // 6
+            pos = np.searchsorted(keys[skey], bk)
+            pos = np.minimum(pos, nb - 1)
+            assert (keys[skey][pos] == bk).all(), "an entry outside the graphs' pattern"
+            out = np.zeros((nb, 36))
+            np.add.at(out, (skey[pos], (Mx.row % 6) * 6 + Mx.col % 6), Mx.data)
+            return out.reshape(nb, 6, 6)
+
+        def per_block(Mx):
+            Mx = Mx.tocoo()
+            bk = Mx.row.astype(np.int64) * D + Mx.col
+            out = np.zeros(nb)
+            pos = np.searchsorted(keys[skey], bk)
+            out[skey[np.minimum(pos, nb - 1)]] = Mx.data
+            return out
+
+        self.blocks = blockify(H)
+        self.habs = blockify(Hw) + damping * np.eye(6) * (ra == cb)[:, None, None]  # |J|^T W |J|: the entries' scale
+        cab = per_block(C)
+        eab = per_block(R + R.T) + np.where(ra == cb, np.bincount(n_e, minlength=D)[ra] + np.bincount(m_e, minlength=D)[ra], 0)
+        T = np.asarray(B.sum(0)).ravel()
+        owner = np.minimum(ra, cb)
+        upper = np.bincount(ra[cb > ra], minlength=D)
+        Bw = 1 + upper[owner]
+        Tw = np.maximum(T[owner], 1)
+        nu = 2 * (1 + np.floor((128 - Bw) * cab / Tw))
+        depth = np.ceil(cab / nu) + nu + eab + 20
+        self.T, self.pairs, self.edges_in = T, cab, np.bincount(m_e, minlength=D)
+        self.bud = (blockify(Hb) + (U32 * depth)[:, None, None] * blockify(Hw) + U32 * np.abs(self.blocks)
+                    + (blockify(Ha) if Ja.shape[0] else 0.0))
+        # g: the records' sums ride on slot 0's units
+        nud = 2 * (1 + np.floor((128 - (1 + upper)) * T / np.maximum(T, 1)))
+        gdepth = np.ceil(T / nud) + nud + self.edges_in + k + 20
+        gb = Jb.T @ ((kap * W + dW) * np.abs(rr) + W * dr)
+        gw = Jb.T @ (W * np.abs(rr))
+        ga = Ja.T @ np.full(Ja.shape[0], 2.0 * rmax) if Ja.shape[0] else 0.0
+        self.g_bud = (gb + U32 * np.repeat(gdepth, 6) * gw + ga).reshape(D, 6) + U32 * np.abs(self.g)
+        self.damping = damping
+        self.wreg2 = wreg2
+
+    def residuals(self, node_dq):
+        """the rows of this linearisation (data rows with its association, then 3 per regularisation edge) evaluated at
+        other node transforms: n . (p - l) and T_n(g_m) - T_m(g_m)"""
+        node_pos, idx, wn, nz, c, L, Ln, ok, n_e, m_e = self._keep
+        dq = np.asarray(node_dq, np.float64)
+        q = dq[np.maximum(idx, 0)]
+        first = np.where(nz.any(1), nz.argmax(1), 0)
+        r0 = q[np.arange(len(idx)), first, :4]
+        s = np.where((q[..., :4] * r0[:, None, :]).sum(-1) < 0, -1.0, 1.0)
+        f = np.where(nz, wn, 0.0) * s
+        a = (f[..., None] * q[..., :4]).sum(1)
+        b = (f[..., None] * q[..., 4:]).sum(1)
+        m = np.maximum((a * a).sum(1), 1e-300)
+        p = (qmul(qmul(a, pure(c)), conj(a))[:, 1:] + 2.0 * qmul(b, conj(a))[:, 1:]) / m[:, None]
+        rd = np.where(ok, (Ln * (p - L)).sum(1), 0.0)
+        e = dq_point(dq[n_e], node_pos[m_e]) - dq_point(dq[m_e], node_pos[m_e])
+        return np.concatenate([rd, e.reshape(-1)])
+
+    def weights(self):
+        """the frozen weights a later linearisation of the same outer iteration uses"""
+        return dict(rho=self.rho, drho=self.drho, hub=self.hub, dhub=self.dhub, amb=self.amb)
+
+    def block_coo(self):
+        """(rows, cols, blocks) of the pattern"""
+        return np.repeat(np.arange(self.D), self.row_blocks), self.cols, self.blocks
+
+    def solve(self):
+        """x* of H x = g, float64, (D, 6)"""
+        from scipy.sparse.linalg import spsolve
+        return spsolve(self.H.tocsc(), self.g.reshape(-1)).reshape(self.D, 6)
+
+    def lambda_min(self):
+        """the smallest eigenvalue of H: dense up to 3 000 unknowns, else shift-invert Lanczos about 0 (to 1e-6 relative,
+        taken 1e-4 low; the damping if it does not converge in 100 restarts); never below the damping, since
+        H = J^T W J + damping I"""
+        if 6 * self.D <= 3000:
+            return float(np.linalg.eigvalsh(self.H.toarray())[0])
+        from scipy.sparse.linalg import ArpackNoConvergence, eigsh
+        try:
+            lam = float(eigsh(self.H.tocsc(), k=1, sigma=0, which="LM", tol=1e-6, maxiter=100,
+                              return_eigenvectors=False).min()) * (1 - 1e-4)
+        except ArpackNoConvergence:
+            lam = self.damping
+        return max(lam, self.damping * (1 - 1e-6))
