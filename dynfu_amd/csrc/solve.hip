@@ -22,11 +22,11 @@
 //     frame, then ONE WAVE PER NODE reduces its ~128 k rows into an LDS hash keyed by column
 //     (LDS float atomics stay on the CU; no global atomics on the matrix at all) and writes
 //     one ELL row + one rhs entry + the Jacobi diagonal.
-//   * the PCG is a single persistent 1024-thread workgroup: at 2 k - 8 k nodes the solve is
-//     bound by synchronisation latency, not bandwidth — a workgroup barrier
-//     costs ~0.1 us where a grid-wide barrier costs 4-5 us — with the direction vector in
-//     LDS (16 B / node, ds_read_b128 gathers), x / r / p of the thread's own rows in
-//     registers and dot products reduced by wave shuffles in double.
+//   * the PCG is bound by synchronisation latency, not bandwidth, and comes in the forms that keep
+//     it cheap at each size: register-resident (one workgroup per coordinate, up to 2 048 nodes; streaming inside the
+//     same launch when a row pair does not fit), teams of persistent workgroups with their guard launch (up to
+//     19 584 nodes), one launch per iteration above that.  route_pcg chooses; what an iteration IS — preconditioner,
+//     stopping rules, Chronopoulos-Gear scalars, row update, booking — is stated once, in pcg_rules.hpp.
 #include <hip/hip_runtime.h>
 #include <cstring>
 
@@ -39,6 +39,7 @@
 #include "dq_device.hpp"
 #include "dev_switch.hpp"
 #include "kernels.hpp"
+#include "pcg_rules.hpp"
 #include "solve.hpp"
 
 namespace dfa {
@@ -928,12 +929,6 @@ __device__ __forceinline__ double block_sum(float v, float* red) {
     return tot;
 }
 
-// PCG targets never go below the round-off floor of the SOLVE: 1e-12 of the first linearisation's (r0, z0), the level
-// at which a whole linearisation is skipped.  A late Gauss-Newton iteration starts from a small gradient, and 1e-12 of
-// THAT is out of float's reach — its PCG would polish noise until the iteration cap (C2: the third iteration spent 108
-// PCG iterations to move the translations by 2e-7 m).
-__device__ __forceinline__ float solve_floor(const SolveState* st) { return (float)(1e-12 * st->grad_first); }
-
 // DFA_PCG_PROFILE builds accumulate shader cycles per PCG phase (thread 0) into SolveState::prof
 #ifdef DFA_PCG_PROFILE
 #define PROF_MARK(i)                      \
@@ -1044,8 +1039,7 @@ __device__ __forceinline__ void pcg_stream_body(const SolveView& s, SolveState* 
 #pragma unroll
     for (int i = 0; i < RPT; ++i) {
         if (row[i] >= 0) {
-            const float d = s.diag[row[i]];
-            minv[i]       = d > FLT_EPSILON ? 1.0f / d : 1.0f;
+            minv[i] = jacobi_inv(s.diag[row[i]]);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 x[i][c] = 0.f;
@@ -1065,7 +1059,7 @@ __device__ __forceinline__ void pcg_stream_body(const SolveView& s, SolveState* 
     const double floor_ = 1e-12;  // squared-residual-ratio floor of float arithmetic
     const double tol2   = (double)pcg_tol * (double)pcg_tol > floor_ ? (double)pcg_tol * (double)pcg_tol : floor_;
     int it              = 0;
-    const bool skip     = st->grad_first > 0.0 && rz0 <= floor_ * st->grad_first;
+    const bool skip     = pcg_at_floor(st, rz0);
     const double target = fmax(tol2 * rz0, (double)solve_floor(st));
     if (!skip) {
         while (it < max_iter) {
@@ -1141,12 +1135,7 @@ __device__ __forceinline__ void pcg_stream_body(const SolveView& s, SolveState* 
             for (int c = 0; c < 3; ++c) s.t[3 * row[i] + c] += x[i][c];
         }
     }
-    if (tid == 0) {
-        if (st->grad_first == 0.0) st->grad_first = rz0;
-        st->pcg_iters += it;
-        st->gn_iters += 1;
-        if (skip) solve_mark_at_floor(st);
-    }
+    if (tid == 0) pcg_book_launch(st, rz0, it, skip);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1171,7 +1160,7 @@ __device__ __forceinline__ void pcg_stream_body(const SolveView& s, SolveState* 
 // solves coordinate c on its own CU.  The gather shrinks from one ds_read_b128 + 3 FMAs per non-zero to one
 // ds_read_b32 + 1 FMA (the LDS pipe moves 128 B/clk: 8 clocks per wave-wide b128 read, 2 per b32 read).  Every
 // coordinate stops at (r, z)_c <= tol^2 (r0, z0)_joint / 3, which implies the joint stopping rule.
-template <int NT, int P, int E, int NC>
+template <int NT, int E, int NC>
 __global__ __launch_bounds__(NT) void pcg_paired_kernel(SolveView s, SolveState* __restrict__ st, int max_iter,
                                                         float pcg_tol) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1189,6 +1178,9 @@ __global__ __launch_bounds__(NT) void pcg_paired_kernel(SolveView s, SolveState*
         if (tid == 0 && blockIdx.x == 0) st->gn_iters += 1, st->gn_noop += 1;
         return;
     }
+    // pairs of rows per thread.  Every instantiation has one; the [P] dimension of the register arrays stays because the
+    // compiler allots 112 / 210 VGPRs without it where it allots 114 / 212 with it (profiles/pcg_rules_refactor.md).
+    constexpr int P = 1;
     constexpr int R = 2 * P;  // rows per thread
 
     // ---- (r0, z0) of the joint system first, rows in natural order: it scales both stopping rules, and a gradient at
@@ -1198,8 +1190,7 @@ __global__ __launch_bounds__(NT) void pcg_paired_kernel(SolveView s, SolveState*
     for (int h = 0; h < R; ++h) {
         const int row = tid + NT * h;
         if (row < D) {
-            const float d    = s.diag[row];
-            const float minv = d > FLT_EPSILON ? 1.0f / d : 1.0f;
+            const float minv = jacobi_inv(s.diag[row]);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float g = s.g[3 * row + c];
@@ -1208,7 +1199,7 @@ __global__ __launch_bounds__(NT) void pcg_paired_kernel(SolveView s, SolveState*
         }
     }
     const float rz0 = block_sum_f<NT / 64>(rzj_loc, red1);
-    const bool skip = st->grad_first > 0.0 && (double)rz0 <= 1e-12 * st->grad_first;
+    const bool skip = pcg_at_floor(st, rz0);
     if (skip) {  // the same decision in every workgroup; the first one books the (empty) iteration
         if (tid == 0 && blockIdx.x == 0) {
             st->gn_iters += 1;
@@ -1327,14 +1318,8 @@ __global__ __launch_bounds__(NT) void pcg_paired_kernel(SolveView s, SolveState*
 #pragma unroll
     for (int j = 0; j < P; ++j) {
         minvA[j] = minvB[j] = 0.f;
-        if (rowA[j] >= 0) {
-            const float d = s.diag[rowA[j]];
-            minvA[j]      = d > FLT_EPSILON ? 1.0f / d : 1.0f;
-        }
-        if (rowB[j] >= 0) {
-            const float d = s.diag[rowB[j]];
-            minvB[j]      = d > FLT_EPSILON ? 1.0f / d : 1.0f;
-        }
+        if (rowA[j] >= 0) minvA[j] = jacobi_inv(s.diag[rowA[j]]);
+        if (rowB[j] >= 0) minvB[j] = jacobi_inv(s.diag[rowB[j]]);
 #pragma unroll
         for (int cc = 0; cc < NC; ++cc) {
             const int c    = c0 + cc;
@@ -1354,13 +1339,9 @@ __global__ __launch_bounds__(NT) void pcg_paired_kernel(SolveView s, SolveState*
     }
     __syncthreads();  // p in LDS
     float rz = rz0;   // (NC = 1 forms its own (r, z) inside the loop)
-    const float floor_ = 1e-12f;
-    const float tol2   = pcg_tol * pcg_tol > floor_ ? pcg_tol * pcg_tol : floor_;
-    // (never below the solve's round-off floor, see solve_floor)
-    const float joint  = fmaxf(tol2 * rz0, solve_floor(st));
+    const float joint  = pcg_joint_target(st, pcg_tol, rz0);
     // NC = 1: this coordinate's share of the joint target; a coordinate already below it does no iteration
     const float target = NC == 3 ? joint : joint * (1.0f / 3.0f);
-    const float rz_min = NC == 3 ? 0.f : target;
     int it             = 0;
     const char* pbase   = (const char*)p_s;
 #ifdef DFA_PCG_PROFILE
@@ -1453,7 +1434,7 @@ __global__ __launch_bounds__(NT) void pcg_paired_kernel(SolveView s, SolveState*
     if (NC == 3) {
         // textbook PCG: two reductions and the publication of p = three barriers per iteration
         while (it < max_iter) {
-            if (!(rz > rz_min)) break;
+            if (!(rz > 0.f)) break;
             PROF_MARK(5);
             float aA[P][NC], aB[P][NC];
             float pap_loc = 0.f;
@@ -1532,23 +1513,17 @@ __global__ __launch_bounds__(NT) void pcg_paired_kernel(SolveView s, SolveState*
 #pragma unroll
             for (int i = 0; i < NT / 64; ++i) gamma += red0[i], delta += red1[i];
             PROF_MARK(1);
-            if (!(gamma > rz_min)) break;  // converged: (r, M^-1 r) of the iterate in x
-            const float beta  = it == 0 ? 0.f : gamma / gamma_old;
-            const float denom = it == 0 ? delta : delta - beta * gamma / alpha_old;
+            if (!(gamma > target)) break;  // converged: (r, M^-1 r) of the iterate in x
+            const float beta  = cg_beta(it == 0, gamma, gamma_old);
+            const float denom = cg_denom(it == 0, gamma, delta, beta, alpha_old);
             if (!(denom > 0.f)) break;
             const float alpha = gamma / denom;
 #pragma unroll
             for (int j = 0; j < P; ++j)
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
-                    pA[j][c]  = fmaf(beta, pA[j][c], uA[j][c]);
-                    pB[j][c]  = fmaf(beta, pB[j][c], uB[j][c]);
-                    sA[j][c]  = fmaf(beta, sA[j][c], wA[j][c]);
-                    sB[j][c]  = fmaf(beta, sB[j][c], wB[j][c]);
-                    xA[j][c]  = fmaf(alpha, pA[j][c], xA[j][c]);
-                    xB[j][c]  = fmaf(alpha, pB[j][c], xB[j][c]);
-                    rA_[j][c] = fmaf(-alpha, sA[j][c], rA_[j][c]);
-                    rB_[j][c] = fmaf(-alpha, sB[j][c], rB_[j][c]);
+                    cg_update_row(alpha, beta, uA[j][c], wA[j][c], pA[j][c], sA[j][c], xA[j][c], rA_[j][c]);
+                    cg_update_row(alpha, beta, uB[j][c], wB[j][c], pB[j][c], sB[j][c], xB[j][c], rB_[j][c]);
                     uA[j][c]  = minvA[j] * rA_[j][c];
                     uB[j][c]  = minvB[j] * rB_[j][c];
                 }
@@ -1572,22 +1547,8 @@ __global__ __launch_bounds__(NT) void pcg_paired_kernel(SolveView s, SolveState*
             if (rowB[j] >= 0) s.t[3 * rowB[j] + c0 + c] += xB[j][c];
         }
     if (tid == 0) {
-        if (NC == 3) {
-            if (st->grad_first == 0.0) st->grad_first = (double)rz0;
-            st->pcg_iters += it;
-            st->gn_iters += 1;
-        } else {
-            // iterations of this launch = those of its slowest coordinate; the last workgroup to arrive books them
-            atomicMax(&st->split_iters, it);
-            __threadfence();
-            if (atomicAdd(&st->split_ticket, 1u) == 2u) {
-                __threadfence();
-                st->pcg_iters += atomicExch(&st->split_iters, 0);
-                st->split_ticket = 0u;
-                if (st->grad_first == 0.0) st->grad_first = (double)rz0;
-                st->gn_iters += 1;
-            }
-        }
+        if (NC == 3) pcg_book_launch(st, rz0, it, false);
+        else pcg_book_launch_of_three(st, rz0, it, false);
     }
 }
 
@@ -1707,8 +1668,7 @@ __global__ __launch_bounds__(256) void pcg_mb_init_kernel(SolveView s, SolveStat
     }
     float rz = 0.f;
     if (a < s.D) {
-        const float d    = s.diag[a];
-        const float minv = d > FLT_EPSILON ? 1.0f / d : 1.0f;
+        const float minv = jacobi_inv(s.diag[a]);
         const float4 r   = make_float4(s.g[3 * a], s.g[3 * a + 1], s.g[3 * a + 2], 0.f);
         const float4 z   = make_float4(minv * r.x, minv * r.y, minv * r.z, 0.f);
         const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1769,22 +1729,21 @@ __global__ __launch_bounds__(256) void pcg_mb_step_kernel(SolveView s, SolveStat
         if ((threadIdx.x & 63) == 0) sh[0][threadIdx.x >> 6] = g, sh[1][threadIdx.x >> 6] = d;
         __syncthreads();
         const float gamma = (sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3]), delta = (sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3]);
-        const float floor_ = 1e-12f;
-        const float tol2   = pcg_tol * pcg_tol > floor_ ? pcg_tol * pcg_tol : floor_;
-        float rz0 = gamma, denom = delta;
-        bool stop = !(gamma > 0.f);
+        float denom = delta;
+        bool stop   = !(gamma > 0.f);
         if (it == 0) {
-            const bool at_floor = st->grad_first > 0.0 && (double)gamma <= (double)floor_ * st->grad_first;
+            // (the float constant as the at-floor level is this form's own: DESIGN_NOTES.md, "Open differences between the
+            // PCG forms")
+            const bool at_floor = pcg_at_floor(st, gamma, (double)1e-12f);
             stop                = stop || at_floor;  // nothing left to solve
             if (blockIdx.x == 0 && threadIdx.x == 0) {
                 st->mb_rz0 = gamma;
                 if (at_floor) solve_mark_at_floor(st);
             }
         } else {
-            rz0   = st->mb_rz0;
-            beta  = gamma / st->mb_gamma_prev[(it + 1) & 1];
-            denom = delta - beta * gamma / st->mb_alpha_prev[(it + 1) & 1];
-            stop  = stop || gamma <= fmaxf(tol2 * rz0, solve_floor(st));
+            beta  = cg_beta(false, gamma, st->mb_gamma_prev[(it + 1) & 1]);
+            denom = cg_denom(false, gamma, delta, beta, st->mb_alpha_prev[(it + 1) & 1]);
+            stop  = stop || gamma <= pcg_joint_target(st, pcg_tol, st->mb_rz0);
         }
         stop = stop || !(denom > 0.f);  // converged, or breakdown: the same decision in every workgroup
         if (stop) {
@@ -1815,8 +1774,7 @@ __global__ __launch_bounds__(256) void pcg_mb_step_kernel(SolveView s, SolveStat
     for (int c = 0; c < 3; ++c) au[c] = group16_sum(au[c]), am[c] = group16_sum(am[c]), at[c] = group16_sum(at[c]);
     float gpart = 0.f, dpart = 0.f;
     if (row_ok && lane16 == 0) {
-        const float dg   = s.diag[a];
-        const float minv = dg > FLT_EPSILON ? 1.0f / dg : 1.0f;
+        const float minv = jacobi_inv(s.diag[a]);
         float4 u = ucur[a], r = s.mb_r[a];
         float w[3] = {au[0], au[1], au[2]};
         if (it >= 0) {
@@ -1857,11 +1815,7 @@ __global__ __launch_bounds__(256) void pcg_mb_finish_kernel(SolveView s, SolveSt
         const float4 x = s.mb_x[a];
         s.t[3 * a] += x.x, s.t[3 * a + 1] += x.y, s.t[3 * a + 2] += x.z;
     }
-    if (a == 0) {
-        if (st->grad_first == 0.0) st->grad_first = (double)st->mb_rz0;
-        st->pcg_iters += st->mb_iters;
-        st->gn_iters += 1;
-    }
+    if (a == 0) pcg_book_launch(st, st->mb_rz0, st->mb_iters, false);  // (launch 0 has set the at-floor mark)
 }
 
 // The iteration count is only known on the device.  With a pinned host word the launches go out in chunks (16, 32,
@@ -2128,7 +2082,7 @@ __device__ __forceinline__ void team_member(const SolveView& s, SolveState* __re
 #pragma unroll
         for (int i = 0; i < E / 2; ++i) ucol[h0 + i] = s.diag[col[i]], gcol[i] = s.g[3 * col[i] + c];  // (both in one round trip)
 #pragma unroll
-        for (int i = 0; i < E / 2; ++i) ucol[h0 + i] = (ucol[h0 + i] > FLT_EPSILON ? 1.0f / ucol[h0 + i] : 1.0f) * gcol[i];
+        for (int i = 0; i < E / 2; ++i) ucol[h0 + i] = jacobi_inv(ucol[h0 + i]) * gcol[i];
 #pragma unroll
         for (int i = 0; i < E / 2; i += 2) colp[(h0 + i) / 2] = (uint32_t)col[i] | ((uint32_t)col[i + 1] << 16);
         __builtin_amdgcn_sched_barrier(0);
@@ -2136,8 +2090,7 @@ __device__ __forceinline__ void team_member(const SolveView& s, SolveState* __re
     // ---- row owners: r = g, u = M^-1 g, x = p = s = t = 0; (r0, z0) of the JOINT system scales the stopping rules
     float minv = 0.f, r = 0.f, u = 0.f, x = 0.f, pv = 0.f, sv = 0.f, tv = 0.f, w = 0.f, m = 0.f, joint_loc = 0.f;
     if (owner) {
-        const float d = s.diag[a];
-        minv          = d > FLT_EPSILON ? 1.0f / d : 1.0f;
+        minv = jacobi_inv(s.diag[a]);
 #pragma unroll
         for (int cc = 0; cc < 3; ++cc) {
             const float g = s.g[3 * a + cc];
@@ -2206,8 +2159,6 @@ __device__ __forceinline__ void team_member(const SolveView& s, SolveState* __re
     publish(0, epoch0, r * u, w * u, joint_loc, true);
     PROF_MARK(5);  // (prologue's product + first publication)
 
-    const float floor_ = 1e-12f;
-    const float tol2   = pcg_tol * pcg_tol > floor_ ? pcg_tol * pcg_tol : floor_;
     float target = 0.f, gamma_old = 1.f, alpha_old = 1.f;
     int it = 0;
     bool gave_up = false;
@@ -2217,10 +2168,10 @@ __device__ __forceinline__ void team_member(const SolveView& s, SolveState* __re
         if (it == 0) {
             if (!team_wait<true>(words_at(0), round, sm, &ctl->abort[c], TEAM_TICKS_FIRST, bc)) { gave_up = true; break; }
             const float rz0    = sm[2];
-            const bool at_floor = st->grad_first > 0.0 && (double)rz0 <= 1e-12 * st->grad_first;  // the same in every team
+            const bool at_floor = pcg_at_floor(st, rz0);  // the same in every team
             if (tid == 0 && rank == 0) ctl->rz0[c] = rz0, ctl->at_floor[c] = at_floor;
             if (at_floor) break;  // (x = 0: nothing to solve)
-            target = fmaxf(tol2 * rz0, solve_floor(st)) * (1.0f / 3.0f);  // this coordinate's share of the joint target
+            target = pcg_joint_target(st, pcg_tol, rz0) * (1.0f / 3.0f);  // this coordinate's share of the joint target
         } else {
 #ifdef DFA_PCG_PROFILE
             if (!team_wait<false>(words_at(it), round, sm, &ctl->abort[c], TEAM_TICKS, bc, tid == 0 && c == 0 && rank == 0 ? pw_ : nullptr, rank)) { gave_up = true; break; }
@@ -2234,8 +2185,8 @@ __device__ __forceinline__ void team_member(const SolveView& s, SolveState* __re
             gave_up = late_give_up;  // (development builds: a member that gives up behind the last barrier its team passed)
             break;
         }
-        const float beta  = it == 0 ? 0.f : gamma / gamma_old;
-        const float denom = it == 0 ? delta : delta - beta * gamma / alpha_old;
+        const float beta  = cg_beta(it == 0, gamma, gamma_old);
+        const float denom = cg_denom(it == 0, gamma, delta, beta, alpha_old);
         if (!(denom > 0.f)) break;
         const float alpha = gamma / denom;
         {   // the published (m_i, t_(i-1)) of every row -> LDS by plain wide loads (first and only read of round i's area by
@@ -2279,12 +2230,7 @@ __device__ __forceinline__ void team_member(const SolveView& s, SolveState* __re
                     ucol[e0 + 3] = fmaf(-alpha, fmaf(beta, g3.y, g3.x), ucol[e0 + 3]);
                 }
             }
-        if (owner) {
-            pv = fmaf(beta, pv, u), sv = fmaf(beta, sv, w);
-            x  = fmaf(alpha, pv, x), r = fmaf(-alpha, sv, r);
-            tv = fmaf(beta, tv, m);
-            u  = fmaf(-alpha, tv, u);
-        }
+        if (owner) cg_update_row(alpha, beta, u, w, pv, sv, x, r), cg_update_u(alpha, beta, m, tv, u);
         PROF_MARK(2);  // replicas
         w = row_product();  // (its barrier also orders this iteration's reads of mt_s before the next copy)
         m = minv * w;
@@ -2386,8 +2332,7 @@ __global__ __launch_bounds__(1024) void pcg_team_guard_kernel(SolveView s, Solve
         float *rs = (float*)s.mb_r + c, *ps = (float*)s.mb_p + c, *ss = (float*)s.mb_s + c;
         float joint_loc = 0.f;
         for (int a = tid; a < D; a += 1024) {
-            const float d    = s.diag[a];
-            const float minv = d > FLT_EPSILON ? 1.0f / d : 1.0f;
+            const float minv = jacobi_inv(s.diag[a]);
 #pragma unroll
             for (int cc = 0; cc < 3; ++cc) {
                 const float g = s.g[3 * a + cc];
@@ -2398,11 +2343,9 @@ __global__ __launch_bounds__(1024) void pcg_team_guard_kernel(SolveView s, Solve
             u_s[a] = minv * g;
         }
         rz0      = block_sum_f<16>(joint_loc, red0);  // (its barrier publishes u_s)
-        at_floor = st->grad_first > 0.0 && (double)rz0 <= 1e-12 * st->grad_first;
+        at_floor = pcg_at_floor(st, rz0);
         it       = 0;
-        const float floor_ = 1e-12f;
-        const float tol2   = pcg_tol * pcg_tol > floor_ ? pcg_tol * pcg_tol : floor_;
-        const float target = fmaxf(tol2 * rz0, solve_floor(st)) * (1.0f / 3.0f);
+        const float target = pcg_joint_target(st, pcg_tol, rz0) * (1.0f / 3.0f);
         float gamma_old = 1.f, alpha_old = 1.f;
         __syncthreads();
         while (!at_floor && it < max_iter) {
@@ -2424,17 +2367,16 @@ __global__ __launch_bounds__(1024) void pcg_team_guard_kernel(SolveView s, Solve
 #pragma unroll
             for (int i = 0; i < 16; ++i) gamma += red0[i], delta += red1[i];
             if (!(gamma > target)) break;
-            const float beta  = it == 0 ? 0.f : gamma / gamma_old;
-            const float denom = it == 0 ? delta : delta - beta * gamma / alpha_old;
+            const float beta  = cg_beta(it == 0, gamma, gamma_old);
+            const float denom = cg_denom(it == 0, gamma, delta, beta, alpha_old);
             if (!(denom > 0.f)) break;
             const float alpha = gamma / denom;
             for (int a = tid; a < D; a += 1024) {
-                const float d    = s.diag[a];
-                const float minv = d > FLT_EPSILON ? 1.0f / d : 1.0f;
-                const float p = fmaf(beta, ps[4 * a], u_s[a]), sn = fmaf(beta, ss[4 * a], ((float*)s.mb_w)[4 * a + c]);
-                const float rn = fmaf(-alpha, sn, rs[4 * a]);
-                ps[4 * a] = p, ss[4 * a] = sn, xs[4 * a] = fmaf(alpha, p, xs[4 * a]), rs[4 * a] = rn;
-                u_s[a] = minv * rn;  // (own row only; the gathers of this iteration are behind the reduction's barrier)
+                const float minv = jacobi_inv(s.diag[a]);
+                float p = ps[4 * a], sn = ss[4 * a], x = xs[4 * a], r = rs[4 * a];
+                cg_update_row(alpha, beta, u_s[a], ((float*)s.mb_w)[4 * a + c], p, sn, x, r);
+                ps[4 * a] = p, ss[4 * a] = sn, xs[4 * a] = x, rs[4 * a] = r;
+                u_s[a] = minv * r;  // (own row only; the gathers of this iteration are behind the reduction's barrier)
             }
             ++it;
             gamma_old = gamma, alpha_old = alpha;
@@ -2454,20 +2396,7 @@ __global__ __launch_bounds__(1024) void pcg_team_guard_kernel(SolveView s, Solve
                 if (a0 + q * 1024 < D) s.t[3 * (a0 + q * 1024) + c] = tv[q] + xv[q];
         }
     }
-    if (tid == 0) {
-        // iterations of this launch = those of its slowest coordinate; the last workgroup to arrive books them (at the
-        // floor: no iterations, and the mark — the same decision in every coordinate)
-        atomicMax(&st->split_iters, it);
-        __threadfence();
-        if (atomicAdd(&st->split_ticket, 1u) == 2u) {
-            __threadfence();
-            st->pcg_iters += atomicExch(&st->split_iters, 0);
-            st->split_ticket = 0u;
-            if (st->grad_first == 0.0) st->grad_first = (double)rz0;
-            st->gn_iters += 1;
-            if (at_floor) solve_mark_at_floor(st);
-        }
-    }
+    if (tid == 0) pcg_book_launch_of_three(st, rz0, it, at_floor);  // (at the floor: no iterations, and the mark)
 }
 
 // plans the team form can serve: (m, t) of every row + the partial sums in one CU's LDS (Dpad <= 19 584), a member's rows on
@@ -2545,15 +2474,15 @@ static hipError_t allow_big_lds(Kernel* k) {
     return allow_dynamic_lds((const void*)k, 160 * 1024 - 1024);  // once per (device, kernel)
 }
 
-// register-resident kernel: NT threads own 2*P*NT rows, P pairs of E matrix slots per thread
+// register-resident kernel: NT threads own 2*NT rows, a pair of rows in E matrix slots per thread
 // (NC = 3: one workgroup for the joint system; NC = 1: three workgroups, one coordinate each)
-template <int NT, int P, int E, int NC>
+template <int NT, int E, int NC>
 static hipError_t launch_paired_pcg(const SolveView& s, SolveState* state, int max_iter, float pcg_tol,
                                     hipStream_t st) {
-    hipError_t e = allow_big_lds(pcg_paired_kernel<NT, P, E, NC>);
+    hipError_t e = allow_big_lds(pcg_paired_kernel<NT, E, NC>);
     if (e != hipSuccess) return e;
     const size_t sh = sizeof(float4) * (size_t)s.Dpad + 32 * sizeof(float) + sizeof(int) * (260 + (size_t)s.Dpad * (s.deterministic ? 2 : 1));
-    pcg_paired_kernel<NT, P, E, NC><<<NC == 1 ? 3 : 1, NT, sh, st>>>(s, state, max_iter, pcg_tol);
+    pcg_paired_kernel<NT, E, NC><<<NC == 1 ? 3 : 1, NT, sh, st>>>(s, state, max_iter, pcg_tol);
     return hipGetLastError();
 }
 
@@ -2564,28 +2493,33 @@ static hipError_t launch_paired_pcg(const SolveView& s, SolveState* state, int m
 // Development builds (-DDFA_DEV_AB) also hold the forms the tests compare against, selected by DFA_PCG_VARIANT (read at
 // every call: the tests switch it): 1 register-resident with the three coordinates in ONE workgroup (shared CG scalars,
 // as the oracle), 3 many-workgroup at any size.
+// May this plan's PCG take the team form now?  gave_up: it could, but a team of an earlier launch (placement, starvation, a
+// row too long) has said so in pinned memory — no synchronisation: the word is read as it stands.
+// (development builds: DFA_MB_TEAM=0 the launched form, =2 the team form at any size)
+enum class TeamUse { no, yes, gave_up };
+static TeamUse team_pcg_use(const TeamPcg* team, int D, int max_iter) {
+    if (!(team && team->ctl && !team->disabled && solve_team_pcg_fits(D) && max_iter < TEAM_ROUNDS && dev_env_int("DFA_MB_TEAM", 1) != 0))
+        return TeamUse::no;
+    return team->host_abort && *(volatile int*)team->host_abort != 0 ? TeamUse::gave_up : TeamUse::yes;
+}
+
 static hipError_t route_pcg(const SolveView& s, SolveState* state, int max_iter, float pcg_tol, int* host_flag, MbGraphCache* gc,
                             TeamPcg* team, hipEvent_t& main_done, hipStream_t st) {
     const int D = s.D;
 #ifdef DFA_DEV_AB
     const int v2 = dev_env_int("DFA_PCG_VARIANT", -1);
-    if (dev_env_int("DFA_MB_TEAM", 1) == 2 && team && team->ctl && !team->disabled && solve_team_pcg_fits(D) && max_iter < TEAM_ROUNDS &&
-        !(team->host_abort && *(volatile int*)team->host_abort != 0))
+    if (dev_env_int("DFA_MB_TEAM", 1) == 2 && team_pcg_use(team, D, max_iter) == TeamUse::yes)
         return launch_team_pcg(s, state, max_iter, pcg_tol, team, st);
     if (v2 == 3) return launch_mb_pcg(s, state, max_iter, pcg_tol, host_flag, gc, st);
-    if (v2 == 1 && D <= 1024) return launch_paired_pcg<512, 1, 64, 3>(s, state, max_iter, pcg_tol, st);
-    if (v2 == 1 && D <= 2048) return launch_paired_pcg<1024, 1, 32, 3>(s, state, max_iter, pcg_tol, st);
+    if (v2 == 1 && D <= 1024) return launch_paired_pcg<512, 64, 3>(s, state, max_iter, pcg_tol, st);
+    if (v2 == 1 && D <= 2048) return launch_paired_pcg<1024, 32, 3>(s, state, max_iter, pcg_tol, st);
 #endif
     // 512 threads leave 256 VGPRs per lane (64 slots per row pair: k = 8 rows fit), 1024 threads 128 VGPRs (32 slots: k = 4)
-    if (D <= 1024) return launch_paired_pcg<512, 1, 64, 1>(s, state, max_iter, pcg_tol, st);
-    if (D <= 2048) return launch_paired_pcg<1024, 1, 32, 1>(s, state, max_iter, pcg_tol, st);
-    // (development builds: DFA_MB_TEAM=0 the launched form, =2 the team form at any size)
-    if (team && team->ctl && !team->disabled && solve_team_pcg_fits(D) && max_iter < TEAM_ROUNDS && dev_env_int("DFA_MB_TEAM", 1) != 0) {
-        // a team that gave up in an earlier launch (placement, starvation, a row too long) has said so in pinned memory: from
-        // then on this plan takes the launched form (no synchronisation: the word is read as it stands)
-        if (team->host_abort && *(volatile int*)team->host_abort != 0) team->disabled = true;
-        else return launch_team_pcg(s, state, max_iter, pcg_tol, team, st);
-    }
+    if (D <= 1024) return launch_paired_pcg<512, 64, 1>(s, state, max_iter, pcg_tol, st);
+    if (D <= 2048) return launch_paired_pcg<1024, 32, 1>(s, state, max_iter, pcg_tol, st);
+    const TeamUse use = team_pcg_use(team, D, max_iter);
+    if (use == TeamUse::yes) return launch_team_pcg(s, state, max_iter, pcg_tol, team, st);
+    if (use == TeamUse::gave_up) team->disabled = true;  // from then on this plan takes the launched form
     return launch_mb_pcg(s, state, max_iter, pcg_tol, host_flag, gc, st);
 }
 
@@ -2593,9 +2527,7 @@ static hipError_t route_pcg(const SolveView& s, SolveState* state, int max_iter,
 // launched many-workgroup form reads its stop flag back once per chunk of launches — and the plan's `converged` flag with it.
 bool solve_pcg_is_async(const SolveView& s, const TeamPcg* team, int max_iter) {
     if (s.D <= 2048) return dev_env_int("DFA_PCG_VARIANT", -1) != 3;
-    return team && team->ctl && !team->disabled && solve_team_pcg_fits(s.D) && max_iter < TEAM_ROUNDS &&
-           dev_env_int("DFA_MB_TEAM", 1) != 0 && dev_env_int("DFA_PCG_VARIANT", -1) != 3 &&
-           !(team->host_abort && *(volatile int*)team->host_abort != 0);
+    return dev_env_int("DFA_PCG_VARIANT", -1) != 3 && team_pcg_use(team, s.D, max_iter) == TeamUse::yes;
 }
 
 hipError_t solve_pcg(const SolveView& s, SolveState* state, int max_iter, float pcg_tol, int* host_flag, MbGraphCache* gc,

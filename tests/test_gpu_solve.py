@@ -627,7 +627,7 @@ def _threads():
 @pytest.mark.parametrize("name,noise", [("C2", 0.0), ("C2", 1e-3), ("C3", 0.0), ("C3", 1e-3), ("C4", 0.0)])
 def test_translations_match_oracle_at_baseline_sizes(A, name, noise):
     """One frame of BASELINE config C2 (2 048 nodes, k = 4, 262 144 vertices: the headline's own kernel instantiation,
-    pcg_paired_kernel<1024,1,32,1>), of C3 (4 096 nodes, k = 8, 524 288 vertices) and of C4 (8 192 nodes, 1 048 576
+    pcg_paired_kernel<1024,32,1>), of C3 (4 096 nodes, k = 8, 524 288 vertices) and of C4 (8 192 nodes, 1 048 576
     vertices: both the team PCG, pcg_team_kernel — three teams of persistent workgroups, a coordinate per XCD) with
     bench.py's parameters — 5 / 10 outer iterations, PCG <= 256 at 1e-6, lambda = 200 — HIP against the fp64 statement
     (O.solve_ref(use_double=True): energy.t:50-55, opt_solver.cpp:204-231): node translations within 2e-5 m, energies
