@@ -747,12 +747,13 @@ __global__ __launch_bounds__(256) void assemble_kernel(SolveView s, SolveState* 
 }
 
 // ------------------------------------------------------------------------------------------
-// Order-stable variant (SolveView::deterministic).  Three things make two runs of the default path differ in the last
-// bits: the transposition fills a node's row list in the order its LDS cursor atomics land, the assembly above adds
-// into LDS with float atomics from four waves and compacts the hash in slot order (which depends on who inserted a key
-// first), and the PCG kernels place rows of equal length by an atomic cursor (which thread owns which row decides the
-// order of the inner products' partial sums).  Here: lists sorted, per-wave private sums added in wave order, rows of
-// the matrix sorted by column, equal-length rows in index order.
+// Order-stable variant (SolveView::deterministic).  Both assemblies sum the off-diagonal entries on the fixed-point grid
+// and write every row in ascending column order: those bits are the same (tests/test_gpu_pcg_sorted_rows.py).  Three
+// things still make two runs of the default path differ in the last bits: the transposition fills a node's row list in
+// the order its LDS cursor atomics land, and that order feeds the float sums of the gradient and the diagonal; the
+// diagonal's four wave sums are added in float here, on the fixed-point grid above; and the PCG kernels place rows of
+// equal length by an atomic cursor (which thread owns which row decides the order of the inner products' partial
+// sums).  Here: lists sorted, float sums per wave added in wave order, equal-length rows in index order.
 constexpr int DET_SORT_MAX = 4096;
 
 __global__ __launch_bounds__(256) void sort_node_lists_kernel(const int32_t* __restrict__ node_ptr, uint32_t* __restrict__ node_list) {
@@ -1698,7 +1699,6 @@ __device__ __forceinline__ float group16_sum(float v) {
 // Same iterates as the textbook form in exact arithmetic; the stopping rules are evaluated on gamma = (r, M^-1 r).
 __global__ __launch_bounds__(256) void pcg_mb_step_kernel(SolveView s, SolveState* __restrict__ st, int it, float pcg_tol) {
     __shared__ float sh[2][4];
-    __shared__ float scal[2];
     const int nb  = solve_mb_blocks(s.D);
     const int cur = it >= 0 ? (it & 1) : 0, nxt = cur ^ 1;  // u, m: read [cur], write [nxt]; t: read [nxt], write [cur]
     const float4* ucur  = s.mb_u[cur];
@@ -1804,7 +1804,6 @@ __global__ __launch_bounds__(256) void pcg_mb_step_kernel(SolveView s, SolveStat
         s.mb_gpart[slot][blockIdx.x] = (sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3]);
         s.mb_dpart[slot][blockIdx.x] = (sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3]);
     }
-    (void)scal;
 }
 
 // t += delta and the counters the single-workgroup kernels keep
