@@ -9,7 +9,7 @@ _LIB = None
 # every symbol include/dynfu_amd.h declares (tests/test_capi_symbols.py checks the .so exports them)
 SYMBOLS = [
     "dfa_last_error", "dfa_version", "dfa_abi_version", "dfa_abi_struct_size", "dfa_compute_dists", "dfa_tsdf_clear", "dfa_tsdf_integrate",
-    "dfa_tsdf_clear_integrate", "dfa_tsdf_raycast_points", "dfa_tsdf_raycast_depth", "dfa_tsdf_raycast_tally", "dfa_tsdf_vertex_normals", "dfa_tsdf_extract_cloud", "dfa_tsdf_extract_cloud_occ", "dfa_tsdf_extract_normals", "dfa_correspond_projective", "dfa_knn", "dfa_warp_to_live",
+    "dfa_tsdf_clear_integrate", "dfa_tsdf_raycast_points", "dfa_tsdf_raycast_depth", "dfa_tsdf_raycast_tally", "dfa_tsdf_raycast_render", "dfa_render_image_points", "dfa_render_image_depth", "dfa_render_tangent_colors", "dfa_tsdf_vertex_normals", "dfa_tsdf_extract_cloud", "dfa_tsdf_extract_cloud_occ", "dfa_tsdf_extract_normals", "dfa_correspond_projective", "dfa_knn", "dfa_warp_to_live",
     "dfa_calc_dqb", "dfa_unsupported_vertices", "dfa_icp_sums", "dfa_repack_points", "dfa_compact_points", "dfa_transform_points", "dfa_warp_to_live_graph",
     "dfa_correspond", "dfa_marching_cubes", "dfa_mc_default_tables",
     "dfa_tsdf_occupancy_bytes", "dfa_tsdf_clear_occ", "dfa_tsdf_integrate_occ", "dfa_tsdf_clear_integrate_occ", "dfa_tsdf_clear_integrate_known_occ", "dfa_marching_cubes_occ",
@@ -166,6 +166,10 @@ def load(path=None):
     L.dfa_tsdf_raycast_points.argtypes = ray
     L.dfa_tsdf_raycast_depth.argtypes = ray
     L.dfa_tsdf_raycast_tally.argtypes = [vp, i, i, i, vp, f, vp, vp, f, f, f, f, f, f, i, i, vp, vp, vp]
+    L.dfa_tsdf_raycast_render.argtypes = [vp, i, i, i, vp, f, vp, vp, f, f, f, f, f, f, i, i, vp, i, vp, i, vp]
+    L.dfa_render_image_points.argtypes = [vp, i, vp, i, i, i, vp, vp, i, vp]
+    L.dfa_render_image_depth.argtypes = [vp, i, vp, i, i, i, f, f, f, f, vp, vp, i, vp]
+    L.dfa_render_tangent_colors.argtypes = [vp, i, i, i, vp, i, vp]
     L.dfa_tsdf_vertex_normals.argtypes = [vp, i, i, i, vp, f, vp, i, vp, vp]
     L.dfa_tsdf_extract_cloud.argtypes = [vp, i, i, i, vp, vp, vp, i, vp, vp]
     L.dfa_tsdf_extract_cloud_occ.argtypes = [vp, vp, i, i, i, vp, vp, vp, i, vp, vp]
@@ -363,6 +367,56 @@ def tsdf_raycast_depth(vol, voxel_size, trunc, cam2vol, Rinv, fx, fy, cx, cy, st
                                          delta_factor, _dev(depth, torch.uint16, "depth"), depth.stride(0) * 2,
                                          _dev(normals, torch.float32, "normals"), normals.stride(0) * 4, cols, rows,
                                          _stream()))
+
+
+RENDER_PHONG, RENDER_NORMALS, RENDER_BOTH = 0, 1, 2  # dfa_tsdf_raycast_render's mode (include/dynfu_amd.h)
+
+
+def _image(image, cols, rows):
+    """(rows, cols, 4) uint8 pixels b, g, r, 0 — a view with a row stride is a pitched image"""
+    torch = _torch()
+    if image.dim() != 3 or tuple(image.shape) != (rows, cols, 4) or image.stride(2) != 1 or image.stride(1) != 4:
+        raise DynfuAmdError("image must be a (%d, %d, 4) uint8 tensor of packed pixels" % (rows, cols))
+    return _dev(image, torch.uint8, "image"), image.stride(0)
+
+
+def render_image_points(points, normals, light_pose, image):
+    """Phong view of a float4 point map and its normal map into `image` ((rows, cols, 4) uint8: b, g, r, 0)"""
+    torch = _torch()
+    rows, cols = points.shape[:2]
+    img, step = _image(image, cols, rows)
+    _check(load().dfa_render_image_points(_dev(points, torch.float32, "points"), points.stride(0) * 4,
+                                          _dev(normals, torch.float32, "normals"), normals.stride(0) * 4, cols, rows,
+                                          _farr(light_pose, 3), img, step, _stream()))
+
+
+def render_image_depth(depth, normals, fx, fy, cx, cy, light_pose, image):
+    """Phong view of a u16 millimetre depth map and a float4 normal map"""
+    torch = _torch()
+    rows, cols = depth.shape[:2]
+    img, step = _image(image, cols, rows)
+    _check(load().dfa_render_image_depth(_dev(depth, torch.uint16, "depth"), depth.stride(0) * 2,
+                                         _dev(normals, torch.float32, "normals"), normals.stride(0) * 4, cols, rows, fx, fy,
+                                         cx, cy, _farr(light_pose, 3), img, step, _stream()))
+
+
+def render_tangent_colors(normals, image):
+    """the normal map as colours"""
+    torch = _torch()
+    rows, cols = normals.shape[:2]
+    img, step = _image(image, cols, rows)
+    _check(load().dfa_render_tangent_colors(_dev(normals, torch.float32, "normals"), normals.stride(0) * 4, cols, rows, img,
+                                            step, _stream()))
+
+
+def tsdf_raycast_render(vol, voxel_size, trunc, cam2vol, Rinv, fx, fy, cx, cy, step_factor, delta_factor, cols, rows,
+                        light_pose, mode, image):
+    """raycast + shade in one launch; `image` is (rows, cols, 4) uint8, (rows, 2 * cols, 4) for RENDER_BOTH"""
+    X, Y, Z = _vol_dims(vol)
+    img, step = _image(image, cols * (2 if mode == RENDER_BOTH else 1), rows)
+    _check(load().dfa_tsdf_raycast_render(_dev(vol), X, Y, Z, _farr(voxel_size, 3), trunc, _aff12(cam2vol),
+                                          _farr(list(map(float, _flat(Rinv))), 9), fx, fy, cx, cy, step_factor,
+                                          delta_factor, cols, rows, _farr(light_pose, 3), int(mode), img, step, _stream()))
 
 
 def tsdf_raycast_tally(vol, voxel_size, trunc, cam2vol, Rinv, fx, fy, cx, cy, step_factor, delta_factor, cols, rows,

@@ -413,6 +413,70 @@ int dfa_tsdf_raycast_tally(const uint32_t* volume, int X, int Y, int Z, const fl
     return DFA_OK;
 }
 
+// -------------------------------------------------------------------- render seam
+
+int dfa_render_image_points(const float* points, int points_step, const float* normals, int normals_step, int cols, int rows,
+                            const float light_pose[3], uint8_t* image, int image_step, dfa_stream_t stream) {
+    REQUIRE(points && normals && image, "null image");
+    REQUIRE(cols > 0 && rows > 0, "non-positive image size");
+    REQUIRE(points_step >= cols * 16 && normals_step >= cols * 16, "row step smaller than a float4 row");
+    REQUIRE(image_step >= cols * 4, "row step smaller than a pixel row");
+    REQUIRE(light_pose, "null light pose");
+    REQUIRE((((uintptr_t)points | (uintptr_t)normals | (uintptr_t)points_step | (uintptr_t)normals_step) & 15) == 0,
+            "points / normals rows must be 16-byte aligned");
+    REQUIRE((((uintptr_t)image | (uintptr_t)image_step) & 3) == 0, "image rows must be 4-byte aligned");
+    HIP_TRY(dfa::launch_render_points(points, points_step, normals, normals_step, cols, rows, light_pose, image, image_step,
+                                      S(stream)));
+    return DFA_OK;
+}
+
+int dfa_render_image_depth(const uint16_t* depth, int depth_step, const float* normals, int normals_step, int cols, int rows,
+                           float fx, float fy, float cx, float cy, const float light_pose[3], uint8_t* image, int image_step,
+                           dfa_stream_t stream) {
+    REQUIRE(depth && normals && image, "null image");
+    REQUIRE(cols > 0 && rows > 0, "non-positive image size");
+    REQUIRE(depth_step >= cols * 2 && normals_step >= cols * 16, "row step smaller than a row");
+    REQUIRE(image_step >= cols * 4, "row step smaller than a pixel row");
+    REQUIRE(light_pose, "null light pose");
+    REQUIRE((((uintptr_t)depth | (uintptr_t)depth_step) & 1) == 0, "depth rows must be 2-byte aligned");
+    REQUIRE((((uintptr_t)normals | (uintptr_t)normals_step) & 15) == 0, "normals rows must be 16-byte aligned");
+    REQUIRE((((uintptr_t)image | (uintptr_t)image_step) & 3) == 0, "image rows must be 4-byte aligned");
+    HIP_TRY(dfa::launch_render_depth(depth, depth_step, normals, normals_step, cols, rows, fx, fy, cx, cy, light_pose, image,
+                                     image_step, S(stream)));
+    return DFA_OK;
+}
+
+int dfa_render_tangent_colors(const float* normals, int normals_step, int cols, int rows, uint8_t* image, int image_step,
+                              dfa_stream_t stream) {
+    REQUIRE(normals && image, "null image");
+    REQUIRE(cols > 0 && rows > 0, "non-positive image size");
+    REQUIRE(normals_step >= cols * 16, "row step smaller than a float4 row");
+    REQUIRE(image_step >= cols * 4, "row step smaller than a pixel row");
+    REQUIRE((((uintptr_t)normals | (uintptr_t)normals_step) & 15) == 0, "normals rows must be 16-byte aligned");
+    REQUIRE((((uintptr_t)image | (uintptr_t)image_step) & 3) == 0, "image rows must be 4-byte aligned");
+    HIP_TRY(dfa::launch_tangent_colors(normals, normals_step, cols, rows, image, image_step, S(stream)));
+    return DFA_OK;
+}
+
+int dfa_tsdf_raycast_render(const uint32_t* volume, int X, int Y, int Z, const float voxel_size[3], float trunc_dist,
+                            const float cam2vol[12], const float Rinv[9], float fx, float fy, float cx, float cy,
+                            float step_factor, float delta_factor, int cols, int rows, const float light_pose[3], int mode,
+                            uint8_t* image, int image_step, dfa_stream_t stream) {
+    REQUIRE(image, "null image");
+    REQUIRE(volume_args_ok(volume, X, Y, Z), "bad volume");
+    REQUIRE(X >= 2 && Y >= 2 && Z >= 2, "volume needs at least 2 voxels per axis");
+    REQUIRE(cols > 0 && rows > 0, "non-positive image size");
+    REQUIRE(mode == DFA_RENDER_PHONG || mode == DFA_RENDER_NORMALS || mode == DFA_RENDER_BOTH, "unknown render mode");
+    REQUIRE(cols <= 0x1fffffff / (mode == DFA_RENDER_BOTH ? 2 : 1) && image_step >= cols * 4 * (mode == DFA_RENDER_BOTH ? 2 : 1),
+            "row step smaller than a pixel row");
+    REQUIRE((((uintptr_t)image | (uintptr_t)image_step) & 3) == 0, "image rows must be 4-byte aligned");
+    REQUIRE(voxel_size && cam2vol && Rinv && light_pose, "null parameter block");
+    REQUIRE(trunc_dist > 0.f && step_factor > 0.f, "non-positive ray step");
+    HIP_TRY(dfa::launch_raycast_render(volume, X, Y, Z, voxel_size, trunc_dist, cam2vol, Rinv, fx, fy, cx, cy, step_factor,
+                                       delta_factor, cols, rows, light_pose, mode, image, image_step, S(stream)));
+    return DFA_OK;
+}
+
 // -------------------------------------------------------------------- depth pre-processing seam
 
 int dfa_depth_bilateral_filter(const uint16_t* src, int src_step, uint16_t* dst, int dst_step, int cols, int rows,

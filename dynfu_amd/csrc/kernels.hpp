@@ -122,6 +122,19 @@ hipError_t launch_extract_normals(const uint32_t* vol, int X, int Y, int Z, cons
                                   const float Rinv[9], float delta_factor, const float* points, int n, float* normals,
                                   hipStream_t s);
 
+// render.hip — the Phong / normal-colour views (kfusion imgproc.cu:363-514) and the raycast fused with them
+hipError_t launch_render_points(const float* points, int points_step, const float* normals, int normals_step, int cols,
+                                int rows, const float light[3], uint8_t* image, int image_step, hipStream_t s);
+hipError_t launch_render_depth(const uint16_t* depth, int depth_step, const float* normals, int normals_step, int cols,
+                               int rows, float fx, float fy, float cx, float cy, const float light[3], uint8_t* image,
+                               int image_step, hipStream_t s);
+hipError_t launch_tangent_colors(const float* normals, int normals_step, int cols, int rows, uint8_t* image, int image_step,
+                                 hipStream_t s);
+hipError_t launch_raycast_render(const uint32_t* vol, int X, int Y, int Z, const float voxel_size[3], float trunc_dist,
+                                 const float cam2vol[12], const float Rinv[9], float fx, float fy, float cx, float cy,
+                                 float step_factor, float delta_factor, int cols, int rows, const float light[3], int mode,
+                                 uint8_t* image, int image_step, hipStream_t s);
+
 // img.hip
 hipError_t launch_bilateral(const uint16_t* src, int src_step, uint16_t* dst, int dst_step, int cols, int rows, int ksz,
                             float sigma_spatial, float sigma_depth, hipStream_t s);

@@ -72,6 +72,9 @@ class DeviceArray2D {
 public:
     DeviceArray2D() : rows_(0), cols_(0), step_(0) {}
     DeviceArray2D(int rows, int cols) { create(rows, cols); }
+    // non-owning window over user memory (device_array.hpp: DeviceArray2D(rows, cols, data, stepBytes))
+    DeviceArray2D(int rows, int cols, T* ptr, size_t step_bytes)
+        : mem_((void*)ptr, step_bytes * (size_t)rows), rows_(rows), cols_(cols), step_(step_bytes) {}
     void create(int rows, int cols) {
         if (rows == rows_ && cols == cols_ && !mem_.empty()) return;
         rows_ = rows, cols_ = cols;

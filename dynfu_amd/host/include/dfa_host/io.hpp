@@ -40,6 +40,11 @@ DepthImage decodeDepthPng(const uint8_t* bytes, size_t size);
 std::vector<uint8_t> encodeDepthPng(const uint16_t* pixels, int cols, int rows);
 void writeDepthPng(const std::string& path, const uint16_t* pixels, int cols, int rows);
 
+// A rendered image (kfusion::RGB pixels: the bytes b, g, r, 0; `step_bytes` per row, 0 = dense) as an 8-bit RGB PNG:
+// colour type 2, filter 0, one IDAT.  What KinFu::renderImage produces, in a form any viewer opens.
+std::vector<uint8_t> encodeImagePng(const uint8_t* bgr0, int cols, int rows, size_t step_bytes = 0);
+void writeImagePng(const std::string& path, const uint8_t* bgr0, int cols, int rows, size_t step_bytes = 0);
+
 // files of <dir>/depth and <dir>/color, each sorted lexicographically (cv::glob + std::sort, demo.cpp:39-55);
 // throws if <dir>, <dir>/depth or <dir>/color is missing (the demo exits there)
 struct SequenceFiles {

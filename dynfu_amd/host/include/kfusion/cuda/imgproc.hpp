@@ -10,7 +10,12 @@
 //   computePointNormals           dfa_compute_points_normals          points_normals_kernel :187
 //   resizeDepthNormals            dfa_resize_depth_normals            resize_depth_normals_kernel :258
 //   resizePointsNormals           dfa_resize_points_normals           resize_points_normals_kernel :314
-//   (computeDists, waitAllDefaultStream: kfusion/types.hpp; renderImage / renderTangentColors: visualisation, absent)
+//   renderImage (points)          dfa_render_image_points             render_image_kernel :413
+//   renderImage (depth)           dfa_render_image_depth              render_image_kernel :363
+//   renderTangentColors           dfa_render_tangent_colors           tangent_colors_kernel :485
+//   (computeDists, waitAllDefaultStream: kfusion/types.hpp)
+// The render functions write into the image they are given when it already has the maps' size — it may be a window of
+// a wider image (KinFu::renderImage's side-by-side view) — and create it otherwise.
 #pragma once
 #include <kfusion/types.hpp>
 
@@ -29,6 +34,11 @@ void computeNormalsAndMaskDepth(const Intr& intr, Depth& depth /* masked in plac
 void depthBuildPyramid(const Depth& depth, Depth& pyramid, float sigma_depth);
 void resizePointsNormals(const Cloud& points, const Normals& normals, Cloud& points_out, Normals& normals_out);
 void resizeDepthNormals(const Depth& depth, const Normals& normals, Depth& depth_out, Normals& normals_out);
+
+// views of a model (include/kfusion/cuda/imgproc.hpp:26-33): pixels b, g, r, 0; light_pose in the camera frame
+void renderTangentColors(const Normals& normals, Image& image);
+void renderImage(const Depth& depth, const Normals& normals, const Intr& intr, const Vec3f& light_pose, Image& image);
+void renderImage(const Cloud& points, const Normals& normals, const Intr& intr, const Vec3f& light_pose, Image& image);
 
 }  // namespace cuda
 }  // namespace kfusion

@@ -58,6 +58,10 @@ public:
     void clearAndIntegrate(const Dists& dists, const Affine3f& camera_pose, const Intr& intr);
     virtual void raycast(const Affine3f& camera_pose, const Intr& intr, Depth& depth, Normals& normals);
     virtual void raycast(const Affine3f& camera_pose, const Intr& intr, Cloud& points, Normals& normals);
+    // the rays of raycast(points) shaded in the same launch (dfa_tsdf_raycast_render; KinFu::renderImage(image, pose, flag)):
+    // `image` must hold rows x cols pixels, rows x 2 cols for DFA_RENDER_BOTH.  Extension of the reference's interface.
+    void raycastRender(const Affine3f& camera_pose, const Intr& intr, int cols, int rows, const Vec3f& light_pose, int mode,
+                       Image& image) const;
     virtual void applyAffine(const Affine3f& affine) { cfg_.pose = affine * cfg_.pose; }
     // the zero crossings on the voxel edges, in the world frame (pose), as float4 {x, y, z, 0} (tsdf_volume.hpp:49,
     // tsdf_volume.cpp:131-147): an empty buffer is created with 10 000 000 points; returns a non-owning array over the

@@ -5,7 +5,7 @@
 //   -> pose chain -> clear + integrate -> raycast the model from the new pose -> down-sampled model maps.
 // Every device step is one call of the dynfu_amd C ABI through the adaptor functions of kfusion/cuda/*.hpp; the class
 // itself is host control flow.  Built is the reference's default compile path (point maps; `USE_DEPTH` undefined).
-// Not here: renderImage / the light pose (visualisation) and the colour image argument (never read, kinfu.cpp:140).
+// Not here: the colour image argument (never read, kinfu.cpp:140).
 #pragma once
 #include <memory>
 #include <vector>
@@ -18,8 +18,7 @@
 
 namespace kfusion {
 
-// kfusion::KinFuParams (include/kfusion/kinfu.hpp:33-61, defaults src/kfusion/kinfu.cpp:10-44) without the light pose
-// (rendering)
+// kfusion::KinFuParams (include/kfusion/kinfu.hpp:33-61, defaults src/kfusion/kinfu.cpp:10-44)
 struct KinFuParams {
     static KinFuParams default_params();
     int cols, rows;
@@ -36,6 +35,7 @@ struct KinFuParams {
     float tsdf_trunc_dist;
     int tsdf_max_weight;
     float raycast_step_factor, gradient_delta_factor;
+    Vec3f light_pose;  // the light of renderImage, in the camera frame; default the camera itself (kinfu.cpp:41)
 };
 
 class KinFu {
@@ -54,6 +54,16 @@ public:
 
     // kinfu.cpp:140-234.  false for the first two frames and after a lost track (which resets), true afterwards.
     bool operator()(const cuda::Depth& depth);
+
+    // Views of the model as an image of b, g, r, 0 pixels (kinfu.cpp:264-316).  flag 2: the normals as colours; flag 3: the
+    // Phong view and the normal colours side by side, 2 * cols wide; any other flag: the Phong view, lit from
+    // params().light_pose.  The one deliberate deviation from the reference: there flag == 1 falls into the side-by-side
+    // branch with an image only `cols` wide and writes past the end of every row; here it renders the Phong view.
+    //   renderImage(image, flag)        the model maps the tracker aligns against (prev_, level 0): what the last
+    //                                   operator() raycast; throws before one has (DynFusion keeps no such maps)
+    //   renderImage(image, pose, flag)  the volume seen from `pose`, raycast and shaded in one launch
+    void renderImage(cuda::Image& image, int flag = 0);
+    void renderImage(cuda::Image& image, const Affine3f& pose, int flag = 0);
 
     // marching cubes of the current volume in KinFu::convertToMesh's layout (:236-262)
     std::shared_ptr<dfa::PolygonMesh> extractMesh();

@@ -12,12 +12,21 @@ struct Point {  // include/kfusion/types.hpp:27-34
     float x, y, z, w;
 };
 typedef Point Normal;
+struct RGB {  // :38-45: a pixel of a rendered image, the bytes b, g, r, 0
+    union {
+        struct {
+            unsigned char b, g, r;
+        };
+        int bgra;
+    };
+};
 namespace cuda {
 typedef dfa::DeviceMemory CudaData;                // :51
 typedef dfa::DeviceArray2D<unsigned short> Depth;  // :52
 typedef dfa::DeviceArray2D<unsigned short> Dists;  // :53
-typedef dfa::DeviceArray2D<Normal> Normals;        // :55
-typedef dfa::DeviceArray2D<Point> Cloud;           // :56
+typedef dfa::DeviceArray2D<RGB> Image;             // :55
+typedef dfa::DeviceArray2D<Normal> Normals;        // :56
+typedef dfa::DeviceArray2D<Point> Cloud;           // :57
 // cuda::computeDists (src/kfusion/imgproc.cpp:38-41)
 void computeDists(const Depth& depth, Dists& dists, const Intr& intr);
 // cuda::waitAllDefaultStream

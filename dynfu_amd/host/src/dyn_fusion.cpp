@@ -27,6 +27,7 @@ kfusion::KinFuParams kfusion::KinFuParams::default_params() {  // src/kfusion/ki
     p.tsdf_min_camera_movement = 0.f;
     p.tsdf_trunc_dist = 0.04f, p.tsdf_max_weight = 64;
     p.raycast_step_factor = 0.75f, p.gradient_delta_factor = 0.5f;
+    p.light_pose = Vec3f::all(0.f);  // :41
     return p;
 }
 

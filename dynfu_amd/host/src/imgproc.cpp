@@ -60,5 +60,28 @@ void resizePointsNormals(const Cloud& points, const Normals& normals, Cloud& poi
                "resizePointsNormals");
 }
 
+void renderTangentColors(const Normals& normals, Image& image) {  // imgproc.cpp:79-83
+    image.create(normals.rows(), normals.cols());
+    dfa::check(dfa_render_tangent_colors((const float*)normals.ptr(), (int)normals.step(), normals.cols(), normals.rows(),
+                                         (uint8_t*)image.ptr(), (int)image.step(), nullptr),
+               "renderTangentColors");
+}
+
+void renderImage(const Depth& depth, const Normals& normals, const Intr& intr, const Vec3f& light_pose, Image& image) {  // :68-72
+    image.create(depth.rows(), depth.cols());
+    dfa::check(dfa_render_image_depth(depth.ptr(), (int)depth.step(), (const float*)normals.ptr(), (int)normals.step(),
+                                      depth.cols(), depth.rows(), intr.fx, intr.fy, intr.cx, intr.cy, light_pose.v,
+                                      (uint8_t*)image.ptr(), (int)image.step(), nullptr),
+               "renderImage(depth)");
+}
+
+void renderImage(const Cloud& points, const Normals& normals, const Intr&, const Vec3f& light_pose, Image& image) {  // :74-77
+    image.create(points.rows(), points.cols());
+    dfa::check(dfa_render_image_points((const float*)points.ptr(), (int)points.step(), (const float*)normals.ptr(),
+                                       (int)normals.step(), points.cols(), points.rows(), light_pose.v, (uint8_t*)image.ptr(),
+                                       (int)image.step(), nullptr),
+               "renderImage(points)");
+}
+
 }  // namespace cuda
 }  // namespace kfusion

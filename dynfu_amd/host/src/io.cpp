@@ -149,6 +149,35 @@ void writeDepthPng(const std::string& path, const uint16_t* px, int cols, int ro
     if (!f.write((const char*)bytes.data(), (std::streamsize)bytes.size())) bad("cannot write " + path);
 }
 
+std::vector<uint8_t> encodeImagePng(const uint8_t* px, int cols, int rows, size_t step) {
+    if (!px || cols <= 0 || rows <= 0) bad("empty image");
+    if (step == 0) step = (size_t)cols * 4;
+    if (step < (size_t)cols * 4) bad("row step smaller than a pixel row");
+    std::vector<uint8_t> raw;
+    raw.reserve(((size_t)cols * 3 + 1) * rows);
+    for (int y = 0; y < rows; ++y) {
+        const uint8_t* row = px + (size_t)y * step;
+        raw.push_back(0);  // filter type None
+        for (int x = 0; x < cols; ++x) raw.push_back(row[4 * x + 2]), raw.push_back(row[4 * x + 1]), raw.push_back(row[4 * x]);  // r, g, b
+    }
+    std::vector<uint8_t> z(compressBound((uLong)raw.size()));
+    uLongf zn = (uLongf)z.size();
+    if (compress2(z.data(), &zn, raw.data(), (uLong)raw.size(), 6) != Z_OK) bad("deflate failed");
+    z.resize(zn);
+    std::vector<uint8_t> out(PNG_SIG, PNG_SIG + 8), ihdr;
+    put32(ihdr, (uint32_t)cols), put32(ihdr, (uint32_t)rows);
+    const uint8_t tail[5] = {8, 2, 0, 0, 0};  // 8 bits, truecolour, deflate, adaptive filtering, no interlace
+    ihdr.insert(ihdr.end(), tail, tail + 5);
+    chunk(out, "IHDR", ihdr), chunk(out, "IDAT", z), chunk(out, "IEND", {});
+    return out;
+}
+
+void writeImagePng(const std::string& path, const uint8_t* px, int cols, int rows, size_t step) {
+    const std::vector<uint8_t> bytes = encodeImagePng(px, cols, rows, step);
+    std::ofstream f(path, std::ios::binary);
+    if (!f.write((const char*)bytes.data(), (std::streamsize)bytes.size())) bad("cannot write " + path);
+}
+
 SequenceFiles listSequence(const std::string& dir) {
     namespace fs = std::filesystem;
     if (!fs::exists(dir)) throw Error(1, "Directory '" + dir + "' does not exist");  // demo.cpp:40-43

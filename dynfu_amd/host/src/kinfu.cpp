@@ -75,6 +75,29 @@ bool KinFu::operator()(const cuda::Depth& depth) {
     return ++frame_counter_, true;
 }
 
+void KinFu::renderImage(cuda::Image& image, int flag) {  // :264-287
+    const KinFuParams& p = params_;
+    const cuda::Cloud& points    = prev_.points_pyr[0];
+    const cuda::Normals& normals = prev_.normals_pyr[0];
+    if (points.empty() || normals.empty() || points.rows() != p.rows || points.cols() != p.cols)
+        throw dfa::Error(DFA_ERR_INVALID, "KinFu::renderImage: no model maps yet (use renderImage(image, pose, flag))");
+    image.create(p.rows, flag != 3 ? p.cols : p.cols * 2);  // :266
+    if (flag == 2) cuda::renderTangentColors(normals, image);
+    else if (flag != 3) cuda::renderImage(points, normals, p.intr, p.light_pose, image);  // (flag == 1: see the header)
+    else {
+        cuda::Image i1(p.rows, p.cols, image.ptr(), image.step()), i2(p.rows, p.cols, image.ptr() + p.cols, image.step());  // :280-281
+        cuda::renderImage(points, normals, p.intr, p.light_pose, i1);
+        cuda::renderTangentColors(normals, i2);
+    }
+}
+
+void KinFu::renderImage(cuda::Image& image, const Affine3f& pose, int flag) {  // :289-316, without points_ / normals_
+    const KinFuParams& p = params_;
+    image.create(p.rows, flag != 3 ? p.cols : p.cols * 2);  // :291
+    const int mode = flag == 2 ? DFA_RENDER_NORMALS : flag == 3 ? DFA_RENDER_BOTH : DFA_RENDER_PHONG;
+    volume_->raycastRender(pose, p.intr, p.cols, p.rows, p.light_pose, mode, image);
+}
+
 std::shared_ptr<dfa::PolygonMesh> KinFu::extractMesh() {
     dfa::DeviceArray<cuda::MarchingCubes::PointType> buffer;
     auto triangles = mc_->run(*volume_, buffer);

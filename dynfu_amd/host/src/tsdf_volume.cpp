@@ -92,6 +92,21 @@ void TsdfVolume::raycast(const Affine3f& camera_pose, const Intr& intr, Cloud& p
                "TsdfVolume::raycast(points)");
 }
 
+void TsdfVolume::raycastRender(const Affine3f& camera_pose, const Intr& intr, int cols, int rows, const Vec3f& light_pose, int mode,
+                               Image& image) const {
+    if (image.rows() != rows || image.cols() != cols * (mode == DFA_RENDER_BOTH ? 2 : 1))
+        throw dfa::Error(DFA_ERR_INVALID, "TsdfVolume::raycastRender: image size does not fit the mode");
+    Affine3f cam2vol = cfg_.pose.inv() * camera_pose;
+    float aff[12], rinv[9];
+    cam2vol.to12(aff);
+    cam2vol.inverse_rotation(rinv);
+    const Vec3f vsz = getVoxelSize();
+    dfa::check(dfa_tsdf_raycast_render(blob_.ptr<uint32_t>(), cfg_.dims[0], cfg_.dims[1], cfg_.dims[2], vsz.v, cfg_.trunc, aff, rinv,
+                                       intr.fx, intr.fy, intr.cx, intr.cy, cfg_.ray_step, cfg_.grad_delta, cols, rows,
+                                       light_pose.v, mode, (uint8_t*)image.ptr(), (int)image.step(), nullptr),
+               "TsdfVolume::raycastRender");
+}
+
 dfa::DeviceArray<Point> TsdfVolume::fetchCloud(dfa::DeviceArray<Point>& cloud_buffer) const {  // :131-147
     enum { DEFAULT_CLOUD_BUFFER_SIZE = 10 * 1000 * 1000 };
     if (cloud_buffer.empty()) cloud_buffer.create(DEFAULT_CLOUD_BUFFER_SIZE);

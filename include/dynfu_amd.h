@@ -185,6 +185,46 @@ int dfa_tsdf_raycast_tally(const uint32_t* volume, int X, int Y, int Z, const fl
                            uint32_t* touched_bits, dfa_stream_t stream);
 
 /* ===================================================================================== */
+/* Render seam — replaces kfusion::device::renderImage (both overloads) and renderTangentColors */
+/* (include/kfusion/internal.hpp, src/kfusion/cuda/imgproc.cu:363-514), called by              */
+/* KinFu::renderImage (src/kfusion/kinfu.cpp:264-316).                                          */
+/* ===================================================================================== */
+/* image: rows of 4-byte pixels b, g, r, 0 (kfusion::RGB, types.hpp), image_step bytes per row, 4-byte aligned; the
+ * bytes of a row beyond its last pixel are not touched.  light_pose: the light's position in the camera frame
+ * (KinFuParams::light_pose, kinfu.cpp:41).  The three CUDA intrinsics of the reference kernels (__powf, __saturatef, the
+ * float -> uchar casts) are fixed IEEE sequences, stated in csrc/render.hip and tests/render_statement.py. */
+
+/* Phong view of a point map — render_image_kernel(PtrStep<Point>, ...), imgproc.cu:413-461, 474-481.  A pixel whose
+ * point has a NaN x gets the background ramp, every other one 0.3 + 0.5 max(0, N.L) + 0.2 max(0, R.V)^20 as a grey.
+ * (The reference's Reprojector argument is not read by this overload and is not passed.) */
+int dfa_render_image_points(const float* points, int points_step, const float* normals, int normals_step, int cols, int rows,
+                            const float light_pose[3], uint8_t* image, int image_step, dfa_stream_t stream);
+
+/* Phong view of a depth map — render_image_kernel(PtrStep<ushort>, ...), imgproc.cu:363-411, 465-472 (compiled there
+ * under USE_DEPTH only).  The point is reproj(x, y, depth * 0.001f); a depth of 0 gets the background. */
+int dfa_render_image_depth(const uint16_t* depth, int depth_step, const float* normals, int normals_step, int cols, int rows,
+                           float fx, float fy, float cx, float cy, const float light_pose[3], uint8_t* image, int image_step,
+                           dfa_stream_t stream);
+
+/* Normal colours — tangent_colors_kernel, imgproc.cu:485-504 (the `#else` branch), 508-514:
+ * r, g, b = (5 - n.x 3.5) 25.5, (5 - n.y 2.5) 25.5, (5 - n.z 3.5) 25.5; NaN -> 0, otherwise clamped to [0, 255]. */
+int dfa_render_tangent_colors(const float* normals, int normals_step, int cols, int rows, uint8_t* image, int image_step,
+                              dfa_stream_t stream);
+
+/* mode of dfa_tsdf_raycast_render */
+enum { DFA_RENDER_PHONG = 0, DFA_RENDER_NORMALS = 1, DFA_RENDER_BOTH = 2 };
+
+/* Raycast and shade in one launch — KinFu::renderImage(image, pose, flag), kinfu.cpp:289-316, which raycasts into
+ * points_ / normals_ only to shade them (tsdf_volume.cu:258-318 + imgproc.cu:413-461, 485-504).  The rays are those of
+ * dfa_tsdf_raycast_points and the pixels those of dfa_render_image_points / dfa_render_tangent_colors on its maps,
+ * byte for byte.  mode: DFA_RENDER_PHONG, DFA_RENDER_NORMALS, or DFA_RENDER_BOTH — the Phong view in columns
+ * [0, cols) and the normal colours in [cols, 2 cols) of an image 2 cols wide. */
+int dfa_tsdf_raycast_render(const uint32_t* volume, int X, int Y, int Z, const float voxel_size[3], float trunc_dist,
+                            const float cam2vol[12], const float Rinv[9], float fx, float fy, float cx, float cy,
+                            float step_factor, float delta_factor, int cols, int rows, const float light_pose[3], int mode,
+                            uint8_t* image, int image_step, dfa_stream_t stream);
+
+/* ===================================================================================== */
 /* Depth pre-processing seam — replaces the image kernels of kfusion::device declared in    */
 /* include/kfusion/internal.hpp:190-204 (src/kfusion/cuda/imgproc.cu), called by            */
 /* DynFusion::operator() (src/dynfu/dyn_fusion.cpp:58-66) and KinFu::operator()             */
