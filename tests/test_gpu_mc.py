@@ -291,3 +291,187 @@ def test_fused_sweep_over_a_known_occupancy_map_leaves_the_same_volume_and_map(A
     assert bool(left.any()) and not bool((left & (ref != 0)).any())  # only where the frame writes zeros
     A.tsdf_clear_integrate(vol, dists[0], *args, pose(0), fx, fy, cx, cy, occupancy=occ)  # the sweep without the promise repairs it
     same()
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Against tests/mc_statement.py: the numpy statement of the reference's marching cubes (not the oracle's C, which shares
+# the kernels' author and operation order), and its table-free fp64 checker.  Inputs that reach what the kernels are
+# sized for (tests/test_mc_statement_cpu.py asserts that they do), and the sizes the benchmark runs.
+import mc_statement as MS  # noqa: E402
+from mc_util import checkerboard_volume, sign_noise_volume, special_values_volume  # noqa: E402
+
+NOISE_DIMS = (512, 24, 24)   # vec4 path, two 256-cube segments per row, two z chunks
+RAGGED_DIMS = (130, 11, 9)   # X % 4 != 0: the scalar path, three 64-cube segments per row
+
+
+def _cell(dims):
+    return np.array([3.0 / dims[0], 2.5 / dims[1], 3.5 / dims[2]], np.float32)
+
+
+def _new_volume(kind, dims):
+    return {"noise": lambda: sign_noise_volume(dims, 0), "checkerboard": lambda: checkerboard_volume(dims),
+            "special": lambda: special_values_volume(dims, 0)}[kind]()
+
+
+def _same_bits(got, ref):
+    """NaN positions first, then the bits elsewhere (as test_vertex_normals_bit_exact does)"""
+    assert got.shape == ref.shape
+    assert np.array_equal(np.isnan(got), np.isnan(ref))
+    ok = ~np.isnan(ref)
+    assert np.array_equal(bits(got)[ok], bits(ref)[ok])
+
+
+@pytest.mark.parametrize("which", ["default", "reference"])
+@pytest.mark.parametrize("dims", [NOISE_DIMS, RAGGED_DIMS])
+@pytest.mark.parametrize("kind", ["noise", "checkerboard", "special"])
+def test_dense_ambiguous_and_special_volumes_equal_the_statement(A, kind, dims, which):
+    """all 254 cases, 20 triangles in a lane's four cubes, segments of 2 600 and 3 072 vertices; fp16 denormals, +-0,
+    +-65504, +-inf and NaN as distances (the statement defines the bits: NaN < 0 is false, inf gives t = 0 or NaN)"""
+    tri, nv = _tables(which)
+    vol, cell = _new_volume(kind, dims), _cell(dims)
+    ref, total = MS.marching_cubes(vol, cell, tri, nv)
+    got, gtotal = _run(A, vol, cell, tri, nv, max(total, 1))
+    assert gtotal == total > 100
+    _same_bits(got, ref)
+    if kind == "noise":  # the geometry itself, with no table and no order: the kernel's output
+        MS.check_voxel_order(MS.check_mesh_fp64(got, vol, cell), dims)
+
+
+def test_volume_pointer_that_is_not_16_byte_aligned(A):
+    """X % 4 == 0 but the volume starts 4 bytes into a buffer: the scalar path, chosen by the pointer"""
+    import torch
+    tri, nv = reference_data.mc_tables()
+    dims = NOISE_DIMS
+    vol, cell = sign_noise_volume(dims, 1), _cell(dims)
+    buf = torch.zeros(vol.size + 1, dtype=torch.int32, device="cuda")
+    buf[1:] = dev(vol).reshape(-1)
+    view = buf[1:].view(vol.shape)
+    assert view.data_ptr() % 16 == 4 and view.is_contiguous()
+    ref, total = MS.marching_cubes(vol, cell, tri, nv)
+    pts, gtotal = A.marching_cubes(view, cell, dev(tri), dev(nv), total)
+    assert int(host(gtotal)[0]) == total
+    assert np.array_equal(bits(host(pts)), bits(ref))
+
+
+def test_segment_count_that_is_an_exact_multiple_of_the_scan_chunk(A):
+    """(256, 64, 128): one segment per row, 64 * 128 = 8 192 segments = exactly one scan chunk — the total is written by
+    the thread whose last entry is the array's last (`first + PER == n`)"""
+    tri, nv = default_tables()
+    for dims in [(256, 64, 128), (256, 128, 128)]:
+        assert (dims[1] * dims[2]) % 8192 == 0
+        vol, cell = blob_volume(dims, seed=3), _cell(dims)
+        ref, total = MS.marching_cubes(vol, cell, tri, nv)
+        got, gtotal = _run(A, vol, cell, tri, nv, total)
+        assert gtotal == total > 10000
+        assert np.array_equal(bits(got), bits(ref))
+
+
+def test_capacity_that_ends_inside_a_heavy_segment(A):
+    """the first `cap` vertices and nothing beyond, where cap falls in the middle of the noise volume's fullest 256-cube
+    segment"""
+    import torch
+    from dynfu_amd import _lib
+    tri, nv = reference_data.mc_tables()
+    dims = NOISE_DIMS
+    X, Y, Z = dims
+    vol, cell = sign_noise_volume(dims, 0), _cell(dims)
+    ref, total = MS.marching_cubes(vol, cell, tri, nv)
+    n = MS.cube_counts(vol, nv)
+    pad = np.zeros(n.shape[:2] + (512,), np.int64)
+    pad[:, :, :X - 1] = n
+    segs = pad.reshape(Z - 1, Y - 1, 2, 256).sum(-1)  # the vec4 path's segments, in output order
+    flat = segs.reshape(-1)
+    s = int(flat.argmax())
+    assert flat[s] >= 2000
+    cap = int(flat[:s].sum() + flat[s] // 2 + 1)
+    pts = torch.full((cap + 64, 4), -7.0, dtype=torch.float32, device="cuda")
+    tot = torch.zeros(1, dtype=torch.int32, device="cuda")
+    dvol, dtri, dnv = dev(vol), dev(tri), dev(nv)  # (held until the call has run: a temporary's memory may be handed out again)
+    _lib._check(_lib.load().dfa_marching_cubes(_lib._dev(dvol), X, Y, Z, _lib._farr(cell, 3), _lib._dev(dtri), _lib._dev(dnv),
+                                               _lib._dev(pts), cap, _lib._dev(tot), _lib._stream()))
+    assert int(host(tot)[0]) == total
+    assert np.array_equal(bits(host(pts)[:cap]), bits(ref[:cap]))
+    assert np.all(host(pts)[cap:] == -7.0)
+
+
+def _integrated_volume(A, name):
+    import torch
+    cfg = synth.CONFIGS[name]
+    fx, fy, cx, cy = synth.intrinsics(cfg)
+    voxel, trunc, vol2cam, _, _ = synth.volume_params(cfg)
+    dim = cfg["dim"]
+    d = torch.empty((cfg["height"], cfg["width"]), dtype=torch.uint16, device="cuda")
+    A.compute_dists(dev(synth.depth_frame(cfg, 0)), d, fx, fy, cx, cy)
+    vol = torch.empty((dim, dim, dim), dtype=torch.int32, device="cuda")
+    occ = A.tsdf_occupancy(vol)
+    A.tsdf_clear_integrate(vol, d, voxel, trunc, synth.MAX_WEIGHT, vol2cam, fx, fy, cx, cy, occupancy=occ)
+    return vol, occ, np.asarray(voxel, np.float32)
+
+
+def test_c2_size_equals_the_statement_slab_by_slab(A):
+    """512^3 (benchmark config C2: two segments per row, 64 scan chunks, z chunks of 32 slices): a synthetic depth frame
+    integrated, extracted by the plain entry point and with the occupancy map — total and bits against the statement run
+    slab by slab over the whole volume, and the geometry against the fp64 checker"""
+    tri, nv = default_tables()
+    vol, occ, cell = _integrated_volume(A, "C2")
+    _, t = A.marching_cubes(vol, cell, dev(tri), dev(nv), 1)
+    total = int(host(t)[0])
+    assert total > 100000
+    pts, t0 = A.marching_cubes(vol, cell, dev(tri), dev(nv), total)
+    pts_occ, t1 = A.marching_cubes(vol, cell, dev(tri), dev(nv), total, occupancy=occ)
+    assert int(host(t0)[0]) == int(host(t1)[0]) == total
+    got, got_occ = host(pts), host(pts_occ)
+    hv = host(vol).view(np.uint32)
+    Z, slab, off = hv.shape[0], 16, 0
+    for z in range(0, Z - 1, slab):
+        c = MS.count(hv, nv, z, z + slab)
+        if c:
+            ref = MS.vertices(hv, cell, tri, nv, z, z + slab)
+            assert len(ref) == c
+            assert np.array_equal(bits(got[off:off + c]), bits(ref)), z
+            assert np.array_equal(bits(got_occ[off:off + c]), bits(ref)), z
+        off += c
+    assert off == total
+    MS.check_voxel_order(MS.check_mesh_fp64(got, hv, cell), hv.shape[::-1])
+
+
+def test_c4_size_count_of_every_slab_and_the_fullest_slabs_in_full(A):
+    """1024^3 (benchmark config C4: four segments per row, 512 scan chunks, z chunks of 256 slices).  The statement's
+    count-only pass runs over ALL 64 slabs of 16 slices, fetched from the device a slab at a time: it gives the total and
+    every slab's offset in the output.  The vertices are compared in full on the first non-empty slab, the last non-empty
+    one and the fullest one, plus the next fullest until the compared slabs hold at least 10 % of all vertices."""
+    tri, nv = default_tables()
+    vol, occ, cell = _integrated_volume(A, "C4")
+    _, t = A.marching_cubes(vol, cell, dev(tri), dev(nv), 1)
+    total = int(host(t)[0])
+    assert total > 400000
+    pts, t0 = A.marching_cubes(vol, cell, dev(tri), dev(nv), total, occupancy=occ)
+    assert int(host(t0)[0]) == total
+    del occ
+    Z, slab = vol.shape[0], 16
+    starts = list(range(0, Z - 1, slab))
+    fetch = lambda z: host(vol[z:min(z + slab, Z - 1) + 1]).view(np.uint32)
+    counts = np.array([MS.count(fetch(z), nv, z, z + slab, z_base=z, Z=Z) for z in starts])
+    assert counts.sum() == total  # the counted total is the kernel's
+    offs = np.cumsum(counts) - counts
+    nonempty = np.flatnonzero(counts)
+    by_size = np.argsort(-counts, kind="stable")
+    chosen = [int(nonempty[0]), int(nonempty[-1]), int(by_size[0])]
+    for s in by_size[1:]:
+        if counts[sorted(set(chosen))].sum() >= 0.1 * total:
+            break
+        chosen.append(int(s))
+    chosen = sorted(set(chosen))
+    assert counts[chosen].sum() >= 0.1 * total
+    print("1024^3: %d vertices, %d of %d slabs non-empty, %d slabs compared in full (%d vertices, %.1f %%)"
+          % (total, len(nonempty), len(starts), len(chosen), counts[chosen].sum(), 100.0 * counts[chosen].sum() / total))
+    for s in chosen:
+        z = starts[s]
+        ref = MS.vertices(fetch(z), cell, tri, nv, z, z + slab, z_base=z, Z=Z)
+        got = host(pts[int(offs[s]):int(offs[s] + counts[s])])
+        assert len(ref) == counts[s] and np.array_equal(bits(got), bits(ref)), z
+    # the plain entry point's output is the same array (on the device)
+    import torch
+    del ref, got
+    plain, t1 = A.marching_cubes(vol, cell, dev(tri), dev(nv), total)
+    assert int(host(t1)[0]) == total and torch.equal(plain, pts)

@@ -398,3 +398,161 @@ def test_transform_points_matches_the_host_loop_bit_for_bit(A, n):
         if with_t:
             ref = ref + t
         assert np.array_equal(bits(out), bits(ref.astype(np.float32)))
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Against tests/warp_statement.py: the k-NN contract and the support flags stated in numpy (exact), the blend and the warp
+# stated in fp64 (the mathematical statement, not the oracle's float32 copy of the kernels' operation order).
+import warp_statement as WS  # noqa: E402
+
+# Twice the float32 oracle's own largest deviation from the fp64 statement over WS.MATRIX, the inputs below (measured on
+# the CPU: 8.783e-07 m, recorded as 9.0e-07 in warp_statement.ORACLE_DEVIATION and measured again by
+# tests/test_warp_statement_cpu.py): 1.8e-06.  Kernel and oracle share the operation order and differ by exp's last bit.
+WARP_BOUND = WS.KERNEL_BOUND
+
+
+@pytest.mark.parametrize("D,k,n", [(2048, 4, 20000), (500, 8, 5000), (3000, 16, 3000), (5, 8, 100), (1, 4, 10), (1025, 5, 777)]
+                         + [(300, k, n) for k in (1, 3, 7, 9, 16) for n in (2000, 40000)]   # brute force | grid, a lane per query
+                         + [(1500, k, 3000) for k in (1, 3, 7, 9, 16)]                        # grid, a wave per query
+                         + [(63, 9, 70000), (64, 9, 65535), (64, 9, 65536), (1023, 3, 4000), (1024, 3, 4000)])  # want_grid's edges
+def test_knn_and_weights_equal_the_statement(A, D, k, n):
+    rng = np.random.default_rng(D + k)
+    nodes = rng.uniform(-1, 1, (D, 3)).astype(np.float32)
+    node_w = rng.uniform(0.05, 0.5, D).astype(np.float32)
+    q = rng.uniform(-1.2, 1.2, (n, 3)).astype(np.float32)
+    q[: min(n, D)] = nodes[: min(n, D)]
+    q[-1, 1] = np.nan  # a NaN query: no neighbour
+    idx, w = A.knn(dev(nodes), dev(node_w), dev(q), k)
+    ref = WS.knn(nodes, q, k)
+    assert (ref[-1] == -1).all()
+    assert np.array_equal(host(idx), ref)
+    wref = WS.weights(nodes, node_w, q, ref)
+    assert _ulp_diff(host(w)[ref >= 0], wref[ref >= 0]).max() <= 1
+    assert np.all(host(w)[ref < 0] == 0)
+
+
+@pytest.mark.parametrize("D", WS.D_LIST)
+@pytest.mark.parametrize("k", WS.K_LIST)
+def test_warp_shape_matrix_against_the_fp64_statement(A, D, k):
+    """dfa_warp_to_live, dfa_warp_to_live_graph and dfa_calc_dqb at every (D, k), K = 16 instantiations and k below the
+    template's K included, D < k (absent neighbours), brute force and grid: within WARP_BOUND of the fp64 statement;
+    the graph form bit-equal to the searching form — also with an idx that is not 16-byte aligned, and normals absent."""
+    import torch
+    for n in WS.matrix_sizes(D):
+        c = WS.matrix_case(D, k, n)
+        args = (dev(c["nodes"]), dev(c["dq"]), dev(c["node_w"]))
+        verts, nrm = dev(c["verts"]), dev(c["normals"])
+        idx = WS.knn(c["nodes"], c["verts"], k)
+        assert (idx[:, min(D, k):] == -1).all() and (idx[:, :min(D, k)] >= 0).all()
+        sv, sn = WS.warp_graph(c["nodes"], c["dq"], c["node_w"], idx, c["verts"], c["normals"])
+        ov, on = A.warp_to_live(*args, k, verts, nrm)
+        assert WS.deviation(host(ov), sv) <= WARP_BOUND and WS.deviation(host(on), sn) <= WARP_BOUND
+        ov2, on2 = A.warp_to_live(*args, k, verts)  # normals absent
+        assert on2 is None and torch.equal(ov2, ov)
+        m = 500
+        sq = WS.calc_dqb_graph(c["nodes"], c["dq"], c["node_w"], idx[:m], c["verts"][:m])
+        assert WS.deviation(host(A.calc_dqb(*args, k, verts[:m])), sq) <= WARP_BOUND
+        # the given graph: the statement's own neighbour lists (not the kernel's), -1 entries where D < k
+        gi = dev(idx)
+        gv, gn = A.warp_to_live_graph(*args, gi, verts, nrm)
+        assert torch.equal(gv, ov) and torch.equal(gn, on)
+        gv2, gn2 = A.warp_to_live_graph(*args, gi, verts)
+        assert gn2 is None and torch.equal(gv2, ov)
+        # ... from an idx array that starts one int32 into a buffer: the scalar neighbour loads
+        buf = torch.full((idx.size + 1,), -5, dtype=torch.int32, device="cuda")
+        buf[1:] = gi.reshape(-1)
+        view = buf[1:].view(idx.shape)
+        assert view.data_ptr() % 16 == 4
+        gv3, gn3 = A.warp_to_live_graph(*args, view, verts, nrm)
+        assert torch.equal(gv3, ov) and torch.equal(gn3, on)
+
+
+@pytest.mark.parametrize("k", [4, 8, 16])
+def test_warp_with_a_graph_that_has_holes(A, k):
+    """-1 entries anywhere in a given graph (a caller's pruned graph, not only the padding of D < k) are skipped: the
+    statement with the same lists"""
+    c = WS.matrix_case(300, k, 2000)
+    idx = WS.knn(c["nodes"], c["verts"], k)
+    rng = np.random.default_rng(k)
+    idx[rng.random(idx.shape) < 0.3] = -1
+    idx[:5] = -1  # no neighbour at all: the identity
+    args = (dev(c["nodes"]), dev(c["dq"]), dev(c["node_w"]))
+    gv, gn = A.warp_to_live_graph(*args, dev(idx), dev(c["verts"]), dev(c["normals"]))
+    sv, sn = WS.warp_graph(c["nodes"], c["dq"], c["node_w"], idx, c["verts"], c["normals"])
+    assert WS.deviation(host(gv), sv) <= WARP_BOUND and WS.deviation(host(gn), sn) <= WARP_BOUND
+    assert np.array_equal(host(gv)[:5], c["verts"][:5])
+
+
+@pytest.mark.parametrize("D,n", [(40, 1000), (2048, 1000)])  # brute force | grid
+@pytest.mark.parametrize("k", [1, 4, 8, 16])
+def test_warp_of_degenerate_vertices(A, D, k, n):
+    c = WS.matrix_case(D, k, n)
+    verts = c["verts"].copy()
+    # NaN coordinates: every distance is NaN, so the vertex has no neighbour (include/dynfu_amd.h: dfa_knn pads with -1 and
+    # the warp is the blend of the neighbours given) — the blend is the identity and the output is the NaN input
+    verts[100] = np.nan
+    verts[101, 1] = np.nan
+    # exactly on a node (weight exp(0) = 1) — the first min(n, D) vertices already are
+    verts[102] = c["nodes"][D - 1]
+    # so far from every node that all weights underflow to 0 in float32: the dual part of the blend vanishes, the real
+    # part is the ordered product of the neighbours' rotations
+    verts[103] = [60.0, -70.0, 80.0]
+    verts[104] = [-1e3, 2e3, 1e3]
+    idx = WS.knn(c["nodes"], verts, k)
+    assert (idx[100] == -1).all() and (idx[101] == -1).all()
+    assert (WS.weights(c["nodes"], c["node_w"], verts, idx)[103:105] == 0).all()
+    sv, sn = WS.warp_graph(c["nodes"], c["dq"], c["node_w"], idx, verts, c["normals"])
+    assert np.isnan(sv[100]).all() and np.isnan(sv[101]).all() and np.isfinite(sv[102:105]).all()
+    ov, on = A.warp_to_live(dev(c["nodes"]), dev(c["dq"]), dev(c["node_w"]), k, dev(verts), dev(c["normals"]))
+    ov, on = host(ov), host(on)
+    assert np.isnan(ov[100]).all() and np.isnan(ov[101]).all()
+    # the far vertices: float32 rounding of a rotated coordinate of magnitude 2e3 is relative, so the absolute bound is
+    # applied in units of the coordinate magnitude there (bound * max(1, |v|))
+    near = np.ones(n, bool)
+    near[[103, 104]] = False
+    assert WS.deviation(ov[near], sv[near]) <= WARP_BOUND and WS.deviation(on[near], sn[near]) <= WARP_BOUND
+    for v in (103, 104):
+        scale = max(1.0, float(np.abs(verts[v]).max()))
+        assert np.abs(ov[v] - sv[v]).max() <= WARP_BOUND * scale
+        assert np.abs(on[v] - sn[v]).max() <= WARP_BOUND
+    got = host(A.calc_dqb(dev(c["nodes"]), dev(c["dq"]), dev(c["node_w"]), k, dev(verts[100:105])))
+    sq = WS.calc_dqb_graph(c["nodes"], c["dq"], c["node_w"], idx[100:105], verts[100:105])
+    assert WS.deviation(got, sq) <= WARP_BOUND
+    assert np.array_equal(got[0], WS.IDENTITY.astype(np.float32)) and (got[3:, 4:] == 0).all()
+
+
+@pytest.mark.parametrize("D,k,n", [(300, 1, 20000), (300, 16, 20000), (2048, 1, 30000), (2048, 16, 30000), (2048, 8, 30000),
+                                    (3, 16, 500), (8192, 5, 40000)])
+def test_unsupported_vertices_equal_the_statement(A, D, k, n):
+    rng = np.random.default_rng(D + k)
+    nodes = rng.uniform(-1, 1, (D, 3)).astype(np.float32)
+    node_w = rng.uniform(0.05, 0.3, D).astype(np.float32)
+    verts = rng.uniform(-1.3, 1.3, (n, 3)).astype(np.float32)
+    verts[:D] = nodes[:n]
+    verts[-1] = np.nan
+    ref = WS.unsupported_flags(nodes, node_w, k, verts)
+    assert 0 < ref.mean() < 1 and not ref[:min(D, n)].any() and ref[-1] == 1
+    assert np.array_equal(host(A.unsupported_vertices(dev(nodes), dev(node_w), k, dev(verts))), ref)
+
+
+@pytest.mark.parametrize("D,n", [(200, 5000), (2048, 30000)])  # brute force | grid (the flags-only early exit)
+def test_unsupported_vertices_with_very_different_radii(A, D, n):
+    """a far node with a wide radius supports a vertex its nearest node does not: the 1-NN early exit of the flags-only
+    kernel must fall through to the full search there"""
+    rng = np.random.default_rng(D)
+    nodes = rng.uniform(-1, 1, (D, 3)).astype(np.float32)
+    node_w = np.where(rng.random(D) < 0.1, 0.6, 0.01).astype(np.float32)  # a few wide nodes among narrow ones
+    verts = rng.uniform(-1, 1, (n, 3)).astype(np.float32)
+    k = 8
+    idx = WS.knn(nodes, verts, k)
+    d = np.linalg.norm(verts[:, None, :].astype(np.float64) - nodes[idx], axis=2)
+    q = d / node_w[idx]
+    by_far_node_only = (q[:, 0] >= 1) & (q[:, 1:].min(1) < 1)
+    assert by_far_node_only.sum() > n // 20  # the input contains such vertices
+    ref = WS.unsupported_flags(nodes, node_w, k, verts)
+    assert not ref[by_far_node_only].any() and 0 < ref.mean() < 1
+    assert np.array_equal(host(A.unsupported_vertices(dev(nodes), dev(node_w), k, dev(verts))), ref)
+    # with k = 1 the same vertices are unsupported
+    ref1 = WS.unsupported_flags(nodes, node_w, 1, verts)
+    assert ref1[by_far_node_only].all()
+    assert np.array_equal(host(A.unsupported_vertices(dev(nodes), dev(node_w), 1, dev(verts))), ref1)
