@@ -139,7 +139,7 @@ def build_cpp_tests(force=False, verbose=False):
     for name, needs in (("test_host_dq", []), ("test_host_solver", ["host"]), ("test_host_tsdf", ["host", "oracle"]),
                         ("test_host_dynfusion", ["host", "oracle"]), ("test_host_icp", ["host"]),
                         ("test_tsdf_classify", ["oracle", "ieee"]), ("test_host_io", ["host"]), ("test_host_kinfu", ["host"]),
-                        ("test_host_extract", ["host"]), ("test_host_render", ["host"])):
+                        ("test_host_extract", ["host"]), ("test_host_render", ["host"]), ("test_host_mc_indexed", ["host"])):
         src = os.path.join(tdir, name + ".cpp")
         exe = os.path.join(out, name)
         deps = [src, os.path.join(tdir, "minitest.hpp"), host, os.path.join(CSRC, "tsdf_classify.hpp")]

@@ -136,7 +136,21 @@ struct McScratch {
         return hipSuccess;
     }
 };
-
+// scratch of dfa_marching_cubes_indexed: two offset arrays (vertices, indices) over its own segments, one set of partials
+struct McIndexedScratch {
+    McScratch vert;
+    int32_t* idx_off = nullptr;
+    long cap_segs    = 0;
+    hipError_t reserve(long nsegs) {
+        hipError_t e = vert.reserve(nsegs);
+        if (e != hipSuccess || nsegs <= cap_segs) return e;
+        (void)hipFree(idx_off);
+        idx_off = nullptr, cap_segs = 0;
+        if ((e = hipMalloc((void**)&idx_off, sizeof(int32_t) * (size_t)(nsegs + 1))) != hipSuccess) return e;
+        cap_segs = nsegs;
+        return hipSuccess;
+    }
+};
 
 // exhaustive scan below this many distance evaluations (grid build = 4 small launches)
 // the uniform-grid k-NN (three small launches to build, ~40 us) against the exhaustive scan: worth it for many queries, and for
@@ -609,6 +623,26 @@ int dfa_marching_cubes_occ(const uint32_t* volume, const uint8_t* occupancy, int
     REQUIRE(occupancy, "null occupancy map");
     return marching_cubes_common(volume, X, Y, Z, cell_size, tri_table, num_verts_table, out_points, max_vertices,
                                  total_vertices, occupancy, stream);
+}
+
+int dfa_marching_cubes_indexed(const uint32_t* volume, const uint8_t* occupancy, int X, int Y, int Z, const float cell_size[3],
+                               const int32_t* tri_table, const int32_t* num_verts_table, float* out_vertices,
+                               int max_vertices, int32_t* out_indices, int max_indices, int32_t* totals,
+                               dfa_stream_t stream) {
+    REQUIRE(volume && X >= 2 && Y >= 2 && Z >= 2, "bad volume");
+    REQUIRE(cell_size && tri_table && num_verts_table, "null parameter block / case tables");
+    REQUIRE(max_vertices >= 0 && (max_vertices == 0 || out_vertices), "bad vertex buffer");
+    REQUIRE(max_indices >= 0 && (max_indices == 0 || out_indices), "bad index buffer");
+    REQUIRE(((uintptr_t)out_vertices & 15) == 0, "out_vertices must be 16-byte aligned");
+    REQUIRE(totals, "null totals");
+    REQUIRE((long)X * Y * Z / 64 < (1L << 31), "volume too large");
+    const long nsegs = dfa::mci_segments(X, Y, Z);
+    McIndexedScratch& scratch = stream_scratch<McIndexedScratch>(S(stream));
+    HIP_TRY(scratch.reserve(nsegs));
+    HIP_TRY(dfa::launch_marching_cubes_indexed(volume, X, Y, Z, cell_size, tri_table, num_verts_table, out_vertices,
+                                               max_vertices, out_indices, max_indices, totals, scratch.vert.seg_off,
+                                               scratch.idx_off, scratch.vert.chunk_sums, occupancy, S(stream)));
+    return DFA_OK;
 }
 
 // -------------------------------------------------------------- TSDF seam: point-cloud extraction

@@ -108,6 +108,14 @@ hipError_t launch_marching_cubes(const uint32_t* vol, int X, int Y, int Z, const
                                  const int32_t* tri_table, const int32_t* num_verts_table, float* out_points,
                                  int max_vertices, int32_t* total_vertices, int32_t* seg_off, int32_t* chunk_sums,
                                  const uint8_t* occ /* occupancy map of the volume or null */, hipStream_t s);
+// indexed mesh (dfa_marching_cubes_indexed): voff / ioff hold mci_segments(X, Y, Z) + 1 entries each (segments of 256
+// voxels, whatever the alignment), chunk_sums mc_scan_chunks of that; totals: device, 2 ints
+long mci_segments(int X, int Y, int Z);
+hipError_t launch_marching_cubes_indexed(const uint32_t* vol, int X, int Y, int Z, const float cell_size[3],
+                                         const int32_t* tri_table, const int32_t* num_verts_table, float* out_vertices,
+                                         int max_vertices, int32_t* out_indices, int max_indices, int32_t* totals,
+                                         int32_t* voff, int32_t* ioff, int32_t* chunk_sums, const uint8_t* occ,
+                                         hipStream_t s);
 void mc_default_tables(int32_t tri_table[256 * 16], int32_t num_verts_table[256]);
 // exclusive scan of n segment counts in place (counts: n + 1 entries; counts[n] and *total (device, optional) receive the
 // sum; chunk_sums: mc_scan_chunks(n) entries) — marching cubes' step 2, shared with the point-cloud extraction

@@ -361,7 +361,436 @@ __global__ __launch_bounds__(256) void mc_emit_kernel(const McArgs a, const int3
     }
 }
 
+// ------------------------------------------------------------------------------- indexed mesh
+// dfa_marching_cubes_indexed: every crossed lattice edge once (the VERTEX, owned by the edge's lower voxel, key
+// 3 * voxel + axis) and, per soup vertex of the extraction above, the id of its edge's vertex.  Same shape — count sweep,
+// scans, persistent emit waves — with segments of its own: always 64 lanes x 4 voxels (ragged rows and unaligned volumes
+// load voxel by voxel), all Y * Z rows (the last row and the last slice own edges too).
+//
+// Everything but the interpolation works on BITS.  A lane reduces a row to two 7-bit masks over the voxels
+// x0 - 1 .. x0 + 5 (bit 0: the voxel before the lane's four, bits 1..4 its own, bits 5, 6 the two after them): W = weight
+// != 0, N = distance < 0.  Cubes, cases and crossed edges are shifts and ANDs of those masks, so the sweep keeps three
+// slices of four rows in 24 registers, and an emit wave recomputes the owned edges of the (up to) eight segments a cube's
+// edges belong to from 16 row loads instead of reading an id map: the id of an edge is its segment's vertex offset plus
+// its rank among the segment's owned edges, a wave prefix sum of popcounts.  No scratch beyond the two offset arrays.
+struct IdxArgs {
+    const uint32_t* vol;
+    int X, Y, Z;
+    int nseg;    // row segments per row: ceil(X / 256)
+    int zchunk;  // count sweep: slices per workgroup
+    int vec4;    // X % 4 == 0 and the volume 16-byte aligned: one 16-byte load per lane and row
+    float csx, csy, csz;
+    const int32_t* tri;
+    const int32_t* nverts;
+    const uint8_t* occ;
+    int ox, oy, oz;
+};
+
+constexpr uint32_t IDX_OWN = 0x1eu;  // a lane's own voxels in a row mask
+
+// bit 0: weight != 0, bit 8: distance < 0
+__device__ __forceinline__ uint32_t voxel_bits(uint32_t v) {
+    return ((v >> 16) != 0u ? 1u : 0u) | (half_bits_to_float(v & 0xffffu) < 0.f ? 0x100u : 0u);
+}
+
+// NR consecutive rows y .. y + NR - 1 (NR <= 4) of slice z as masks; rows, slices and voxels that do not exist (y or z
+// may be -1 or past the end) give zeros: weight 0.  The three voxels around the segment come by ONE load for all rows.
+template <int NR>
+__device__ __forceinline__ void load_row_bits(const IdxArgs& a, int seg, int y, int z, uint32_t* W, uint32_t* N) {
+    const int lane = threadIdx.x & 63, xs = seg * 256, x0 = xs + lane * 4;
+    const bool z_ok = z >= 0 && z < a.Z;
+    uint32_t own[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        uint32_t v0 = 0u, v1 = 0u, v2 = 0u, v3 = 0u;
+        const int yy = y + r;
+        if (z_ok && yy >= 0 && yy < a.Y && x0 < a.X) {
+            const uint32_t* p = a.vol + (size_t)a.X * ((size_t)yy + (size_t)a.Y * (size_t)z) + x0;
+            if (a.vec4) {
+                const uint4 q = *reinterpret_cast<const uint4*>(p);
+                v0 = q.x, v1 = q.y, v2 = q.z, v3 = q.w;
+            } else {
+                v0 = p[0];
+                if (x0 + 1 < a.X) v1 = p[1];
+                if (x0 + 2 < a.X) v2 = p[2];
+                if (x0 + 3 < a.X) v3 = p[3];
+            }
+        }
+        own[r] = voxel_bits(v0) | voxel_bits(v1) << 1 | voxel_bits(v2) << 2 | voxel_bits(v3) << 3;
+    }
+    uint32_t extra = 0u;  // lane 4 r + k: row r, voxel xs - 1 (k = 0), xs + 256 (1), xs + 257 (2)
+    {
+        const int r = lane >> 2, k = lane & 3, yy = y + r;
+        const int x = k == 0 ? xs - 1 : xs + 255 + k;
+        if (r < NR && k < 3 && z_ok && yy >= 0 && yy < a.Y && x >= 0 && x < a.X)
+            extra = voxel_bits(a.vol[(size_t)x + (size_t)a.X * ((size_t)yy + (size_t)a.Y * (size_t)z)]);
+    }
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        const uint32_t up = __shfl_up(own[r], 1, 64), down = __shfl_down(own[r], 1, 64);
+        const uint32_t e0 = __shfl(extra, 4 * r, 64), e1 = __shfl(extra, 4 * r + 1, 64), e2 = __shfl(extra, 4 * r + 2, 64);
+        const uint32_t before = lane == 0 ? e0 : (up >> 3) & 0x101u;
+        const uint32_t after  = lane == 63 ? (e1 | e2 << 1) : down & 0x303u;
+        const uint32_t m      = before | own[r] << 1 | after << 5;
+        W[r] = m & 0x7fu, N[r] = (m >> 8) & 0x7fu;
+    }
+}
+
+// the four voxels of the face (row, row + 1) of one slice have weights: bit i = the face at x0 - 1 + i (bits 0..5)
+__device__ __forceinline__ uint32_t face_bits(uint32_t w0, uint32_t w1) { return w0 & (w0 >> 1) & w1 & (w1 >> 1); }
+
+// The crossed edges with a valid cube around them whose lower voxel lies in the centre row of a 3 x 3 neighbourhood of
+// row masks, [slice z - 1 .. z + 1][row y - 1 .. y + 1] with a stride of `ld` masks per slice: bit i of ex / ey / ez = the
+// edge from voxel x0 - 1 + i to +x / +y / +z (bits 1..5: the lane's own voxels and the one after them).  A cube is valid
+// when its eight weights are non-zero, and every cube around an edge holds the edge's two voxels.
+__device__ __forceinline__ void row_edges(const uint32_t* W, const uint32_t* N, int ld, uint32_t& ex, uint32_t& ey,
+                                          uint32_t& ez) {
+    uint32_t F[3][2];
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) F[s][j] = face_bits(W[s * ld + j], W[s * ld + j + 1]);
+    // cubes [slice z - 1, z][row y - 1, y]
+    const uint32_t v00 = F[0][0] & F[1][0], v01 = F[0][1] & F[1][1], v10 = F[1][0] & F[2][0], v11 = F[1][1] & F[2][1];
+    const uint32_t n = N[ld + 1];
+    const uint32_t vy = v01 | v11, vz = v10 | v11;
+    ex = (n ^ (n >> 1)) & (v00 | v01 | v10 | v11);  // cubes (x, y - 1 .. y, z - 1 .. z)
+    ey = (n ^ N[ld + 2]) & (vy | vy << 1);          // cubes (x - 1 .. x, y, z - 1 .. z)
+    ez = (n ^ N[2 * ld + 1]) & (vz | vz << 1);      // cubes (x - 1 .. x, y - 1 .. y, z)
+}
+
+// case of the lane's cube i (0..3) from the N masks of the rows (y,z) (y+1,z) (y,z+1) (y+1,z+1); corner order :37-60
+__device__ __forceinline__ int mask_case(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, int i) {
+    const uint32_t p = (a0 >> (i + 1)) & 3u, q = (a1 >> (i + 1)) & 3u, r = (b0 >> (i + 1)) & 3u, s = (b1 >> (i + 1)) & 3u;
+    return (int)(p | (q >> 1) << 2 | (q & 1u) << 3 | r << 4 | (s >> 1) << 6 | (s & 1u) << 7);
+}
+
+// count sweep: per segment the vertices it owns (vcount) and the soup vertices of its cubes (icount).  A wave marches
+// along z over MC_ROWS rows and keeps the masks of slices z - 1, z, z + 1, rows y - 1 .. y + MC_ROWS.
+__global__ __launch_bounds__(256) void mci_count_kernel(const IdxArgs a, int32_t* __restrict__ vcount,
+                                                        int32_t* __restrict__ icount) {
+    __shared__ uint8_t ntri_lds[256];
+    __shared__ int wave_work[4];
+    constexpr int NR = MC_ROWS + 2;
+    const int seg = blockIdx.x;
+    const int y = (blockIdx.y * 4 + threadIdx.y) * MC_ROWS;
+    const int z0 = blockIdx.z * a.zchunk, z1 = min(z0 + a.zchunk, a.Z);
+    // With an occupancy map: an owned edge has a weight at its lower voxel, in slice z, and a negative distance there or at
+    // the voxel after it in x, y or z; a cube with triangles has weights at all corners and a negative distance at one.  So
+    // slice z gives this wave something only if the map shows weights in ITS layer over the wave's footprint — its 256
+    // voxels and the one after them (9 boxes), rows y .. y + MC_ROWS (two rows of boxes) — and a possibly negative distance
+    // there or in the layer of slice z + 1.
+    auto layer_marks = [&](int z8) -> unsigned {
+        if (!a.occ) return 3u;
+        const int lane = threadIdx.x, by = y / 2 + lane / 9, bx = seg * 8 + lane % 9;
+        unsigned v = 0u;
+        if (lane < 18 && by < a.oy && bx < a.ox && z8 < a.oz) v = a.occ[((size_t)z8 * a.oy + by) * a.ox + bx];
+        return (__ballot(v & 1u) != 0ull ? 1u : 0u) | (__ballot(v & 2u) != 0ull ? 2u : 0u);
+    };
+    bool work = y < a.Y && z0 < z1;
+    if (work && a.occ && a.zchunk <= 8) {  // (chunks with a map are one layer long)
+        const unsigned m0 = layer_marks(z0 / 8), m1 = layer_marks(z0 / 8 + 1);
+        work = (m0 & 1u) && ((m0 | m1) & 2u);
+    }
+    if (threadIdx.x == 0) wave_work[threadIdx.y] = work;
+    __syncthreads();
+    if (!(wave_work[0] | wave_work[1] | wave_work[2] | wave_work[3])) return;
+    {
+        const int t  = threadIdx.y * 64 + threadIdx.x;
+        const int nv = a.nverts[t];
+        ntri_lds[t]  = (t == 0 || t == 255) ? 0 : (uint8_t)(min(max(nv, 0), 15) / 3);
+    }
+    __syncthreads();
+    if (!work) return;
+    int cur8 = z0 / 8;
+    unsigned cur = layer_marks(cur8);
+    bool held = false;
+    uint32_t W[3 * NR], N[3 * NR];
+    for (int z = z0; z < z1; ++z) {
+        const int nxt8 = (z + 1) / 8;
+        const unsigned nxt = nxt8 == cur8 ? cur : layer_marks(nxt8);
+        const bool need = (cur & 1u) && ((cur | nxt) & 2u);  // (wave-uniform)
+        cur = nxt, cur8 = nxt8;
+        if (!need) {
+            held = false;
+            continue;
+        }
+        if (held) {
+#pragma unroll
+            for (int j = 0; j < 2 * NR; ++j) W[j] = W[j + NR], N[j] = N[j + NR];
+        } else {
+            load_row_bits<NR>(a, seg, y - 1, z - 1, W, N);
+            load_row_bits<NR>(a, seg, y - 1, z, W + NR, N + NR);
+        }
+        load_row_bits<NR>(a, seg, y - 1, z + 1, W + 2 * NR, N + 2 * NR);
+        held = true;
+#pragma unroll
+        for (int r = 0; r < MC_ROWS; ++r) {
+            uint32_t ex, ey, ez;
+            row_edges(W + r, N + r, NR, ex, ey, ez);
+            int nvert = __popc(ex & IDX_OWN) + __popc(ey & IDX_OWN) + __popc(ez & IDX_OWN);
+            // the cubes of row y + r, slice z: rows r + 1, r + 2 of slices 1, 2
+            const uint32_t valid = face_bits(W[NR + r + 1], W[NR + r + 2]) & face_bits(W[2 * NR + r + 1], W[2 * NR + r + 2]);
+            int ntri = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if ((valid >> (i + 1)) & 1u)
+                    ntri += ntri_lds[mask_case(N[NR + r + 1], N[NR + r + 2], N[2 * NR + r + 1], N[2 * NR + r + 2], i)];
+            nvert = wave_sum_5bit(nvert);  // <= 12 per lane
+            ntri  = wave_sum_5bit(ntri);   // <= 20 per lane
+            if (threadIdx.x == 0 && y + r < a.Y) {
+                const size_t s = ((size_t)z * a.Y + y + r) * a.nseg + seg;
+                if (nvert) vcount[s] = nvert;
+                if (ntri) icount[s] = 3 * ntri;
+            }
+        }
+    }
+}
+
+// per-wave staging of the emit kernels
+struct IdxVertStage {
+    uint16_t list[768];  // the segment's owned edges in key order: 4 * voxel-in-segment + axis
+};
+struct IdxTriStage {
+    uint16_t start[256];     // per cube: offset of its first soup vertex in the segment
+    uint8_t ci[256];         // per cube: case
+    uint16_t rank[4][258];   // rows (y,z) (y+1,z) (y,z+1) (y+1,z+1): rank of a voxel's first owned edge in ITS segment;
+    uint8_t em[4][258];      //   which of its three edges are vertices.  Entry 256 = the first voxel of the next segment
+    int32_t seg_off[8];      // vertex offset of [row][this segment, the next one]
+};
+
+// vertices of one segment in key order: lanes first own voxels (edge masks, wave prefix sum, the list), then VERTICES
+__device__ __forceinline__ void emit_vertices_segment(const IdxArgs& a, IdxVertStage& st, long s, int begin, int count,
+                                                      float4* __restrict__ out, int max_vertices) {
+    const int seg = (int)(s % a.nseg);
+    const long yz = s / a.nseg;
+    const int y = (int)(yz % a.Y), z = (int)(yz / a.Y);
+    const int lane = threadIdx.x & 63;
+    uint32_t W[9], N[9], ex, ey, ez;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) load_row_bits<3>(a, seg, y - 1, z - 1 + k, W + 3 * k, N + 3 * k);
+    row_edges(W, N, 3, ex, ey, ez);
+    const int mine = __popc(ex & IDX_OWN) + __popc(ey & IDX_OWN) + __popc(ez & IDX_OWN);
+    int incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    int off = incl - mine;  // (at most 768 in all: the list cannot overflow)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = lane * 4 + i;
+        if ((ex >> (i + 1)) & 1u) st.list[off++] = (uint16_t)(4 * c);
+        if ((ey >> (i + 1)) & 1u) st.list[off++] = (uint16_t)(4 * c + 1);
+        if ((ez >> (i + 1)) & 1u) st.list[off++] = (uint16_t)(4 * c + 2);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int total = __shfl(incl, 63, 64);  // = count; the list holds no more than this
+    for (int t = lane; t < min(count, total); t += 64) {
+        const int entry = st.list[t], axis = entry & 3, x = seg * 256 + (entry >> 2);
+        const size_t lo = (size_t)x + (size_t)a.X * ((size_t)y + (size_t)a.Y * (size_t)z);
+        const size_t hi = lo + (axis == 0 ? (size_t)1 : axis == 1 ? (size_t)a.X : (size_t)a.X * (size_t)a.Y);
+        // (the edge exists, so both voxels do; the rows were loaded a moment ago: these hit the L2)
+        const float f0 = half_bits_to_float(a.vol[lo] & 0xffffu), f1 = half_bits_to_float(a.vol[hi] & 0xffffu);
+        const f3 p0 = mk3(((float)x + 0.5f) * a.csx, ((float)y + 0.5f) * a.csy, ((float)z + 0.5f) * a.csz);
+        const f3 p1 = mk3(((float)(x + (axis == 0)) + 0.5f) * a.csx, ((float)(y + (axis == 1)) + 0.5f) * a.csy,
+                          ((float)(z + (axis == 2)) + 0.5f) * a.csz);
+        const f3 p  = vertex_interp(p0, p1, f0, f1);  // always from the low voxel to the high one
+        if (begin + t < max_vertices) out[begin + t] = make_float4(p.x, p.y, p.z, 1.0f);
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
+__global__ __launch_bounds__(256) void mci_emit_vertices_kernel(const IdxArgs a, const int32_t* __restrict__ voff,
+                                                                float4* __restrict__ out, int max_vertices,
+                                                                long nsegs_total) {
+    __shared__ IdxVertStage stage[4];
+    const long nwaves = (long)gridDim.x * 4;
+    const long w      = (long)blockIdx.x * 4 + threadIdx.y;
+    const int lane    = threadIdx.x;
+    for (long base = w; base < nsegs_total; base += 64 * nwaves) {
+        const long s = base + (long)lane * nwaves;
+        int begin = 0, end = 0;
+        if (s < nsegs_total) begin = voff[s], end = voff[s + 1];
+        unsigned long long todo = __ballot(end > begin && begin < max_vertices);
+        while (todo) {
+            const int l = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int b = __shfl(begin, l, 64);
+            emit_vertices_segment(a, stage[threadIdx.y], base + (long)l * nwaves, b, __shfl(end, l, 64) - b, out, max_vertices);
+        }
+    }
+}
+
+// indices of one segment's cubes, in the soup's order.  The edges of the cubes of row (y, z) have their lower voxels in the
+// rows (y .. y + 1, z .. z + 1), at x .. x + 1: this segment's voxels and the first one of the next segment.
+__device__ __forceinline__ void emit_indices_segment(const IdxArgs& a, const uint8_t* __restrict__ tri_lds,
+                                                     const uint8_t* __restrict__ nv_lds, IdxTriStage& st, long s, int begin,
+                                                     int count, const int32_t* __restrict__ voff, int32_t* __restrict__ out,
+                                                     int max_indices) {
+    const int seg = (int)(s % a.nseg);
+    const long yz = s / a.nseg;
+    const int y = (int)(yz % a.Y), z = (int)(yz / a.Y);
+    const int lane = threadIdx.x & 63;
+    uint32_t W[16], N[16];  // [slice z - 1 .. z + 2][row y - 1 .. y + 2]
+#pragma unroll
+    for (int k = 0; k < 4; ++k) load_row_bits<4>(a, seg, y - 1, z - 1 + k, W + 4 * k, N + 4 * k);
+    uint32_t ex[4], ey[4], ez[4];
+    int cnt[4];
+#pragma unroll
+    for (int R = 0; R < 4; ++R) {
+        const int o = 4 * (R >> 1) + (R & 1);
+        row_edges(W + o, N + o, 4, ex[R], ey[R], ez[R]);
+        cnt[R] = __popc(ex[R] & IDX_OWN) + __popc(ey[R] & IDX_OWN) + __popc(ez[R] & IDX_OWN);
+    }
+    // two prefix sums at a time: a segment owns at most 768 edges
+    int p01 = cnt[0] | cnt[1] << 16, p23 = cnt[2] | cnt[3] << 16;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t01 = __shfl_up(p01, o, 64), t23 = __shfl_up(p23, o, 64);
+        if (lane >= o) p01 += t01, p23 += t23;
+    }
+#pragma unroll
+    for (int R = 0; R < 4; ++R) {
+        const int incl = ((R < 2 ? p01 : p23) >> (16 * (R & 1))) & 0xffff;
+        int rank = incl - cnt[R];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t em = ((ex[R] >> (i + 1)) & 1u) | ((ey[R] >> (i + 1)) & 1u) << 1 | ((ez[R] >> (i + 1)) & 1u) << 2;
+            st.rank[R][lane * 4 + i] = (uint16_t)rank;
+            st.em[R][lane * 4 + i]   = (uint8_t)em;
+            rank += __popc(em);
+        }
+        if (lane == 63) {
+            st.rank[R][256] = 0;
+            st.em[R][256]   = (uint8_t)(((ex[R] >> 5) & 1u) | ((ey[R] >> 5) & 1u) << 1 | ((ez[R] >> 5) & 1u) << 2);
+        }
+    }
+    if (lane < 8) {
+        const int R = lane >> 1, k = lane & 1;
+        const int yy = y + (R & 1), zz = z + (R >> 1);
+        int32_t v = 0;
+        if (yy < a.Y && zz < a.Z && seg + k < a.nseg) v = voff[((long)zz * a.Y + yy) * a.nseg + seg + k];
+        st.seg_off[lane] = v;
+    }
+    // the cubes, as the soup emit has them
+    const uint32_t valid = face_bits(W[5], W[6]) & face_bits(W[9], W[10]);
+    int ci[4], mine = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        ci[i] = ((valid >> (i + 1)) & 1u) ? mask_case(N[5], N[6], N[9], N[10], i) : 0;
+        mine += nv_lds[ci[i]];
+    }
+    int incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    int off = incl - mine;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        st.ci[lane * 4 + i]    = (uint8_t)ci[i];
+        st.start[lane * 4 + i] = (uint16_t)off;
+        off += nv_lds[ci[i]];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (int t = lane; t < count; t += 64) {
+        int lo = 0, hi = 256;
+#pragma unroll
+        for (int step = 0; step < 8; ++step) {
+            const int mid = (lo + hi) >> 1;
+            if ((int)st.start[mid] <= t) lo = mid;
+            else hi = mid;
+        }
+        const int c  = lo;
+        const int cs = st.ci[c];
+        const int e  = tri_lds[cs * 16 + min(t - (int)st.start[c], 15)];
+        // edge e joins corners (e0, e1), as in emit_segment: the corners differ along one axis, the lower one has the 0 there
+        const int e0 = e < 8 ? e : e - 8;
+        const int e1 = e < 4 ? ((e + 1) & 3) : e < 8 ? 4 + ((e + 1) & 3) : e - 4;
+        const int dx0 = (0x66 >> e0) & 1, dy0 = (0xCC >> e0) & 1, dz0 = e0 >> 2;
+        const int dx1 = (0x66 >> e1) & 1, dy1 = (0xCC >> e1) & 1, dz1 = e1 >> 2;
+        const int axis = dx0 != dx1 ? 0 : dy0 != dy1 ? 1 : 2;
+        const int R = (dy0 & dy1) + 2 * (dz0 & dz1), cc = c + (dx0 & dx1);
+        const int id = st.seg_off[2 * R + (cc >> 8)] + (int)st.rank[R][cc] + __popc((uint32_t)st.em[R][cc] & ((1u << axis) - 1u));
+        if (begin + t < max_indices) out[begin + t] = id;
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
+__global__ __launch_bounds__(256) void mci_emit_indices_kernel(const IdxArgs a, const int32_t* __restrict__ ioff,
+                                                               const int32_t* __restrict__ voff, int32_t* __restrict__ out,
+                                                               int max_indices, long nsegs_total) {
+    __shared__ uint8_t tri_lds[256 * 16], nv_lds[256];
+    __shared__ IdxTriStage stage[4];
+    {
+        const int t = threadIdx.y * 64 + threadIdx.x;
+        for (int j = 0; j < 16; ++j) tri_lds[t * 16 + j] = (uint8_t)(a.tri[t * 16 + j] & 15);
+        nv_lds[t] = (t == 0 || t == 255) ? 0 : (uint8_t)(3 * (min(max(a.nverts[t], 0), 15) / 3));
+    }
+    __syncthreads();
+    const long nwaves = (long)gridDim.x * 4;
+    const long w      = (long)blockIdx.x * 4 + threadIdx.y;
+    const int lane    = threadIdx.x;
+    for (long base = w; base < nsegs_total; base += 64 * nwaves) {
+        const long s = base + (long)lane * nwaves;
+        int begin = 0, end = 0;
+        if (s < nsegs_total) begin = ioff[s], end = ioff[s + 1];
+        unsigned long long todo = __ballot(end > begin && begin < max_indices);
+        while (todo) {
+            const int l = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int b = __shfl(begin, l, 64);
+            emit_indices_segment(a, tri_lds, nv_lds, stage[threadIdx.y], base + (long)l * nwaves, b, __shfl(end, l, 64) - b, voff,
+                                 out, max_indices);
+        }
+    }
+}
+
 }  // namespace
+
+long mci_segments(int X, int Y, int Z) { return (long)((X + 255) / 256) * Y * Z; }
+
+hipError_t launch_marching_cubes_indexed(const uint32_t* vol, int X, int Y, int Z, const float cell_size[3],
+                                         const int32_t* tri_table, const int32_t* num_verts_table, float* out_vertices,
+                                         int max_vertices, int32_t* out_indices, int max_indices, int32_t* totals,
+                                         int32_t* voff, int32_t* ioff, int32_t* chunk_sums, const uint8_t* occ,
+                                         hipStream_t s) {
+    IdxArgs a;
+    a.vol = vol, a.X = X, a.Y = Y, a.Z = Z;
+    a.vec4 = (X % 4 == 0) && (((uintptr_t)vol & 15) == 0);
+    const OccDims od = occ_dims(X, Y, Z);
+    a.occ = occ, a.ox = od.ox, a.oy = od.oy, a.oz = od.oz;
+    a.nseg = (X + 255) / 256;
+    a.csx = cell_size[0], a.csy = cell_size[1], a.csz = cell_size[2];
+    a.tri = tri_table, a.nverts = num_verts_table;
+    const long nsegs = mci_segments(X, Y, Z);
+    // z chunks as launch_marching_cubes chooses them; one layer of the map per workgroup with a map
+    const long columns = (long)a.nseg * ((Y + 4 * MC_ROWS - 1) / (4 * MC_ROWS));
+    int zchunk         = Z;
+    while (columns * ((Z + zchunk - 1) / zchunk) < 2048 && zchunk > 16) zchunk = (zchunk + 1) / 2;
+    if (occ) zchunk = 8;
+    a.zchunk = zchunk;
+    hipError_t e = hipMemsetAsync(voff, 0, sizeof(int32_t) * (size_t)(nsegs + 1), s);
+    if (e != hipSuccess) return e;
+    if ((e = hipMemsetAsync(ioff, 0, sizeof(int32_t) * (size_t)(nsegs + 1), s)) != hipSuccess) return e;
+    dim3 block(64, 4), grid(a.nseg, (Y + 4 * MC_ROWS - 1) / (4 * MC_ROWS), (Z + zchunk - 1) / zchunk);
+    mci_count_kernel<<<grid, block, 0, s>>>(a, voff, ioff);
+    launch_segment_scan(voff, nsegs, chunk_sums, totals, s);
+    launch_segment_scan(ioff, nsegs, chunk_sums, totals + 1, s);
+    const unsigned eblocks = (unsigned)std::min<long>((nsegs + 3) / 4, 8192);
+    if (out_vertices && max_vertices > 0)
+        mci_emit_vertices_kernel<<<eblocks, block, 0, s>>>(a, voff, (float4*)out_vertices, max_vertices, nsegs);
+    if (out_indices && max_indices > 0)
+        mci_emit_indices_kernel<<<eblocks, block, 0, s>>>(a, ioff, voff, out_indices, max_indices, nsegs);
+    return hipGetLastError();
+}
 
 long mc_segments(int X, int Y, int Z, bool vec4) {
     const int vx = vec4 ? 4 : 1;

@@ -25,6 +25,9 @@ struct PolygonMesh {
     std::vector<std::vector<uint32_t>> polygons;
 };
 PolygonMesh convertToMesh(const std::vector<PointXYZ>& triangles);
+// ... and of an indexed mesh (MarchingCubes::runIndexed): the cloud is the distinct vertices, polygon i =
+// (indices[3i], indices[3i + 2], indices[3i + 1]) — convertToMesh's winding; vtkMeshString / saveVTKFile take it as it is
+PolygonMesh convertToIndexedMesh(const std::vector<PointXYZ>& vertices, const std::vector<int>& indices);
 
 namespace io {
 

@@ -1,6 +1,6 @@
 // kfusion/cuda/marching_cubes.hpp — kfusion::cuda::MarchingCubes (reference interface:
 // include/kfusion/cuda/marching_cubes.hpp:19-60; behaviour: src/kfusion/marching_cubes.cpp:12-61) on
-// dfa_marching_cubes.
+// dfa_marching_cubes / dfa_marching_cubes_indexed.
 //
 // What differs from the reference, all visible here:
 //   * any volume dimensions (the reference's kernels are fixed to 128^3);
@@ -17,8 +17,8 @@ namespace kfusion {
 namespace cuda {
 
 class MarchingCubes {
-    dfa::DeviceArray<int> tri_dev_, nverts_dev_, total_dev_;  // 256 x 16, 256, 1
-    int last_total_ = 0;
+    dfa::DeviceArray<int> tri_dev_, nverts_dev_, total_dev_, totals_dev_;  // 256 x 16, 256, 1, 2 (runIndexed)
+    int last_total_ = 0, last_unique_ = 0;
     void uploadTables(const int* tri, const int* nverts);
 
 public:
@@ -36,8 +36,25 @@ public:
     // vertices the last run() found; larger than the buffer means only the buffer's worth was written
     int totalVertices() const { return last_total_; }
 
-    // Normals of the extracted vertices from the gradient of the TSDF (the raycaster's compute_normal,
-    // tsdf_volume.cu:320-336, with the volume's gradient delta factor).  Extension: the reference leaves the mesh
+    // Extension (no counterpart in the reference): the same surface as an indexed mesh, dfa_marching_cubes_indexed — every
+    // crossed lattice edge once in `vertex_buffer`, and in `index_buffer` one vertex id per vertex of run()'s soup, in its
+    // order.  Empty buffers are allocated at DEFAULT_TRIANGLES_BUFFER_SIZE indices and a third as many vertices.  Returns
+    // NON-owning views of what was written; when the mesh does not fit one of the buffers BOTH views are empty and
+    // totalUniqueVertices() / totalVertices() say what the buffers need.  Uses the volume's occupancy map when it is
+    // trusted.  ONE host synchronisation, to size the views.
+    struct IndexedMesh {
+        dfa::DeviceArray<PointType> vertices;
+        dfa::DeviceArray<int> indices;
+    };
+    IndexedMesh runIndexed(const TsdfVolume& volume, dfa::DeviceArray<PointType>& vertex_buffer,
+                           dfa::DeviceArray<int>& index_buffer);
+
+    // distinct vertices the last runIndexed() found (totalVertices(): the indices = run()'s vertices)
+    int totalUniqueVertices() const { return last_unique_; }
+
+    // Normals of vertices from the gradient of the TSDF — ANY array of points in the volume's metric frame: run()'s soup or
+    // runIndexed()'s distinct vertices (a fifth of the work for the same surface) — the raycaster's compute_normal,
+    // tsdf_volume.cu:320-336, with the volume's gradient delta factor.  Extension: the reference leaves the mesh
     // without normals (dyn_fusion.cpp:80-88 "temporary workaround until normals are computed via mc").
     void computeNormals(const TsdfVolume& volume, const dfa::DeviceArray<PointType>& vertices,
                         dfa::DeviceArray<dfa::Normal>& normals);

@@ -22,6 +22,16 @@ PolygonMesh convertToMesh(const std::vector<PointXYZ>& triangles) {  // kinfu.cp
     return mesh;
 }
 
+PolygonMesh convertToIndexedMesh(const std::vector<PointXYZ>& vertices, const std::vector<int>& indices) {
+    PolygonMesh mesh;
+    if (vertices.empty() || indices.size() < 3) return mesh;
+    mesh.cloud.points = vertices;
+    mesh.polygons.resize(indices.size() / 3);
+    for (size_t i = 0; i < mesh.polygons.size(); ++i)
+        mesh.polygons[i] = {(uint32_t)indices[i * 3 + 0], (uint32_t)indices[i * 3 + 2], (uint32_t)indices[i * 3 + 1]};
+    return mesh;
+}
+
 namespace io {
 namespace {
 

@@ -106,4 +106,14 @@ std::shared_ptr<dfa::PolygonMesh> KinFu::extractMesh() {
     return std::make_shared<dfa::PolygonMesh>(dfa::convertToMesh(host));
 }
 
+std::shared_ptr<dfa::PolygonMesh> KinFu::extractIndexedMesh() {
+    dfa::DeviceArray<cuda::MarchingCubes::PointType> vertex_buffer;
+    dfa::DeviceArray<int> index_buffer;
+    const auto mesh = mc_->runIndexed(*volume_, vertex_buffer, index_buffer);
+    std::vector<cuda::MarchingCubes::PointType> vertices;
+    std::vector<int> indices;
+    if (!mesh.vertices.empty()) mesh.vertices.download(vertices), mesh.indices.download(indices);
+    return std::make_shared<dfa::PolygonMesh>(dfa::convertToIndexedMesh(vertices, indices));
+}
+
 }  // namespace kfusion

@@ -51,6 +51,29 @@ dfa::DeviceArray<MarchingCubes::PointType> MarchingCubes::run(const TsdfVolume& 
     return dfa::DeviceArray<PointType>(triangles_buffer.ptr(), n);
 }
 
+MarchingCubes::IndexedMesh MarchingCubes::runIndexed(const TsdfVolume& volume, dfa::DeviceArray<PointType>& vertex_buffer,
+                                                     dfa::DeviceArray<int>& index_buffer) {
+    if (index_buffer.empty()) index_buffer.create(DEFAULT_TRIANGLES_BUFFER_SIZE);
+    if (vertex_buffer.empty()) vertex_buffer.create(DEFAULT_TRIANGLES_BUFFER_SIZE / POINTS_PER_TRIANGLE);
+    if (totals_dev_.empty()) totals_dev_.create(2);
+    const Vec3i dims = volume.getDims();
+    const Vec3f size = volume.getSize();
+    const float cell[3] = {size[0] / dims[0], size[1] / dims[1], size[2] / dims[2]};
+    dfa::check(dfa_marching_cubes_indexed(volume.data().ptr<uint32_t>(), volume.occupancy(), dims[0], dims[1], dims[2], cell,
+                                          tri_dev_.ptr(), nverts_dev_.ptr(), (float*)vertex_buffer.ptr(),
+                                          (int)vertex_buffer.size(), index_buffer.ptr(), (int)index_buffer.size(),
+                                          totals_dev_.ptr(), nullptr),
+               "MarchingCubes::runIndexed");
+    std::vector<int> t;
+    totals_dev_.download(t);  // synchronises
+    last_unique_ = t[0], last_total_ = t[1];
+    IndexedMesh mesh;
+    if (t[0] == 0 || t[1] == 0 || (size_t)t[0] > vertex_buffer.size() || (size_t)t[1] > index_buffer.size()) return mesh;
+    mesh.vertices = dfa::DeviceArray<PointType>(vertex_buffer.ptr(), (size_t)t[0]);
+    mesh.indices  = dfa::DeviceArray<int>(index_buffer.ptr(), (size_t)t[1]);
+    return mesh;
+}
+
 void MarchingCubes::computeNormals(const TsdfVolume& volume, const dfa::DeviceArray<PointType>& vertices,
                                    dfa::DeviceArray<dfa::Normal>& normals) {
     if (normals.size() < vertices.size()) normals.create(vertices.size());

@@ -295,6 +295,31 @@ int dfa_marching_cubes_occ(const uint32_t* volume, const uint8_t* occupancy, int
                            const int32_t* tri_table, const int32_t* num_verts_table, float* out_points, int max_vertices,
                            int32_t* total_vertices, dfa_stream_t stream);
 
+/* The same surface as an INDEXED mesh: every crossed lattice edge once, plus a triangle index list.  (The soup repeats a
+ * shared vertex about five times, and its copies are not bit-equal — two cubes may interpolate one edge from opposite
+ * ends — so a caller cannot weld it by comparing positions; the edge identity is known only here.)
+ * volume, cell_size, tri_table, num_verts_table, stream: as dfa_marching_cubes; every dim >= 2.  occupancy: the volume's
+ *   map as for dfa_marching_cubes_occ, or NULL; identical output either way.
+ * Vertex set: a lattice edge whose two voxels differ in `distance < 0` and that has, among the up to four cubes around it,
+ *   one with eight non-zero weights.  PRECONDITION on the table: every case references exactly its crossed edges (the
+ *   reference's table and dfa_mc_default_tables do, all 256 cases); then this is the set of edges the triangles reference.
+ *   With another table an index may name an arbitrary vertex.
+ * out_vertices (device, 16-byte aligned): max_vertices float4 {x, y, z, 1} in ascending key 3 * (z*X*Y + y*X + x) + axis,
+ *   (x, y, z) the edge's lower voxel, axis 0 / 1 / 2 = +x / +y / +z; always interpolated from the lower voxel to the
+ *   upper one with dfa_marching_cubes' arithmetic, so a position does not depend on the cubes that use it.
+ * out_indices (device): out_indices[i] = the vertex of soup vertex i of dfa_marching_cubes on the same inputs, same order:
+ *   three per triangle.
+ * totals (device, 2 ints, required): vertices, indices (= dfa_marching_cubes' total_vertices) the volume produces — always
+ *   exact.  Nothing is written past either capacity; when a total exceeds its capacity the contents of BOTH buffers are
+ *   unspecified: size them from `totals` and call again.  NULL buffers with zero capacities count only.
+ * Scratch (kept per stream by the library, as dfa_marching_cubes' is): two int32 per row segment of 256 voxels,
+ *   8 * (ceil(X / 256) * Y * Z + 1) bytes, plus 4 bytes per 8192 segments — 4 MiB at 512^3, 32 MiB at 1024^3.  There is no
+ *   per-voxel id map: an emit wave recomputes the ranks of the edges it needs from the volume. */
+int dfa_marching_cubes_indexed(const uint32_t* volume, const uint8_t* occupancy /* may be NULL */, int X, int Y, int Z,
+                               const float cell_size[3], const int32_t* tri_table, const int32_t* num_verts_table,
+                               float* out_vertices, int max_vertices, int32_t* out_indices, int max_indices,
+                               int32_t* totals /* device, 2 ints: vertices, indices */, dfa_stream_t stream);
+
 /* A valid case table pair for callers that do not have the reference's (HOST buffers, 256 x 16
  * and 256 ints): derived from the face-by-face rule described in csrc/mc.hip.  Same corner / edge
  * numbering and winding as the reference's table (src/kfusion/marching_cubes.cpp:86-343) but not
