@@ -3,7 +3,13 @@
 // level -> ICP.  The reference has no ICP test; here a synthetic scene is rendered from two camera poses and the
 // estimate must recover the relative pose.
 #include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iterator>
+#include <string>
 
+#include <kfusion/cuda/icp_update.hpp>
 #include <kfusion/cuda/imgproc.hpp>
 #include <kfusion/cuda/projective_icp.hpp>
 
@@ -106,6 +112,87 @@ TEST(ProjectiveIcpTest, EstimateTransformRecoversTheCameraMotion) {
     }
     Affine3f est;
     ASSERT_TRUE(!icp.estimateTransform(est, intr, empty, nempty, prev.depth, prev.normals));
+}
+
+namespace {
+// minimal reader of tests/golden/icp_update_kat.json (tests/golden/make_icp_update_kat.py): per case the keys "sums",
+// "before", "ok", "check_affine", "after" in that order; a null among the sums is a NaN (JSON has no token for it)
+struct KatCase {
+    std::string name;
+    float sums[27], before[12], after[12];
+    bool ok, check_affine;
+};
+const char* after_key(const std::string& s, size_t& at, const char* key) {
+    at = s.find(std::string("\"") + key + "\":", at);
+    if (at == std::string::npos) throw mt::Failure{std::string("icp_update_kat.json: missing key ") + key};
+    at += std::strlen(key) + 3;
+    return s.c_str() + at;
+}
+void read_floats(const std::string& s, size_t& at, const char* key, float* out, int n) {
+    const char* p = std::strchr(after_key(s, at, key), '[') + 1;
+    for (int i = 0; i < n; ++i) {
+        while (*p == ' ' || *p == '\n') ++p;
+        char* end;
+        if (std::strncmp(p, "null", 4) == 0) out[i] = std::nanf(""), end = const_cast<char*>(p) + 4;
+        else out[i] = (float)std::strtod(p, &end);  // the fixture holds float32 values: exact
+        if (end == p) throw mt::Failure{std::string("icp_update_kat.json: short array ") + key};
+        p = end;
+        while (*p == ',' || *p == ' ' || *p == '\n') ++p;
+    }
+}
+bool read_bool(const std::string& s, size_t& at, const char* key) {
+    const char* p = after_key(s, at, key);
+    while (*p == ' ') ++p;
+    return std::strncmp(p, "true", 4) == 0;
+}
+std::vector<KatCase> read_kat() {
+    std::string dir = __FILE__;  // tests/cpp/test_host_icp.cpp
+    dir = dir.substr(0, dir.find_last_of('/') + 1) + "../golden/icp_update_kat.json";
+    const char* env = std::getenv("DFA_ICP_UPDATE_KAT");
+    std::ifstream in(env ? std::string(env) : dir);
+    if (!in) in.open("tests/golden/icp_update_kat.json");
+    if (!in) throw mt::Failure{"icp_update_kat.json not found (DFA_ICP_UPDATE_KAT names it)"};
+    const std::string s((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    std::vector<KatCase> out;
+    for (size_t at = s.find("\"name\":"); at != std::string::npos; at = s.find("\"name\":", at)) {
+        KatCase c;
+        const size_t q0 = s.find('"', at + 7) + 1;
+        c.name          = s.substr(q0, s.find('"', q0) - q0);
+        read_floats(s, at, "sums", c.sums, 27);
+        read_floats(s, at, "before", c.before, 12);
+        c.ok           = read_bool(s, at, "ok");
+        c.check_affine = read_bool(s, at, "check_affine");
+        read_floats(s, at, "after", c.after, 12);
+        out.push_back(c);
+    }
+    return out;
+}
+}  // namespace
+
+// kfusion::cuda::icp_update against the float64 statement's known answers (tests/img_statement.py:icp_update): `ok`
+// exactly; every entry of the next affine within 2 float32 ulps of its magnitude or 1e-7, whichever is larger (both
+// sides solve in double).  At the two systems on the determinant gate only `ok`.  Needs no GPU.
+TEST(ProjectiveIcpTest, IcpUpdateKnownAnswers) {
+    const std::vector<KatCase> kat = read_kat();
+    ASSERT_EQ(kat.size(), (size_t)9);
+    for (const KatCase& c : kat) {
+        Affine3f a;
+        for (int i = 0; i < 9; ++i) a.R[i] = c.before[i];
+        for (int i = 0; i < 3; ++i) a.t[i] = c.before[9 + i];
+        const bool ok = cuda::icp_update(c.sums, a);
+        if (ok != c.ok) throw mt::Failure{c.name + ": ok differs from the statement's"};
+        if (!c.check_affine) continue;
+        float got[12];
+        a.to12(got);
+        for (int i = 0; i < 12; ++i) {
+            const double want = c.after[i], tol = std::fmax(2.0 * std::ldexp(1.0, std::ilogb(std::fabs(want) > 0 ? std::fabs(want) : 1e-30) - 23), 1e-7);
+            if (!(std::fabs((double)got[i] - want) <= tol)) {
+                char buf[200];
+                std::snprintf(buf, sizeof buf, "%s: affine[%d] = %.9g, statement %.9g, tolerance %.3g", c.name.c_str(), i, got[i], want, tol);
+                throw mt::Failure{buf};
+            }
+        }
+    }
 }
 
 int main(int argc, char** argv) { return mt::run_all(argc, argv); }

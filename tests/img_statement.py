@@ -14,7 +14,9 @@ Undefined outputs are the reference's numeric_limits<float>::quiet_NaN(), the bi
 
 The ICP statement forms the correspondence tests, the `float row[7]` and every product row[i] * row[j] in float32 as
 proj_icp.cu:28-100 and :335-353 do, and adds the 27 products in float64: the reference's float tree reduction depends
-on its tile order and is not restated.
+on its tile order and is not restated.  icp64() adds the same sums with rows and products in float64 (sum64), their
+rounding scale (abs64) and the number of knife-edge pixels; icp_update() is the host's 6x6 step (projective_icp.cpp:136-152)
+in float64.
 """
 import numpy as np
 
@@ -210,11 +212,25 @@ def resize_points_normals(points, normals):
 
 
 # ---------------------------------------------------------------------------------------------------------- ICP ----
-def icp(curr, ncurr, prev, nprev, aff12, intr, dist_thres=0.1, angle_thres=0.3490658503988659):
-    """One linearisation of proj_icp.cu: find_coresp (:41-99; the depth variant when curr is a uint16 depth image,
-    the points variant for (H, W, 4) vertex maps) and the row of icp_helper_kernel (:335-353) at every pixel.
-    Returns (27 float64 sums in StreamHelper::get's order, i <= j < 7, projective_icp.cpp:39-57; matched mask (H, W);
-    the float32 rows (H, W, 7), zero where unmatched)."""
+SUM_PAIRS = [(i, j) for i in range(6) for j in range(i, 7)]  # StreamHelper::get's order (projective_icp.cpp:39-57)
+B_SUMS = [6, 12, 17, 21, 24, 26]                             # the right-hand side b among the 27
+KNIFE_ULPS = 4
+
+
+def _ulp(*mags):
+    """float32 spacing at the largest of the given magnitudes (elementwise)"""
+    m = np.zeros(np.broadcast(*mags).shape, np.float32)
+    for v in mags:
+        m = np.fmax(m, np.abs(np.asarray(v, np.float32)))  # fmax: a NaN magnitude never marks a pixel
+    return np.spacing(m)
+
+
+def _icp_terms(curr, ncurr, prev, nprev, aff12, intr, dist_thres, angle_thres, fused=False):
+    """find_coresp and the row in float32 -> dict.  The matched mask `ok`, the correspondence (iw, iu) and `knife` (the
+    pixels with a gate quantity within KNIFE_ULPS float32 ulps of its threshold, counted only while the pixel is still
+    alive at that gate; the ulp is taken at the larger of the quantity's operands and the threshold) never depend on
+    `fused`.  With fused=True every a*b + c of s (R p + t as one chain of three fmas), of the cross product and of the
+    dots is evaluated with one rounding: the other legitimate float32 reading of the same source lines."""
     depth_variant = np.asarray(curr).dtype == np.uint16
     H, W = np.shape(curr)[:2]
     a = np.asarray(aff12, np.float32).reshape(-1)
@@ -237,8 +253,12 @@ def icp(curr, ncurr, prev, nprev, aff12, intr, dist_thres=0.1, angle_thres=0.349
         p = [vc[..., k] for k in range(3)]
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         s = [(dot(R[k], p) + t[k]).astype(np.float32) for k in range(3)]  # aff * p = R p + t
-        coox = fma32(fx, s[0] / s[2], cx)  # proj (:28-33)
-        cooy = fma32(fy, s[1] / s[2], cy)
+        qx, qy = s[0] / s[2], s[1] / s[2]
+        coox = fma32(fx, qx, cx)  # proj (:28-33)
+        cooy = fma32(fy, qy, cy)
+        knife = ok & ((np.abs(s[2]) <= KNIFE_ULPS * _ulp(R[2, 0] * p[0], R[2, 1] * p[1], R[2, 2] * p[2], t[2]))
+                      | (np.minimum(np.abs(coox), np.abs(coox - f32(W))) <= KNIFE_ULPS * _ulp(fx * qx, cx, f32(W)))
+                      | (np.minimum(np.abs(cooy), np.abs(cooy - f32(H))) <= KNIFE_ULPS * _ulp(fy * qy, cy, f32(H))))
         ok &= ~((s[2] <= 0) | (coox < 0) | (cooy < 0) | (coox >= f32(W)) | (cooy >= f32(H)))  # :50 / :80
         ok &= np.isfinite(coox) & np.isfinite(cooy)
         iu = np.where(ok, np.floor(np.where(ok, coox, 0)), 0).astype(np.int64)  # point-sampled texture
@@ -252,18 +272,123 @@ def icp(curr, ncurr, prev, nprev, aff12, intr, dist_thres=0.1, angle_thres=0.349
             ok &= ~np.isnan(vp[..., 0])  # :84
             d = [vp[..., k] for k in range(3)]
         sd = [s[k] - d[k] for k in range(3)]
-        ok &= ~(dot(sd, sd) > dist2)  # :59-61 norm_sqr
+        sqr = dot(sd, sd)
+        knife |= ok & (np.abs(sqr - dist2) <= KNIFE_ULPS * _ulp(sqr, dist2))
+        ok &= ~(sqr > dist2)  # :59-61 norm_sqr
         ns = [dot(R[k], [nc[..., j] for j in range(3)]) for k in range(3)]  # aff.R * ncurr
         npv = nprev[iw, iu]
         n = [npv[..., k] for k in range(3)]
-        ok &= ~(np.abs(dot(ns, n)) < min_cosine)  # :66-68
-        row = [s[1] * n[2] - s[2] * n[1], s[2] * n[0] - s[0] * n[2], s[0] * n[1] - s[1] * n[0],  # cross(s, n)
-               n[0], n[1], n[2], dot(n, [d[k] - s[k] for k in range(3)])]  # :346-348
+        cosine = np.abs(dot(ns, n))
+        knife |= ok & (np.abs(cosine - min_cosine) <= KNIFE_ULPS * _ulp(ns[0] * n[0], ns[1] * n[1], ns[2] * n[2], min_cosine))
+        ok &= ~(cosine < min_cosine)  # :66-68
+        if fused:
+            s = [fma32(R[k, 2], p[2], fma32(R[k, 1], p[1], fma32(R[k, 0], p[0], t[k]))) for k in range(3)]
+            cross = [fma32(s[1], n[2], -(s[2] * n[1])), fma32(s[2], n[0], -(s[0] * n[2])), fma32(s[0], n[1], -(s[1] * n[0]))]
+        else:
+            cross = [s[1] * n[2] - s[2] * n[1], s[2] * n[0] - s[0] * n[2], s[0] * n[1] - s[1] * n[0]]  # cross(s, n)
+        row = cross + [n[0], n[1], n[2], dot(n, [d[k] - s[k] for k in range(3)])]  # :346-348
     rows = np.zeros((H, W, 7), np.float32)
     for k in range(7):
         rows[..., k] = np.where(ok, row[k], f32(0))  # :350
-    sums = []
-    for i in range(6):
-        for j in range(i, 7):
-            sums.append(np.sum((rows[..., i] * rows[..., j]).astype(np.float64)))  # float32 product, float64 sum
-    return np.array(sums, np.float64), ok, rows
+    return dict(ok=ok, rows=rows, knife=knife, iu=iu, iw=iw, n=n, depth_variant=depth_variant, R=R, t=t,
+                intr=(fx, fy, cx, cy), finv=(finvx, finvy))
+
+
+def sums_of_rows(rows):
+    """the 27 sums of float32 rows (H, W, 7): float32 products added in float64"""
+    return np.array([np.sum((rows[..., i] * rows[..., j]).astype(np.float64)) for i, j in SUM_PAIRS], np.float64)
+
+
+def icp(curr, ncurr, prev, nprev, aff12, intr, dist_thres=0.1, angle_thres=0.3490658503988659, fused=False):
+    """One linearisation of proj_icp.cu: find_coresp (:41-99; the depth variant when curr is a uint16 depth image,
+    the points variant for (H, W, 4) vertex maps) and the row of icp_helper_kernel (:335-353) at every pixel.
+    Returns (27 float64 sums in StreamHelper::get's order, i <= j < 7, projective_icp.cpp:39-57; matched mask (H, W);
+    the float32 rows (H, W, 7), zero where unmatched).  fused: see _icp_terms; the mask is the same."""
+    T = _icp_terms(curr, ncurr, prev, nprev, aff12, intr, dist_thres, angle_thres, fused)
+    return sums_of_rows(T["rows"]), T["ok"], T["rows"]
+
+
+def icp64(curr, ncurr, prev, nprev, aff12, intr, dist_thres=0.1, angle_thres=0.3490658503988659):
+    """icp() plus the exact statement.  Returns (sums, ok, rows, sum64, abs64, knife):
+    sum64[q]  the 27 sums over the pixels matched in float32 (that mask and its correspondences are the contract), with
+              s = R p + t, the re-projections, the row and the products formed in float64 from the same float32 inputs
+              (images, affine, intrinsics and the float32 1 / f and 0.001f the kernel holds);
+    abs64[q]  sum over those pixels of |row_i row_j|: the scale of legitimate rounding of sum q;
+    knife     the number of knife-edge pixels (see _icp_terms): where a contracted a*b + c may decide a gate otherwise."""
+    T = _icp_terms(curr, ncurr, prev, nprev, aff12, intr, dist_thres, angle_thres)
+    ok, iu, iw = T["ok"], T["iu"], T["iw"]
+    f8 = np.float64
+    R, t = T["R"].astype(f8), T["t"].astype(f8)
+    fx, fy, cx, cy = (f8(v) for v in T["intr"])
+    finvx, finvy = (f8(v) for v in T["finv"])
+    H, W = ok.shape
+    mm = f8(f32(0.001))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        if T["depth_variant"]:
+            z = np.asarray(curr, np.uint16).astype(f8) * mm
+            uu, vv = np.arange(W, dtype=f8)[None, :], np.arange(H, dtype=f8)[:, None]
+            p = [z * (uu - cx) * finvx, z * (vv - cy) * finvy, z]
+        else:
+            p = [np.asarray(curr, np.float32)[..., k].astype(f8) for k in range(3)]
+        s = [R[k, 0] * p[0] + R[k, 1] * p[1] + R[k, 2] * p[2] + t[k] for k in range(3)]
+        if T["depth_variant"]:
+            z = np.asarray(prev, np.uint16)[iw, iu].astype(f8) * mm
+            coox, cooy = fx * (s[0] / s[2]) + cx, fy * (s[1] / s[2]) + cy
+            d = [z * (coox - cx) * finvx, z * (cooy - cy) * finvy, z]
+        else:
+            vp = np.asarray(prev, np.float32)[iw, iu]
+            d = [vp[..., k].astype(f8) for k in range(3)]
+        n = [c.astype(f8) for c in T["n"]]
+        row = [s[1] * n[2] - s[2] * n[1], s[2] * n[0] - s[0] * n[2], s[0] * n[1] - s[1] * n[0], n[0], n[1], n[2],
+               n[0] * (d[0] - s[0]) + n[1] * (d[1] - s[1]) + n[2] * (d[2] - s[2])]
+        row = [r[ok] for r in row]
+        sum64 = np.array([np.sum(row[i] * row[j]) for i, j in SUM_PAIRS], f8)
+        abs64 = np.array([np.sum(np.abs(row[i] * row[j])) for i, j in SUM_PAIRS], f8)
+    return sums_of_rows(T["rows"]), ok, T["rows"], sum64, abs64, int(T["knife"].sum())
+
+
+def per_sum_units(got, sum64, abs64):
+    """|got[q] - sum64[q]| in units of 2^-24 abs64[q], per sum (0 where both are exactly equal, also at abs64 = 0)"""
+    got, sum64, abs64 = (np.asarray(v, np.float64) for v in (got, sum64, abs64))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        diff = np.abs(got - sum64)
+        return np.where(diff == 0, 0.0, diff / (2.0 ** -24 * abs64))
+
+
+def unpack_sums(sums27):
+    """StreamHelper::get (projective_icp.cpp:39-57): the 27 sums -> (A symmetric 6x6, b), float64"""
+    A, b = np.zeros((6, 6)), np.zeros(6)
+    for q, (i, j) in enumerate(SUM_PAIRS):
+        if j == 6:
+            b[i] = sums27[q]
+        else:
+            A[i, j] = A[j, i] = sums27[q]
+    return A, b
+
+
+def rodrigues(r):
+    """cv::Affine3(rvec, t)'s rotation: the identity below DBL_EPSILON, else cos I + (1 - cos) k k^T + sin [k]x"""
+    r = np.asarray(r, np.float64)
+    th = np.sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2])
+    if not th > np.finfo(np.float64).eps:
+        return np.eye(3)
+    k = r / th
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.cos(th) * np.eye(3) + (1 - np.cos(th)) * np.outer(k, k) + np.sin(th) * K
+
+
+def icp_update(sums27, aff12):
+    """The host step of one iteration (projective_icp.cpp:136-152) in float64: unpack A and b, refuse a system with
+    |det A| < 1e-15 or a NaN determinant, otherwise solve A x = b and put the increment (Rodrigues of x[:3],
+    translation x[3:]) on the left of the current affine.  -> (ok, 12 float32: R row-major then t; the input when not ok).
+    The product is formed in float64 and rounded to float32 once."""
+    a = np.asarray(aff12, np.float32).reshape(-1)
+    A, b = unpack_sums(np.asarray(sums27, np.float64))
+    with np.errstate(all="ignore"):
+        det = np.linalg.det(A)
+    if np.isnan(det) or abs(det) < 1e-15:
+        return False, a.copy()
+    x = np.linalg.solve(A, b)
+    Ri = rodrigues(x[:3])
+    R, t = a[:9].reshape(3, 3).astype(np.float64), a[9:].astype(np.float64)
+    return True, np.concatenate([(Ri @ R).reshape(-1), Ri @ t + x[3:]]).astype(np.float32)

@@ -83,6 +83,21 @@ def test_depth_png_decoder_against_pillow_and_the_golden_frame(exes, tmp_path):
     assert r.returncode != 0 and "greyscale" in (r.stdout + r.stderr)
 
 
+def test_icp_update_known_answers(exes):
+    """kfusion::cuda::icp_update (the 6x6 solve, the determinant gate and the pose update of ProjectiveICP::runLevel) on
+    the float64 statement's known answers, tests/golden/icp_update_kat.json; the fixture regenerates byte for byte."""
+    import importlib.util
+    kat = os.path.join(ROOT, "tests", "golden", "icp_update_kat.json")
+    r = subprocess.run([exes["test_host_icp"], "IcpUpdateKnownAnswers"], capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, DFA_ICP_UPDATE_KAT=kat))
+    assert r.returncode == 0 and "1 tests, 0 failed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    spec = importlib.util.spec_from_file_location("make_icp_update_kat", os.path.join(ROOT, "tests", "golden", "make_icp_update_kat.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    import json
+    assert json.dumps(dict(cases=gen.cases()), indent=1) + "\n" == open(kat).read()
+
+
 def test_host_library_exports_the_adaptor_classes(exes):
     lib = os.path.join(ROOT, "dynfu_amd", "libdynfu_amd_host.so")
     syms = subprocess.run(["nm", "-DC", lib], capture_output=True, text=True).stdout
@@ -126,7 +141,7 @@ def test_host_kinfu_rigid_pipeline(exes):
 @pytest.mark.gpu
 def test_host_projective_icp(exes):
     out = _run(exes["test_host_icp"])
-    assert "2 tests, 0 failed" in out
+    assert "3 tests, 0 failed" in out
 
 
 @pytest.mark.gpu
