@@ -181,6 +181,7 @@ struct dfa_solver {
                                   // rows longer than J x 20 entries make the first launch give up and the plan fall back)
     bool deterministic = false;  // order-stable variant (dfa_solver_set_deterministic), applied by the next set_problem
     bool just_reset = false;  // the unknowns and the state block were zeroed by set_problem and not touched since
+    bool graph_rows = false;  // the last set_problem built graphs and rows with the fused launch (solve_build_graph_rows)
     long long* iters_total = nullptr;  // device: PCG iterations of all solves since enable_timing(1)
     dfa_overlap_fn overlap_fn = nullptr;  // called behind the first assembly launch of every solve
     void* overlap_user        = nullptr;
@@ -1018,15 +1019,23 @@ int dfa_solver_set_problem(dfa_solver* s, const float* node_pos, const float* no
     hipStream_t st = S(stream);
     // initializeDataGraph (opt_solver.cpp:56-72): rows [0, N) = k-NN of the canonical vertices + RBF weights
     const dfa::KnnGridView* grid = nullptr;
-    if (want_grid(D, (long)N + D)) {
+    // (development builds: DFA_GRAPH_GRID=1 puts the nodes of ANY problem in the grid — the tests of the fused graph build
+    // reach its branches with a few dozen nodes)
+    if (want_grid(D, (long)N + D) || dfa::dev_env_int("DFA_GRAPH_GRID", 0) != 0) {
         HIP_TRY(dfa::knn_grid_build(s->grid.v, node_pos, D, st));
         grid = &s->grid.v;
     }
-    if (N > 0) HIP_TRY(dfa::launch_knn(node_pos, node_w, D, canon_vertices, N, s->k, v.ridx, v.rw, grid, st));
-    // initializeRegGraph (:74-105): k-NN of every node among the nodes (itself included at distance 0)
-    HIP_TRY(dfa::launch_knn(node_pos, node_w, D, node_pos, D, s->k, v.reg_idx, nullptr, grid, st));
-    // rows + transposition; resetGPUMemory (:149-202): unknowns start at zero (same launch as the row set-up)
-    HIP_TRY(dfa::solve_build_graph(v, s->state, s->ticket, 64, st));
+    s->graph_rows = grid && dfa::solve_graph_rows_fits(v);
+    if (s->graph_rows) {
+        // both searches, the rows and the reset as one launch, then the transposition: the same bits as the sequence below
+        HIP_TRY(dfa::solve_build_graph_rows(v, *grid, s->state, s->ticket, 64, st));
+    } else {
+        if (N > 0) HIP_TRY(dfa::launch_knn(node_pos, node_w, D, canon_vertices, N, s->k, v.ridx, v.rw, grid, st));
+        // initializeRegGraph (:74-105): k-NN of every node among the nodes (itself included at distance 0)
+        HIP_TRY(dfa::launch_knn(node_pos, node_w, D, node_pos, D, s->k, v.reg_idx, nullptr, grid, st));
+        // rows + transposition; resetGPUMemory (:149-202): unknowns start at zero (same launch as the row set-up)
+        HIP_TRY(dfa::solve_build_graph(v, s->state, s->ticket, 64, st));
+    }
     s->has_problem = true;
     s->just_reset  = true;
     return DFA_OK;
@@ -1595,6 +1604,17 @@ int dfa_solver6_get_stats(dfa_solver6* s, dfa_solve6_stats* out, dfa_stream_t st
 }
 
 }  // extern "C"
+
+#ifdef DFA_DEV_AB  // development flavour only: the plan's graph-build outputs, for the tests that compare the two launch sequences
+// out[0..10] = ridx, rw, rb, re, reg_idx, node_ptr, node_list, t, state block, tickets, (size_t) bytes of the state block;
+// returns 1 if the last set_problem took the fused graph build
+extern "C" __attribute__((visibility("default"))) int dfa_dev_solver_graph_ptrs(dfa_solver* s, void** out) {
+    const dfa::SolveView& v = s->v;
+    void* p[] = {v.ridx, v.rw, v.rb, v.re, v.reg_idx, v.node_ptr, v.node_list, v.t, s->state, s->ticket, (void*)sizeof(dfa::SolveState)};
+    for (size_t i = 0; i < sizeof(p) / sizeof(p[0]); ++i) out[i] = p[i];
+    return s->graph_rows ? 1 : 0;
+}
+#endif
 
 #ifdef DFA_S6_DEBUG  // development builds only: device pointers of the north-star plan (tools/_dbg*.py)
 extern "C" __attribute__((visibility("default"))) int dfa_dev_solver6_ptrs(dfa_solver6* s, void** out) {

@@ -14,6 +14,14 @@
 // (D x D) serves the x, y and z systems:  A = sum_rows tau w w^T,  g = sum_rows tau w e,
 // e = b - sum w t.
 //
+// Launches of one problem (dfa_solver_set_problem), nodes in the grid, k in {4, 8, 16}:
+//   grid_build_one_kernel (warp.hip) -> graph_rows_kernel<K> (both k-NN searches, rows, reset) -> tg_count_kernel ->
+//   tg_colscan_kernel -> tg_fill_kernel [-> sort_node_lists_kernel, order-stable variant]
+// otherwise (no grid, another k, no vertices; DFA_GRAPH_ROWS=0 in development builds):
+//   [grid build ->] knn_kernel / knn_wave_kernel (vertices) -> knn_wave_kernel / knn_kernel (nodes) ->
+//   prepare_rows_kernel<K> -> tg_count_kernel -> tg_colscan_kernel -> tg_fill_kernel [-> sort_node_lists_kernel]
+// Both leave the same bits (tests/test_gpu_graph_rows.py).
+//
 // MI355X mapping
 //   * Opt re-walks all N*k graph edges with global atomics in every PCG iteration; here A is
 //     assembled once per linearisation and the PCG iterates on ~20 D non-zeros that never
@@ -39,6 +47,7 @@
 #include "dq_device.hpp"
 #include "dev_switch.hpp"
 #include "kernels.hpp"
+#include "knn_device.hpp"
 #include "pcg_rules.hpp"
 #include "solve.hpp"
 
@@ -374,52 +383,10 @@ __global__ __launch_bounds__(256) void reset_kernel(float* __restrict__ t, int n
     }
 }
 
-// The per-problem row set-up as ONE launch, a thread per row: regularisation rows (opt_solver.cpp:74-105), right-hand
-// sides of the data rows (energy.t:55), packed record heads and the zeroing of the
-// unknowns / state block / tickets (reset_kernel) — four launches of 5-16 us each at C2 in round 1.
+// head of row r's packed record (the words before (e, tau)): its k node ids — 16-bit where solve_rec_ids16(k) — and k weights
 template <int K>
-__global__ __launch_bounds__(256) void prepare_rows_kernel(SolveView s, SolveState* __restrict__ st,
-                                                           unsigned int* __restrict__ ticket, int nticket) {
-    const size_t R = (size_t)s.N + (size_t)s.D * s.k;
-    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < (size_t)3 * s.D) s.t[r] = 0.f;
-    if (blockIdx.x == 0) {
-        unsigned int* w = (unsigned int*)st;
-        for (int j = threadIdx.x; j < (int)(sizeof(SolveState) / 4); j += blockDim.x) w[j] = 0u;
-        for (int j = threadIdx.x; j < nticket; j += blockDim.x) ticket[j] = 0u;
-    }
-    if (r >= R) return;
+__device__ __forceinline__ void store_record_head(const SolveView& s, size_t r, const int (&ids)[K], const float (&ws)[K], bool wide) {
     const int k = s.k;
-    int ids[K];
-    float ws[K];
-    const bool wide = k == K && K % 4 == 0;  // (uniform) the common case: every row's ids / weights / record head by 16-byte accesses
-    if (r < (size_t)s.N) {  // data row: k-NN + RBF weights already in ridx / rw; b = live - canonical (energy.t:55)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) s.rb[3 * r + c] = s.live[3 * r + c] - s.canon[3 * r + c];
-        if (wide) load_row_graph<K>(s, r, ids, ws);
-        else {
-#pragma unroll
-            for (int j = 0; j < K; ++j)
-                if (j < k) ids[j] = s.ridx[r * k + j], ws[j] = s.rw[r * k + j];
-        }
-    } else {  // regularisation row N + n k + i <- {reg_idx[n][i]: -1, n: +1} (opt_solver.cpp:74-105, energy.t:75-78)
-        const int e = (int)(r - (size_t)s.N), n = e / k, m = s.reg_idx[e];
-#pragma unroll
-        for (int j = 0; j < K; ++j) ids[j] = -1, ws[j] = 0.f;
-        if (m >= 0 && m != n) ids[0] = m, ws[0] = -1.f, ids[1] = n, ws[1] = +1.f;  // k >= 2 whenever a non-self neighbour exists
-        if (wide) {
-#pragma unroll
-            for (int q = 0; q < K / 4; ++q) {
-                reinterpret_cast<int4*>(s.ridx + r * K)[q]  = make_int4(ids[4 * q], ids[4 * q + 1], ids[4 * q + 2], ids[4 * q + 3]);
-                reinterpret_cast<float4*>(s.rw + r * K)[q] = make_float4(ws[4 * q], ws[4 * q + 1], ws[4 * q + 2], ws[4 * q + 3]);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < K; ++j)
-                if (j < k) s.ridx[r * k + j] = ids[j], s.rw[r * k + j] = ws[j];
-        }
-        s.rb[3 * r + 0] = s.rb[3 * r + 1] = s.rb[3 * r + 2] = 0.f;
-    }
     float* rec = s.re + r * (size_t)solve_rec_words(k);
     if (wide) {  // the record's head (the words before (e, tau)) as float4 stores: a lane's record is 48 or 64 contiguous bytes
         float4* rec4 = reinterpret_cast<float4*>(rec);
@@ -454,6 +421,125 @@ __global__ __launch_bounds__(256) void prepare_rows_kernel(SolveView s, SolveSta
 #pragma unroll
     for (int j = 0; j < K; ++j)
         if (j < k) rec[j] = __int_as_float(ids[j]), rec[k + j] = ws[j];
+}
+
+// slots of the regularisation row of node n and its neighbour m: {m: -1, n: +1}; all empty for an absent neighbour and for
+// the self edge (opt_solver.cpp:74-105, energy.t:75-78)
+template <int K>
+__device__ __forceinline__ void reg_row_slots(int m, int n, int (&ids)[K], float (&ws)[K]) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) ids[j] = -1, ws[j] = 0.f;
+    if (m >= 0 && m != n) ids[0] = m, ws[0] = -1.f, ids[1] = n, ws[1] = +1.f;  // k >= 2 whenever a non-self neighbour exists
+}
+
+// row r's K node ids and weights by 16-byte stores (k == K, K a multiple of 4)
+template <int K>
+__device__ __forceinline__ void store_row_graph(const SolveView& s, size_t r, const int (&ids)[K], const float (&ws)[K]) {
+#pragma unroll
+    for (int q = 0; q < K / 4; ++q) {
+        reinterpret_cast<int4*>(s.ridx + r * K)[q]  = make_int4(ids[4 * q], ids[4 * q + 1], ids[4 * q + 2], ids[4 * q + 3]);
+        reinterpret_cast<float4*>(s.rw + r * K)[q] = make_float4(ws[4 * q], ws[4 * q + 1], ws[4 * q + 2], ws[4 * q + 3]);
+    }
+}
+
+// The per-problem row set-up as ONE launch, a thread per row: regularisation rows (opt_solver.cpp:74-105), right-hand
+// sides of the data rows (energy.t:55), packed record heads and the zeroing of the
+// unknowns / state block / tickets (reset_kernel) — four launches of 5-16 us each at C2 in round 1.
+template <int K>
+__global__ __launch_bounds__(256) void prepare_rows_kernel(SolveView s, SolveState* __restrict__ st,
+                                                           unsigned int* __restrict__ ticket, int nticket) {
+    const size_t R = (size_t)s.N + (size_t)s.D * s.k;
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < (size_t)3 * s.D) s.t[r] = 0.f;
+    if (blockIdx.x == 0) {
+        unsigned int* w = (unsigned int*)st;
+        for (int j = threadIdx.x; j < (int)(sizeof(SolveState) / 4); j += blockDim.x) w[j] = 0u;
+        for (int j = threadIdx.x; j < nticket; j += blockDim.x) ticket[j] = 0u;
+    }
+    if (r >= R) return;
+    const int k = s.k;
+    int ids[K];
+    float ws[K];
+    const bool wide = k == K && K % 4 == 0;  // (uniform) the common case: every row's ids / weights / record head by 16-byte accesses
+    if (r < (size_t)s.N) {  // data row: k-NN + RBF weights already in ridx / rw; b = live - canonical (energy.t:55)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s.rb[3 * r + c] = s.live[3 * r + c] - s.canon[3 * r + c];
+        if (wide) load_row_graph<K>(s, r, ids, ws);
+        else {
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+                if (j < k) ids[j] = s.ridx[r * k + j], ws[j] = s.rw[r * k + j];
+        }
+    } else {  // regularisation row N + n k + i <- {reg_idx[n][i]: -1, n: +1} (opt_solver.cpp:74-105, energy.t:75-78)
+        const int e = (int)(r - (size_t)s.N), n = e / k, m = s.reg_idx[e];
+        reg_row_slots<K>(m, n, ids, ws);
+        if (wide) store_row_graph<K>(s, r, ids, ws);
+        else {
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+                if (j < k) s.ridx[r * k + j] = ids[j], s.rw[r * k + j] = ws[j];
+        }
+        s.rb[3 * r + 0] = s.rb[3 * r + 1] = s.rb[3 * r + 2] = 0.f;
+    }
+    store_record_head<K>(s, r, ids, ws, wide);
+}
+
+// Both graphs and the row set-up as ONE launch (plans whose nodes are in the grid, k == K, K a multiple of 4): what
+// knn_kernel<K, true> (vertex -> nodes), knn_wave_kernel<K> (node -> nodes) and prepare_rows_kernel<K> do one after the
+// other, with the rows written by the searches that find them — prepare_rows_kernel re-read ridx / rw / reg_idx / canon
+// a few microseconds after they were written, only to pack them again.  The two searches do not depend on each other: the
+// node search's waves (one per node) run beside the vertex search, a chain of dependent loads at 4 waves per SIMD.
+//   workgroups [0, ceil(N / 256))       data role: a lane per canonical vertex — knn_grid_query, RBF weights, ridx / rw,
+//                                       rb = live - canonical (the query itself), the record head
+//   the next ceil(D / 4) workgroups     regularisation role: a wave per node — knn_wave_search, reg_idx, and lanes j < k
+//                                       write row N + n k + j; their first 3 D threads zero the unknowns, the first
+//                                       workgroup the state block and the tickets (reset_kernel)
+// Same searches, same expressions, same operands: every output holds the bits the three launches leave.
+template <int K>
+__global__ __launch_bounds__(256) void graph_rows_kernel(SolveView s, KnnGridView grid, SolveState* __restrict__ st,
+                                                         unsigned int* __restrict__ ticket, int nticket, int data_blocks) {
+    static_assert(K % 4 == 0, "rows by 16-byte stores");
+    if ((int)blockIdx.x < data_blocks) {
+        const int v = blockIdx.x * blockDim.x + threadIdx.x;
+        if (v >= s.N) return;
+        const f3 q = mk3(s.canon[3 * (size_t)v], s.canon[3 * (size_t)v + 1], s.canon[3 * (size_t)v + 2]);
+        KnnList<K> best;
+        knn_grid_query<K>(*grid.desc, grid.cell_start, grid.sorted, q, best);
+        int ids[K];
+        float ws[K];
+        knn_ids_weights<K>(best, K, s.node_pos, s.node_w, true, q, ids, ws);
+        const size_t r = (size_t)v;
+        store_row_graph<K>(s, r, ids, ws);
+        s.rb[3 * r + 0] = s.live[3 * r + 0] - q.x, s.rb[3 * r + 1] = s.live[3 * r + 1] - q.y, s.rb[3 * r + 2] = s.live[3 * r + 2] - q.z;
+        store_record_head<K>(s, r, ids, ws, true);
+        return;
+    }
+    const int b = (int)blockIdx.x - data_blocks;
+    const int i = b * (int)blockDim.x + (int)threadIdx.x;
+    if (i < 3 * s.D) s.t[i] = 0.f;
+    if (b == 0) {
+        unsigned int* w = (unsigned int*)st;
+        for (int j = threadIdx.x; j < (int)(sizeof(SolveState) / 4); j += blockDim.x) w[j] = 0u;
+        for (int j = threadIdx.x; j < nticket; j += blockDim.x) ticket[j] = 0u;
+    }
+    const int n = b * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (n >= s.D) return;
+    const f3 q = mk3(s.node_pos[3 * (size_t)n], s.node_pos[3 * (size_t)n + 1], s.node_pos[3 * (size_t)n + 2]);
+    int near[K];
+    knn_wave_search<K>(*grid.desc, grid.cell_start, grid.sorted, q, lane, near);
+    if (lane >= K) return;
+    int m = -1;
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+        if (j == lane) m = near[j];
+    const size_t e = (size_t)n * K + lane, r = (size_t)s.N + e;
+    s.reg_idx[e] = m;
+    int ids[K];
+    float ws[K];
+    reg_row_slots<K>(m, n, ids, ws);
+    store_row_graph<K>(s, r, ids, ws);
+    s.rb[3 * r + 0] = s.rb[3 * r + 1] = s.rb[3 * r + 2] = 0.f;
+    store_record_head<K>(s, r, ids, ws, true);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1573,17 +1659,40 @@ hipError_t solve_transpose_graph(const int32_t* ridx, size_t total, int D, int32
     return hipGetLastError();
 }
 
-hipError_t solve_build_graph(const SolveView& s, SolveState* state, unsigned int* ticket, int nticket, hipStream_t st) {
-    const int D = s.D, N = s.N, k = s.k;
-    const size_t R = (size_t)N + (size_t)D * k, total = R * k;
-    const size_t threads = R > (size_t)3 * D ? R : (size_t)3 * D;
-    KDISPATCH(prepare_rows_kernel, k, <<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(s, state, ticket, nticket));
+// the node -> rows transposition of the rows in place, sorted lists in the order-stable variant
+static hipError_t transpose_rows(const SolveView& s, hipStream_t st) {
+    const int D = s.D, k = s.k;
+    const size_t total = ((size_t)s.N + (size_t)D * k) * k;
     const size_t lds = sizeof(int32_t) * (size_t)D;
     tg_count_kernel<<<TG_BLOCKS, 1024, lds, st>>>(s.ridx, total, D, s.blk_hist);
     tg_colscan_kernel<<<(D + 255) / 256, 256, 0, st>>>(s.blk_hist, D);
     tg_fill_kernel<<<TG_BLOCKS, 1024, lds, st>>>(s.ridx, total, D, s.blk_hist, s.node_ptr, s.node_list);
     if (s.deterministic) sort_node_lists_kernel<<<D, 256, 0, st>>>(s.node_ptr, s.node_list);
     return hipGetLastError();
+}
+
+hipError_t solve_build_graph(const SolveView& s, SolveState* state, unsigned int* ticket, int nticket, hipStream_t st) {
+    const int D = s.D, N = s.N, k = s.k;
+    const size_t R = (size_t)N + (size_t)D * k;
+    const size_t threads = R > (size_t)3 * D ? R : (size_t)3 * D;
+    KDISPATCH(prepare_rows_kernel, k, <<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(s, state, ticket, nticket));
+    return transpose_rows(s, st);
+}
+
+bool solve_graph_rows_fits(const SolveView& s) {
+    const int k = s.k;
+    // (the template's K is k itself, and the rows go out as 16-byte stores; DFA_GRAPH_ROWS=0 — development builds — keeps
+    // the searches and prepare_rows_kernel as launches of their own, for the comparison)
+    return s.N > 0 && (k == 4 || k == 8 || k == 16) &&
+           ((reinterpret_cast<uintptr_t>(s.ridx) | reinterpret_cast<uintptr_t>(s.rw) | reinterpret_cast<uintptr_t>(s.re)) & 15u) == 0 &&
+           dev_env_int("DFA_GRAPH_ROWS", 1) != 0;
+}
+
+hipError_t solve_build_graph_rows(const SolveView& s, const KnnGridView& grid, SolveState* state, unsigned int* ticket,
+                                  int nticket, hipStream_t st) {
+    const int data_blocks = (s.N + 255) / 256, reg_blocks = (s.D + 3) / 4;
+    KDISPATCH(graph_rows_kernel, s.k, <<<data_blocks + reg_blocks, 256, 0, st>>>(s, grid, state, ticket, nticket, data_blocks));
+    return transpose_rows(s, st);
 }
 
 int solve_residual_blocks(const SolveView& s) {

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernels.hpp"
+
 namespace dfa {
 
 // Device-resident scalars of one solve (read back by dfa_solver_get_stats).
@@ -119,6 +121,12 @@ constexpr int SOLVE_TG_BLOCKS = 256;  // one workgroup of the counting sort per 
 // rows (regularisation rows, right-hand sides, packed record heads), reset of the unknowns / state / tickets, and the
 // node -> rows transposition of the problem in `s`
 hipError_t solve_build_graph(const SolveView& s, SolveState* state, unsigned int* ticket, int nticket, hipStream_t st);
+// The same, searches included, for a plan whose nodes are in the grid: ONE launch finds both graphs (vertex -> nodes with
+// the RBF weights, node -> nodes) and writes the rows, then the transposition.  Leaves what launch_knn (twice) followed by
+// solve_build_graph leave, bit for bit (node lists: as sets).  Only where solve_graph_rows_fits holds.
+bool solve_graph_rows_fits(const SolveView& s);
+hipError_t solve_build_graph_rows(const SolveView& s, const KnnGridView& grid, SolveState* state, unsigned int* ticket,
+                                  int nticket, hipStream_t st);
 // counting-sort transposition of an (rows x k) node-index array: blk_hist = (SOLVE_TG_BLOCKS + 1) x D scratch,
 // node_ptr = D + 1, node_list = flat (row * k + slot) indices grouped by node (entries < 0 skipped)
 hipError_t solve_transpose_graph(const int32_t* ridx, size_t total, int D, int32_t* blk_hist, int32_t* node_ptr,
