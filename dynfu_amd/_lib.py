@@ -9,14 +9,14 @@ _LIB = None
 # every symbol include/dynfu_amd.h declares (tests/test_capi_symbols.py checks the .so exports them)
 SYMBOLS = [
     "dfa_last_error", "dfa_version", "dfa_abi_version", "dfa_abi_struct_size", "dfa_compute_dists", "dfa_tsdf_clear", "dfa_tsdf_integrate",
-    "dfa_tsdf_clear_integrate", "dfa_tsdf_raycast_points", "dfa_tsdf_raycast_depth", "dfa_tsdf_raycast_tally", "dfa_tsdf_raycast_render", "dfa_render_image_points", "dfa_render_image_depth", "dfa_render_tangent_colors", "dfa_tsdf_vertex_normals", "dfa_tsdf_extract_cloud", "dfa_tsdf_extract_cloud_occ", "dfa_tsdf_extract_normals", "dfa_correspond_projective", "dfa_knn", "dfa_warp_to_live",
+    "dfa_tsdf_clear_integrate", "dfa_tsdf_raycast_points", "dfa_tsdf_raycast_depth", "dfa_tsdf_raycast_tally", "dfa_tsdf_raycast_render", "dfa_render_image_points", "dfa_render_image_depth", "dfa_render_tangent_colors", "dfa_mesh_rasterize", "dfa_tsdf_vertex_normals", "dfa_tsdf_extract_cloud", "dfa_tsdf_extract_cloud_occ", "dfa_tsdf_extract_normals", "dfa_correspond_projective", "dfa_knn", "dfa_warp_to_live",
     "dfa_calc_dqb", "dfa_unsupported_vertices", "dfa_icp_sums", "dfa_repack_points", "dfa_compact_points", "dfa_transform_points", "dfa_warp_to_live_graph",
     "dfa_correspond", "dfa_marching_cubes", "dfa_mc_default_tables",
     "dfa_tsdf_occupancy_bytes", "dfa_tsdf_clear_occ", "dfa_tsdf_integrate_occ", "dfa_tsdf_clear_integrate_occ", "dfa_tsdf_clear_integrate_known_occ", "dfa_marching_cubes_occ", "dfa_marching_cubes_indexed",
     "dfa_depth_bilateral_filter", "dfa_depth_truncate", "dfa_depth_build_pyramid", "dfa_compute_normals_mask_depth",
     "dfa_resize_depth_normals", "dfa_resize_points_normals",
     "dfa_compute_points_normals", "dfa_solver6_create", "dfa_solver6_destroy", "dfa_solver6_set_problem",
-    "dfa_solver6_solve", "dfa_solver6_set_node_transforms", "dfa_solver6_node_dq", "dfa_solver6_warp", "dfa_solver6_get_stats",
+    "dfa_solver6_solve", "dfa_solver6_set_node_transforms", "dfa_solver6_node_dq", "dfa_solver6_warp", "dfa_solver6_warp_with", "dfa_solver6_get_stats",
     "dfa_solver6_enable_timing", "dfa_solver6_get_timing", "dfa_solver6_matrix_blocks", "dfa_solver6_matrix_columns",
     "dfa_solver6_matrix_row_blocks", "dfa_solver6_gradient", "dfa_solver6_step", "dfa_solver6_data_graph", "dfa_solver6_reg_graph",
     "dfa_solver_create", "dfa_solver_destroy", "dfa_solver_set_problem", "dfa_solver_solve", "dfa_solver_set_deterministic", "dfa_solver_matrix_entries", "dfa_solver_matrix_row_lengths", "dfa_solver_gradient",
@@ -170,6 +170,7 @@ def load(path=None):
     L.dfa_render_image_points.argtypes = [vp, i, vp, i, i, i, vp, vp, i, vp]
     L.dfa_render_image_depth.argtypes = [vp, i, vp, i, i, i, f, f, f, f, vp, vp, i, vp]
     L.dfa_render_tangent_colors.argtypes = [vp, i, i, i, vp, i, vp]
+    L.dfa_mesh_rasterize.argtypes = [vp, vp, i, vp, i, vp, f, f, f, f, f, i, i, vp, vp, i, vp, i, vp]
     L.dfa_tsdf_vertex_normals.argtypes = [vp, i, i, i, vp, f, vp, i, vp, vp]
     L.dfa_tsdf_extract_cloud.argtypes = [vp, i, i, i, vp, vp, vp, i, vp, vp]
     L.dfa_tsdf_extract_cloud_occ.argtypes = [vp, vp, i, i, i, vp, vp, vp, i, vp, vp]
@@ -193,6 +194,7 @@ def load(path=None):
     L.dfa_solver6_node_dq.argtypes = [vp]
     L.dfa_solver6_node_dq.restype = vp
     L.dfa_solver6_warp.argtypes = [vp, vp, vp, vp]
+    L.dfa_solver6_warp_with.argtypes = [vp, vp, vp, vp, vp]
     L.dfa_solver6_get_stats.argtypes = [vp, C.POINTER(_Solve6Stats), vp]
     L.dfa_solver6_enable_timing.argtypes = [vp, i]
     L.dfa_solver6_get_timing.argtypes = [vp, C.POINTER(_Solve6Timing), vp]
@@ -418,6 +420,29 @@ def tsdf_raycast_render(vol, voxel_size, trunc, cam2vol, Rinv, fx, fy, cx, cy, s
     _check(load().dfa_tsdf_raycast_render(_dev(vol), X, Y, Z, _farr(voxel_size, 3), trunc, _aff12(cam2vol),
                                           _farr(list(map(float, _flat(Rinv))), 9), fx, fy, cx, cy, step_factor,
                                           delta_factor, cols, rows, _farr(light_pose, 3), int(mode), img, step, _stream()))
+
+
+def mesh_rasterize(vertices, normals, indices, world2cam, fx, fy, cx, cy, z_near, cols, rows, zbuffer, points=None,
+                   out_normals=None):
+    """dfa_mesh_rasterize: the indexed mesh (vertices / normals (N, 4) float32, normals may be None; indices int32, three per
+    triangle) seen through world2cam (12 floats or [R|t], None = identity) into `points` / `out_normals` ((rows, cols, 4)
+    float32, a row stride makes a pitched map, either may be None; misses are NaN).  zbuffer: (rows, cols) int64 CUDA
+    tensor, on return (bits(depth) << 32) | triangle per pixel, -1 where nothing is drawn."""
+    torch = _torch()
+    N, T = int(vertices.shape[0]), int(indices.numel()) // 3
+    for m, name in ((points, "points"), (out_normals, "out_normals")):
+        if m is not None and (tuple(m.shape) != (rows, cols, 4) or m.stride(2) != 1 or m.stride(1) != 4):
+            raise DynfuAmdError("%s must be a (%d, %d, 4) float32 tensor of packed float4 pixels" % (name, rows, cols))
+    if tuple(zbuffer.shape) != (rows, cols) or not zbuffer.is_contiguous():
+        raise DynfuAmdError("zbuffer must be a contiguous (%d, %d) int64 tensor" % (rows, cols))
+    _check(load().dfa_mesh_rasterize(_dev(vertices, torch.float32, "vertices") if N else None,
+                                     _dev(normals, torch.float32, "normals") if N else None, N,
+                                     _dev(indices, torch.int32, "indices") if T else None, T,
+                                     None if world2cam is None else _aff12(world2cam), fx, fy, cx, cy, z_near, cols, rows,
+                                     _dev(zbuffer, torch.int64, "zbuffer"), _dev(points, torch.float32, "points"),
+                                     points.stride(0) * 4 if points is not None else 0,
+                                     _dev(out_normals, torch.float32, "out_normals"),
+                                     out_normals.stride(0) * 4 if out_normals is not None else 0, _stream()))
 
 
 def tsdf_raycast_tally(vol, voxel_size, trunc, cam2vol, Rinv, fx, fy, cx, cy, step_factor, delta_factor, cols, rows,
@@ -896,6 +921,14 @@ class Solver6:
         out_v = torch.empty((self.N, 3), dtype=torch.float32, device="cuda")
         out_n = torch.empty_like(out_v) if want_normals and self._keep[4] is not None else None
         _check(self._L.dfa_solver6_warp(self._h, _dev(out_v), _dev(out_n), _stream()))
+        return out_v, out_n
+
+    def warp_with(self, node_dq, want_normals=True):
+        """dfa_solver6_warp_with: the plan's vertices warped by node_dq (D, 8) instead of the solved transforms; no solve needed"""
+        torch = _torch()
+        out_v = torch.empty((self.N, 3), dtype=torch.float32, device="cuda")
+        out_n = torch.empty_like(out_v) if want_normals and self._keep[4] is not None else None
+        _check(self._L.dfa_solver6_warp_with(self._h, _dev(node_dq, torch.float32, "node_dq"), _dev(out_v), _dev(out_n), _stream()))
         return out_v, out_n
 
     def enable_timing(self, on=True):

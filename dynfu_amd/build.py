@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libdynfu_amd.so")
-SOURCES = ["tsdf.hip", "warp.hip", "solve.hip", "solve6.hip", "mc.hip", "extract.hip", "img.hip", "render.hip", "icp.hip", "points.hip", "capi.cpp"]
+SOURCES = ["tsdf.hip", "warp.hip", "solve.hip", "solve6.hip", "mc.hip", "extract.hip", "img.hip", "render.hip", "raster.hip", "icp.hip", "points.hip", "capi.cpp"]
 ARCH = "gfx950"
 EXTRA = os.environ.get("DFA_EXTRA_CXXFLAGS", "").split()
 FLAGS = EXTRA + ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall", "-Wno-unused-function",
@@ -81,7 +81,7 @@ def build(force=False, verbose=False, dev=False):
 HOST = os.path.join(HERE, "host")
 HOST_LIB = os.path.join(HERE, "libdynfu_amd_host.so")
 HOST_SOURCES = ["device.cpp", "frame.cpp", "tsdf_volume.cpp", "warp_field.cpp", "opt_solver.cpp", "northstar_solver.cpp", "dyn_fusion.cpp",
-                "marching_cubes.cpp", "imgproc.cpp", "projective_icp.cpp", "io.cpp", "kinfu.cpp"]
+                "marching_cubes.cpp", "imgproc.cpp", "projective_icp.cpp", "io.cpp", "kinfu.cpp", "mesh_render.cpp"]
 
 
 def build_host(force=False, verbose=False):
@@ -139,7 +139,7 @@ def build_cpp_tests(force=False, verbose=False):
     for name, needs in (("test_host_dq", []), ("test_host_solver", ["host"]), ("test_host_tsdf", ["host", "oracle"]),
                         ("test_host_dynfusion", ["host", "oracle"]), ("test_host_icp", ["host"]),
                         ("test_tsdf_classify", ["oracle", "ieee"]), ("test_host_io", ["host"]), ("test_host_kinfu", ["host"]),
-                        ("test_host_extract", ["host"]), ("test_host_render", ["host"]), ("test_host_mc_indexed", ["host"])):
+                        ("test_host_extract", ["host"]), ("test_host_render", ["host"]), ("test_host_mc_indexed", ["host"]), ("test_host_mesh_view", ["host"])):
         src = os.path.join(tdir, name + ".cpp")
         exe = os.path.join(out, name)
         deps = [src, os.path.join(tdir, "minitest.hpp"), host, os.path.join(CSRC, "tsdf_classify.hpp")]

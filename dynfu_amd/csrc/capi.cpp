@@ -492,6 +492,27 @@ int dfa_tsdf_raycast_render(const uint32_t* volume, int X, int Y, int Z, const f
     return DFA_OK;
 }
 
+int dfa_mesh_rasterize(const float* vertices, const float* normals, int N, const int32_t* indices, int T,
+                       const float world2cam[12], float fx, float fy, float cx, float cy, float z_near, int cols, int rows,
+                       uint64_t* zbuffer, float* points, int points_step, float* out_normals, int normals_step,
+                       dfa_stream_t stream) {
+    REQUIRE(zbuffer, "null z-buffer");
+    REQUIRE(cols > 0 && rows > 0, "non-positive image size");
+    REQUIRE(cols <= 8192 && rows <= 8192, "image larger than 8192 pixels a side");
+    REQUIRE(z_near > 0.f, "z_near must be positive");
+    REQUIRE(N >= 0 && T >= 0 && T <= 0x7fffffff / 3, "bad mesh size");
+    REQUIRE(T == 0 || (vertices && indices && N > 0), "null mesh");
+    REQUIRE(!points || points_step >= cols * 16, "row step smaller than a float4 row");
+    REQUIRE(!out_normals || normals_step >= cols * 16, "row step smaller than a float4 row");
+    REQUIRE((((uintptr_t)vertices | (uintptr_t)normals) & 15) == 0, "vertices / normals must be 16-byte aligned");
+    REQUIRE(((uintptr_t)zbuffer & 7) == 0, "z-buffer must be 8-byte aligned");
+    REQUIRE(!points || (((uintptr_t)points | (uintptr_t)points_step) & 15) == 0, "point rows must be 16-byte aligned");
+    REQUIRE(!out_normals || (((uintptr_t)out_normals | (uintptr_t)normals_step) & 15) == 0, "normal rows must be 16-byte aligned");
+    HIP_TRY(dfa::launch_mesh_rasterize(vertices, normals, N, indices, T, world2cam, fx, fy, cx, cy, z_near, cols, rows, zbuffer,
+                                       points, points_step, out_normals, normals_step, S(stream)));
+    return DFA_OK;
+}
+
 // -------------------------------------------------------------------- depth pre-processing seam
 
 int dfa_depth_bilateral_filter(const uint16_t* src, int src_step, uint16_t* dst, int dst_step, int cols, int rows,
@@ -1576,6 +1597,13 @@ int dfa_solver6_warp(dfa_solver6* s, float* out_vertices, float* out_normals, df
     REQUIRE(s && s->has_problem, "no problem set");
     REQUIRE(out_vertices, "null output");
     HIP_TRY(dfa::s6_warp(s->v, s->v.dq, out_vertices, out_normals, S(stream)));
+    return DFA_OK;
+}
+
+int dfa_solver6_warp_with(dfa_solver6* s, const float* node_dq, float* out_vertices, float* out_normals, dfa_stream_t stream) {
+    REQUIRE(s && s->has_problem, "no problem set");
+    REQUIRE(node_dq && out_vertices, "null transforms / output");
+    HIP_TRY(dfa::s6_warp(s->v, node_dq, out_vertices, out_normals, S(stream)));
     return DFA_OK;
 }
 

@@ -143,6 +143,13 @@ hipError_t launch_raycast_render(const uint32_t* vol, int X, int Y, int Z, const
                                  float step_factor, float delta_factor, int cols, int rows, const float light[3], int mode,
                                  uint8_t* image, int image_step, hipStream_t s);
 
+// raster.hip — the mesh rasteriser (z-buffer fill, draw, resolve)
+hipError_t launch_mesh_rasterize(const float* vertices, const float* normals, int N, const int32_t* indices, int T,
+                                 const float world2cam[12], float fx, float fy, float cx, float cy, float z_near, int cols,
+                                 int rows, uint64_t* zbuffer, float* points, int points_step, float* out_normals,
+                                 int normals_step, hipStream_t s);
+
+
 // img.hip
 hipError_t launch_bilateral(const uint16_t* src, int src_step, uint16_t* dst, int dst_step, int cols, int rows, int ksz,
                             float sigma_spatial, float sigma_depth, hipStream_t s);

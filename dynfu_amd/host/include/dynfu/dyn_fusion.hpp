@@ -20,6 +20,7 @@
 #include <dynfu/warp_field.hpp>
 #include <kfusion/cuda/imgproc.hpp>
 #include <kfusion/cuda/marching_cubes.hpp>
+#include <kfusion/cuda/mesh_render.hpp>
 #include <kfusion/cuda/tsdf_volume.hpp>
 #include <kfusion/kinfu.hpp>
 
@@ -44,7 +45,18 @@ struct DynFuParams {  // dyn_fusion.hpp:25-42
     // depth maps); getLiveFrame() / getMesh() stay the volume-frame marching-cubes output.
     bool north_star = false;
     NorthStarParameters northStarParams;
+    // Extension — the view of the canonical model: frame 0 also extracts the fused volume as a welded mesh
+    // with normals (MarchingCubes::runIndexed / computeNormals) and keeps it in HBM, in the frame of the canonical cloud;
+    // DynFusion::renderWarpedModel carries it through the warp field and rasterises it from the live camera.  Off: nothing
+    // of this runs.  On or off, everything else a frame produces is the same, bit for bit.  The warp is the one the mode's
+    // solve fitted: Warpfield::warpToLive (the reference's blend) in reference mode, the dual-quaternion blend of the
+    // north-star solve (dfa_solver6_warp_with on a plan of the view's own) in north-star mode — the two differ as soon as
+    // a transform is not the identity, and the model has to move as getCanonicalWarpedToLive() does.
+    bool model_view = false;
+    float model_view_z_near = 0.05f;  // metres: triangles with a vertex nearer to the camera are not drawn
 };
+
+struct dfa_solver6;  // include/dynfu_amd.h
 
 class DynFusion : public kfusion::KinFu {  // include/dynfu/dyn_fusion.hpp:45
 public:
@@ -67,6 +79,25 @@ public:
     // lets go of the mesh getMesh() built (one small vector per triangle: freeing them takes milliseconds, which a
     // caller may want outside its timed region; the next frame would do it otherwise)
     void dropMesh() { mesh_.reset(); }
+    // model_view: the canonical model, warped to the live frame and seen from the current camera (getCameraPose(), the
+    // model being in the volume's frame; the origin in north-star mode, where the model already is in the camera frame), shaded with
+    // params().kinfuParams.light_pose.  Flags and image sizes are KinFu::renderImage's: 2 the normal colours, 3 the Phong
+    // view and the normal colours side by side (2 * cols wide), anything else the Phong view.  Throws dfa::Error when
+    // model_view is off or before frame 0.
+    void renderWarpedModel(kfusion::cuda::Image& image, int flag = 0);
+    // what renderWarpedModel rasterises: the canonical mesh's vertices and normals (one per vertex of getCanonicalMesh())
+    // carried through the current warp field by the mode's blend.  Throws as renderWarpedModel does.
+    std::shared_ptr<dynfu::Frame> warpCanonicalMesh();
+    // the point and normal maps of the last renderWarpedModel: the visible surface of the warped model, camera frame,
+    // NaN where nothing is seen (empty before the first call)
+    struct ModelMaps {
+        kfusion::cuda::Cloud points;
+        kfusion::cuda::Normals normals;
+    };
+    ModelMaps getWarpedModelMaps() const { return ModelMaps{model_points_, model_normals_}; }
+    // the canonical mesh kept by frame 0 (empty before it, or with model_view off): float4 vertices in the frame of the
+    // canonical cloud, three indices per triangle; views that stay valid while this object lives
+    kfusion::cuda::MarchingCubes::IndexedMesh getCanonicalMesh() const { return canonical_mesh_; }
     // north-star mode: energy before / after the last frame's solve and the data rows that found an association
     double northStarInitialCost() const { return ns_initial_cost_; }
     double northStarFinalCost() const { return ns_final_cost_; }
@@ -118,6 +149,23 @@ private:
     bool northStarFrame(const kfusion::cuda::Depth& depth);  // operator() in north-star mode
     kfusion::cuda::Cloud live_points_;
     kfusion::cuda::Normals live_normals_;
+    // model_view: the canonical mesh (frame 0) as a frame for Warpfield::warpToLive and as float4 vertices + indices, the
+    // buffers behind them, and what the last renderWarpedModel made
+    void keepCanonicalMesh(const float* to_canonical_frame /* 12 floats, or null: the volume's frame */);
+    std::shared_ptr<dynfu::Frame> canonical_mesh_frame_;
+    kfusion::cuda::MarchingCubes::IndexedMesh canonical_mesh_;
+    dfa::DeviceArray<kfusion::cuda::MarchingCubes::PointType> mesh_vertex_buffer_, warped_vertices_;
+    dfa::DeviceArray<int> mesh_index_buffer_;
+    dfa::DeviceArray<dfa::Normal> warped_normals_;
+    dfa::DeviceArray<uint64_t> model_zbuffer_;
+    // north-star mode: a dfa_solver6 plan over (nodes, mesh vertices) that only ever warps, its graphs rebuilt when the
+    // node set has grown; the arrays it borrows, and the node set they were built from
+    std::shared_ptr<dfa_solver6> mesh_plan_;
+    int mesh_plan_D_ = 0;
+    dfa::DeviceArray<float> mesh_node_pos_, mesh_node_w_, mesh_node_dq_;
+    std::vector<float> mesh_nodes_built_pos_, mesh_nodes_built_w_;
+    kfusion::cuda::Cloud model_points_;
+    kfusion::cuda::Normals model_normals_;
 };
 
 // DynFuApp::execute of the reference's demo (src/apps/demo.cpp:68-124) without its windows and command line: every

@@ -207,6 +207,7 @@ bool DynFusion::operator()(const kfusion::cuda::Depth& depth) {
     if (frame_counter_ == 0) {
         tsdf().integrate(dists_, camera, p.intr);  // :71
         initFromFrame(extractSurface(0, dynfuParams.mesh_normals));  // :73-95
+        if (dynfuParams.model_view) keepCanonicalMesh(nullptr);
         return ++frame_counter_, false;
     }
     StageClock clk;
@@ -243,6 +244,7 @@ bool DynFusion::northStarFrame(const kfusion::cuda::Depth& depth) {
         dfa::check(dfa_transform_points(v.vertices, (int)n, aff, 1, cv.ptr(), nullptr), "DynFusion: canonical vertices to the camera frame");
         dfa::check(dfa_transform_points(v.normals, (int)n, aff, 0, cn.ptr(), nullptr), "DynFusion: canonical normals to the camera frame");
         initFromFrame(dynfu::Frame::fromDevice(0, cv, cn, n));
+        if (dynfuParams.model_view) keepCanonicalMesh(aff);
         return ++frame_counter_, false;
     }
     StageClock clk;
@@ -261,6 +263,92 @@ bool DynFusion::northStarFrame(const kfusion::cuda::Depth& depth) {
     warpfield->update(canonicalFrameWarpedToLive);
     clk.mark("warp + warpfield->update");
     return ++frame_counter_, true;
+}
+
+// ------------------------------------------------------------------------- the view of the canonical model
+
+// frame 0, model_view: the volume just fused as a welded mesh with normals from the TSDF gradient, moved to the frame of the
+// canonical cloud exactly as the cloud is (north-star mode: the camera frame)
+void DynFusion::keepCanonicalMesh(const float* to_canonical_frame) {
+    auto mesh = mc_->runIndexed(tsdf(), mesh_vertex_buffer_, mesh_index_buffer_);
+    if (mesh.vertices.empty() && mc_->totalUniqueVertices() > 0) {  // it did not fit the default buffers: size them and run again
+        mesh_vertex_buffer_.create((size_t)mc_->totalUniqueVertices());
+        mesh_index_buffer_.create((size_t)mc_->totalVertices());
+        mesh = mc_->runIndexed(tsdf(), mesh_vertex_buffer_, mesh_index_buffer_);
+    }
+    const size_t n = mesh.vertices.size();
+    if (n == 0) throw dfa::Error(DFA_ERR_INVALID, "DynFusion (model_view): the first frame has no surface");
+    dfa::DeviceArray<dfa::Normal> normals4;
+    mc_->computeNormals(tsdf(), mesh.vertices, normals4);
+    dfa::DeviceArray<float> v3(3 * n), n3(3 * n);
+    dfa::check(dfa_repack_points((const float*)mesh.vertices.ptr(), 4, v3.ptr(), 3, (int)n, 0.f, nullptr), "DynFusion: mesh vertices");
+    dfa::check(dfa_repack_points((const float*)normals4.ptr(), 4, n3.ptr(), 3, (int)n, 0.f, nullptr), "DynFusion: mesh normals");
+    if (to_canonical_frame) {
+        dfa::check(dfa_transform_points(v3.ptr(), (int)n, to_canonical_frame, 1, v3.ptr(), nullptr), "DynFusion: mesh vertices to the camera frame");
+        dfa::check(dfa_transform_points(n3.ptr(), (int)n, to_canonical_frame, 0, n3.ptr(), nullptr), "DynFusion: mesh normals to the camera frame");
+        // the float4 vertices getCanonicalMesh() hands out follow (in place: the buffer is this object's)
+        dfa::check(dfa_repack_points(v3.ptr(), 3, (float*)mesh.vertices.ptr(), 4, (int)n, 1.f, nullptr), "DynFusion: mesh vertices");
+    }
+    canonical_mesh_frame_ = dynfu::Frame::fromDevice(0, v3, n3, n);
+    canonical_mesh_       = mesh;
+}
+
+// The mesh moves as the canonical cloud does: by the blend of the solve that fitted the transforms.  Reference mode:
+// Warpfield::warpToLive.  North-star mode: the solve's own warp (solve6.hip, s6_warp) on a plan that holds the mesh as its
+// cloud and never solves — the frame's plan is not touched, so a frame cannot notice the view.
+std::shared_ptr<dynfu::Frame> DynFusion::warpCanonicalMesh() {
+    if (!dynfuParams.model_view) throw dfa::Error(DFA_ERR_INVALID, "DynFusion::renderWarpedModel: DynFuParams::model_view is off");
+    if (!canonical_mesh_frame_ || !warpfield) throw dfa::Error(DFA_ERR_INVALID, "DynFusion::renderWarpedModel before the first frame");
+    if (!dynfuParams.north_star) return warpfield->warpToLive(canonical_mesh_frame_);
+    std::vector<float> pos, w, dq;
+    warpfield->hostArrays(pos, w, dq);
+    const int D = (int)w.size();
+    const size_t n = canonical_mesh_frame_->size();
+    if (D == 0) throw dfa::Error(DFA_ERR_INVALID, "DynFusion::renderWarpedModel: the warp field has no nodes");
+    mesh_node_dq_.upload(dq);
+    if (!mesh_plan_ || pos != mesh_nodes_built_pos_ || w != mesh_nodes_built_w_) {
+        if (!mesh_plan_ || D > mesh_plan_D_) {
+            mesh_plan_.reset();
+            dfa_solver6* plan = nullptr;
+            const int cap = D + D / 4 + 16;  // (room for the nodes Warpfield::update adds, as NorthStarSolver sizes its plan)
+            dfa::check(dfa_solver6_create(cap, (int)n, std::min(warpfield->getKnn(), 8), &plan), "DynFusion (model_view): dfa_solver6_create");
+            mesh_plan_ = std::shared_ptr<dfa_solver6>(plan, dfa_solver6_destroy);
+            mesh_plan_D_ = cap;
+        }
+        // fresh arrays: the plan borrows them until the next set_problem
+        mesh_node_pos_ = dfa::DeviceArray<float>(), mesh_node_w_ = dfa::DeviceArray<float>();
+        mesh_node_pos_.upload(pos), mesh_node_w_.upload(w);
+        const dynfu::Frame::DeviceView m = canonical_mesh_frame_->device();
+        dfa::check(dfa_solver6_set_problem(mesh_plan_.get(), mesh_node_pos_.ptr(), mesh_node_dq_.ptr(), mesh_node_w_.ptr(), D, m.vertices,
+                                           m.normals, (int)n, nullptr),
+                   "DynFusion (model_view): dfa_solver6_set_problem");
+        mesh_nodes_built_pos_ = pos, mesh_nodes_built_w_ = w;
+    }
+    dfa::DeviceArray<float> ov(3 * n), on(3 * n);
+    dfa::check(dfa_solver6_warp_with(mesh_plan_.get(), mesh_node_dq_.ptr(), ov.ptr(), on.ptr(), nullptr), "DynFusion (model_view): dfa_solver6_warp_with");
+    return dynfu::Frame::fromDevice(0, ov, on, n);
+}
+
+void DynFusion::renderWarpedModel(kfusion::cuda::Image& image, int flag) {
+    const auto warped = warpCanonicalMesh();
+    const kfusion::KinFuParams& p = params_;
+    const dynfu::Frame::DeviceView w = warped->device();
+    if (w.n != canonical_mesh_frame_->size()) throw dfa::Error(DFA_ERR_INVALID, "DynFusion::renderWarpedModel: the warp field has no nodes");
+    if (warped_vertices_.size() != w.n) warped_vertices_.create(w.n), warped_normals_.create(w.n);
+    dfa::check(dfa_repack_points(w.vertices, 3, (float*)warped_vertices_.ptr(), 4, (int)w.n, 1.f, nullptr), "DynFusion: warped vertices");
+    dfa::check(dfa_repack_points(w.normals, 3, (float*)warped_normals_.ptr(), 4, (int)w.n, 0.f, nullptr), "DynFusion: warped normals");
+    // north-star mode keeps the model in the camera frame; otherwise it is in the volume's frame, as the canonical cloud is
+    const dfa::Affine3f world2cam = dynfuParams.north_star ? dfa::Affine3f() : getCameraPose().inv() * tsdf().getPose();
+    kfusion::cuda::rasterizeMesh(warped_vertices_, warped_normals_, canonical_mesh_.indices, world2cam, p.intr, p.cols, p.rows,
+                                 dynfuParams.model_view_z_near, model_points_, model_normals_, model_zbuffer_);
+    image.create(p.rows, flag != 3 ? p.cols : p.cols * 2);  // as KinFu::renderImage
+    if (flag == 2) kfusion::cuda::renderTangentColors(model_normals_, image);
+    else if (flag != 3) kfusion::cuda::renderImage(model_points_, model_normals_, p.intr, p.light_pose, image);
+    else {
+        kfusion::cuda::Image i1(p.rows, p.cols, image.ptr(), image.step()), i2(p.rows, p.cols, image.ptr() + p.cols, image.step());
+        kfusion::cuda::renderImage(model_points_, model_normals_, p.intr, p.light_pose, i1);
+        kfusion::cuda::renderTangentColors(model_normals_, i2);
+    }
 }
 
 SequenceReport runSequence(DynFusion& dynfu, const std::string& dir, int max_frames) {

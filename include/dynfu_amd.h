@@ -224,6 +224,29 @@ int dfa_tsdf_raycast_render(const uint32_t* volume, int X, int Y, int Z, const f
                             float step_factor, float delta_factor, int cols, int rows, const float light_pose[3], int mode,
                             uint8_t* image, int image_step, dfa_stream_t stream);
 
+/* Mesh rasteriser (no reference counterpart): an indexed triangle mesh — dfa_marching_cubes_indexed's, after
+ * dfa_warp_to_live has moved its vertices and normals — seen by a pinhole camera, as the point and normal maps of its
+ * visible surface.  The maps have the layout and the miss value (quiet NaN) of dfa_tsdf_raycast_points, so they feed
+ * dfa_render_image_points, dfa_render_tangent_colors and dfa_solver6_solve as they are.
+ *   vertices / normals: N float4 (device, 16-byte aligned), normals may be NULL: the face normal turned towards the camera.
+ *   indices: 3 T vertex numbers.  world2cam: R row-major then t (12 floats, host), NULL = identity.
+ *   zbuffer (device, 8-byte aligned, required): rows * cols uint64, the only scratch; on return
+ *     (bits(depth) << 32) | triangle of the nearest surface, all ones where nothing is drawn.
+ *   points / out_normals: float4 images with their row steps in bytes (16-byte aligned); either may be NULL.  Bytes of a
+ *     row beyond its last pixel are not touched.
+ * Pixel (i, j) has its centre at u = i, v = j.  Triangles are drawn in both windings and never clipped: one with an index
+ * outside [0, N), a non-finite vertex, a vertex nearer than z_near, a projection more than 16384 pixels from the origin or
+ * no area is skipped whole.  Coverage is exact on coordinates snapped to 1/256 pixel (top-left rule: a pixel centre on an
+ * edge two triangles share belongs to one of them), depth is perspective-correct, the nearest depth wins and the lower
+ * triangle number on equal depths: the result does not depend on the order of the atomics.  T == 0 leaves every pixel a
+ * miss.  The arithmetic is stated in csrc/raster.hip and tests/raster_statement.py.  Fill, draw and resolve are enqueued on
+ * `stream`; nothing is allocated and the host does not wait. */
+int dfa_mesh_rasterize(const float* vertices, const float* normals /* may be NULL */, int N, const int32_t* indices, int T,
+                       const float world2cam[12] /* may be NULL */, float fx, float fy, float cx, float cy, float z_near,
+                       int cols, int rows, uint64_t* zbuffer, float* points, int points_step, float* out_normals,
+                       int normals_step, dfa_stream_t stream);
+
+
 /* ===================================================================================== */
 /* Depth pre-processing seam — replaces the image kernels of kfusion::device declared in    */
 /* include/kfusion/internal.hpp:190-204 (src/kfusion/cuda/imgproc.cu), called by            */
@@ -675,6 +698,10 @@ int dfa_solver6_solve(dfa_solver6* s, const float* live_vertex_map, int vertex_s
 const float* dfa_solver6_node_dq(const dfa_solver6* s); /* device, D x 8: solved node transforms */
 /* canonical vertices (and normals) of the plan warped by the solved transforms (DQ blend) */
 int dfa_solver6_warp(dfa_solver6* s, float* out_vertices, float* out_normals, dfa_stream_t stream);
+/* The same warp of the plan's vertices by transforms the caller gives (device, D x 8, read by the work this call enqueues
+ * only): needs a dfa_solver6_set_problem, no solve.  With dfa_solver6_node_dq of a plan over the same nodes it carries a
+ * second cloud — a mesh of the canonical surface, say — through exactly the deformation that plan's solve found. */
+int dfa_solver6_warp_with(dfa_solver6* s, const float* node_dq, float* out_vertices, float* out_normals, dfa_stream_t stream);
 int dfa_solver6_get_stats(dfa_solver6* s, dfa_solve6_stats* out, dfa_stream_t stream);
 
 /* The normal equations H x = g of the LAST Gauss-Newton iteration of the last solve, and what came of them (for inspection
