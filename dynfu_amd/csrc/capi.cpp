@@ -1,6 +1,7 @@
-// capi.cpp — the C ABI declared in include/dynfu_amd.h: argument checking, error strings,
-// the solver plan's device memory, and the per-frame launch sequences.  No arithmetic lives
-// here; the kernels are in tsdf.hip / warp.hip / solve.hip.
+// capi.cpp — the C ABI declared in include/dynfu_amd.h: argument checking, error strings, the scratch each entry point
+// keeps per stream, the two solver plans (their field lists, graphs and timing brackets) and the per-frame launch
+// sequences.  What owns memory is in device_memory.hpp, the north-star launch budget in launch_budget.hpp; no arithmetic
+// lives here, and the kernels are in the .hip files.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -8,14 +9,14 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
-#include <mutex>
 #include <new>
-#include <utility>
 #include <vector>
 
 #include "../../include/dynfu_amd.h"
 #include "kernels.hpp"
 #include "dev_switch.hpp"
+#include "device_memory.hpp"
+#include "launch_budget.hpp"
 #include "solve.hpp"
 #include "solve6.hpp"
 
@@ -47,110 +48,69 @@ inline hipStream_t S(dfa_stream_t s) { return (hipStream_t)s; }
 
 bool volume_args_ok(const void* vol, int X, int Y, int Z) { return vol && X > 0 && Y > 0 && Z > 0; }
 
-// Scratch of the entry points that have no plan to keep it in (dfa_knn, dfa_warp_to_live, dfa_correspond,
-// dfa_marching_cubes, dfa_icp_sums ...): one instance per (device, stream), created on first use and kept.  Work on one
-// stream is ordered, so a call never overwrites the scratch of a call still running — whichever host threads and
-// however many streams the caller uses (round 1 kept these per host THREAD: two streams driven by one thread shared
-// them).  Growing frees the old block with hipFree, which waits for the device.
-template <class T>
-T& stream_scratch(hipStream_t s) {
-    static std::mutex mu;
-    static std::map<std::pair<int, hipStream_t>, T> table;  // (device, stream): the null stream exists on every device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lock(mu);
-    return table[std::make_pair(dev, s)];  // std::map nodes never move
-}
+using dfa::DeviceBuffer;
+using dfa::stream_scratch;
 
-// device scratch of one node grid (warp.hip); grows on demand, never shrinks
+// device scratch of one uniform grid (warp.hip): the node grid of the k-NN searches and, with more cells, the grid part
+// of dfa_correspond's point grid
 struct GridScratch {
-    dfa::KnnGridView v{};
-    int cap_nodes = 0;
+    DeviceBuffer<dfa::KnnGridDesc> desc;
+    DeviceBuffer<int32_t> cell_count, cell_start, node_cell;
+    DeviceBuffer<float4> sorted;
+    dfa::KnnGridView v{};  // the buffers as the kernels take them
     void release() {
-        (void)hipFree(v.desc), (void)hipFree(v.cell_count), (void)hipFree(v.cell_start);
-        (void)hipFree(v.node_cell), (void)hipFree(v.sorted);
-        v         = dfa::KnnGridView{};
-        cap_nodes = 0;
+        desc.release(), cell_count.release(), cell_start.release(), node_cell.release(), sorted.release();
+        v = dfa::KnnGridView{};
     }
-    hipError_t reserve(int D_needed) {
-        if (D_needed <= cap_nodes) return hipSuccess;
-        // a warp field grows by a few nodes per frame: a quarter of headroom, so that growing (hipFree waits for the
-        // device, and a fresh hipMalloc costs milliseconds) happens a handful of times in a sequence, not every frame
-        const int D = D_needed + D_needed / 4 + 64;
-        release();
+    hipError_t reserve(size_t cells, size_t points, size_t headroom) {
         hipError_t e;
-        if ((e = hipMalloc((void**)&v.desc, sizeof(dfa::KnnGridDesc))) != hipSuccess) return e;
-        if ((e = hipMalloc((void**)&v.cell_count, sizeof(int32_t) * dfa::KNN_GRID_MAX_CELLS)) != hipSuccess) return e;
-        if ((e = hipMalloc((void**)&v.cell_start, sizeof(int32_t) * (dfa::KNN_GRID_MAX_CELLS + 1))) != hipSuccess)
-            return e;
-        if ((e = hipMalloc((void**)&v.node_cell, sizeof(int32_t) * (size_t)D)) != hipSuccess) return e;
-        if ((e = hipMalloc((void**)&v.sorted, sizeof(float4) * (size_t)D)) != hipSuccess) return e;
-        cap_nodes = D;
-        return hipSuccess;
+        if ((e = desc.reserve(1)) || (e = cell_count.reserve(cells)) || (e = cell_start.reserve(cells + 1)) ||
+            (e = node_cell.reserve(points, headroom)) || (e = sorted.reserve(points, headroom)))
+            release();  // (nothing half-allocated stays behind a failure)
+        else v = dfa::KnnGridView{desc.data, cell_count.data, cell_start.data, node_cell.data, sorted.data};
+        return e;
     }
+    // a warp field grows by a few nodes per frame: a quarter of headroom, so that growing (hipFree waits for the
+    // device, and a fresh hipMalloc costs milliseconds) happens a handful of times in a sequence, not every frame
+    hipError_t reserve(int D) { return reserve(dfa::KNN_GRID_MAX_CELLS, (size_t)D, (size_t)D / 4 + 64); }
 };
 
-// scratch of the 128^3 point grid of dfa_correspond; grows on demand, never shrinks
+// scratch of the 128^3 point grid of dfa_correspond
 struct PointGridScratch {
+    GridScratch g;
+    DeviceBuffer<int32_t> chunk_sums;
+    DeviceBuffer<float> bbox_partials;
     dfa::PointGridView v{};
-    int cap_points = 0;
-    void release() {
-        (void)hipFree(v.g.desc), (void)hipFree(v.g.cell_count), (void)hipFree(v.g.cell_start);
-        (void)hipFree(v.g.node_cell), (void)hipFree(v.g.sorted), (void)hipFree(v.chunk_sums);
-        (void)hipFree(v.bbox_partials);
-        v          = dfa::PointGridView{};
-        cap_points = 0;
-    }
-    hipError_t reserve(int n_needed) {
-        if (n_needed <= cap_points) return hipSuccess;
-        const int n = n_needed + n_needed / 4 + 1024;  // clouds of consecutive frames differ by a few per cent (see GridScratch)
-        release();
-        hipError_t e;
+    hipError_t reserve(int n) {  // clouds of consecutive frames differ by a few per cent (see GridScratch)
         const size_t cells = dfa::PGRID_MAX_CELLS;
-        if ((e = hipMalloc((void**)&v.g.desc, sizeof(dfa::KnnGridDesc))) != hipSuccess) return e;
-        if ((e = hipMalloc((void**)&v.g.cell_count, sizeof(int32_t) * cells)) != hipSuccess) return e;
-        if ((e = hipMalloc((void**)&v.g.cell_start, sizeof(int32_t) * (cells + 1))) != hipSuccess) return e;
-        if ((e = hipMalloc((void**)&v.g.node_cell, sizeof(int32_t) * (size_t)n)) != hipSuccess) return e;
-        if ((e = hipMalloc((void**)&v.g.sorted, sizeof(float4) * (size_t)n)) != hipSuccess) return e;
-        if ((e = hipMalloc((void**)&v.chunk_sums, sizeof(int32_t) * (cells / dfa::PGRID_CHUNK))) != hipSuccess) return e;
-        if ((e = hipMalloc((void**)&v.bbox_partials, sizeof(float) * 6 * dfa::PGRID_BBOX_BLOCKS)) != hipSuccess) return e;
-        cap_points = n;
-        return hipSuccess;
+        hipError_t e;
+        if ((e = g.reserve(cells, (size_t)n, (size_t)n / 4 + 1024)) || (e = chunk_sums.reserve(cells / dfa::PGRID_CHUNK)) ||
+            (e = bbox_partials.reserve(6 * dfa::PGRID_BBOX_BLOCKS)))
+            v = dfa::PointGridView{};
+        else v = dfa::PointGridView{g.v, chunk_sums.data, bbox_partials.data};
+        return e;
     }
 };
 
-// scratch of dfa_marching_cubes (segment offsets + scan partials); grows on demand
+// scratch of dfa_marching_cubes and of the point-cloud extraction (segment offsets + scan partials)
 struct McScratch {
-    int32_t* seg_off    = nullptr;
-    int32_t* chunk_sums = nullptr;
-    long cap_segs       = 0;
+    DeviceBuffer<int32_t> seg_off, chunk_sums;
     hipError_t reserve(long nsegs) {
-        if (nsegs <= cap_segs) return hipSuccess;
-        (void)hipFree(seg_off), (void)hipFree(chunk_sums);
-        seg_off = chunk_sums = nullptr, cap_segs = 0;
-        hipError_t e;
-        if ((e = hipMalloc((void**)&seg_off, sizeof(int32_t) * (size_t)(nsegs + 1))) != hipSuccess) return e;
-        if ((e = hipMalloc((void**)&chunk_sums, sizeof(int32_t) * (size_t)dfa::mc_scan_chunks(nsegs))) != hipSuccess)
-            return e;
-        cap_segs = nsegs;
-        return hipSuccess;
+        const hipError_t e = seg_off.reserve((size_t)nsegs + 1);
+        return e != hipSuccess ? e : chunk_sums.reserve((size_t)dfa::mc_scan_chunks(nsegs));
     }
 };
 // scratch of dfa_marching_cubes_indexed: two offset arrays (vertices, indices) over its own segments, one set of partials
 struct McIndexedScratch {
     McScratch vert;
-    int32_t* idx_off = nullptr;
-    long cap_segs    = 0;
+    DeviceBuffer<int32_t> idx_off;
     hipError_t reserve(long nsegs) {
-        hipError_t e = vert.reserve(nsegs);
-        if (e != hipSuccess || nsegs <= cap_segs) return e;
-        (void)hipFree(idx_off);
-        idx_off = nullptr, cap_segs = 0;
-        if ((e = hipMalloc((void**)&idx_off, sizeof(int32_t) * (size_t)(nsegs + 1))) != hipSuccess) return e;
-        cap_segs = nsegs;
-        return hipSuccess;
+        const hipError_t e = vert.reserve(nsegs);
+        return e != hipSuccess ? e : idx_off.reserve((size_t)nsegs + 1);
     }
 };
+struct IcpScratch : DeviceBuffer<float> {};        // partial sums of dfa_icp_sums
+struct CompactScratch : DeviceBuffer<int32_t> {};  // chunk counts of dfa_compact_points
 
 // exhaustive scan below this many distance evaluations (grid build = 4 small launches)
 // the uniform-grid k-NN (three small launches to build, ~40 us) against the exhaustive scan: worth it for many queries, and for
@@ -158,23 +118,33 @@ struct McIndexedScratch {
 // all, 0.86 ms in the adaptor's 512^3 sequence
 bool want_grid(int D, long n_query) { return D >= 64 && ((long)D * n_query >= (1L << 22) || D >= 1024); }
 
+// the grid of a search over D points where it pays (built in the stream's scratch), null where the exhaustive scan does
+int scratch_grid(const float* pos, int D, long n_query, hipStream_t st, const dfa::KnnGridView** grid) {
+    *grid = nullptr;
+    if (!want_grid(D, n_query)) return DFA_OK;
+    GridScratch& gs = stream_scratch<GridScratch>(st);
+    HIP_TRY(gs.reserve(D));
+    HIP_TRY(dfa::knn_grid_build(gs.v, pos, D, st));
+    *grid = &gs.v;
+    return DFA_OK;
+}
+
 }  // namespace
 
 struct dfa_solver {
     int max_D, max_N, k;
     size_t max_R;
     int ell_cap;
-    dfa::SolveView v;          // pointers into `blocks`
+    dfa::SolveView v;          // pointers into `mem`
     dfa::SolveState* state;    // device
     double* cost_partials;     // device
     unsigned int* ticket;      // device: arrival counter of the linearise kernel (self re-arming)
-    std::vector<void*> blocks;  // every hipMalloc of this plan
+    dfa::PlanArena mem;         // every hipMalloc and pinned block of this plan
     GridScratch grid;           // node grid of the current problem
     bool has_problem;
     bool timing;
-    std::vector<hipEvent_t> events;  // pool of timing events: they accumulate from enable_timing(1) on
+    dfa::EventPool ev;               // timing events, in begin / end pairs: they accumulate from enable_timing(1) on
     std::vector<int> ev_pcg, ev_asm; // indices of the begin events of each bracketed launch
-    size_t ev_used;
     int timed_solves = 0;
     dfa::MbGraphCache mb_graphs;  // HIP graphs of the many-workgroup PCG's launch chunks
     dfa::TeamPcg team;            // host side of the team PCG (plans of 2 049 nodes up to solve_team_pcg_fits: 19 584;
@@ -196,71 +166,36 @@ struct dfa_solver6 {
     float* raw_w;       // N x k un-normalised weights of the k-NN pass
     int32_t* raw_reg;   // D x (k + 1)
     const float* node_dq;  // borrowed: transforms at set_problem time
-    std::vector<void*> blocks;
+    dfa::PlanArena mem;
     GridScratch grid;
     bool has_problem;
     // the PCG of one Gauss-Newton iteration (linear_iter + 2 dependent launches) captured as a HIP graph:
     // re-captured when the problem size or the iteration parameters change
     std::map<int, hipGraphExec_t> pcg_graphs;  // by the number of step launches
     int last_launches = 0;  // step launches enqueued by the last solve
-    // Adaptive launch budget (dfa_solve6_params.adaptive_launch).  The device writes the PCG iterations of every
-    // Gauss-Newton iteration of solve n into slot n % S6_RING of a pinned mirror; the budget of solve n is a function of
-    // the solves up to n - 2 ONLY, folded into the history in order behind their completion events — never of how far
-    // the device happens to have got: the same sequence of solves gets the same budgets in every run.
-    static constexpr int S6_RING = 4;
-    int* mirror = nullptr;                        // pinned int[S6_RING][S6_HIST]
-    hipEvent_t done_ev[S6_RING] = {};             // end of solve n, n % S6_RING
-    int slot_gn[S6_RING] = {};                    // Gauss-Newton iterations solve n enqueued
-    unsigned long long solve_seq = 0, folded = 0;  // solves started; solves whose counts are in the history
-    int pred[dfa::S6_HIST] = {};                  // iterations per Gauss-Newton iteration: raised at once, lowered by one per solve
-    struct BudgetKey { int D, N, num_iter, gn_iter, linear_iter; float tol, tol_first, tol_decay, tol_adapt, gn_tol; } budget_key = {};
+    dfa::LaunchBudget budget;                  // dfa_solve6_params.adaptive_launch (launch_budget.hpp)
+    int* mirror = nullptr;                     // pinned int[S6_RING][S6_HIST]: the device's counts, solve n in slot n % S6_RING
+    hipEvent_t done_ev[dfa::S6_RING] = {};     // end of solve n, n % S6_RING
     bool graph_disabled = false;
     hipStream_t capture_stream = nullptr;  // capture is not allowed on the legacy default stream
     bool timing = false;  // hipEvent brackets around linearise / assemble / PCG of every Gauss-Newton iteration
-    std::vector<hipEvent_t> events;
-    size_t ev_used = 0;
+    dfa::EventPool ev;  // 4 per Gauss-Newton iteration
     int pcg_key_D = -1;  // node count the captured PCG graphs were recorded for
 };
 
 namespace {
-template <class T>
-int plan6_alloc(dfa_solver6* s, T** out, size_t count) {
-    void* p      = nullptr;
-    hipError_t e = hipMalloc(&p, sizeof(T) * (count ? count : 1));
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc (solver6 plan)");
-    s->blocks.push_back(p);
-    *out = (T*)p;
-    return DFA_OK;
-}
-}  // namespace
-
-namespace {
-// returns the index of a fresh event pair's begin event, recorded on st
-int timing_begin(dfa_solver* s, hipStream_t st) {
-    if (s->ev_used + 2 > s->events.size()) {
-        for (int i = 0; i < 2; ++i) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return -1;
-            s->events.push_back(e);
-        }
-    }
-    const int idx = (int)s->ev_used;
-    s->ev_used += 2;
-    (void)hipEventRecord(s->events[idx], st);
+// a begin / end pair of timing events: the begin event's index, recorded on st (-1: no events, the bracket is not taken)
+int bracket_open(dfa_solver* s, hipStream_t st) {
+    const int idx = s->timing ? s->ev.take(2) : -1;
+    if (idx >= 0) (void)hipEventRecord(s->ev.events[idx], st);
     return idx;
 }
-void timing_end(dfa_solver* s, int idx, hipStream_t st) {
-    if (idx >= 0) (void)hipEventRecord(s->events[idx + 1], st);
-}
 
-template <class T>
-int plan_alloc(dfa_solver* s, T** out, size_t count) {
-    void* p       = nullptr;
-    hipError_t e  = hipMalloc(&p, sizeof(T) * (count ? count : 1));
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc (solver plan)");
-    s->blocks.push_back(p);
-    *out = (T*)p;
-    return DFA_OK;
+// behind the field list of a plan: the arena's first failure as the C ABI reports it
+int plan_status(const dfa::PlanArena& mem) { return mem.ok() ? DFA_OK : hip_fail(mem.error, mem.what); }
+int plan_grid(GridScratch& grid, int max_D) {
+    const hipError_t e = grid.reserve(max_D);
+    return e == hipSuccess ? DFA_OK : hip_fail(e, "hipMalloc (node grid)");
 }
 }  // namespace
 
@@ -580,21 +515,6 @@ int dfa_resize_points_normals(const float* points, int points_step, const float*
 
 // ------------------------------------------------------------------------------ rigid-ICP seam
 
-namespace {
-struct IcpScratch {
-    float* partial = nullptr;
-    size_t cap     = 0;
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        (void)hipFree(partial);
-        partial = nullptr, cap = 0;
-        hipError_t e = hipMalloc((void**)&partial, sizeof(float) * n);
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-};
-}  // namespace
-
 int dfa_icp_sums(int depth_variant, const void* curr, int curr_step, const float* ncurr, int ncurr_step, const void* prev,
                  int prev_step, const float* nprev, int nprev_step, int cols, int rows, const float aff[12], float fx,
                  float fy, float cx, float cy, float dist_thres, float angle_thres, float* sums27, unsigned int* matched,
@@ -605,10 +525,10 @@ int dfa_icp_sums(int depth_variant, const void* curr, int curr_step, const float
     REQUIRE(curr_step >= cols * px && prev_step >= cols * px && ncurr_step >= cols * 16 && nprev_step >= cols * 16,
             "row step smaller than a row");
     REQUIRE(fx != 0.f && fy != 0.f && dist_thres >= 0.f, "bad intrinsics / threshold");
-    IcpScratch& scratch = stream_scratch<IcpScratch>(S(stream));
-    HIP_TRY(scratch.reserve(dfa::icp_partial_floats(cols, rows)));
+    IcpScratch& partial = stream_scratch<IcpScratch>(S(stream));
+    HIP_TRY(partial.reserve(dfa::icp_partial_floats(cols, rows)));
     HIP_TRY(dfa::launch_icp_sums(depth_variant != 0, curr, curr_step, ncurr, ncurr_step, prev, prev_step, nprev, nprev_step,
-                                 cols, rows, aff, fx, fy, cx, cy, dist_thres, angle_thres, scratch.partial, sums27,
+                                 cols, rows, aff, fx, fy, cx, cy, dist_thres, angle_thres, partial.data, sums27,
                                  matched, S(stream)));
     return DFA_OK;
 }
@@ -627,8 +547,8 @@ static int marching_cubes_common(const uint32_t* volume, int X, int Y, int Z, co
     McScratch& scratch = stream_scratch<McScratch>(S(stream));
     HIP_TRY(scratch.reserve(nsegs));
     HIP_TRY(dfa::launch_marching_cubes(volume, X, Y, Z, cell_size, tri_table, num_verts_table, out_points,
-                                       max_vertices, total_vertices, scratch.seg_off, scratch.chunk_sums, occupancy,
-                                       S(stream)));
+                                       max_vertices, total_vertices, scratch.seg_off.data, scratch.chunk_sums.data,
+                                       occupancy, S(stream)));
     return DFA_OK;
 }
 
@@ -662,8 +582,8 @@ int dfa_marching_cubes_indexed(const uint32_t* volume, const uint8_t* occupancy,
     McIndexedScratch& scratch = stream_scratch<McIndexedScratch>(S(stream));
     HIP_TRY(scratch.reserve(nsegs));
     HIP_TRY(dfa::launch_marching_cubes_indexed(volume, X, Y, Z, cell_size, tri_table, num_verts_table, out_vertices,
-                                               max_vertices, out_indices, max_indices, totals, scratch.vert.seg_off,
-                                               scratch.idx_off, scratch.vert.chunk_sums, occupancy, S(stream)));
+                                               max_vertices, out_indices, max_indices, totals, scratch.vert.seg_off.data,
+                                               scratch.idx_off.data, scratch.vert.chunk_sums.data, occupancy, S(stream)));
     return DFA_OK;
 }
 
@@ -681,7 +601,7 @@ static int extract_cloud_common(const uint32_t* volume, int X, int Y, int Z, con
     McScratch& scratch = stream_scratch<McScratch>(S(stream));  // (the row segments and the scan are marching cubes')
     HIP_TRY(scratch.reserve(dfa::mc_segments(X, Y, Z, vec4)));
     HIP_TRY(dfa::launch_extract_cloud(volume, X, Y, Z, voxel_size, vol2world, out_points, max_points, total_points,
-                                      scratch.seg_off, scratch.chunk_sums, occupancy, S(stream)));
+                                      scratch.seg_off.data, scratch.chunk_sums.data, occupancy, S(stream)));
     return DFA_OK;
 }
 
@@ -726,16 +646,8 @@ int dfa_knn(const float* node_pos, const float* node_w, int D, const float* quer
     REQUIRE(n_query >= 0 && (n_query == 0 || (query && idx)), "bad query / output");
     REQUIRE(k >= 1 && k <= DFA_MAX_KNN, "k out of range 1..16");
     REQUIRE(!weights || node_w, "weights requested without node_w");
-    const dfa::KnnGridView* grid = nullptr;
-    if (want_grid(D, n_query)) {
-        GridScratch& gs = stream_scratch<GridScratch>(S(stream));
-
-        HIP_TRY(gs.reserve(D));
-
-        HIP_TRY(dfa::knn_grid_build(gs.v, node_pos, D, S(stream)));
-
-        grid = &gs.v;
-    }
+    const dfa::KnnGridView* grid;
+    if (int rc = scratch_grid(node_pos, D, n_query, S(stream), &grid)) return rc;
     HIP_TRY(dfa::launch_knn(node_pos, node_w, D, query, n_query, k, idx, weights, grid, S(stream)));
     return DFA_OK;
 }
@@ -746,16 +658,8 @@ int dfa_warp_to_live(const float* node_pos, const float* node_dq, const float* n
     REQUIRE(node_pos && node_dq && node_w && D > 0, "no nodes");
     REQUIRE(N >= 0 && (N == 0 || (vertices && out_vertices)), "bad vertices / output");
     REQUIRE(k >= 1 && k <= DFA_MAX_KNN, "k out of range 1..16");
-    const dfa::KnnGridView* grid = nullptr;
-    if (want_grid(D, N)) {
-        GridScratch& gs = stream_scratch<GridScratch>(S(stream));
-
-        HIP_TRY(gs.reserve(D));
-
-        HIP_TRY(dfa::knn_grid_build(gs.v, node_pos, D, S(stream)));
-
-        grid = &gs.v;
-    }
+    const dfa::KnnGridView* grid;
+    if (int rc = scratch_grid(node_pos, D, N, S(stream), &grid)) return rc;
     HIP_TRY(dfa::launch_warp_to_live(node_pos, node_dq, node_w, D, k, vertices, normals, N, out_vertices,
                                      out_normals, grid, S(stream)));
     return DFA_OK;
@@ -778,16 +682,8 @@ int dfa_calc_dqb(const float* node_pos, const float* node_dq, const float* node_
     REQUIRE(node_pos && node_dq && node_w && D > 0, "no nodes");
     REQUIRE(n >= 0 && (n == 0 || (points && out_dq)), "bad points / output");
     REQUIRE(k >= 1 && k <= DFA_MAX_KNN, "k out of range 1..16");
-    const dfa::KnnGridView* grid = nullptr;
-    if (want_grid(D, n)) {
-        GridScratch& gs = stream_scratch<GridScratch>(S(stream));
-
-        HIP_TRY(gs.reserve(D));
-
-        HIP_TRY(dfa::knn_grid_build(gs.v, node_pos, D, S(stream)));
-
-        grid = &gs.v;
-    }
+    const dfa::KnnGridView* grid;
+    if (int rc = scratch_grid(node_pos, D, n, S(stream), &grid)) return rc;
     HIP_TRY(dfa::launch_dqb_support(node_pos, node_dq, node_w, D, k, points, n, out_dq, nullptr, grid, S(stream)));
     return DFA_OK;
 }
@@ -801,16 +697,8 @@ int dfa_unsupported_vertices(const float* node_pos, const float* node_w, int D, 
         return DFA_OK;
     }
     REQUIRE(node_pos && node_w && D > 0, "bad nodes");
-    const dfa::KnnGridView* grid = nullptr;
-    if (want_grid(D, N)) {
-        GridScratch& gs = stream_scratch<GridScratch>(S(stream));
-
-        HIP_TRY(gs.reserve(D));
-
-        HIP_TRY(dfa::knn_grid_build(gs.v, node_pos, D, S(stream)));
-
-        grid = &gs.v;
-    }
+    const dfa::KnnGridView* grid;
+    if (int rc = scratch_grid(node_pos, D, N, S(stream), &grid)) return rc;
     HIP_TRY(dfa::launch_dqb_support(node_pos, nullptr, node_w, D, k, vertices, N, nullptr, flags, grid, S(stream)));
     return DFA_OK;
 }
@@ -833,30 +721,15 @@ int dfa_transform_points(const float* points, int n, const float aff[12], int wi
     return DFA_OK;
 }
 
-namespace {
-struct CompactScratch {
-    int32_t* chunks = nullptr;
-    int cap         = 0;
-    hipError_t reserve(int n_needed) {
-        if (n_needed <= cap) return hipSuccess;
-        const int n = n_needed + n_needed / 4 + 16;
-        (void)hipFree(chunks);
-        chunks = nullptr, cap = 0;
-        hipError_t e = hipMalloc((void**)&chunks, sizeof(int32_t) * (size_t)n);
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-};
-}  // namespace
-
 int dfa_compact_points(const float* points, const uint8_t* flags, int N, float* out_points, int32_t* out_index,
                        int32_t* count, dfa_stream_t stream) {
     REQUIRE(count, "count is required");
     REQUIRE(N >= 0 && (N == 0 || flags), "bad flags");
     REQUIRE(!out_points || points || N == 0, "out_points requested without points");
-    CompactScratch& cs = stream_scratch<CompactScratch>(S(stream));
-    HIP_TRY(cs.reserve(dfa::compact_chunks(N > 0 ? N : 1)));
-    HIP_TRY(dfa::launch_compact_points(points, flags, N, out_points, out_index, count, cs.chunks, S(stream)));
+    CompactScratch& chunks = stream_scratch<CompactScratch>(S(stream));
+    const size_t n         = (size_t)dfa::compact_chunks(N > 0 ? N : 1);
+    HIP_TRY(chunks.reserve(n, n / 4 + 16));
+    HIP_TRY(dfa::launch_compact_points(points, flags, N, out_points, out_index, count, chunks.data, S(stream)));
     return DFA_OK;
 }
 
@@ -865,21 +738,14 @@ int dfa_correspond(const float* canon_vertices, const float* canon_normals, int 
     REQUIRE(canon_vertices && n_canon > 0, "no canonical vertices");
     REQUIRE(n_live >= 0 && (n_live == 0 || live_vertices), "bad live vertices");
     REQUIRE(!out_normals || canon_normals, "normals requested without canonical normals");
-    const dfa::KnnGridView* grid = nullptr;
+    const dfa::KnnGridView* grid;
     if (n_canon >= 16384 && want_grid(n_canon, n_live)) {  // large cloud: 128^3 point grid
         PointGridScratch& pg = stream_scratch<PointGridScratch>(S(stream));
         HIP_TRY(pg.reserve(n_canon));
         HIP_TRY(dfa::point_grid_build(pg.v, canon_vertices, n_canon, S(stream)));
         grid = &pg.v.g;
-    } else if (want_grid(n_canon, n_live)) {
-        GridScratch& gs = stream_scratch<GridScratch>(S(stream));
-
-        HIP_TRY(gs.reserve(n_canon));
-
-        HIP_TRY(dfa::knn_grid_build(gs.v, canon_vertices, n_canon, S(stream)));
-
-        grid = &gs.v;
-    }
+    } else if (int rc = scratch_grid(canon_vertices, n_canon, n_live, S(stream), &grid))
+        return rc;
     HIP_TRY(dfa::launch_correspond(canon_vertices, canon_normals, n_canon, live_vertices, n_live, out_vertices,
                                    out_normals, out_index, grid, S(stream)));
     return DFA_OK;
@@ -925,12 +791,10 @@ int dfa_solver_create(int max_D, int max_N, int k, dfa_solver** out) {
         const char* e    = getenv("DFA_ASSEMBLE_DETERMINISTIC");
         s->deterministic = e && atoi(e) != 0;
     }
-    s->ev_used     = 0;
     std::memset(&s->v, 0, sizeof(s->v));
     const size_t R = s->max_R, D = (size_t)max_D;
-    int rc = DFA_OK;
-#define A(field, count) \
-    if (rc == DFA_OK) rc = plan_alloc(s, &s->v.field, (count))
+    dfa::PlanArena& mem = s->mem;
+#define A(field, count) mem.alloc(&s->v.field, (count))
     A(ridx, R * k);
     A(rw, R * k);
     A(rtau, R);
@@ -969,39 +833,34 @@ int dfa_solver_create(int max_D, int max_N, int k, dfa_solver** out) {
     A(huber, D);
     A(node_dq_out, D * 8);
 #undef A
-    if (rc == DFA_OK) {
-        hipError_t e = s->grid.reserve(max_D);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMalloc (node grid)");
-    }
+    int rc = plan_status(mem);
+    if (rc == DFA_OK) rc = plan_grid(s->grid, max_D);
     // (plans of up to 2 048 nodes solve in the register-resident kernels: no team buffers for them outside development builds)
     if (rc == DFA_OK && dfa::solve_team_pcg_fits(max_D) && (max_D > 2048 || dfa::kDevAB)) {
         // team PCG: control block and flag words (zeroed once: barrier rounds grow; the words are cleared again only where
         // the rounds would wrap), exchange buffer, the pinned abort count
         s->v.team_stride = (max_D + 3) & ~3;
-        rc = plan_alloc(s, &s->v.team_ctl, 1);
         const size_t areas = (size_t)3 * dfa::solve_team_pcg_rounds();  // an area per barrier round and coordinate (50 MB at 8 k nodes)
-        if (rc == DFA_OK) rc = plan_alloc(s, &s->v.team_mt, areas * s->v.team_stride);
-        if (rc == DFA_OK) rc = plan_alloc(s, &s->v.team_words, dfa::solve_team_pcg_words());
-        if (rc == DFA_OK && (hipMemset(s->v.team_ctl, 0, sizeof(dfa::TeamCtl)) != hipSuccess ||
-                             hipMemset(s->v.team_words, 0, sizeof(unsigned long long) * dfa::solve_team_pcg_words()) != hipSuccess ||
-                             hipMemset(s->v.team_mt, 0, sizeof(float2) * areas * (size_t)s->v.team_stride) != hipSuccess))
-            rc = fail(DFA_ERR_HIP, "hipMemset (team PCG)");
-        if (rc == DFA_OK && hipHostMalloc((void**)&s->team.host_abort, sizeof(int), hipHostMallocDefault) == hipSuccess) {
-            *s->team.host_abort = 0;
+        mem.alloc(&s->v.team_ctl, 1, true);
+        mem.alloc(&s->v.team_mt, areas * s->v.team_stride, true);
+        mem.alloc(&s->v.team_words, dfa::solve_team_pcg_words(), true);
+        s->team.host_abort = mem.pinned<int>(1);
+        if ((rc = plan_status(mem)) == DFA_OK && !s->team.host_abort) rc = fail(DFA_ERR_HIP, "hipHostMalloc (team PCG abort count)");
+        if (rc == DFA_OK) {
             s->team.ctl = s->v.team_ctl;
             // (development builds: DFA_MB_TEAM_EPOCH = the first barrier round, e.g. just below 2^32 for the wrap's test)
             if (const char* e0 = dfa::dev_env("DFA_MB_TEAM_EPOCH")) s->team.epoch = (unsigned)std::strtoul(e0, nullptr, 0);
         }
     }
-    if (rc == DFA_OK) rc = plan_alloc(s, &s->state, 1);
-    if (rc == DFA_OK) rc = plan_alloc(s, &s->iters_total, 1);
-    if (rc == DFA_OK && hipMemset(s->iters_total, 0, sizeof(long long)) != hipSuccess) rc = DFA_ERR_HIP;
-    if (rc == DFA_OK && hipHostMalloc((void**)&s->host_flag, 4 * sizeof(int), hipHostMallocDefault) != hipSuccess) s->host_flag = nullptr;
-    // (per linearise workgroup, at most 1024 of them: its share of the energy; behind those its largest matrix addend)
-    if (rc == DFA_OK) rc = plan_alloc(s, &s->cost_partials, std::max<size_t>((R + 255) / 256 + 1, 1024) + 1024);
-    if (rc == DFA_OK) rc = plan_alloc(s, &s->ticket, 64);
-    if (rc == DFA_OK && hipMemset(s->ticket, 0, 64 * sizeof(unsigned int)) != hipSuccess)
-        rc = fail(DFA_ERR_HIP, "hipMemset (ticket)");
+    if (rc == DFA_OK) {
+        mem.alloc(&s->state, 1);
+        mem.alloc(&s->iters_total, 1, true);
+        s->host_flag = mem.pinned<int>(4);  // (none: the solve does without the read-backs)
+        // (per linearise workgroup, at most 1024 of them: its share of the energy; behind those its largest matrix addend)
+        mem.alloc(&s->cost_partials, std::max<size_t>((R + 255) / 256 + 1, 1024) + 1024);
+        mem.alloc(&s->ticket, 64, true);
+        rc = plan_status(mem);
+    }
     if (rc != DFA_OK) {
         dfa_solver_destroy(s);
         return rc;
@@ -1012,13 +871,9 @@ int dfa_solver_create(int max_D, int max_N, int k, dfa_solver** out) {
 
 void dfa_solver_destroy(dfa_solver* s) {
     if (!s) return;
-    for (void* p : s->blocks) (void)hipFree(p);
     s->grid.release();
-    for (hipEvent_t e : s->events) (void)hipEventDestroy(e);
-    if (s->host_flag) (void)hipHostFree(s->host_flag);
-    if (s->team.host_abort) (void)hipHostFree(s->team.host_abort);
     s->mb_graphs.release();
-    delete s;
+    delete s;  // (the arena frees the plan's memory, the pool its events)
 }
 
 int dfa_solver_set_problem(dfa_solver* s, const float* node_pos, const float* node_dq, const float* node_w, int D,
@@ -1091,6 +946,21 @@ int dfa_solver_solve(dfa_solver* s, const dfa_solve_params* p, dfa_stream_t stre
     const bool big_budget = (long)p->num_iter * p->nonlinear_iter > 8;
     const bool pcg_async  = dfa::solve_pcg_is_async(v, &s->team, p->linear_iter);  // (else the PCG itself reads the flags back)
     const bool no_regradient = dfa::dev_env("DFA_NO_REGRADIENT") != nullptr;  // (development builds: the tests compare both ways)
+    // Behind the launch that left this iteration's system (the assembly, or the regradient that stands in for one) in the
+    // bracket ev_asm: this iteration's PCG starts here — the caller's chip-wide work may run in its shadow
+    auto run_pcg = [&](int ev_asm) -> int {
+        if (ev_asm >= 0) {  // close that bracket and book it
+            (void)hipEventRecord(s->ev.events[ev_asm + 1], st);
+            s->ev_asm.push_back(ev_asm);
+        }
+        if (s->overlap_fn) s->overlap_fn(s->overlap_user, stream, gn_launched);
+        ++gn_launched;
+        const int ev = bracket_open(s, st);  // closed behind the solving kernel, before the fallback launch
+        HIP_TRY(dfa::solve_pcg(v, s->state, p->linear_iter, p->pcg_tol, s->host_flag, &s->mb_graphs, &s->team,
+                               ev >= 0 ? s->ev.events[ev + 1] : nullptr, st));
+        if (ev >= 0) s->ev_pcg.push_back(ev);
+        return DFA_OK;
+    };
     for (int outer = 0; outer < p->num_iter; ++outer) {
         // preNonlinearSolve (opt_solver.cpp:135-140): the Huber weights are only observable after
         // the solve, so they are evaluated for the last outer iteration alone
@@ -1123,33 +993,18 @@ int dfa_solver_solve(dfa_solver* s, const dfa_solve_params* p, dfa_stream_t stre
             // none; measured: two of the eight OptTest scenes leave their 1e-3 tolerance): the long way as well.
             // DFA_NO_REGRADIENT=1: the long way always (A/B).
             if (gn > 0 && p->gn_tol == 0.f && p->lambda > 0.f && !no_regradient) {
-                int evg = s->timing ? timing_begin(s, st) : -1;  // booked with the assemblies: it stands in for one
+                const int ev = bracket_open(s, st);  // booked with the assemblies: it stands in for one
                 HIP_TRY(dfa::solve_regradient(v, s->state, st));
-                timing_end(s, evg, st);
-                if (evg >= 0) s->ev_asm.push_back(evg);
-                if (s->overlap_fn) s->overlap_fn(s->overlap_user, stream, gn_launched);
-                ++gn_launched;
-                int evr = s->timing ? timing_begin(s, st) : -1;
-                HIP_TRY(dfa::solve_pcg(v, s->state, p->linear_iter, p->pcg_tol, s->host_flag, &s->mb_graphs, &s->team,
-                                       evr >= 0 ? s->events[evr + 1] : nullptr, st));
-                if (evr >= 0) s->ev_pcg.push_back(evr);
+                if (int rc = run_pcg(ev)) return rc;
                 continue;
             }
             const bool with_huber = gn == 0 && outer == p->num_iter - 1;
             HIP_TRY(dfa::solve_linearise(v, s->state, s->cost_partials, s->ticket, gn == 0, gn == 0 ? 0 : 1,
                                          p->gn_tol, p->tukey_offset, p->psi_data, w_reg_sq, with_huber ? p->psi_reg : 0.f, nullptr, st));
             huber_done |= with_huber;
-            int ev = s->timing ? timing_begin(s, st) : -1;
+            const int ev = bracket_open(s, st);
             HIP_TRY(dfa::solve_assemble(v, s->state, gn == 0 && p->nonlinear_iter > 1, w_reg_sq, st));
-            timing_end(s, ev, st);
-            if (ev >= 0) s->ev_asm.push_back(ev);
-            // this iteration's PCG starts here: the caller's chip-wide work may run in its shadow
-            if (s->overlap_fn) s->overlap_fn(s->overlap_user, stream, gn_launched);
-            ++gn_launched;
-            ev = s->timing ? timing_begin(s, st) : -1;  // closed behind the solving kernel, before the fallback launch
-            HIP_TRY(dfa::solve_pcg(v, s->state, p->linear_iter, p->pcg_tol, s->host_flag, &s->mb_graphs, &s->team,
-                                   ev >= 0 ? s->events[ev + 1] : nullptr, st));
-            if (ev >= 0) s->ev_pcg.push_back(ev);
+            if (int rc = run_pcg(ev)) return rc;
         }
     }
     if (s->overlap_fn && gn_launched == 0) s->overlap_fn(s->overlap_user, stream, -1);  // no iteration ran: the caller's work still goes out
@@ -1215,7 +1070,7 @@ int dfa_solver_enable_timing(dfa_solver* s, int enable) {
     REQUIRE(s, "null plan");
     s->timing = enable != 0;
     if (enable == 1) {  // a new measurement: forget the brackets collected so far (2 = resume, keeps them)
-        s->ev_used = 0, s->timed_solves = 0;
+        s->ev.rewind(), s->timed_solves = 0;
         s->ev_pcg.clear(), s->ev_asm.clear();
         if (s->iters_total) HIP_TRY(hipMemset(s->iters_total, 0, sizeof(long long)));
     }
@@ -1234,16 +1089,12 @@ int dfa_solver_get_timing(dfa_solver* s, dfa_solve_timing* out, dfa_stream_t str
     REQUIRE(s && out, "null plan / out");
     HIP_TRY(hipStreamSynchronize(S(stream)));
     std::memset(out, 0, sizeof(*out));
-    for (int idx : s->ev_pcg) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, s->events[idx], s->events[idx + 1]));
-        out->pcg_ms += ms;
-    }
-    for (int idx : s->ev_asm) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, s->events[idx], s->events[idx + 1]));
-        out->assemble_ms += ms;
-    }
+    for (const std::vector<int>* brackets : {&s->ev_pcg, &s->ev_asm})
+        for (int idx : *brackets) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, s->ev.events[idx], s->ev.events[idx + 1]));
+            (brackets == &s->ev_pcg ? out->pcg_ms : out->assemble_ms) += ms;
+        }
     out->pcg_launches      = (int)s->ev_pcg.size();
     out->assemble_launches = (int)s->ev_asm.size();
     out->solves            = s->timed_solves;
@@ -1284,9 +1135,8 @@ int dfa_solver6_create(int max_D, int max_N, int k, dfa_solver6** out) {
     std::memset(&s->v, 0, sizeof(s->v));
     s->v.cap = DFA_SOLVE6_ROW_BLOCKS;  // = S6_MAXSLOT of solve6.hip
     const size_t N = (size_t)max_N, D = (size_t)max_D, cap = (size_t)s->v.cap;
-    int rc = DFA_OK;
-#define A(field, count) \
-    if (rc == DFA_OK) rc = plan6_alloc(s, &s->v.field, (count))
+    dfa::PlanArena& mem = s->mem;
+#define A(field, count) mem.alloc(&s->v.field, (count))
     A(idx, N * k);
     A(wn, N * k);
     A(idx_nat, N * k);
@@ -1340,24 +1190,17 @@ int dfa_solver6_create(int max_D, int max_N, int k, dfa_solver6** out) {
     A(d_part[0], (size_t)dfa::s6_matvec_blocks(max_D));
     A(d_part[1], (size_t)dfa::s6_matvec_blocks(max_D));
 #undef A
-    if (rc == DFA_OK) rc = plan6_alloc(s, &s->raw_w, N * k);
-    if (rc == DFA_OK) rc = plan6_alloc(s, &s->raw_reg, D * (k + 1));
-    if (rc == DFA_OK) rc = plan6_alloc(s, &s->state, 1);
-    if (rc == DFA_OK) {
-        bool ok = hipHostMalloc((void**)&s->mirror, dfa_solver6::S6_RING * dfa::S6_HIST * sizeof(int), hipHostMallocDefault) == hipSuccess;
-        for (int i = 0; ok && i < dfa_solver6::S6_RING; ++i)
+    mem.alloc(&s->raw_w, N * k);
+    mem.alloc(&s->raw_reg, D * (k + 1));
+    mem.alloc(&s->state, 1);
+    int rc = plan_status(mem);
+    if (rc == DFA_OK) {  // the launch budget's mirror and completion events (none: every PCG gets its full budget)
+        bool ok = true;
+        for (int i = 0; ok && i < dfa::S6_RING; ++i)
             ok = hipEventCreateWithFlags(&s->done_ev[i], hipEventDisableTiming) == hipSuccess;
-        if (ok) {
-            std::memset(s->mirror, 0, dfa_solver6::S6_RING * dfa::S6_HIST * sizeof(int));
-        } else {  // no mirror: every PCG gets its full budget
-            (void)hipGetLastError();
-            if (s->mirror) (void)hipHostFree(s->mirror);
-            s->mirror = nullptr;
-        }
-    }
-    if (rc == DFA_OK) {
-        hipError_t e = s->grid.reserve(max_D);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMalloc (node grid)");
+        if (ok) s->mirror = mem.pinned<int>(dfa::S6_RING * dfa::S6_HIST);
+        else (void)hipGetLastError();
+        rc = plan_grid(s->grid, max_D);
     }
     if (rc != DFA_OK) {
         dfa_solver6_destroy(s);
@@ -1370,14 +1213,11 @@ int dfa_solver6_create(int max_D, int max_N, int k, dfa_solver6** out) {
 void dfa_solver6_destroy(dfa_solver6* s) {
     if (!s) return;
     for (auto& g : s->pcg_graphs) (void)hipGraphExecDestroy(g.second);
-    if (s->mirror) (void)hipHostFree(s->mirror);
     for (hipEvent_t e : s->done_ev)
         if (e) (void)hipEventDestroy(e);
     if (s->capture_stream) (void)hipStreamDestroy(s->capture_stream);
-    for (hipEvent_t e : s->events) (void)hipEventDestroy(e);
-    for (void* p : s->blocks) (void)hipFree(p);
     s->grid.release();
-    delete s;
+    delete s;  // (the arena frees the plan's memory, the pool its events)
 }
 
 int dfa_solver6_set_problem(dfa_solver6* s, const float* node_pos, const float* node_dq, const float* node_w, int D,
@@ -1431,50 +1271,27 @@ int dfa_solver6_solve(dfa_solver6* s, const float* live_vertex_map, int vertex_s
     const bool early = p.gn_tol > 0.f;
     dfa::Solve6Image img{live_vertex_map, live_normal_map, vertex_step, normal_step, cols, rows, fx, fy, cx, cy};
     hipStream_t st = S(stream);
-    s->ev_used = 0;
+    s->ev.rewind();
     HIP_TRY(dfa::s6_begin(s->v, s->state, s->node_dq, early ? p.num_iter * p.gn_iter : 0, st));
     s->last_launches = 0;
-    // ---- launch budget: fold the solves up to n - 2 into the history (in order, each behind its completion event)
-    const bool adaptive = prm->adaptive_launch && s->mirror;
-    const unsigned long long n = s->solve_seq++;
-    const int slot         = (int)(n % dfa_solver6::S6_RING);
-    if (adaptive) {
-        const dfa_solver6::BudgetKey key{s->v.D, s->v.N, p.num_iter, p.gn_iter, p.linear_iter, p.pcg_tol, p.pcg_tol_first,
-                                         p.pcg_tol_decay, p.pcg_tol_adapt, p.gn_tol};
-        const dfa_solver6::BudgetKey& old = s->budget_key;
-        auto far = [](int a, int b) { return std::abs(a - b) * 8 > std::max(a, b); };  // changed by more than an eighth
-        const bool reset = far(key.D, old.D) || far(key.N, old.N) || key.num_iter != old.num_iter || key.gn_iter != old.gn_iter ||
-                           key.linear_iter != old.linear_iter || key.tol != old.tol || key.tol_first != old.tol_first ||
-                           key.tol_decay != old.tol_decay || key.tol_adapt != old.tol_adapt || key.gn_tol != old.gn_tol;
-        s->budget_key = key;
-        for (; s->folded + 2 <= n; ++s->folded) {
-            const int fs = (int)(s->folded % dfa_solver6::S6_RING);
-            HIP_TRY(hipEventSynchronize(s->done_ev[fs]));  // two solves back: complete long ago unless the caller is far ahead
-            for (int gi = 0; gi < std::min(s->slot_gn[fs], dfa::S6_HIST); ++gi) {
-                const int seen = s->mirror[fs * dfa::S6_HIST + gi];
-                int& pred      = s->pred[gi];
-                // (an iteration behind the end of its outer iteration ran no PCG: its budget decays like one that needed
-                // little — the launches enqueued for it are no-ops every time it is skipped again — but stays known)
-                if (seen == dfa::S6_MIRROR_SKIPPED) pred = pred > 1 ? pred - 1 : 1;  // (never back to 0 = unknown = the full cap)
-                else if (seen > 0) pred = std::max(seen, pred - 1);
-                else if (seen < 0) pred = std::max(pred, -2 * seen);  // cut short: twice as many
-            }
-        }
-        if (reset) {  // another problem (or other stopping rules): what the previous one needed says nothing
-            std::memset(s->pred, 0, sizeof(s->pred));
-            s->folded = n;  // (solves n - 2, n - 1 of the old problem are never folded)
-        }
-    } else {
-        s->folded = n + 1 >= 2 ? n - 1 : 0;  // nothing to fold later from solves without a budget
-        std::memset(s->pred, 0, sizeof(s->pred));
+    // ---- launch budget (launch_budget.hpp): the solves up to n - 2 enter the history, in order, each behind its completion event
+    dfa::LaunchBudget& budget = s->budget;
+    const auto b = budget.start(prm->adaptive_launch && s->mirror,
+                                dfa::BudgetKey{s->v.D, s->v.N, p.num_iter, p.gn_iter, p.linear_iter, p.pcg_tol, p.pcg_tol_first,
+                                               p.pcg_tol_decay, p.pcg_tol_adapt, p.gn_tol});
+    for (unsigned long long f = b.fold_from; f < b.fold_to; ++f) {
+        const int fs = (int)(f % dfa::S6_RING);
+        HIP_TRY(hipEventSynchronize(s->done_ev[fs]));  // two solves back: complete long ago unless the caller is far ahead
+        budget.fold(s->mirror + fs * dfa::S6_HIST);
     }
-    int* mirror_slot = s->mirror ? s->mirror + slot * dfa::S6_HIST : nullptr;
+    if (b.reset) budget.forget(b.n);
+    int* mirror_slot = s->mirror ? s->mirror + b.slot * dfa::S6_HIST : nullptr;
     if (mirror_slot) {
         // the slot's previous owner, solve n - S6_RING, must have finished writing it (it has, unless the caller runs more
         // than S6_RING - 1 solves ahead of the device)
-        if (n >= (unsigned long long)dfa_solver6::S6_RING) HIP_TRY(hipEventSynchronize(s->done_ev[slot]));
+        if (b.slot_reused) HIP_TRY(hipEventSynchronize(s->done_ev[b.slot]));
         std::memset(mirror_slot, 0, dfa::S6_HIST * sizeof(int));
-        s->slot_gn[slot] = p.num_iter * p.gn_iter;
+        budget.slot_gn[b.slot] = p.num_iter * p.gn_iter;
     }
     // the graphs replay launches over the plan's own buffers: only the node count is part of what they captured
     if (s->pcg_key_D != s->v.D) {
@@ -1484,15 +1301,7 @@ int dfa_solver6_solve(dfa_solver6* s, const float* live_vertex_map, int vertex_s
     }
     for (int outer = 0; outer < p.num_iter; ++outer)
         for (int gn = 0; gn < p.gn_iter; ++gn) {
-            auto mark = [&]() {  // 4 events per Gauss-Newton iteration: | linearise | assemble | pcg |
-                if (!s->timing) return;
-                if (s->ev_used == s->events.size()) {
-                    hipEvent_t e;
-                    if (hipEventCreate(&e) != hipSuccess) return;
-                    s->events.push_back(e);
-                }
-                (void)hipEventRecord(s->events[s->ev_used++], st);
-            };
+            auto mark = [&]() { if (s->timing) (void)s->ev.record(st); };  // 4 per Gauss-Newton iteration: | linearise | assemble | pcg |
             const int gi = outer * p.gn_iter + gn;
             mark();
             // gn_tol > 0: the launch's last workgroup applies the stopping rule on the device — launches behind the end of an
@@ -1502,18 +1311,7 @@ int dfa_solver6_solve(dfa_solver6* s, const float* live_vertex_map, int vertex_s
             mark();
             HIP_TRY(dfa::s6_assemble(s->v, s->state, p, gn, st));
             mark();
-            // Launches of this PCG: the caller's cap, or (adaptive_launch) what this Gauss-Newton iteration needed in the
-            // plan's earlier solves (a maximum that decays by one per solve) plus a quarter, at least two.  (Measured at C2 /
-            // C3 over 30-frame sequences: consecutive frames move a count by up to 2 where it is small and by up to a
-            // quarter where it is 30-40; one launch of slack instead of two cut 1-2 PCGs short in a fifth of the frames.)
-            int launches = p.linear_iter;
-            // (VERDICT r05 item 7 — one launch of slack where a slot's count had repeated in two solves running, one launch for a
-            // slot skipped twice running — was built and measured in round 6: 58 launches for 41 iterations instead of 60 for 36
-            // at C2, 83 for 53 instead of 92 for 47 at C3, and the frames/s inside the run-to-run spread (863.6 against 860,
-            // 331 against 343 over the whole period): a launch that returns at entry costs 3.5 us, a dozen of them 3 % of a
-            // C2 frame.  Not kept.)
-            if (adaptive && gi < dfa::S6_HIST && s->pred[gi] > 0)
-                launches = std::min(p.linear_iter, s->pred[gi] + std::max(2, s->pred[gi] / 4));
+            int launches = budget.launches(gi, p.linear_iter);  // the caller's cap, or what this iteration has needed
             // the PCG launches of one Gauss-Newton iteration are replayed as a HIP graph (one per launch count); if capture
             // is not possible here (it never is on some stream configurations) the launches are issued one by one
             bool replayed = false;
@@ -1553,7 +1351,7 @@ int dfa_solver6_solve(dfa_solver6* s, const float* live_vertex_map, int vertex_s
         HIP_TRY(dfa::s6_linearise(s->v, s->state, img, p, 0, gi, p.gn_iter, 1, st));
         HIP_TRY(dfa::s6_update(s->v, s->state, 0, p.linear_iter, nullptr, gi, 0, st));
     }
-    if (mirror_slot) HIP_TRY(hipEventRecord(s->done_ev[slot], st));
+    if (mirror_slot) HIP_TRY(hipEventRecord(s->done_ev[b.slot], st));
     return DFA_OK;
 }
 
@@ -1567,11 +1365,12 @@ int dfa_solver6_get_timing(dfa_solver6* s, dfa_solve6_timing* out, dfa_stream_t 
     REQUIRE(s && out, "null plan / out");
     HIP_TRY(hipStreamSynchronize(S(stream)));
     std::memset(out, 0, sizeof(*out));
-    for (size_t i = 0; i + 3 < s->ev_used; i += 4) {
+    const std::vector<hipEvent_t>& ev = s->ev.events;
+    for (size_t i = 0; i + 3 < s->ev.used; i += 4) {
         float a = 0.f, b = 0.f, c = 0.f;
-        HIP_TRY(hipEventElapsedTime(&a, s->events[i], s->events[i + 1]));
-        HIP_TRY(hipEventElapsedTime(&b, s->events[i + 1], s->events[i + 2]));
-        HIP_TRY(hipEventElapsedTime(&c, s->events[i + 2], s->events[i + 3]));
+        HIP_TRY(hipEventElapsedTime(&a, ev[i], ev[i + 1]));
+        HIP_TRY(hipEventElapsedTime(&b, ev[i + 1], ev[i + 2]));
+        HIP_TRY(hipEventElapsedTime(&c, ev[i + 2], ev[i + 3]));
         out->linearise_ms += a, out->assemble_ms += b, out->pcg_ms += c;
         out->gn_iterations += 1;
     }

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch_budget.hpp"  // S6_HIST, S6_MIRROR_SKIPPED
+
 namespace dfa {
 
 struct Solve6Params {
@@ -21,10 +23,8 @@ struct Solve6Params {
     float gn_tol;
 };
 
-constexpr int S6_HIST = 32;  // = DFA_SOLVE6_HIST of include/dynfu_amd.h
 constexpr int S6_ROW_BLOCKS = 48;  // 6x6 blocks per block row of the normal matrix (= DFA_SOLVE6_ROW_BLOCKS of include/dynfu_amd.h)
 constexpr int S6_LIN_SHARDS = 32;  // arrival counters of the linearisation (one word would serialise ~2 000 atomics at ~11 ns)
-constexpr int S6_MIRROR_SKIPPED = -(1 << 30);  // launch-budget mirror: the Gauss-Newton iteration ran no PCG (its outer iteration had ended)
 
 // Device-resident scalars of one solve
 struct Solve6State {

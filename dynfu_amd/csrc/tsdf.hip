@@ -16,11 +16,9 @@
 // Every kernel is HBM-bound integer/half work; nothing here is GEMM-shaped, no MFMA.
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-#include <map>
-
 #include "device_math.hpp"
 #include "dev_switch.hpp"
+#include "device_memory.hpp"
 #include "kernels.hpp"
 #include "raycast_device.hpp"
 #include "tsdf_classify.hpp"
@@ -473,32 +471,12 @@ hipError_t launch_tsdf_clear(uint32_t* vol, int X, int Y, int Z, hipStream_t s) 
     return launch_status();
 }
 
-// Scratch for the tile table of one sweep (19 KiB at VGA).  The C ABI's caller owns every buffer it passes and the
-// kernels allocate nothing it can see; this table is internal, so it is cached per stream: work on one stream is
-// ordered, so a sweep never overwrites the table of a sweep still running, whatever the host threads do.  Grows with
-// hipMalloc (hipFree of the old block waits for the device).
-static hipError_t tile_scratch(hipStream_t s, size_t bytes, uint32_t** out) {
-    struct Block {
-        uint32_t* p = nullptr;
-        size_t cap  = 0;
-    };
-    static std::mutex mu;
-    static std::map<std::pair<int, hipStream_t>, Block> cache;  // (device, stream): the null stream exists on every device
-    int dev = 0;
-    hipError_t de = hipGetDevice(&dev);
-    if (de != hipSuccess) return de;
-    std::lock_guard<std::mutex> lock(mu);
-    Block& b = cache[std::make_pair(dev, s)];
-    if (b.cap < bytes) {
-        if (b.p) (void)hipFree(b.p);
-        b.p = nullptr, b.cap = 0;
-        hipError_t e = hipMalloc((void**)&b.p, bytes);
-        if (e != hipSuccess) return e;
-        b.cap = bytes;
-    }
-    *out = b.p;
-    return hipSuccess;
-}
+// Scratch for the tile table of one sweep (19 KiB at VGA): internal, so kept per stream (device_memory.hpp).
+namespace {
+struct TileScratch {
+    DeviceBuffer<uint32_t> tiles;
+};
+}  // namespace
 
 // z-chunk heuristic: enough workgroups to fill 256 CUs several times over, while keeping the
 // replayed-additions prologue (z0 adds per chunk) a small fraction of a chunk's work.
@@ -542,9 +520,10 @@ hipError_t launch_tsdf_integrate(bool fused_clear, const uint16_t* dists, int di
     const bool legacy = dev_env("DFA_TSDF_LEGACY") != nullptr;
     if (!legacy) {
         const int tcols = (cols + 7) >> TSDF_TILE_SHIFT, trows = (rows + 7) >> TSDF_TILE_SHIFT;
-        uint32_t* tiles = nullptr;
-        hipError_t e    = tile_scratch(s, (size_t)tcols * trows * sizeof(uint32_t), &tiles);
+        DeviceBuffer<uint32_t>& table = stream_scratch<TileScratch>(s).tiles;
+        hipError_t e                  = table.reserve((size_t)tcols * trows);
         if (e != hipSuccess) return e;
+        uint32_t* tiles = table.data;
         dists_tiles_kernel<<<(tcols * trows + 3) / 4, 256, 0, s>>>(dists, dists_step, cols, rows, tiles, tcols, tcols * trows);
         // bound of |component| over every voxel position in camera space: the 8 corners of the volume
         float extent = 0.f;

@@ -34,6 +34,14 @@ def test_tsdf_run_classification_model_matches_oracle(exes):
     assert "6 tests, 0 failed" in out
 
 
+def test_launch_budget_decisions(exes):
+    """The adaptive launch budget of the north-star solve (csrc/launch_budget.hpp) against a model of the device and the
+    pinned mirror ring: cap, running maximum plus a quarter, cut / skipped / silent slots, reset, solves without a budget,
+    fold order with the host three solves ahead."""
+    out = _run(exes["test_launch_budget"])
+    assert "7 tests, 0 failed" in out
+
+
 def test_host_io_formats(exes):
     """PNG depth codec, PCD / VTK writers, sequence listing (dfa_host/io.hpp; reference: src/apps/demo.cpp)."""
     out = _run(exes["test_host_io"])
