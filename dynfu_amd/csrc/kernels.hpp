@@ -172,7 +172,7 @@ hipError_t launch_icp_sums(bool depth_variant, const void* curr, int curr_step, 
 
 
 // Several kernels publish partial results with write-through stores and then arrive at a ticket / raise a flag word, ordering
-// the two by `s_waitcnt vmcnt(0)` (solve.hip: linearise tail, team PCG; solve6.hip: linearise tail).  That is an ordering
+// the two by `s_waitcnt vmcnt(0)` (solve_linearise.hip: linearise tail; solve_pcg_team.hip; solve6.hip: linearise tail).  That is an ordering
 // on gfx9 parts only, where stores count in vmcnt; gfx10 and later track them in vscnt.  This library is built for gfx950.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__) && !defined(__gfx90a__)
 #error "dynfu_amd orders published stores with s_waitcnt vmcnt(0): gfx90a / gfx942 / gfx950 only"

@@ -1,5 +1,5 @@
 // knn_device.hpp — device side of the exact k-NN searches over the node grid, shared by the kernels of warp.hip and the
-// fused graph-build kernel of solve.hip: the sorted candidate list, the distance expression, the one-lane-per-query grid
+// fused graph-build kernel of solve_graph.hip: the sorted candidate list, the distance expression, the one-lane-per-query grid
 // search (knn_grid_query) and the one-wave-per-query search (knn_wave_search).  The grid itself is built in warp.hip.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // pcg_rules.hpp — what an iteration of the reference-mode block-Jacobi PCG IS, stated once: the preconditioner, the
 // stopping rules, the Chronopoulos-Gear scalars, the row owner's vector update and the booking of a finished launch.
-// The forms in solve.hip (register-resident, streaming, launched, team, guard) say only how they move the data and
+// The forms in solve_pcg.hip (register-resident, streaming), solve_pcg_launched.hip and solve_pcg_team.hip (team, guard) say only how they move the data and
 // call these; the library is built with -ffp-contract=off, so an expression inlined from here is the arithmetic it
 // spells (fmaf where it says fmaf, a product where it says a product).
 #pragma once

@@ -1,4 +1,42 @@
-// solve.hpp — device-side view of a solver plan and the launchers of solve.hip (internal).
+// solve.hpp — device-side view of a solver plan and the launchers of the reference-mode solve (internal): gfx950 kernels
+// of the warp-field solve: residual rows, Tukey / Huber re-weighting, assembly of the sparse normal equations,
+// block-Jacobi PCG, write-back.  One translation unit per stage:
+//   solve_graph.hip         rows, reset, node -> rows transposition        (once per problem)
+//   solve_linearise.hip     robust weights, residuals, cost, GN control; regradient
+//   solve_assemble.hip      normal equations: ELL rows, right-hand side, Jacobi diagonal
+//   solve_pcg.hip           PCG in one workgroup per coordinate (register-resident, streaming); route_pcg
+//   solve_pcg_launched.hip  PCG across many workgroups, one launch per iteration, HIP-graph cache
+//   solve_pcg_team.hip      PCG by three teams of persistent workgroups, guard launch
+// solve_rows.hpp states the row graph and the packed row record; solve_internal.hpp holds what several units share.
+//
+// Replaces what the reference runs through Opt (include/dynfu/utils/terra/energy.t, driven by
+// src/dynfu/utils/opt_solver.cpp) plus the CPU loops updateTukeyBiweights / updateHuberWeights.
+//
+// Formulation.  Unknown t_i in R^3 per node.  Every residual of
+// energy.t is a "row"  r = sqrt(tau) * (b - sum_j w_j t_{n_j})  with at most k node slots:
+//   data row v   (energy.t:50-55): slots = k-NN of the canonical vertex, w = RBF weights,
+//                                  b = live - canonical, tau = Tukey biweight;
+//   reg row (n,i)(energy.t:75-78): slots = {v_i: -1, n: +1}, b = 0, tau = w_reg^2
+//                                  (r = w_reg (t_{v_i} - t_n)); the self edge is empty.
+// J^T J has the block structure D x D with blocks s*I_3, so ONE scalar sparse matrix A
+// (D x D) serves the x, y and z systems:  A = sum_rows tau w w^T,  g = sum_rows tau w e,
+// e = b - sum w t.
+//
+// Launches of one problem (dfa_solver_set_problem): at the top of solve_graph.hip.
+//
+// MI355X mapping
+//   * Opt re-walks all N*k graph edges with global atomics in every PCG iteration; here A is
+//     assembled once per linearisation and the PCG iterates on ~20 D non-zeros that never
+//     leave the chip's caches.
+//   * assembly is a gather, not a scatter: a node -> rows transpose graph is built once per
+//     frame, then ONE WORKGROUP PER NODE reduces its ~128 k rows into an LDS hash keyed by column
+//     (LDS atomics stay on the CU; no global atomics on the matrix at all) and writes
+//     one ELL row + one rhs entry + the Jacobi diagonal.
+//   * the PCG is bound by synchronisation latency, not bandwidth, and comes in the forms that keep
+//     it cheap at each size: register-resident (one workgroup per coordinate, up to 2 048 nodes; streaming inside the
+//     same launch when a row pair does not fit), teams of persistent workgroups with their guard launch (up to
+//     19 584 nodes), one launch per iteration above that.  route_pcg chooses; what an iteration IS — preconditioner,
+//     stopping rules, Chronopoulos-Gear scalars, row update, booking — is stated once, in pcg_rules.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

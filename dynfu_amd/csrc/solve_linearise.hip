@@ -1,0 +1,278 @@
+// solve_linearise.hip — the linearisation of the reference-mode solve (formulation: solve.hpp): robust weights (Tukey for
+// the data rows; Huber for interface parity), residuals into the tails of the row records (solve_rows.hpp), the cost
+// and the Gauss-Newton control in ONE launch per Gauss-Newton iteration; and the regradient that replaces a linearisation
+// and an assembly while the robust weights are frozen.
+#include <hip/hip_runtime.h>
+
+#include "dq_device.hpp"
+#include "solve.hpp"
+#include "solve_internal.hpp"
+#include "solve_rows.hpp"
+
+namespace dfa {
+
+// ------------------------------------------------------------------------------------------
+// linearisation, one launch per Gauss-Newton iteration:
+//   [outer-iteration start only] robust weights: Tukey biweight of the current warp error for
+//       the data rows (opt_solver.cpp:204-231; warp(c) = calcDQB(c)(c) with node transforms
+//       DQ(t_i) * dg_se3_i, :270-285 + node.cpp:19-23), w_reg^2 for the regularisation rows (:30);
+//   residual  e_r = b_r - sum_j w_rj t_{n_rj}  -> tail (e, tau) of the row's packed record;
+//   cost      sum tau |e|^2: one partial per workgroup, the LAST workgroup to arrive (agent-scope
+//       release/acquire around a ticket counter) adds the partials in index order (deterministic)
+//       and runs the Gauss-Newton control logic — no separate control launch.
+
+template <int K>
+__device__ __forceinline__ float tukey_weight(const SolveView& s, size_t v, float tukey_offset, float psi_data) {
+    const f3 c = mk3(s.canon[3 * v], s.canon[3 * v + 1], s.canon[3 * v + 2]);
+    DQ sum     = dq_identity();
+    int n[K];
+    float w[K];
+    load_row_graph<K>(s, v, n, w);
+    // the neighbours' translations and transforms four at a time, by unconditional loads (an absent neighbour reads node 0
+    // and is skipped): loads inside the `if` were k dependent round trips
+#pragma unroll
+    for (int h = 0; h < K; h += 4) {
+        float tx[4], ty[4], tz[4];
+        DQ q[4];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            const int nn = n[h + jj] >= 0 ? n[h + jj] : 0;
+            tx[jj] = s.t[3 * nn], ty[jj] = s.t[3 * nn + 1], tz[jj] = s.t[3 * nn + 2];
+            q[jj]  = dq_load(s.node_dq + 8 * (size_t)nn);
+        }
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            if (n[h + jj] >= 0) {
+                const DQ cur = dq_mul(dq_from_translation(tx[jj], ty[jj], tz[jj]), q[jj]);
+                sum          = dq_mul(sum, dq_scale(cur, w[h + jj]));
+            }
+        }
+    }
+    const f3 warped = dq_transform(dq_normalize(sum), c);
+    const float ex = s.live[3 * v] - warped.x, ey = s.live[3 * v + 1] - warped.y, ez = s.live[3 * v + 2] - warped.z;
+    // calcTukeyBiweight (:204-212)
+    const float d = sqrtf(ex * ex + ey * ey + ez * ez) / tukey_offset;
+    if (d < psi_data) {
+        const double q = 1.0 - ((double)d * (double)d) / ((double)psi_data * (double)psi_data);
+        return (float)(q * q);
+    }
+    return 0.f;
+}
+
+// Huber weights (opt_solver.cpp:233-268): computed for interface parity, energy.t:70 never uses them
+__device__ __forceinline__ void huber_node(const SolveView& s, int i, float psi_reg) {
+    const DQ dq_i = dq_mul(dq_from_translation(s.t[3 * i], s.t[3 * i + 1], s.t[3 * i + 2]),
+                           dq_load(s.node_dq + 8 * (size_t)i));
+    float h = 0.f;
+    for (int j = 0; j < s.k; ++j) {
+        const int m = s.reg_idx[(size_t)i * s.k + j];
+        if (m < 0) break;
+        const f3 pm   = mk3(s.node_pos[3 * m], s.node_pos[3 * m + 1], s.node_pos[3 * m + 2]);
+        const DQ dq_m = dq_mul(dq_from_translation(s.t[3 * m], s.t[3 * m + 1], s.t[3 * m + 2]),
+                               dq_load(s.node_dq + 8 * (size_t)m));
+        const f3 pa = dq_transform(dq_i, pm), pb = dq_transform(dq_m, pm);
+        const float ex = pa.x - pb.x, ey = pa.y - pb.y, ez = pa.z - pb.z;
+        const float err = sqrtf(ex * ex + ey * ey + ez * ez);
+        h               = fabsf(err) <= psi_reg ? 1.f : psi_reg / fabsf(err);  // last neighbour wins (:263)
+    }
+    s.huber[i] = h;
+}
+__global__ __launch_bounds__(256) void huber_kernel(SolveView s, float psi_reg) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < s.D) huber_node(s, i, psi_reg);
+}
+
+struct LineariseArgs {
+    int update_weights;  // first linearisation of an outer iteration
+    int mode;            // 0 first of outer, 1 later GN iteration, 2 final cost only
+    float gn_tol, tukey_offset, psi_data, w_reg_sq;
+    long long* iters_total;  // mode 2, optional (device): += the solve's PCG iterations
+    float huber_psi;  // > 0: also evaluate the nodes' Huber weights at the current t (the last outer iteration's
+                      // preNonlinearSolve, opt_solver.cpp:135-140; a launch of its own before)
+};
+
+constexpr int LIN_SHARDS     = 32;    // ticket counters: one device-scope atomic costs ~11 ns when
+constexpr int LIN_MAX_BLOCKS = 1024;  // serialised on one word, so arrivals are sharded 2-level
+
+template <int K>
+__global__ __launch_bounds__(256) void linearise_kernel(SolveView s, SolveState* __restrict__ st,
+                                                        double* __restrict__ cost_partials,
+                                                        unsigned int* __restrict__ ticket /*[LIN_SHARDS+1]*/,
+                                                        LineariseArgs a) {
+    __shared__ double wsum[4];
+    __shared__ int is_last;
+    if (a.huber_psi > 0.f)
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < s.D; i += gridDim.x * blockDim.x) huber_node(s, i, a.huber_psi);
+    if (a.mode == 2) {
+        // the closing evaluation also composes the result: dg_se3_i <- DQ(0,0,0,t_i) * dg_se3_i (opt_solver.cpp:270-285,
+        // node.cpp:19-23) — t is final here; a launch of its own before
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < s.D; i += gridDim.x * blockDim.x) {
+            const DQ out = dq_mul(dq_from_translation(s.t[3 * i], s.t[3 * i + 1], s.t[3 * i + 2]),
+                                  dq_load(s.node_dq + 8 * (size_t)i));
+            dq_store(s.node_dq_out + 8 * (size_t)i, out);
+        }
+        if (blockIdx.x == 0 && threadIdx.x == 0 && a.iters_total) *a.iters_total += st->pcg_iters;
+    }
+    // after convergence t no longer changes: weights, residual records and cost of this linearisation exist already.
+    // That includes the solve's closing evaluation (mode 2) when an iteration ran: the flag is set by a PCG that found
+    // its gradient at the floor and left t where the linearisation before it had evaluated the cost.
+    if (st->converged == 1 || (st->converged && !a.update_weights)) {
+        if (a.mode != 2 || (st->have_initial && !st->cost_stale)) return;
+    }
+    const size_t R = (size_t)s.N + (size_t)s.D * s.k;
+    double c       = 0.0;
+    float amax     = 0.f;  // re-weighting linearisations: the largest addend tau w_a w_b any row brings to the normal matrix
+    for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r < R; r += (size_t)gridDim.x * blockDim.x) {
+        float tau;
+        if (a.update_weights) {
+            tau       = r < (size_t)s.N ? tukey_weight<K>(s, r, a.tukey_offset, a.psi_data) : a.w_reg_sq;
+            s.rtau[r] = tau;
+        } else {
+            tau = s.rtau[r];
+        }
+        float sx = 0.f, sy = 0.f, sz = 0.f;
+        {   // (ids and weights by 16-byte loads, then the k translations by unconditional loads — an absent neighbour reads
+            // node 0 and is skipped —: two rounds of loads; with the loads inside `if (n >= 0)` it was k dependent ones)
+            int n[K];
+            float w[K], tx[K], ty[K], tz[K];
+            load_row_graph<K>(s, r, n, w);
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const int nn = n[j] >= 0 ? n[j] : 0;
+                tx[j] = s.t[3 * nn], ty[j] = s.t[3 * nn + 1], tz[j] = s.t[3 * nn + 2];
+            }
+            float wm = 0.f;
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+                if (n[j] >= 0) sx += w[j] * tx[j], sy += w[j] * ty[j], sz += w[j] * tz[j], wm = fmaxf(wm, fabsf(w[j]));
+            amax = fmaxf(amax, tau * wm * wm);
+        }
+        const float ex = s.rb[3 * r] - sx, ey = s.rb[3 * r + 1] - sy, ez = s.rb[3 * r + 2] - sz;
+        // tail of the packed row record (head = k ids + k weights, written once per frame)
+        *(float4*)(s.re + r * (size_t)solve_rec_words(s.k) + solve_rec_tail(s.k)) = make_float4(ex, ey, ez, tau);
+        c += (double)tau * ((double)ex * ex + (double)ey * ey + (double)ez * ez);
+    }
+    c = wave_sum_all(c);
+    __shared__ float wmax[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c, wmax[threadIdx.x >> 6] = amax;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        // publish the partial write-through (sc1) — no release fence, which would write back the
+        // whole L2's dirty record tails — then arrive: shard counter first, top counter for the
+        // last arriver of each shard
+        __hip_atomic_store(&cost_partials[blockIdx.x], (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        if (a.update_weights)  // (the second half of the array: one maximum per workgroup)
+            __hip_atomic_store(&cost_partials[LIN_MAX_BLOCKS + blockIdx.x], (double)fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3])),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned int shard   = blockIdx.x % LIN_SHARDS;
+        const unsigned int members = (gridDim.x - shard + LIN_SHARDS - 1) / LIN_SHARDS;
+        const unsigned int nshards = min((unsigned int)LIN_SHARDS, gridDim.x);
+        int last                   = 0;
+        if (__hip_atomic_fetch_add(&ticket[shard], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == members - 1) {
+            __hip_atomic_store(&ticket[shard], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
+            if (__hip_atomic_fetch_add(&ticket[LIN_SHARDS], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
+                nshards - 1) {
+                __hip_atomic_store(&ticket[LIN_SHARDS], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                last = 1;
+            }
+        }
+        is_last = last;
+    }
+    __syncthreads();
+    if (!is_last) return;
+
+    // last workgroup: ordered sum of the partials + Gauss-Newton control
+    __shared__ double sm[256];
+    __shared__ double smx[256];
+    double acc = 0.0, mx = 0.0;
+    {
+        // these loads go past the L2 (~2 us each) and this is the one workgroup the launch — and the assembly behind it — waits
+        // for: all of a thread's partials in flight together (LIN_MAX_BLOCKS / 256 = 4 per array; a load-wait-add loop was four
+        // dependent round trips), clamped addresses, masked sums in the same order as before
+        constexpr int Q = LIN_MAX_BLOCKS / 256;
+        double cq[Q], mq[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const unsigned int i = min(threadIdx.x + 256u * q, gridDim.x - 1);
+            cq[q] = __hip_atomic_load(&cost_partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            mq[q] = a.update_weights ? __hip_atomic_load(&cost_partials[LIN_MAX_BLOCKS + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < Q; ++q)
+            if (threadIdx.x + 256u * q < gridDim.x) acc += cq[q], mx = fmax(mx, mq[q]);
+    }
+    sm[threadIdx.x] = acc, smx[threadIdx.x] = mx;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o], smx[threadIdx.x] = fmax(smx[threadIdx.x], smx[threadIdx.x + o]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double cost = sm[0];
+        if (a.update_weights) st->amax = (float)smx[0];
+        if (!st->have_initial) st->initial_cost = cost, st->have_initial = 1;
+        if (a.mode == 0) st->done = 0;
+        // Gauss-Newton early-out: relative cost decrease of the previous step below gn_tol
+        if (a.mode == 1 && !st->done && a.gn_tol > 0.f && (st->cost - cost) <= (double)a.gn_tol * st->cost)
+            st->done = 1;
+        st->cost       = cost;
+        st->final_cost = cost;
+        st->cost_stale = 0;
+        // robust weights evaluated at THIS t: a gradient at the floor now means the whole solve has converged (with
+        // stale weights it only ends the current outer iteration: the next one re-weights at the moved t)
+        if (a.mode != 2) st->weights_fresh = a.update_weights;
+        if (a.mode != 2 && a.update_weights && st->converged == 2) st->converged = 0;  // a new outer iteration
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// launchers
+
+int solve_residual_blocks(const SolveView& s) {
+    const size_t R  = (size_t)s.N + (size_t)s.D * s.k;
+    const size_t nb = (R + 255) / 256;
+    return (int)(nb < (size_t)LIN_MAX_BLOCKS ? nb : (size_t)LIN_MAX_BLOCKS);
+}
+
+hipError_t solve_linearise(const SolveView& s, SolveState* state, double* cost_partials, unsigned int* ticket,
+                           int update_weights, int mode, float gn_tol, float tukey_offset, float psi_data,
+                           float w_reg_sq, float huber_psi, long long* iters_total, hipStream_t st) {
+    const int nb = solve_residual_blocks(s);
+    LineariseArgs a{update_weights, mode, gn_tol, tukey_offset, psi_data, w_reg_sq, iters_total, huber_psi};
+    KDISPATCH(linearise_kernel, s.k, <<<nb, 256, 0, st>>>(s, state, cost_partials, ticket, a));
+    return hipGetLastError();
+}
+
+hipError_t solve_huber(const SolveView& s, float psi_reg, hipStream_t st) {
+    huber_kernel<<<(s.D + 255) / 256, 256, 0, st>>>(s, psi_reg);
+    return hipGetLastError();
+}
+
+// g = g_base - A (t - t_base): a thread per row over the slot-major ELL (entry q of row a at [q * D + a]: coalesced)
+__global__ __launch_bounds__(256) void regradient_kernel(SolveView s, SolveState* __restrict__ st) {
+    if (st->done || st->converged) return;
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a == 0) st->cost_stale = 1, st->weights_fresh = 0;  // (a floor hit now ends this outer iteration only)
+    if (a >= s.D) return;
+    const int cnt = s.ell_cnt[a];
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    for (int q = 0; q < cnt; ++q) {
+        const float2 e = s.ell[(size_t)q * s.D + a];
+        const int col  = __float_as_int(e.y);
+        sx = fmaf(e.x, s.t[3 * col] - s.t_base[3 * col], sx);
+        sy = fmaf(e.x, s.t[3 * col + 1] - s.t_base[3 * col + 1], sy);
+        sz = fmaf(e.x, s.t[3 * col + 2] - s.t_base[3 * col + 2], sz);
+    }
+    s.g[3 * a] = s.g_base[3 * a] - sx, s.g[3 * a + 1] = s.g_base[3 * a + 1] - sy, s.g[3 * a + 2] = s.g_base[3 * a + 2] - sz;
+}
+
+hipError_t solve_regradient(const SolveView& s, SolveState* state, hipStream_t st) {
+    regradient_kernel<<<(s.D + 255) / 256, 256, 0, st>>>(s, state);
+    return hipGetLastError();
+}
+
+}  // namespace dfa

@@ -18,7 +18,7 @@
 // Both use the same distance expression (nanoflann L2_Simple_Adaptor order of operations) so
 // the neighbour lists are bit-identical to the CPU oracle's.
 // The searches' device side (KnnList, knn_grid_query, knn_wave_search) is in knn_device.hpp: the solver plan's graph build
-// runs both of its searches inside one launch of its own (solve.hip: graph_rows_kernel); launch_knn serves everyone else
+// runs both of its searches inside one launch of its own (solve_graph.hip: graph_rows_kernel); launch_knn serves everyone else
 // (dfa_knn, the host adaptor, plans whose nodes are not in the grid).
 #include <hip/hip_runtime.h>
 

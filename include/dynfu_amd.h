@@ -497,7 +497,7 @@ int dfa_solver_set_problem(dfa_solver* s, const float* node_pos, const float* no
  * `stream`) between its launches, also between two invocations of the overlap callback. */
 /* Order-stable variant of the reference-parity solve: the same bits from the same inputs ("or
  * deterministic segmented reduction for bit-stable results").  Both paths sum a node's rows as 64-bit fixed-point integers
- * in LDS (exact, whatever the order of the adds: csrc/solve.hip, FixedScale) — the matrix ENTRIES are the same bits in
+ * in LDS (exact, whatever the order of the adds: csrc/solve_assemble.hip, FixedScale) — the matrix ENTRIES are the same bits in
  * every run.  What differs from run to run on the default path is their ORDER: the rows are compacted in hash order and
  * rows of equal length are placed by an atomic cursor, so the float sums of the PCG's products (and the gradient's wave
  * sums over an unsorted list) round differently in the last bit (measured in round 3, before the integer sums: up to 2e-5 m

@@ -229,7 +229,7 @@ typedef struct {
     float gn_tol;
     /* != 0: Gauss-Newton iterations >= 1 of an outer iteration keep the normal matrix and the preconditioner of
      * iteration 0 and re-linearise residuals and gradient only (the pattern of the reference-parity solve's inner
-     * iterations: dynfu_amd/csrc/solve.hip regradient) */
+     * iterations: dynfu_amd/csrc/solve_linearise.hip regradient) */
     int reuse_matrix;
 } orc6_params;
 

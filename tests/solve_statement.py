@@ -1,6 +1,6 @@
 """Independent float64 statement of ONE linearisation of the reference-parity solve: the normal matrix JᵀJ = A ⊗ I₃,
 the right-hand side g = -Jᵀr, every row's column set and a per-entry error budget, plus the statement's own solution of
-A x = g.  Written from the reference, not from dynfu_amd/csrc/solve.hip or oracle/solve_oracle_body.inc:
+A x = g.  Written from the reference, not from dynfu_amd/csrc/solve_*.hip or oracle/solve_oracle_body.inc:
 
 * data term (energy.t:50-55): per vertex v with k-NN nodes n_0..n_{k-1} of its canonical position,
   r_v = sqrt(tau_v) (live_v - canon_v - sum_i w_vi t_{n_i}), w_vi the RBF weight exp(-|canon_v - dg_v|^2 / (2 dg_w^2))

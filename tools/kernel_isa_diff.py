@@ -1,14 +1,20 @@
 #!/usr/bin/env python3
-"""Did a refactor of a .hip file change what the compiler makes of it?
+"""Did a refactor of .hip files change what the compiler makes of them?
 
-Compiles the same source file of two checkouts for gfx950 with the flags of dynfu_amd/build.py (product, and again
-with -DDFA_DEV_AB), and prints two markdown tables per build: the kernels' resources as the compiler reports them
+Compiles source files of two checkouts for gfx950 with the flags of dynfu_amd/build.py (product, and again with
+-DDFA_DEV_AB), and prints two markdown tables per build: the kernels' resources as the compiler reports them
 (-Rpass-analysis=kernel-resource-usage) and, per kernel, whether the gfx950 assembly (--save-temps) is identical
-once comments, debug lines and symbol names are stripped.  No GPU needed.  Exit status 1 if any resource differs
-or the sets of kernels differ (a differing ISA alone is reported, not failed).
+once comments, debug lines and symbol names are stripped.  No GPU needed.  Exit status 1 if any resource differs,
+the sets of kernels differ or a kernel appears twice on one side (a differing ISA alone is reported, not failed,
+unless --require-identical).
 
-    python tools/kernel_isa_diff.py PARENT_CHECKOUT BRANCH_CHECKOUT [--file solve.hip] [--drop-arg KERNEL:INDEX]
+    python tools/kernel_isa_diff.py PARENT_CHECKOUT BRANCH_CHECKOUT --file solve6.hip [--drop-arg KERNEL:INDEX]
+    python tools/kernel_isa_diff.py PARENT_CHECKOUT BRANCH_CHECKOUT --parent-files solve.hip \
+        --branch-files solve_graph.hip,solve_linearise.hip,... [--define NAME ...] [--require-identical]
 
+--file names one file, the same on both sides.  --parent-files / --branch-files name a comma-separated list per side
+(code that moved between files): each side's kernels are the union over its files.
+--define NAME adds -DNAME to every compilation (repeatable).
 --drop-arg pcg_paired_kernel:1 matches kernels of the two sides whose template argument lists differ by the one
 argument a change removed (index into the parent's list).
 """
@@ -18,6 +24,7 @@ import re
 import subprocess
 import sys
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from dynfu_amd.build import FLAGS, hipcc  # noqa: E402
@@ -68,7 +75,23 @@ def bodies(asm):
 
 def demangle(names):
     r = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True)
-    return dict(zip(names, (re.sub(r"^(void )?dfa::", "", re.sub(r"\(.*", "", d)) for d in r.stdout.splitlines())))
+    plain = (d.replace("(anonymous namespace)::", "") for d in r.stdout.splitlines())
+    return dict(zip(names, (re.sub(r"^(void )?dfa::", "", re.sub(r"\(.*", "", d)) for d in plain)))
+
+
+def compile_side(checkout, files, extra, out):
+    """the union of the files' kernels: demangled name -> (resources, body); and the names met more than once"""
+    with ThreadPoolExecutor(max_workers=4) as ex:
+        outs = list(ex.map(lambda f: compile_one(checkout, f, extra, os.path.join(out, f)), files))
+    kernels, twice = {}, []
+    for remarks, asm in outs:
+        res, isa = resources(remarks), bodies(asm)
+        names = demangle(list(res))
+        for n in res:
+            if names[n] in kernels:
+                twice.append(names[n])
+            kernels[names[n]] = (res[n], isa[n])
+    return kernels, twice
 
 
 def drop(name, rules):
@@ -85,32 +108,43 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("parent")
     ap.add_argument("branch")
-    ap.add_argument("--file", default="solve.hip")
+    ap.add_argument("--file", help="one file of csrc/, the same on both sides")
+    ap.add_argument("--parent-files", help="comma-separated; instead of --file for the parent")
+    ap.add_argument("--branch-files", help="comma-separated; instead of --file for the branch")
+    ap.add_argument("--define", action="append", default=[], metavar="NAME")
     ap.add_argument("--drop-arg", action="append", default=[])
+    ap.add_argument("--require-identical", action="store_true", help="a differing ISA fails too")
     a = ap.parse_args()
     rules = [(r.split(":")[0], int(r.split(":")[1])) for r in a.drop_arg]
+    if not (a.file or (a.parent_files and a.branch_files)):
+        ap.error("--file, or --parent-files and --branch-files")
+    pfiles = (a.parent_files or a.file).split(",")
+    bfiles = (a.branch_files or a.file).split(",")
+    what = pfiles[0] if pfiles == bfiles else "%s -> %s" % (", ".join(pfiles), ", ".join(bfiles))
+    defines = ["-D" + d for d in a.define]
     bad = False
     for label, extra in (("product", []), ("development (-DDFA_DEV_AB)", ["-DDFA_DEV_AB"])):
         with tempfile.TemporaryDirectory() as tmp:
-            rp, ap_ = compile_one(a.parent, a.file, extra, os.path.join(tmp, "p"))
-            rb, ab_ = compile_one(a.branch, a.file, extra, os.path.join(tmp, "b"))
-        resp, resb, isap, isab = resources(rp), resources(rb), bodies(ap_), bodies(ab_)
-        dp, db = demangle(list(resp)), demangle(list(resb))
-        keyp = {drop(dp[n], rules): n for n in resp}
-        keyb = {db[n]: n for n in resb}
-        print("\n### %s build of %s: %d kernels (parent), %d (branch)\n" % (label, a.file, len(keyp), len(keyb)))
-        for k in sorted(set(keyp) ^ set(keyb)):
-            print("* only in %s: `%s`" % ("parent" if k in keyp else "branch", k))
+            kp, twice_p = compile_side(a.parent, pfiles, defines + extra, os.path.join(tmp, "p"))
+            kb, twice_b = compile_side(a.branch, bfiles, defines + extra, os.path.join(tmp, "b"))
+        kp = {drop(k, rules): v for k, v in kp.items()}
+        print("\n### %s build%s of %s: %d kernels (parent), %d (branch)\n" % (label, "".join(" " + d for d in defines), what, len(kp), len(kb)))
+        for side, twice in (("parent", twice_p), ("branch", twice_b)):
+            for k in twice:
+                print("* twice in %s: `%s`" % (side, k))
+                bad = True
+        for k in sorted(set(kp) ^ set(kb)):
+            print("* only in %s: `%s`" % ("parent" if k in kp else "branch", k))
             bad = True
         print("| kernel (branch name) | " + " | ".join(FIELDS) + " | resources | ISA |")
         print("|---|" + "---|" * (len(FIELDS) + 2))
-        for k in sorted(set(keyp) & set(keyb)):
-            p, b = resp[keyp[k]], resb[keyb[k]]
+        for k in sorted(set(kp) & set(kb)):
+            (p, isap), (b, isab) = kp[k], kb[k]
             same = all(p[f] == b[f] for f in FIELDS)
             bad |= not same
             cells = [b[f] if p[f] == b[f] else "%s -> %s" % (p[f], b[f]) for f in FIELDS]
-            isa = "identical" if isap[keyp[k]] == isab[keyb[k]] else "differs"
-            print("| `%s` | %s | %s | %s |" % (k, " | ".join(cells), "same" if same else "DIFFER", isa))
+            bad |= a.require_identical and isap != isab
+            print("| `%s` | %s | %s | %s |" % (k, " | ".join(cells), "same" if same else "DIFFER", "identical" if isap == isab else "differs"))
     return 1 if bad else 0
 
 

@@ -1,7 +1,7 @@
 // LDS atomic throughput of one CU (one 256-thread workgroup per CU, 256 workgroups): cycles per wave instruction of
 // ds_add_f32 / ds_add_u32 / ds_add_u64 / ds_add_rtn_f32 / plain ds_write_b32 / ds_read + VALU add + ds_write (racy), for
 // NADDR distinct addresses per wave instruction (64 = conflict-free, 8 = eight lanes per address, 1 = all lanes on one
-// word) — what the reference-mode assembly's LDS hash (solve.hip: assemble_kernel) pays per column.
+// word) — what the reference-mode assembly's LDS hash (solve_assemble.hip: assemble_kernel) pays per column.
 //   hipcc --offload-arch=gfx950 -O3 tools/microbench_lds_atomic.hip -o /tmp/lds_atomic && /tmp/lds_atomic
 #include <hip/hip_runtime.h>
 #include <cstdio>

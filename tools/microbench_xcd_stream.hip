@@ -1,5 +1,5 @@
 // What would a ONE-XCD persistent form of the north-star PCG (s6_pcg_step_kernel) pay per iteration just to read its matrix?
-// The team PCG of reference mode (solve.hip: pcg_team_kernel) keeps the matrix in the registers of the 32 CUs that share an
+// The team PCG of reference mode (solve_pcg_team.hip: pcg_team_kernel) keeps the matrix in the registers of the 32 CUs that share an
 // L2.  The 6 x 6-block matrix of the north-star solve is 4.5 MB at C2, 18.7 MB at C3, 37 MB at C4 — more than 32 CUs' registers
 // (16 MiB) and more than the XCD's 4 MiB L2 from C3 on — so a one-XCD form re-reads it every iteration through ONE XCD's path to
 // the Infinity Cache.  This measures that: the workgroups that land on XCD 0 (XCC_ID census, 1024 threads each) stream a buffer
