@@ -413,7 +413,13 @@ int dfa_transform_points(const float* points, int n, const float aff[12], int wi
  * clouds index-aligned with the live one (the "corresponding canonical frame" handed to
  * CombinedSolver::initializeProblemInstance, dyn_fusion.cpp:206).  Replaces the per-frame
  * nanoflann KD-tree over the canonical cloud (:221-224) by a device-built uniform grid.
- * canon_normals / out_normals / out_vertices / out_index may each be NULL (skipped). */
+ * canon_normals / out_normals / out_vertices / out_index may each be NULL (skipped).
+ * The distance is the float32 ((dx dx + dy dy) + dz dz) of live - canonical, nothing fused.  Non-finite input: a NaN
+ * distance (a NaN coordinate on either side, or inf - inf) is never a neighbour; an infinite distance is one, and among
+ * equal distances — infinite ones included — the lower index wins.  out_index is -1 only where no canonical vertex has
+ * a distance that is not NaN (a live vertex with a NaN coordinate, or no usable canonical vertex at all); out_vertices
+ * and out_normals hold canonical vertex 0 and its normal there.  The answer does not depend on which of the search
+ * forms (exhaustive scan, node grid, point grid) the sizes select. */
 int dfa_correspond(const float* canon_vertices, const float* canon_normals, int n_canon, const float* live_vertices,
                    int n_live, float* out_vertices, float* out_normals, int32_t* out_index, dfa_stream_t stream);
 

@@ -8,6 +8,9 @@ node-query pairs on; the shapes here are the smallest that reach each branch of 
 dfa_dev_solver_graph_ptrs hands out the plan's graph arrays.  Every case is also compared with the product's own choice for
 its size (no grid: exhaustive searches, old sequence), which must give the same bits again.
 
+In every mode the data graph and the regularisation graph also equal warp_statement.knn, the numpy statement of the k-NN
+contract: the modes are not only equal to each other.
+
 Not readable through the C ABI and therefore compared through the development accessor: rw, rb, the record heads of re,
 node_ptr, node_list (as a set per node), t, the state block and the tickets."""
 import ctypes as C
@@ -17,6 +20,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+import warp_statement as W  # noqa: E402
 from dynfu_amd import synth  # noqa: E402
 from gpu_util import dev, host  # noqa: E402
 
@@ -102,6 +106,10 @@ def _run(A, monkeypatch, prob, k, mode, plan=None):
     s.set_deterministic(True)
     s.set_problem(*(dev(x) for x in prob))
     fused, graph = _graph_state(s, D, N, k)
+    # both graphs are the k-NN contract itself, whichever launch sequence built them (the modes are otherwise compared
+    # with each other only)
+    assert np.array_equal(host(s.data_graph()), W.knn(nodes, canon, k)), mode
+    assert np.array_equal(host(s.reg_graph()), W.knn(nodes, nodes, k)), mode
     res = _solved(A, s)
     if plan is None:
         s.close()

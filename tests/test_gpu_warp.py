@@ -70,11 +70,26 @@ def test_knn_on_two_streams_from_one_thread(A):
         assert np.array_equal(host(out[i]), sets[i][3])
 
 
-@pytest.mark.parametrize("kind", ["clustered", "planar", "far_queries", "duplicates", "line", "lattice"])
+@pytest.mark.parametrize("kind", ["clustered", "planar", "far_queries", "duplicates", "line", "lattice", "hand_placed"])
 @pytest.mark.parametrize("k", [4, 8])
 def test_knn_grid_path_is_exact_on_awkward_geometry(A, kind, k):
     # sizes above the grid threshold (D * n >= 2^22); the uniform grid must return exactly the
     # exhaustive (distance, index)-ordered answer whatever the node distribution
+    if kind == "hand_placed":
+        # the 32 x 32 x 4 node grid of tests/correspond_cases.py with the queries next to walls, edges and corners of their
+        # cells, exactly on walls, and outside the grid — against the numpy statement.  Once as they are (few queries: one
+        # wave per query) and once repeated beyond 32 768 (one lane per query: knn_grid_query<K>, which shares cell_of,
+        # scan_block3 and the shell stop rule with the 1-NN search of dfa_correspond).
+        import correspond_cases as Cc
+        import warp_statement as W
+        c = Cc.grid_case("node_3d")
+        q = c["queries"][np.isin(c["cls"], ("2", "4", "8"))]
+        want = W.knn(c["canon"], q, k)
+        dn, dw = dev(c["canon"]), dev(np.full(len(c["canon"]), 0.3, np.float32))
+        assert np.array_equal(host(A.knn(dn, dw, dev(q), k)[0]), want)
+        rep = np.resize(np.arange(len(q)), 32768 + 64 + 1)
+        assert np.array_equal(host(A.knn(dn, dw, dev(q[rep]), k)[0]), want[rep])
+        return
     rng = np.random.default_rng(hash(kind) % 1000 + k)
     D, n = 1500, 6000
     q = rng.uniform(-1, 1, (n, 3)).astype(np.float32)
