@@ -12,7 +12,7 @@ SYMBOLS = [
     "dfa_tsdf_clear_integrate", "dfa_tsdf_raycast_points", "dfa_tsdf_raycast_depth", "dfa_tsdf_raycast_tally", "dfa_tsdf_raycast_render", "dfa_render_image_points", "dfa_render_image_depth", "dfa_render_tangent_colors", "dfa_mesh_rasterize", "dfa_tsdf_vertex_normals", "dfa_tsdf_extract_cloud", "dfa_tsdf_extract_cloud_occ", "dfa_tsdf_extract_normals", "dfa_correspond_projective", "dfa_knn", "dfa_warp_to_live",
     "dfa_calc_dqb", "dfa_unsupported_vertices", "dfa_icp_sums", "dfa_repack_points", "dfa_compact_points", "dfa_transform_points", "dfa_warp_to_live_graph",
     "dfa_correspond", "dfa_marching_cubes", "dfa_mc_default_tables",
-    "dfa_tsdf_occupancy_bytes", "dfa_tsdf_clear_occ", "dfa_tsdf_integrate_occ", "dfa_tsdf_clear_integrate_occ", "dfa_tsdf_clear_integrate_known_occ", "dfa_marching_cubes_occ", "dfa_marching_cubes_indexed",
+    "dfa_tsdf_occupancy_bytes", "dfa_tsdf_clear_occ", "dfa_tsdf_integrate_occ", "dfa_tsdf_clear_integrate_occ", "dfa_tsdf_clear_integrate_known_occ", "dfa_tsdf_integrate_warped", "dfa_marching_cubes_occ", "dfa_marching_cubes_indexed",
     "dfa_depth_bilateral_filter", "dfa_depth_truncate", "dfa_depth_build_pyramid", "dfa_compute_normals_mask_depth",
     "dfa_resize_depth_normals", "dfa_resize_points_normals",
     "dfa_compute_points_normals", "dfa_solver6_create", "dfa_solver6_destroy", "dfa_solver6_set_problem",
@@ -157,6 +157,7 @@ def load(path=None):
     L.dfa_tsdf_integrate.argtypes = integ
     L.dfa_tsdf_clear_integrate.argtypes = integ
     L.dfa_tsdf_integrate_occ.argtypes = integ[:-1] + [vp, vp]
+    L.dfa_tsdf_integrate_warped.argtypes = integ[:8] + [vp] + integ[8:-1] + [vp, vp, vp, i, i, i, vp]
     L.dfa_tsdf_clear_integrate_occ.argtypes = integ[:-1] + [vp, vp]
     L.dfa_tsdf_clear_integrate_known_occ.argtypes = integ[:-1] + [vp, vp]
     L.dfa_tsdf_clear_occ.argtypes = [vp, i, i, i, vp, vp]
@@ -337,6 +338,28 @@ def tsdf_integrate(vol, dists, voxel_size, trunc, max_weight, vol2cam, fx, fy, c
     L = load()
     _integrate(L.dfa_tsdf_integrate if occupancy is None else L.dfa_tsdf_integrate_occ, vol, dists, voxel_size, trunc, max_weight,
                vol2cam, fx, fy, cx, cy, occupancy)
+
+
+WARPED_MODES = {"skip": 0, "rigid": 1}  # DFA_WARPED_SKIP, DFA_WARPED_RIGID
+
+
+def tsdf_integrate_warped(vol, dists, voxel_size, trunc, max_weight, vol2cam, fx, fy, cx, cy, node_pos, node_dq, node_w, k,
+                          unsupported="skip", occupancy=None):
+    """dfa_tsdf_integrate_warped: tsdf_integrate with every voxel taken through the warp field first (nodes in the volume's
+    metric frame: node_pos (D, 3), node_dq (D, 8), node_w (D,), all three None for no nodes).  A voxel no node supports is left
+    alone (unsupported="skip") or integrated where it stands ("rigid")."""
+    torch = _torch()
+    if unsupported not in WARPED_MODES:
+        raise DynfuAmdError("unsupported must be 'skip' or 'rigid', got %r" % (unsupported,))
+    X, Y, Z = _vol_dims(vol)
+    rows, cols = dists.shape
+    D = 0 if node_pos is None else int(node_pos.shape[0])
+    f32 = torch.float32
+    _check(load().dfa_tsdf_integrate_warped(_dev(dists, torch.uint16, "dists"), dists.stride(0) * 2, cols, rows, _dev(vol), X, Y, Z,
+                                            _dev(occupancy, torch.uint8, "occupancy"), _farr(voxel_size, 3), trunc, max_weight,
+                                            _aff12(vol2cam), fx, fy, cx, cy, _dev(node_pos, f32, "node_pos") if D else None,
+                                            _dev(node_dq, f32, "node_dq") if D else None, _dev(node_w, f32, "node_w") if D else None,
+                                            D, k, WARPED_MODES[unsupported], _stream()))
 
 
 def tsdf_clear_integrate(vol, dists, voxel_size, trunc, max_weight, vol2cam, fx, fy, cx, cy, occupancy=None, occupancy_known=False):

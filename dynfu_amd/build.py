@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libdynfu_amd.so")
-SOURCES = ["tsdf.hip", "warp.hip", "solve_graph.hip", "solve_linearise.hip", "solve_assemble.hip", "solve_pcg.hip",
+SOURCES = ["tsdf.hip", "tsdf_warped.hip", "warp.hip", "solve_graph.hip", "solve_linearise.hip", "solve_assemble.hip", "solve_pcg.hip",
            "solve_pcg_launched.hip", "solve_pcg_team.hip", "solve6.hip", "mc.hip", "extract.hip", "img.hip", "render.hip", "raster.hip", "icp.hip", "points.hip", "capi.cpp"]
 ARCH = "gfx950"
 EXTRA = os.environ.get("DFA_EXTRA_CXXFLAGS", "").split()
@@ -140,7 +140,8 @@ def build_cpp_tests(force=False, verbose=False):
     for name, needs in (("test_host_dq", []), ("test_host_solver", ["host"]), ("test_host_tsdf", ["host", "oracle"]),
                         ("test_host_dynfusion", ["host", "oracle"]), ("test_host_icp", ["host"]),
                         ("test_tsdf_classify", ["oracle", "ieee"]), ("test_launch_budget", []), ("test_host_io", ["host"]), ("test_host_kinfu", ["host"]),
-                        ("test_host_extract", ["host"]), ("test_host_render", ["host"]), ("test_host_mc_indexed", ["host"]), ("test_host_mesh_view", ["host"])):
+                        ("test_host_extract", ["host"]), ("test_host_render", ["host"]), ("test_host_mc_indexed", ["host"]), ("test_host_mesh_view", ["host"]),
+                        ("test_host_tsdf_warped", ["host"])):
         src = os.path.join(tdir, name + ".cpp")
         exe = os.path.join(out, name)
         if not os.path.exists(src):  # a tests/ tree from before this program was added: the rest still builds

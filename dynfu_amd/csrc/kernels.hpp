@@ -78,6 +78,15 @@ hipError_t launch_warp_to_live(const float* node_pos, const float* node_dq, cons
                                const float* verts, const float* normals, int N, float* out_verts, float* out_normals,
                                const KnnGridView* grid, hipStream_t s);
 
+// tsdf_warped.hip — a depth frame integrated through the warp field (dfa_tsdf_integrate_warped).  bricks: warped_brick_count
+// bytes and wmax: one float, both device scratch of the call; grid: the node grid (knn_grid_build) or null = scan all nodes
+size_t warped_brick_count(int X, int Y, int Z);
+hipError_t launch_tsdf_integrate_warped(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol, int X, int Y,
+                                        int Z, uint8_t* occ, const float voxel_size[3], float trunc_dist, int max_weight,
+                                        const float vol2cam[12], float fx, float fy, float cx, float cy, const float* node_pos,
+                                        const float* node_dq, const float* node_w, int D, int k, bool rigid,
+                                        const KnnGridView* grid, uint8_t* bricks, float* wmax, hipStream_t s);
+
 hipError_t launch_correspond_projective(const float* verts, const float* normals, int n, const float* vmap, int vmap_step,
                                         const float* nmap, int nmap_step, int cols, int rows, float fx, float fy, float cx,
                                         float cy, float dist_thres, float min_cosine, float* out_v, float* out_n,

@@ -1,0 +1,205 @@
+// tsdf_warped.hip — non-rigid TSDF fusion on gfx950: one depth frame integrated into the canonical volume THROUGH the warp
+// field (DynamicFusion's "dense non-rigid surface fusion"; the reference lists the step and never does it,
+// src/dynfu/dyn_fusion.cpp:39-47, :107-116).
+//
+// Per voxel: v = (x, y, z) * voxel_size; its k nearest nodes (knn_device.hpp, dfa_knn's contract); the support rule of
+// Warpfield::getUnsupportedVertices (support_min); a supported voxel moves to p = dq_transform(calcDQB(v), v) — the
+// reference-mode blend of Warpfield::warpToLive (calc_dqb) —, an unsupported one is left alone (DFA_WARPED_SKIP) or stays at
+// p = v (DFA_WARPED_RIGID); from vc = R p + t on, the reference's integrate (tsdf_integrate_device.hpp: voxel_tsdf,
+// voxel_update<false>), unchanged.
+//
+// Layout.  A search per voxel is the cost of this first form, so the voxels that cannot be supported never search:
+//   * a BRICK is the footprint of one workgroup of the sweep, 64 x 4 x 1 voxels (two occupancy boxes wide, two high:
+//     kernels.hpp OccDims).  A pre-pass (one wave per node) marks every brick whose box lies within w_max — the
+//     largest node radius — of the node, by byte stores of 1.  No node within w_max of a voxel means every quotient
+//     |v - g| / w >= |v - g| / w_max >= 1: the marked bricks are a superset of the bricks with a supported voxel;
+//   * an unmarked brick does no search: it returns at once in SKIP mode (no memory touched) and takes p = v in RIGID mode;
+//   * a marked brick: one lane per voxel, a wave along x (its loads and stores are 256-byte row segments; the load is
+//     issued before the search), then the search, the rule, the blend and the update.  A voxel is stored only when the
+//     update changed it.
+// Node radii are positive (a radius <= 0 has no meaning in the support rule).  No fused contraction beyond the fmaf()s of
+// the shared headers, no fast-math; vector stores only.
+#include <hip/hip_runtime.h>
+
+#include "device_math.hpp"
+#include "dq_device.hpp"
+#include "kernels.hpp"
+#include "knn_device.hpp"
+#include "tsdf_integrate_device.hpp"
+
+namespace dfa {
+
+// A brick, in voxels.  One slice deep: a lane's voxels are searched one after the other, and the searches of a brick far from
+// the nodes are long (shells beyond the 3 x 3 x 3 block), so deeper bricks are fewer, longer workgroups with a long tail —
+// measured at 512^3, 2 048 nodes, k = 8 (tools/warped_integrate_timing.py, SKIP mode): 8 slices 9.39 ms, 4: 7.80, 2: 6.98,
+// 1: 4.47.  The code below holds for any depth that divides the occupancy box's 8.
+constexpr int WBX = 64, WBY = 4, WBZ = 1;
+
+size_t warped_brick_count(int X, int Y, int Z) {
+    return (size_t)((X + WBX - 1) / WBX) * (size_t)((Y + WBY - 1) / WBY) * (size_t)((Z + WBZ - 1) / WBZ);
+}
+
+// ------------------------------------------------------------------------------------------ support pre-pass
+// the largest node radius (NaN radii are ignored: fmaxf)
+__global__ __launch_bounds__(1024) void node_wmax_kernel(const float* __restrict__ node_w, int D, float* __restrict__ wmax) {
+    __shared__ float part[16];
+    float m = 0.f;
+    for (int i = threadIdx.x; i < D; i += blockDim.x) m = fmaxf(m, node_w[i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 16; ++w) m = fmaxf(m, part[w]);
+        *wmax = m;
+    }
+}
+
+// One wave per node: the bricks whose box of voxel POSITIONS comes within w_max of the node.  Conservative: the radius
+// is widened by 1e-3 relative and a millionth of the largest coordinate in play (the positions, differences and roots of
+// the support rule are rounded at 1e-7 relative), the candidate range by a voxel either side.
+__global__ __launch_bounds__(64) void mark_bricks_kernel(const float* __restrict__ node_pos, int D,
+                                                         const float* __restrict__ wmax, int X, int Y, int Z, float vsx,
+                                                         float vsy, float vsz, uint8_t* __restrict__ bricks) {
+    const int node = blockIdx.x;
+    if (node >= D) return;
+    const float g[3] = {node_pos[3 * (size_t)node], node_pos[3 * (size_t)node + 1], node_pos[3 * (size_t)node + 2]};
+    const float vs[3] = {vsx, vsy, vsz};
+    const int dim[3]  = {X, Y, Z};
+    const int bs[3]   = {WBX, WBY, WBZ};
+    const float ext   = fmaxf(fmaxf(fabsf(vsx) * (float)X, fabsf(vsy) * (float)Y), fabsf(vsz) * (float)Z);
+    const float r = *wmax * 1.001f + 1e-6f * fmaxf(ext, fmaxf(fmaxf(fabsf(g[0]), fabsf(g[1])), fabsf(g[2])));
+    int b0[3], nb[3];
+    for (int c = 0; c < 3; ++c) {
+        // voxel indices whose position can lie in [g - r, g + r]; the clamps also make the conversions safe (a NaN or an
+        // infinite radius ends as the whole axis)
+        const float inv = 1.f / fabsf(vs[c]);
+        float lo = (g[c] - r) * inv - 1.f, hi = (g[c] + r) * inv + 1.f;
+        if (vs[c] < 0.f) {
+            const float t = -lo;
+            lo = -hi, hi = t;
+        }
+        if (!(lo >= 0.f)) lo = 0.f;
+        if (!(hi <= (float)(dim[c] - 1))) hi = (float)(dim[c] - 1);
+        if (lo > hi) return;  // (uniform) the node is farther than w_max from the volume along this axis
+        b0[c] = (int)lo / bs[c];
+        nb[c] = (int)hi / bs[c] - b0[c] + 1;
+    }
+    const int nbx = (X + WBX - 1) / WBX, nby = (Y + WBY - 1) / WBY;
+    const long total = (long)nb[0] * nb[1] * nb[2];
+    for (long i = threadIdx.x; i < total; i += 64) {
+        const int b[3] = {b0[0] + (int)(i % nb[0]), b0[1] + (int)((i / nb[0]) % nb[1]), b0[2] + (int)(i / ((long)nb[0] * nb[1]))};
+        float d2 = 0.f;
+        for (int c = 0; c < 3; ++c) {
+            // the brick's first and last voxel position on this axis
+            const float pa = (float)(b[c] * bs[c]) * vs[c], pb = (float)min(b[c] * bs[c] + bs[c] - 1, dim[c] - 1) * vs[c];
+            const float d  = fmaxf(fmaxf(fminf(pa, pb) - g[c], g[c] - fmaxf(pa, pb)), 0.f);
+            d2 += d * d;
+        }
+        if (!(d2 > r * r)) bricks[((size_t)b[2] * nby + b[1]) * nbx + b[0]] = 1;  // (racing stores of the same byte)
+    }
+}
+
+// ------------------------------------------------------------------------------------------ the sweep
+// block = (64, 4): a wave spans 64 voxels in x, the block 4 rows in y, a lane WBZ voxels in z — one brick per workgroup.
+// GRID: the neighbours come from the node grid (knn_grid_query); otherwise (few nodes) from a scan of all of them.
+template <int K, bool GRID>
+__global__ __launch_bounds__(256) void integrate_warped_kernel(const IntegrateArgs a, const float* __restrict__ node_pos,
+                                                               const float* __restrict__ node_dq,
+                                                               const float* __restrict__ node_w, int D, int k, int rigid,
+                                                               const uint8_t* __restrict__ bricks, KnnGridView grid) {
+    // (uniform) a brick no node marked holds no supported voxel
+    const bool marked = bricks[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] != 0;
+    if (!marked && !rigid) return;
+    const int x = blockIdx.x * WBX + threadIdx.x;
+    const int y = blockIdx.y * WBY + threadIdx.y;
+    if (x >= a.X || y >= a.Y) return;
+    const int z0 = blockIdx.z * WBZ;
+    const int nz = min(WBZ, a.Z - z0);
+
+    const size_t slice = (size_t)a.X * a.Y;
+    uint32_t* ptr      = a.vol + (size_t)x + (size_t)a.X * y + slice * z0;
+    uint32_t cur[WBZ];
+#pragma unroll
+    for (int u = 0; u < WBZ; ++u) cur[u] = u < nz ? ptr[slice * u] : 0u;
+
+    KnnGridDesc g{};
+    if (GRID && marked) g = *grid.desc;
+    const f3 t = mk3(a.vol2cam.t[0], a.vol2cam.t[1], a.vol2cam.t[2]);
+    bool any   = false;  // an update happened: the voxel may hold a weight now
+    for (int u = 0; u < nz; ++u) {
+        const f3 v = mk3((float)x * a.vsx, (float)y * a.vsy, (float)(z0 + u) * a.vsz);  // the voxel's corner (tsdf_volume.cu:60), by multiplication
+        f3 p       = v;
+        bool go    = rigid != 0;
+        if (marked) {
+            KnnList<K> best;
+            if (GRID) {
+                knn_grid_query<K>(g, grid.cell_start, grid.sorted, v, best);
+            } else {
+                best.init();
+                for (int j = 0; j < D; ++j) best.push(dist2(v, node_pos[3 * j], node_pos[3 * j + 1], node_pos[3 * j + 2]), j);
+            }
+            if (support_min<K>(best, k, node_pos, node_w, v) < 1.f) {  // Warpfield::getUnsupportedVertices' rule
+                p  = dq_transform(calc_dqb<K>(best, k, node_pos, node_dq, node_w, v), v);  // Warpfield::warpToLive, vertex only
+                go = true;
+            }
+        }
+        if (!go) continue;
+        const f3 vc = mulR(a.vol2cam, p) + t;
+        float tsdf;
+        if (!voxel_tsdf(a, vc, tsdf)) continue;
+        const uint32_t upd = voxel_update<false>(a, cur[u], tsdf);
+        if (upd != cur[u]) ptr[slice * u] = upd;
+        any = true;
+    }
+    if (a.occ) {
+        // the two occupancy boxes a wave's row crosses (32 voxels each): lanes 0 and 32 write theirs when a lane of that half
+        // updated a voxel.  Both bits: the update may have left a negative distance.  Rows y and y + 1 share a byte and store
+        // the same value.
+        const unsigned long long m = __ballot(any);
+        if ((threadIdx.x & 31) == 0 && ((m >> threadIdx.x) & 0xffffffffull) != 0ull)
+            a.occ[(size_t)(x / 32) + (size_t)a.ox * ((size_t)(y / 2) + (size_t)a.oy * (size_t)(z0 / 8))] = 3;
+    }
+}
+
+// ------------------------------------------------------------------------------------------ launcher
+hipError_t launch_tsdf_integrate_warped(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol, int X, int Y,
+                                        int Z, uint8_t* occ, const float voxel_size[3], float trunc_dist, int max_weight,
+                                        const float vol2cam[12], float fx, float fy, float cx, float cy, const float* node_pos,
+                                        const float* node_dq, const float* node_w, int D, int k, bool rigid,
+                                        const KnnGridView* grid, uint8_t* bricks, float* wmax, hipStream_t s) {
+    IntegrateArgs a;
+    a.dists = dists, a.dists_step = dists_step, a.cols = cols, a.rows = rows;
+    a.vol = vol, a.X = X, a.Y = Y, a.Z = Z;
+    const OccDims od = occ_dims(X, Y, Z);
+    a.occ = occ, a.ox = od.ox, a.oy = od.oy, a.occ_known = 0;
+    a.vsx = voxel_size[0], a.vsy = voxel_size[1], a.vsz = voxel_size[2];
+    a.trunc      = trunc_dist;
+    a.trunc_inv  = 1.f / trunc_dist;  // tsdf_volume.cu:106
+    a.max_weight = max_weight;
+    for (int i = 0; i < 9; ++i) a.vol2cam.m[i] = vol2cam[i];
+    for (int i = 0; i < 3; ++i) a.vol2cam.t[i] = vol2cam[9 + i];
+    a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy;
+    a.zchunk = WBZ;
+
+    hipError_t e = hipMemsetAsync(bricks, 0, warped_brick_count(X, Y, Z), s);
+    if (e != hipSuccess) return e;
+    if (D > 0) {
+        node_wmax_kernel<<<1, 1024, 0, s>>>(node_w, D, wmax);
+        mark_bricks_kernel<<<D, 64, 0, s>>>(node_pos, D, wmax, X, Y, Z, a.vsx, a.vsy, a.vsz, bricks);
+    }
+    dim3 block(WBX, WBY), g3((X + WBX - 1) / WBX, (Y + WBY - 1) / WBY, (Z + WBZ - 1) / WBZ);
+    const KnnGridView gv = grid ? *grid : KnnGridView{};
+#define WARPED(KK)                                                                                                                   \
+    do {                                                                                                                             \
+        if (grid) integrate_warped_kernel<KK, true><<<g3, block, 0, s>>>(a, node_pos, node_dq, node_w, D, k, rigid ? 1 : 0, bricks, gv);  \
+        else integrate_warped_kernel<KK, false><<<g3, block, 0, s>>>(a, node_pos, node_dq, node_w, D, k, rigid ? 1 : 0, bricks, gv);      \
+    } while (0)
+    if (k <= 4) WARPED(4);
+    else if (k <= 8) WARPED(8);
+    else WARPED(16);
+#undef WARPED
+    return hipGetLastError();
+}
+
+}  // namespace dfa

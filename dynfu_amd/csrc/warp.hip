@@ -491,34 +491,8 @@ __global__ __launch_bounds__(256) void knn_kernel(const float* __restrict__ node
         }
 }
 
-// Warpfield::calcDQB (warp_field.cpp:127-148) given the neighbour list
-template <int K>
-__device__ __forceinline__ DQ calc_dqb(const KnnList<K>& nb, int k, const float* __restrict__ node_pos,
-                                       const float* __restrict__ node_dq, const float* __restrict__ node_w, f3 p) {
-    DQ sum = dq_identity();  // :133
-    // the neighbours' positions, radii and transforms four at a time by unconditional loads (an absent neighbour reads node 0
-    // and is skipped): with the loads inside the `if` they were k dependent round trips.  Same products in the same order.
-    constexpr int G = K < 4 ? K : 4;
-#pragma unroll
-    for (int h = 0; h < K; h += G) {
-        f3 g[G];
-        float r[G];
-        DQ q[G];
-        bool on[G];
-#pragma unroll
-        for (int jj = 0; jj < G; ++jj) {
-            const int j = h + jj;
-            on[jj]      = j < k && nb.index(j) >= 0;
-            const int n = on[jj] ? nb.index(j) : 0;
-            g[jj] = mk3(node_pos[3 * n], node_pos[3 * n + 1], node_pos[3 * n + 2]), r[jj] = node_w[n];
-            q[jj] = dq_load(node_dq + 8 * (size_t)n);
-        }
-#pragma unroll
-        for (int jj = 0; jj < G; ++jj)
-            if (on[jj]) sum = dq_mul(sum, dq_scale(q[jj], transformation_weight(g[jj], r[jj], p)));  // :139-141
-    }
-    return dq_normalize(sum);  // :145
-}
+// (Warpfield::calcDQB given the neighbour list, calc_dqb, and the support quotient of a node, support_quotient: knn_device.hpp —
+// the warped TSDF sweep of tsdf_warped.hip blends and decides with the same functions)
 
 // Warpfield::warpToLive (warp_field.cpp:150-171)
 template <int K, bool GRID>
@@ -640,12 +614,7 @@ __global__ __launch_bounds__(256) void dqb_support_kernel(const float* __restric
     const bool active = v < n;
     f3 p              = mk3(0.f, 0.f, 0.f);
     if (active) p = mk3(pts[3 * (size_t)v], pts[3 * (size_t)v + 1], pts[3 * (size_t)v + 2]);
-    // the support quotient of one node (:45-46 — pow(float, int) is double arithmetic, the root is rounded to float on assignment)
-    auto quotient = [&](int m) __attribute__((always_inline)) {
-        const double dx = (double)(p.x - node_pos[3 * m]), dy = (double)(p.y - node_pos[3 * m + 1]),
-                     dz = (double)(p.z - node_pos[3 * m + 2]);
-        return (float)sqrt(dx * dx + dy * dy + dz * dz) / node_w[m];
-    };
+    auto quotient = [&](int m) __attribute__((always_inline)) { return support_quotient(p, node_pos, node_w, m); };
     KnnList<K> best;
     if (GRID) {
         if (!active) return;

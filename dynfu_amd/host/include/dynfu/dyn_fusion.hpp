@@ -54,6 +54,14 @@ struct DynFuParams {  // dyn_fusion.hpp:25-42
     // a transform is not the identity, and the model has to move as getCanonicalWarpedToLive() does.
     bool model_view = false;
     float model_view_z_near = 0.05f;  // metres: triangles with a vertex nearer to the camera are not drawn
+    // Extension — dense non-rigid surface fusion (step 4 of the reference's pipeline, dyn_fusion.cpp:39-47, which it never
+    // does); reference mode only.  Frame 0 copies the integrated volume into a second TsdfVolume, the CANONICAL volume
+    // (DynFusion::canonicalVolume()); every later frame, once the warp field is solved and before it grows, integrates that
+    // frame's depth into it through the warp field (TsdfVolume::integrateWarped, voxels no node supports left alone).  The
+    // per-frame live volume, the live cloud, the solve and the node insertion are untouched — the canonical cloud stays
+    // frame 0's —: off, nothing of this runs, and on or off every other output of a frame is the same, bit for bit.  With
+    // north_star the constructor throws dfa::Error: that mode has another blend and keeps its nodes in the camera frame.
+    bool fuse_canonical = false;
 };
 
 struct dfa_solver6;  // include/dynfu_amd.h
@@ -128,6 +136,8 @@ public:
     int nodeStep = 128;
 
     std::shared_ptr<Warpfield> getWarpfield() { return warpfield; }
+    // fuse_canonical: the canonical volume (null before frame 0, or with the switch off)
+    std::shared_ptr<kfusion::cuda::TsdfVolume> canonicalVolume() { return canonical_volume_; }
 
 private:
     DynFuParams dynfuParams;
@@ -147,6 +157,7 @@ private:
     // vertices of the volume's zero level set as a point cloud (dyn_fusion.cpp:73-88 / :119-134), device-resident
     std::shared_ptr<dynfu::Frame> extractSurface(int frame_id, bool with_normals);
     bool northStarFrame(const kfusion::cuda::Depth& depth);  // operator() in north-star mode
+    std::shared_ptr<kfusion::cuda::TsdfVolume> canonical_volume_;  // fuse_canonical
     kfusion::cuda::Cloud live_points_;
     kfusion::cuda::Normals live_normals_;
     // model_view: the canonical mesh (frame 0) as a frame for Warpfield::warpToLive and as float4 vertices + indices, the

@@ -2,7 +2,8 @@
 // (include/kfusion/cuda/tsdf_volume.hpp:7-73; behaviour src/kfusion/tsdf_volume.cpp:18-129) on the dynfu_amd C ABI.
 //
 // Layout of this adaptor: the volume's settings live in one plain struct, trivial accessors are inline, the
-// operations that touch the GPU (clear / integrate / raycast / fetchCloud / fetchNormals) are one dfa_tsdf_* call each.
+// operations that touch the GPU (clear / integrate / integrateWarped / raycast / fetchCloud / fetchNormals) are one dfa_tsdf_*
+// call each.
 // Not provided: get,setGridOrigin (not on the DynFusion path).
 #pragma once
 #include <algorithm>
@@ -56,6 +57,17 @@ public:
     // clear() then integrate() as ONE sweep (what DynFusion::operator() does every frame, dyn_fusion.cpp:113-116):
     // same voxels bit for bit, half the HBM traffic.  Extension of the reference's interface.
     void clearAndIntegrate(const Dists& dists, const Affine3f& camera_pose, const Intr& intr);
+    // integrate() with every voxel taken through a warp field first (dfa_tsdf_integrate_warped: non-rigid fusion into a
+    // canonical volume).  The nodes are plain device arrays in the volume's metric frame — D x 3 positions, D x 8 transforms,
+    // D radii, as Warpfield::deviceNodes() hands them out — and not a Warpfield: this header is the kfusion layer, which the
+    // dynfu layer is built on.  A voxel no node supports is left alone (Skip) or integrated where it stands (Rigid).  The
+    // occupancy map is kept as integrate() keeps it.  Extension of the reference's interface.
+    enum class UnsupportedMode { Skip = 0, Rigid = 1 };
+    void integrateWarped(const Dists& dists, const Affine3f& camera_pose, const Intr& intr, const float* node_pos,
+                         const float* node_dq, const float* node_w, int D, int k, UnsupportedMode mode = UnsupportedMode::Skip);
+    // the voxels of another volume of the same dimensions, copied (a copy of the OBJECT shares them); the map comes along
+    // when the source's is trusted.  Extension of the reference's interface.
+    void copyVoxelsFrom(const TsdfVolume& src);
     virtual void raycast(const Affine3f& camera_pose, const Intr& intr, Depth& depth, Normals& normals);
     virtual void raycast(const Affine3f& camera_pose, const Intr& intr, Cloud& points, Normals& normals);
     // the rays of raycast(points) shaded in the same launch (dfa_tsdf_raycast_render; KinFu::renderImage(image, pose, flag)):

@@ -47,6 +47,8 @@ DynFuParams DynFuParams::defaultParams() {  // dyn_fusion.cpp:6-31
 }
 
 DynFusion::DynFusion(const DynFuParams& params) : kfusion::KinFu(params.kinfuParams), dynfuParams(params) {  // dyn_fusion.cpp:33
+    if (params.fuse_canonical && params.north_star)
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion: fuse_canonical is a reference-mode extension (north_star blends otherwise, in the camera frame)");
     solverParams.numIter       = 24;  // dyn_fusion.cpp:183-189
     solverParams.nonLinearIter = 16;
     solverParams.linearIter    = 256;
@@ -208,6 +210,14 @@ bool DynFusion::operator()(const kfusion::cuda::Depth& depth) {
         tsdf().integrate(dists_, camera, p.intr);  // :71
         initFromFrame(extractSurface(0, dynfuParams.mesh_normals));  // :73-95
         if (dynfuParams.model_view) keepCanonicalMesh(nullptr);
+        if (dynfuParams.fuse_canonical) {  // the canonical volume starts as what frame 0 saw
+            canonical_volume_ = std::make_shared<kfusion::cuda::TsdfVolume>(tsdf().getDims());
+            canonical_volume_->setSize(tsdf().getSize()), canonical_volume_->setPose(tsdf().getPose());
+            canonical_volume_->setTruncDist(tsdf().getTruncDist()), canonical_volume_->setMaxWeight(tsdf().getMaxWeight());
+            canonical_volume_->setRaycastStepFactor(tsdf().getRaycastStepFactor());
+            canonical_volume_->setGradientDeltaFactor(tsdf().getGradientDeltaFactor());
+            canonical_volume_->copyVoxelsFrom(tsdf());
+        }
         return ++frame_counter_, false;
     }
     StageClock clk;
@@ -218,6 +228,11 @@ bool DynFusion::operator()(const kfusion::cuda::Depth& depth) {
     addLiveFrame(frame_counter_, live);  // :137
     warpCanonicalToLiveOpt(camera);      // :140
     clk.mark("warpCanonicalToLiveOpt");
+    if (dynfuParams.fuse_canonical) {  // step 4 of :39-47: this frame's depth into the canonical volume, through the solved field
+        const Warpfield::DeviceNodeView nodes = warpfield->deviceNodes();
+        canonical_volume_->integrateWarped(dists_, camera, p.intr, nodes.pos, nodes.dq, nodes.w, nodes.D, warpfield->getKnn());
+        clk.mark("integrateWarped");
+    }
     warpfield->update(getCanonicalWarpedToLive());    // :142
     clk.mark("warpfield->update");
     return ++frame_counter_, true;

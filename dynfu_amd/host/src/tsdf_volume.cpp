@@ -2,6 +2,7 @@
 // (host logic follows src/kfusion/tsdf_volume.cpp:18-129; kernels are in libdynfu_amd.so).
 #include <algorithm>
 
+#include <hip/hip_runtime.h>
 #include <kfusion/cuda/tsdf_volume.hpp>
 
 #include "../../../include/dynfu_amd.h"
@@ -49,6 +50,31 @@ void TsdfVolume::integrate(const Dists& dists, const Affine3f& camera_pose, cons
                                       intr.fy, intr.cx, intr.cy, nullptr),
                    "TsdfVolume::integrate");
     dfa::device_synchronize();  // the reference's device::integrate blocks (tsdf_volume.cu:120)
+}
+
+void TsdfVolume::integrateWarped(const Dists& dists, const Affine3f& camera_pose, const Intr& intr, const float* node_pos,
+                                 const float* node_dq, const float* node_w, int D, int k, UnsupportedMode mode) {
+    Affine3f vol2cam = camera_pose.inv() * cfg_.pose;  // as integrate() forms it
+    float aff[12];
+    vol2cam.to12(aff);
+    const Vec3f vsz = getVoxelSize();
+    // (the call only ADDS to the map, as the accumulating sweep does: it has to be right before)
+    dfa::check(dfa_tsdf_integrate_warped(dists.ptr(), (int)dists.step(), dists.cols(), dists.rows(), blob_.ptr<uint32_t>(), cfg_.dims[0],
+                                         cfg_.dims[1], cfg_.dims[2], mapTrusted() ? occ_.ptr<uint8_t>() : nullptr, vsz.v, cfg_.trunc,
+                                         cfg_.max_weight, aff, intr.fx, intr.fy, intr.cx, intr.cy, node_pos, node_dq, node_w, D, k,
+                                         mode == UnsupportedMode::Rigid ? DFA_WARPED_RIGID : DFA_WARPED_SKIP, nullptr),
+               "TsdfVolume::integrateWarped");
+    dfa::device_synchronize();  // (as integrate())
+}
+
+void TsdfVolume::copyVoxelsFrom(const TsdfVolume& src) {
+    if (src.cfg_.dims[0] != cfg_.dims[0] || src.cfg_.dims[1] != cfg_.dims[1] || src.cfg_.dims[2] != cfg_.dims[2])
+        throw dfa::Error(DFA_ERR_INVALID, "TsdfVolume::copyVoxelsFrom: the volumes differ in their dimensions");
+    const bool with_map = src.mapTrusted();
+    if (hipMemcpy(blob_.ptr<void>(), src.blob_.ptr<void>(), blob_.sizeBytes(), hipMemcpyDeviceToDevice) != hipSuccess ||
+        (with_map && hipMemcpy(occ_.ptr<void>(), src.occ_.ptr<void>(), occ_.sizeBytes(), hipMemcpyDeviceToDevice) != hipSuccess))
+        throw dfa::Error(DFA_ERR_HIP, "TsdfVolume::copyVoxelsFrom: hipMemcpy");
+    occ_known_ = with_map && soleOwner();
 }
 
 void TsdfVolume::clearAndIntegrate(const Dists& dists, const Affine3f& camera_pose, const Intr& intr) {

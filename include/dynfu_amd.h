@@ -387,6 +387,25 @@ int dfa_calc_dqb(const float* node_pos, const float* node_dq, const float* node_
 int dfa_unsupported_vertices(const float* node_pos, const float* node_w, int D, int k, const float* vertices, int N,
                              uint8_t* flags, dfa_stream_t stream);
 
+/* Non-rigid TSDF fusion: dfa_tsdf_integrate with every voxel taken THROUGH the warp field first (DynamicFusion's "dense
+ * non-rigid surface fusion"; the reference lists the step, dyn_fusion.cpp:39-47, and never does it).  Per voxel (x, y, z):
+ *   v = (x, y, z) * voxel_size (float32 products; the voxel's corner, tsdf_volume.cu:60);
+ *   its k nearest nodes by dfa_knn's contract; the support rule of dfa_unsupported_vertices;
+ *   unsupported (always when D == 0): DFA_WARPED_SKIP leaves the voxel untouched, DFA_WARPED_RIGID takes p = v;
+ *   supported: p = transformVertex(calcDQB(v), v), the blend of dfa_warp_to_live;
+ *   vc = R p + t with vol2cam, and from there the reference's integrate (tsdf_volume.cu:65-91) unchanged.
+ * Nodes (layouts of dfa_warp_to_live; radii > 0) live in the volume's metric frame, where reference-mode DynFusion keeps its
+ * canonical cloud and nodes; the north-star blend (dfa_solver6_warp_with: camera frame) is not this one.  D == 0 with NULL
+ * node arrays is valid.  occupancy (may be NULL): the map of dfa_tsdf_integrate_occ — the box of every voxel the call leaves
+ * with a non-zero weight gets marked, bytes are only set.  A search per supported voxel: see DESIGN.md 4.1 for its cost. */
+#define DFA_WARPED_SKIP  0
+#define DFA_WARPED_RIGID 1
+int dfa_tsdf_integrate_warped(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* volume, int X, int Y, int Z,
+                              uint8_t* occupancy, const float voxel_size[3], float trunc_dist, int max_weight,
+                              const float vol2cam[12], float fx, float fy, float cx, float cy, const float* node_pos,
+                              const float* node_dq, const float* node_w, int D, int k, int unsupported_mode,
+                              dfa_stream_t stream);
+
 /* Point-cloud plumbing between the seams (no arithmetic, bit copies).  The reference moves clouds between its
  * stages as pcl::PointCloud objects on the host; with the clouds resident in HBM the same two steps are:
  *
