@@ -12,7 +12,7 @@ SYMBOLS = [
     "dfa_tsdf_clear_integrate", "dfa_tsdf_raycast_points", "dfa_tsdf_raycast_depth", "dfa_tsdf_raycast_tally", "dfa_tsdf_raycast_render", "dfa_render_image_points", "dfa_render_image_depth", "dfa_render_tangent_colors", "dfa_mesh_rasterize", "dfa_tsdf_vertex_normals", "dfa_tsdf_extract_cloud", "dfa_tsdf_extract_cloud_occ", "dfa_tsdf_extract_normals", "dfa_correspond_projective", "dfa_knn", "dfa_warp_to_live",
     "dfa_calc_dqb", "dfa_unsupported_vertices", "dfa_icp_sums", "dfa_repack_points", "dfa_compact_points", "dfa_transform_points", "dfa_warp_to_live_graph",
     "dfa_correspond", "dfa_marching_cubes", "dfa_mc_default_tables",
-    "dfa_tsdf_occupancy_bytes", "dfa_tsdf_clear_occ", "dfa_tsdf_integrate_occ", "dfa_tsdf_clear_integrate_occ", "dfa_tsdf_clear_integrate_known_occ", "dfa_tsdf_integrate_warped", "dfa_marching_cubes_occ", "dfa_marching_cubes_indexed",
+    "dfa_tsdf_occupancy_bytes", "dfa_tsdf_clear_occ", "dfa_tsdf_integrate_occ", "dfa_tsdf_clear_integrate_occ", "dfa_tsdf_clear_integrate_known_occ", "dfa_tsdf_integrate_warped", "dfa_tsdf_integrate_warped6", "dfa_marching_cubes_occ", "dfa_marching_cubes_indexed",
     "dfa_depth_bilateral_filter", "dfa_depth_truncate", "dfa_depth_build_pyramid", "dfa_compute_normals_mask_depth",
     "dfa_resize_depth_normals", "dfa_resize_points_normals",
     "dfa_compute_points_normals", "dfa_solver6_create", "dfa_solver6_destroy", "dfa_solver6_set_problem",
@@ -158,6 +158,7 @@ def load(path=None):
     L.dfa_tsdf_clear_integrate.argtypes = integ
     L.dfa_tsdf_integrate_occ.argtypes = integ[:-1] + [vp, vp]
     L.dfa_tsdf_integrate_warped.argtypes = integ[:8] + [vp] + integ[8:-1] + [vp, vp, vp, i, i, i, vp]
+    L.dfa_tsdf_integrate_warped6.argtypes = integ[:8] + [vp] + integ[8:11] + [vp] + integ[11:-1] + [vp, vp, vp, i, i, i, vp]
     L.dfa_tsdf_clear_integrate_occ.argtypes = integ[:-1] + [vp, vp]
     L.dfa_tsdf_clear_integrate_known_occ.argtypes = integ[:-1] + [vp, vp]
     L.dfa_tsdf_clear_occ.argtypes = [vp, i, i, i, vp, vp]
@@ -360,6 +361,27 @@ def tsdf_integrate_warped(vol, dists, voxel_size, trunc, max_weight, vol2cam, fx
                                             _aff12(vol2cam), fx, fy, cx, cy, _dev(node_pos, f32, "node_pos") if D else None,
                                             _dev(node_dq, f32, "node_dq") if D else None, _dev(node_w, f32, "node_w") if D else None,
                                             D, k, WARPED_MODES[unsupported], _stream()))
+
+
+def tsdf_integrate_warped6(vol, dists, voxel_size, trunc, max_weight, vol2node, node2cam, fx, fy, cx, cy, node_pos, node_dq, node_w, k,
+                           unsupported="skip", occupancy=None):
+    """dfa_tsdf_integrate_warped6: tsdf_integrate_warped through the north-star (6-DoF) warp field.  The nodes live in their
+    own frame: vol2node takes a voxel there, node2cam takes the blended point to this frame's camera (12 floats each, or None
+    for the identity).  A supported voxel moves as Solver6.warp_with moves a vertex at its node-frame position; k is 1..8."""
+    torch = _torch()
+    if unsupported not in WARPED_MODES:
+        raise DynfuAmdError("unsupported must be 'skip' or 'rigid', got %r" % (unsupported,))
+    X, Y, Z = _vol_dims(vol)
+    rows, cols = dists.shape
+    D = 0 if node_pos is None else int(node_pos.shape[0])
+    f32 = torch.float32
+    _check(load().dfa_tsdf_integrate_warped6(_dev(dists, torch.uint16, "dists"), dists.stride(0) * 2, cols, rows, _dev(vol), X, Y, Z,
+                                             _dev(occupancy, torch.uint8, "occupancy"), _farr(voxel_size, 3), trunc, max_weight,
+                                             None if vol2node is None else _aff12(vol2node),
+                                             None if node2cam is None else _aff12(node2cam), fx, fy, cx, cy,
+                                             _dev(node_pos, f32, "node_pos") if D else None,
+                                             _dev(node_dq, f32, "node_dq") if D else None, _dev(node_w, f32, "node_w") if D else None,
+                                             D, k, WARPED_MODES[unsupported], _stream()))
 
 
 def tsdf_clear_integrate(vol, dists, voxel_size, trunc, max_weight, vol2cam, fx, fy, cx, cy, occupancy=None, occupancy_known=False):

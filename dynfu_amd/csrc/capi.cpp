@@ -110,7 +110,7 @@ struct McIndexedScratch {
     }
 };
 struct IcpScratch : DeviceBuffer<float> {};        // partial sums of dfa_icp_sums
-// scratch of dfa_tsdf_integrate_warped: the brick flags of the support pre-pass and the largest node radius
+// scratch of dfa_tsdf_integrate_warped and dfa_tsdf_integrate_warped6: the brick flags of the support pre-pass and the largest node radius
 struct WarpedScratch {
     DeviceBuffer<uint8_t> bricks;
     DeviceBuffer<float> wmax;
@@ -738,6 +738,40 @@ int dfa_tsdf_integrate_warped(const uint16_t* dists, int dists_step, int cols, i
     HIP_TRY(dfa::launch_tsdf_integrate_warped(dists, dists_step, cols, rows, volume, X, Y, Z, occupancy, voxel_size, trunc_dist,
                                               max_weight, vol2cam, fx, fy, cx, cy, node_pos, node_dq, node_w, D, k, rigid, grid,
                                               ws.bricks.data, ws.wmax.data, S(stream)));
+    return DFA_OK;
+}
+
+int dfa_tsdf_integrate_warped6(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* volume, int X, int Y, int Z,
+                               uint8_t* occupancy, const float voxel_size[3], float trunc_dist, int max_weight,
+                               const float vol2node[12], const float node2cam[12], float fx, float fy, float cx, float cy,
+                               const float* node_pos, const float* node_dq, const float* node_w, int D, int k,
+                               int unsupported_mode, dfa_stream_t stream) {
+    REQUIRE(volume_args_ok(volume, X, Y, Z), "bad volume");
+    REQUIRE(dists && cols > 0 && rows > 0 && dists_step >= cols * 2, "bad dists image");
+    REQUIRE(voxel_size, "null parameter block");
+    REQUIRE(trunc_dist > 0.f, "trunc_dist must be positive");
+    REQUIRE(max_weight >= 0 && max_weight <= 65535, "max_weight must fit the 16-bit weight");
+    REQUIRE(D >= 0, "negative node count");
+    REQUIRE(D == 0 || (node_pos && node_dq && node_w), "nodes without positions, transforms or radii");
+    REQUIRE(k >= 1 && k <= 8, "k out of range 1..8");
+    REQUIRE(unsupported_mode == DFA_WARPED_SKIP || unsupported_mode == DFA_WARPED_RIGID, "unknown unsupported_mode");
+    float node2vol[12], stretch, tmax;
+    REQUIRE(dfa::warped6_frame(vol2node, node2vol, &stretch, &tmax), "vol2node must be rigid");
+    const bool rigid = unsupported_mode == DFA_WARPED_RIGID;
+    if (D == 0 && !rigid) return DFA_OK;  // no node supports anything: every voxel is left alone
+    WarpedScratch& ws = stream_scratch<WarpedScratch>(S(stream));
+    HIP_TRY(ws.bricks.reserve(dfa::warped_brick_count(X, Y, Z)));
+    HIP_TRY(ws.wmax.reserve(1));
+    const dfa::KnnGridView* grid = nullptr;  // (as dfa_tsdf_integrate_warped)
+    if (D >= 64) {
+        GridScratch& gs = stream_scratch<GridScratch>(S(stream));
+        HIP_TRY(gs.reserve(D));
+        HIP_TRY(dfa::knn_grid_build(gs.v, node_pos, D, S(stream)));
+        grid = &gs.v;
+    }
+    HIP_TRY(dfa::launch_tsdf_integrate_warped6(dists, dists_step, cols, rows, volume, X, Y, Z, occupancy, voxel_size, trunc_dist,
+                                               max_weight, vol2node, node2cam, node2vol, stretch, tmax, fx, fy, cx, cy, node_pos,
+                                               node_dq, node_w, D, k, rigid, grid, ws.bricks.data, ws.wmax.data, S(stream)));
     return DFA_OK;
 }
 

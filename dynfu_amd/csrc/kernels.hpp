@@ -86,6 +86,16 @@ hipError_t launch_tsdf_integrate_warped(const uint16_t* dists, int dists_step, i
                                         const float vol2cam[12], float fx, float fy, float cx, float cy, const float* node_pos,
                                         const float* node_dq, const float* node_w, int D, int k, bool rigid,
                                         const KnnGridView* grid, uint8_t* bricks, float* wmax, hipStream_t s);
+// ... through the north-star warp field (dfa_tsdf_integrate_warped6).  warped6_frame (host): vol2node checked for rigidity
+// (false: refused) and inverted — node2vol, the pre-pass's relative widening `stretch` and the largest |translation| `tmax`,
+// which the launcher takes beside the two transforms (each may be null: identity)
+bool warped6_frame(const float* vol2node, float node2vol[12], float* stretch, float* tmax);
+hipError_t launch_tsdf_integrate_warped6(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol, int X, int Y,
+                                         int Z, uint8_t* occ, const float voxel_size[3], float trunc_dist, int max_weight,
+                                         const float* vol2node, const float* node2cam, const float node2vol[12], float stretch,
+                                         float tmax, float fx, float fy, float cx, float cy, const float* node_pos,
+                                         const float* node_dq, const float* node_w, int D, int k, bool rigid,
+                                         const KnnGridView* grid, uint8_t* bricks, float* wmax, hipStream_t s);
 
 hipError_t launch_correspond_projective(const float* verts, const float* normals, int n, const float* vmap, int vmap_step,
                                         const float* nmap, int nmap_step, int cols, int rows, float fx, float fy, float cx,

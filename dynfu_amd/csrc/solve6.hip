@@ -29,6 +29,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "blend6_device.hpp"
 #include "dq_device.hpp"
 #include "kernels.hpp"
 #include "solve.hpp"
@@ -38,10 +39,7 @@ namespace dfa {
 
 namespace {
 
-__device__ __forceinline__ Quat qconj(Quat a) { return Quat{a.w, -a.x, -a.y, -a.z}; }
-__device__ __forceinline__ float qdot(Quat a, Quat b) { return a.w * b.w + a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ Quat pureq(f3 v) { return Quat{0.f, v.x, v.y, v.z}; }
-__device__ __forceinline__ f3 qvec(Quat a) { return mk3(a.x, a.y, a.z); }
+// (qconj, qdot, pureq, qvec: blend6_device.hpp)
 __device__ __forceinline__ float dot3(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 // e_c^ (x) q for the basis vectors e_x, e_y, e_z
 __device__ __forceinline__ Quat basis_mul(int c, Quat q) {
@@ -135,11 +133,11 @@ __global__ __launch_bounds__(256) void s6_permute_kernel(Solve6View s, const flo
 #pragma unroll
             for (int j = 0; j < K; ++j) w[j] = j < k ? raw_w[(size_t)v * k + j] : 0.f, id[j] = j < k ? s.idx_nat[(size_t)v * k + j] : -1;
         }
-        float sum = 0.f;
+        float sum = 0.f;  // the row normalisation of blend6_device.hpp
 #pragma unroll
-        for (int j = 0; j < K; ++j) sum += j < k ? w[j] : 0.f;
+        for (int j = 0; j < K; ++j) sum = weight_sum_add(sum, &w[j], j < k);
 #pragma unroll
-        for (int j = 0; j < K; ++j) w[j] = sum > 0.f ? w[j] / sum : 0.f;
+        for (int j = 0; j < K; ++j) w[j] = normalised_weight(&w[j], sum);
         if (wide) {
 #pragma unroll
             for (int q = 0; q < K / 4; ++q) {
@@ -165,61 +163,7 @@ __global__ __launch_bounds__(256) void s6_reg_graph_kernel(const int32_t* __rest
     for (; o < k; ++o) reg_idx[(size_t)n * k + o] = -1;
 }
 
-// ------------------------------------------------------------------------------------ blend
-template <int K>
-struct Blend {
-    Quat a, b;   // un-normalised blended real / dual parts
-    float m;     // |a|^2
-    float s[K];  // hemisphere sign of each neighbour (0 = unused slot)
-};
-
-template <int K>
-__device__ __forceinline__ void blend(const float* __restrict__ dq, const int32_t* idx, const float* wn, int k,
-                                      Blend<K>& B) {
-    B.a = Quat{0.f, 0.f, 0.f, 0.f}, B.b = B.a;
-    Quat r0   = Quat{1.f, 0.f, 0.f, 0.f};
-    bool have = false;
-    // the node transforms four at a time, by unconditional loads (a neighbour that is not there reads node 0 and is not
-    // used): with the load inside the `if` the k gathers were k dependent round trips to L2
-#pragma unroll
-    for (int h = 0; h < K; h += 4) {
-        DQ q[4];
-        bool on[4];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int j = h + jj;
-            on[jj]      = j < k && idx[j] >= 0 && wn[j] != 0.f;
-            q[jj]       = dq_load(dq + 8 * (size_t)(on[jj] ? idx[j] : 0));
-        }
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int j = h + jj;
-            B.s[j]      = 0.f;
-            if (!on[jj]) continue;
-            if (!have) r0 = q[jj].r, have = true;
-            const float sg = qdot(q[jj].r, r0) < 0.f ? -1.f : 1.f;
-            B.s[j]         = sg;
-            const float w  = wn[j] * sg;
-            B.a = qadd(B.a, qscale(q[jj].r, w)), B.b = qadd(B.b, qscale(q[jj].d, w));
-        }
-    }
-    B.m = qdot(B.a, B.a);
-}
-
-template <int K>
-__device__ __forceinline__ f3 blend_point(const Blend<K>& B, f3 c) {
-    const Quat ac = qconj(B.a);
-    const f3 u    = qvec(qmul(qmul(B.a, pureq(c)), ac));
-    const f3 t    = qvec(qmul(B.b, ac));
-    const float im = 1.f / B.m;
-    return mk3((u.x + 2.f * t.x) * im, (u.y + 2.f * t.y) * im, (u.z + 2.f * t.z) * im);
-}
-template <int K>
-__device__ __forceinline__ f3 blend_normal(const Blend<K>& B, f3 n) {
-    const f3 u     = qvec(qmul(qmul(B.a, pureq(n)), qconj(B.a)));
-    const float im = 1.f / B.m;
-    return mk3(u.x * im, u.y * im, u.z * im);
-}
+// (the blend itself — Blend, blend, blend_point, blend_normal — is blend6_device.hpp, shared with the warped TSDF sweep)
 
 // ------------------------------------------------------------------------------- per iteration
 // g^_n = T_n(g_n) and M_n of node n at transform q (part of the launch that produced q: s6_begin / s6_update)

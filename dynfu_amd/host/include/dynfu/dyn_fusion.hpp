@@ -60,8 +60,15 @@ struct DynFuParams {  // dyn_fusion.hpp:25-42
     // frame's depth into it through the warp field (TsdfVolume::integrateWarped, voxels no node supports left alone).  The
     // per-frame live volume, the live cloud, the solve and the node insertion are untouched — the canonical cloud stays
     // frame 0's —: off, nothing of this runs, and on or off every other output of a frame is the same, bit for bit.  With
-    // north_star the constructor throws dfa::Error: that mode has another blend and keeps its nodes in the camera frame.
+    // north_star the constructor throws dfa::Error: that mode has another blend and keeps its nodes in the camera frame —
+    // its switch is north_star_fuse_canonical.
     bool fuse_canonical = false;
+    // Extension — the same fusion in north-star mode (north_star only: without it the constructor throws dfa::Error).  Frame 0
+    // creates the canonical volume as fuse_canonical does; every later frame, once the solve has written its transforms into
+    // the nodes and before the warp field grows, integrates that frame's depth into it through the north-star blend
+    // (TsdfVolume::integrateWarped6; the node frame is frame 0's camera).  Off, nothing of this runs; on or off every other
+    // output of a frame is the same, bit for bit.
+    bool north_star_fuse_canonical = false;
 };
 
 struct dfa_solver6;  // include/dynfu_amd.h
@@ -136,7 +143,7 @@ public:
     int nodeStep = 128;
 
     std::shared_ptr<Warpfield> getWarpfield() { return warpfield; }
-    // fuse_canonical: the canonical volume (null before frame 0, or with the switch off)
+    // fuse_canonical / north_star_fuse_canonical: the canonical volume (null before frame 0, or with the switch off)
     std::shared_ptr<kfusion::cuda::TsdfVolume> canonicalVolume() { return canonical_volume_; }
 
 private:
@@ -157,7 +164,8 @@ private:
     // vertices of the volume's zero level set as a point cloud (dyn_fusion.cpp:73-88 / :119-134), device-resident
     std::shared_ptr<dynfu::Frame> extractSurface(int frame_id, bool with_normals);
     bool northStarFrame(const kfusion::cuda::Depth& depth);  // operator() in north-star mode
-    std::shared_ptr<kfusion::cuda::TsdfVolume> canonical_volume_;  // fuse_canonical
+    std::shared_ptr<kfusion::cuda::TsdfVolume> canonical_volume_;  // fuse_canonical, north_star_fuse_canonical
+    void createCanonicalVolume();  // frame 0: a copy of the live volume
     kfusion::cuda::Cloud live_points_;
     kfusion::cuda::Normals live_normals_;
     // model_view: the canonical mesh (frame 0) as a frame for Warpfield::warpToLive and as float4 vertices + indices, the

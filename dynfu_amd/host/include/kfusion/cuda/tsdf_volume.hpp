@@ -65,6 +65,13 @@ public:
     enum class UnsupportedMode { Skip = 0, Rigid = 1 };
     void integrateWarped(const Dists& dists, const Affine3f& camera_pose, const Intr& intr, const float* node_pos,
                          const float* node_dq, const float* node_w, int D, int k, UnsupportedMode mode = UnsupportedMode::Skip);
+    // ... through a NORTH-STAR warp field (dfa_tsdf_integrate_warped6: the 6-DoF blend of the dfa_solver6 plans).  Its nodes
+    // live in a frame of their own — node_frame_pose is the pose of that frame in the world; for DynFusion's north-star mode
+    // the camera of frame 0 —: a voxel goes there by node_frame_pose^-1 * pose, is searched, supported and blended there, and
+    // goes on to the camera by camera_pose^-1 * node_frame_pose.  k is 1..8.  The map is kept as integrateWarped keeps it.
+    void integrateWarped6(const Dists& dists, const Affine3f& camera_pose, const Intr& intr, const Affine3f& node_frame_pose,
+                          const float* node_pos, const float* node_dq, const float* node_w, int D, int k,
+                          UnsupportedMode mode = UnsupportedMode::Skip);
     // the voxels of another volume of the same dimensions, copied (a copy of the OBJECT shares them); the map comes along
     // when the source's is trusted.  Extension of the reference's interface.
     void copyVoxelsFrom(const TsdfVolume& src);

@@ -48,7 +48,9 @@ DynFuParams DynFuParams::defaultParams() {  // dyn_fusion.cpp:6-31
 
 DynFusion::DynFusion(const DynFuParams& params) : kfusion::KinFu(params.kinfuParams), dynfuParams(params) {  // dyn_fusion.cpp:33
     if (params.fuse_canonical && params.north_star)
-        throw dfa::Error(DFA_ERR_INVALID, "DynFusion: fuse_canonical is a reference-mode extension (north_star blends otherwise, in the camera frame)");
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion: fuse_canonical is a reference-mode extension (north_star blends otherwise, in the camera frame: north_star_fuse_canonical)");
+    if (params.north_star_fuse_canonical && !params.north_star)
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_fuse_canonical needs north_star (reference mode: fuse_canonical)");
     solverParams.numIter       = 24;  // dyn_fusion.cpp:183-189
     solverParams.nonLinearIter = 16;
     solverParams.linearIter    = 256;
@@ -197,6 +199,16 @@ std::shared_ptr<dfa::PolygonMesh> DynFusion::getMesh() {  // KinFu::getMesh (kin
     return mesh_;
 }
 
+// frame 0 with a fusion switch on: the canonical volume starts as what frame 0 saw
+void DynFusion::createCanonicalVolume() {
+    canonical_volume_ = std::make_shared<kfusion::cuda::TsdfVolume>(tsdf().getDims());
+    canonical_volume_->setSize(tsdf().getSize()), canonical_volume_->setPose(tsdf().getPose());
+    canonical_volume_->setTruncDist(tsdf().getTruncDist()), canonical_volume_->setMaxWeight(tsdf().getMaxWeight());
+    canonical_volume_->setRaycastStepFactor(tsdf().getRaycastStepFactor());
+    canonical_volume_->setGradientDeltaFactor(tsdf().getGradientDeltaFactor());
+    canonical_volume_->copyVoxelsFrom(tsdf());
+}
+
 bool DynFusion::operator()(const kfusion::cuda::Depth& depth) {
     const kfusion::KinFuParams& p = params_;                                                       // :51
     kfusion::cuda::Depth& depth_filtered_ = curr_.depth_pyr[0];
@@ -210,14 +222,7 @@ bool DynFusion::operator()(const kfusion::cuda::Depth& depth) {
         tsdf().integrate(dists_, camera, p.intr);  // :71
         initFromFrame(extractSurface(0, dynfuParams.mesh_normals));  // :73-95
         if (dynfuParams.model_view) keepCanonicalMesh(nullptr);
-        if (dynfuParams.fuse_canonical) {  // the canonical volume starts as what frame 0 saw
-            canonical_volume_ = std::make_shared<kfusion::cuda::TsdfVolume>(tsdf().getDims());
-            canonical_volume_->setSize(tsdf().getSize()), canonical_volume_->setPose(tsdf().getPose());
-            canonical_volume_->setTruncDist(tsdf().getTruncDist()), canonical_volume_->setMaxWeight(tsdf().getMaxWeight());
-            canonical_volume_->setRaycastStepFactor(tsdf().getRaycastStepFactor());
-            canonical_volume_->setGradientDeltaFactor(tsdf().getGradientDeltaFactor());
-            canonical_volume_->copyVoxelsFrom(tsdf());
-        }
+        if (dynfuParams.fuse_canonical) createCanonicalVolume();
         return ++frame_counter_, false;
     }
     StageClock clk;
@@ -260,6 +265,7 @@ bool DynFusion::northStarFrame(const kfusion::cuda::Depth& depth) {
         dfa::check(dfa_transform_points(v.normals, (int)n, aff, 0, cn.ptr(), nullptr), "DynFusion: canonical normals to the camera frame");
         initFromFrame(dynfu::Frame::fromDevice(0, cv, cn, n));
         if (dynfuParams.model_view) keepCanonicalMesh(aff);
+        if (dynfuParams.north_star_fuse_canonical) createCanonicalVolume();
         return ++frame_counter_, false;
     }
     StageClock clk;
@@ -274,6 +280,14 @@ bool DynFusion::northStarFrame(const kfusion::cuda::Depth& depth) {
     solver.solveAll(live_points_, live_normals_, p.intr);
     clk.mark("  solveAll");
     ns_initial_cost_ = solver.initialCost(), ns_final_cost_ = solver.finalCost(), ns_valid_rows_ = solver.validRows();
+    if (dynfuParams.north_star_fuse_canonical) {
+        // this frame's depth into the canonical volume through the solved field: the nodes hold the solved transforms now, and
+        // the field has not grown yet.  The node frame is frame 0's camera — `camera`: it stays at the origin
+        const Warpfield::DeviceNodeView nodes = warpfield->deviceNodes();
+        canonical_volume_->integrateWarped6(dists_, camera, p.intr, camera, nodes.pos, nodes.dq, nodes.w, nodes.D,
+                                            std::min(warpfield->getKnn(), 8));
+        clk.mark("integrateWarped6");
+    }
     canonicalFrameWarpedToLive = solver.warpCanonicalToLive();
     warpfield->update(canonicalFrameWarpedToLive);
     clk.mark("warp + warpfield->update");

@@ -67,6 +67,23 @@ void TsdfVolume::integrateWarped(const Dists& dists, const Affine3f& camera_pose
     dfa::device_synchronize();  // (as integrate())
 }
 
+void TsdfVolume::integrateWarped6(const Dists& dists, const Affine3f& camera_pose, const Intr& intr, const Affine3f& node_frame_pose,
+                                  const float* node_pos, const float* node_dq, const float* node_w, int D, int k,
+                                  UnsupportedMode mode) {
+    // the volume's frame -> the node frame -> this frame's camera; together camera_pose^-1 * pose_, as integrate() forms it
+    float vol2node[12], node2cam[12];
+    (node_frame_pose.inv() * cfg_.pose).to12(vol2node);
+    (camera_pose.inv() * node_frame_pose).to12(node2cam);
+    const Vec3f vsz = getVoxelSize();
+    // (the call only ADDS to the map, as the accumulating sweep does: it has to be right before)
+    dfa::check(dfa_tsdf_integrate_warped6(dists.ptr(), (int)dists.step(), dists.cols(), dists.rows(), blob_.ptr<uint32_t>(), cfg_.dims[0],
+                                          cfg_.dims[1], cfg_.dims[2], mapTrusted() ? occ_.ptr<uint8_t>() : nullptr, vsz.v, cfg_.trunc,
+                                          cfg_.max_weight, vol2node, node2cam, intr.fx, intr.fy, intr.cx, intr.cy, node_pos, node_dq,
+                                          node_w, D, k, mode == UnsupportedMode::Rigid ? DFA_WARPED_RIGID : DFA_WARPED_SKIP, nullptr),
+               "TsdfVolume::integrateWarped6");
+    dfa::device_synchronize();  // (as integrate())
+}
+
 void TsdfVolume::copyVoxelsFrom(const TsdfVolume& src) {
     if (src.cfg_.dims[0] != cfg_.dims[0] || src.cfg_.dims[1] != cfg_.dims[1] || src.cfg_.dims[2] != cfg_.dims[2])
         throw dfa::Error(DFA_ERR_INVALID, "TsdfVolume::copyVoxelsFrom: the volumes differ in their dimensions");

@@ -395,7 +395,7 @@ int dfa_unsupported_vertices(const float* node_pos, const float* node_w, int D, 
  *   supported: p = transformVertex(calcDQB(v), v), the blend of dfa_warp_to_live;
  *   vc = R p + t with vol2cam, and from there the reference's integrate (tsdf_volume.cu:65-91) unchanged.
  * Nodes (layouts of dfa_warp_to_live; radii > 0) live in the volume's metric frame, where reference-mode DynFusion keeps its
- * canonical cloud and nodes; the north-star blend (dfa_solver6_warp_with: camera frame) is not this one.  D == 0 with NULL
+ * canonical cloud and nodes; the north-star blend (dfa_solver6_warp_with: camera frame) is dfa_tsdf_integrate_warped6 below.  D == 0 with NULL
  * node arrays is valid.  occupancy (may be NULL): the map of dfa_tsdf_integrate_occ — the box of every voxel the call leaves
  * with a non-zero weight gets marked, bytes are only set.  A search per supported voxel: see DESIGN.md 4.1 for its cost. */
 #define DFA_WARPED_SKIP  0
@@ -405,6 +405,30 @@ int dfa_tsdf_integrate_warped(const uint16_t* dists, int dists_step, int cols, i
                               const float vol2cam[12], float fx, float fy, float cx, float cy, const float* node_pos,
                               const float* node_dq, const float* node_w, int D, int k, int unsupported_mode,
                               dfa_stream_t stream);
+
+/* The same fusion through the NORTH-STAR (6-DoF) warp field: the blend of dfa_solver6_* (normalised weights, hemisphere
+ * sign).  North-star nodes live in their own frame — the camera frame of frame 0 —, so two rigid transforms stand where
+ * vol2cam stood: vol2node (volume -> node frame) and node2cam (node frame -> this frame's camera).  Per voxel (x, y, z):
+ *   1. v = (x, y, z) * voxel_size (float32 products);
+ *   2. c = R_n v + t_n with vol2node (c = v, no product, when vol2node is NULL);
+ *   3. the k nearest nodes of c by dfa_knn's contract; the support rule of dfa_unsupported_vertices evaluated at c;
+ *   4. unsupported (always when D == 0): DFA_WARPED_SKIP leaves the voxel untouched, DFA_WARPED_RIGID takes p = c;
+ *   5. supported: raw weights of dfa_knn (node.cpp:29-36) divided by their float32 sum in slot order; a neighbour is active
+ *      when its id is >= 0 and its normalised weight is not 0; every active transform takes the sign s that puts its real
+ *      part in the hemisphere of the first active neighbour's; a = sum w~ s r, b = sum w~ s d;
+ *      p = (vec(a c a*) + 2 vec(b a*)) / |a|^2 when |a|^2 > 0, else p = c;
+ *   6. vc = R_c p + t_c with node2cam (vc = p, no product, when node2cam is NULL), and from there the reference's integrate
+ *      (tsdf_volume.cu:65-91) unchanged.
+ * A supported voxel moves exactly as dfa_solver6_warp_with moves a vertex at c under the same nodes (positions, radii, k)
+ * and transforms: the same search, weights, normalisation and blend, bit for bit.  k is 1..8, the north-star solve's range.
+ * vol2node must be rigid (|R^T R - I| <= 1e-3 in every entry): the support pre-pass measures distances in the volume's
+ * frame.  Everything else (node layouts, radii > 0, D == 0 with NULL node arrays, occupancy) as dfa_tsdf_integrate_warped.
+ * See DESIGN.md 4.1 for its cost. */
+int dfa_tsdf_integrate_warped6(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* volume, int X, int Y, int Z,
+                               uint8_t* occupancy, const float voxel_size[3], float trunc_dist, int max_weight,
+                               const float vol2node[12] /* may be NULL: identity */, const float node2cam[12] /* may be NULL: identity */,
+                               float fx, float fy, float cx, float cy, const float* node_pos, const float* node_dq,
+                               const float* node_w, int D, int k /* 1..8 */, int unsupported_mode, dfa_stream_t stream);
 
 /* Point-cloud plumbing between the seams (no arithmetic, bit copies).  The reference moves clouds between its
  * stages as pcl::PointCloud objects on the host; with the clouds resident in HBM the same two steps are:

@@ -1,6 +1,7 @@
-"""Device-event timing of dfa_tsdf_integrate_warped (both modes) beside dfa_tsdf_integrate of the same frame, at 512^3 with
-2 k nodes on the surface, VGA, k = 8 (dynfu_amd/synth.py: the C2 scene; the nodes are its canonical nodes taken to the
-volume's frame, each with a translation of up to a centimetre).
+"""Device-event timing of dfa_tsdf_integrate_warped and dfa_tsdf_integrate_warped6 (both modes each) beside
+dfa_tsdf_integrate of the same frame, at 512^3 with 2 k nodes on the surface, VGA, k = 8 (dynfu_amd/synth.py: the C2 scene; the
+nodes are its canonical nodes taken to the volume's frame, each with a translation of up to a centimetre; for the north-star
+call the same nodes stay in the camera frame, where the scene has them — vol2node is the volume's pose, node2cam the identity).
 
 The items alternate inside every window, after a warm-up of each; per item the median over the windows [min, max].  Beside
 the times: the share of bricks (64 x 4 x 1 voxels, a workgroup of the sweep) the support pre-pass marks — restated here in
@@ -76,10 +77,20 @@ def main():
         return lambda: A.tsdf_integrate_warped(vol, nxt, voxel, trunc, synth.MAX_WEIGHT, vol2cam, fx, fy, cx, cy, d_nodes, d_dq,
                                                d_w, k, unsupported=mode)
 
+    # the north-star call: the same volume, frame and nodes, the nodes in the camera frame (the volume's pose takes a voxel
+    # there; the pose is a translation, so the transforms are the same numbers) and the camera where it was
+    d_nodes6 = dev((nodes.astype(np.float64) + np.asarray(vol2cam, np.float64)[9:12]).astype(np.float32))
+
+    def warped6(mode):
+        return lambda: A.tsdf_integrate_warped6(vol, nxt, voxel, trunc, synth.MAX_WEIGHT, vol2cam, None, fx, fy, cx, cy, d_nodes6,
+                                                d_dq, d_w, min(k, 8), unsupported=mode)
+
     items = [
         ("tsdf_integrate (rigid, same frame)", lambda: A.tsdf_integrate(vol, nxt, voxel, trunc, synth.MAX_WEIGHT, vol2cam, fx, fy, cx, cy)),
         ("tsdf_integrate_warped skip", warped("skip")),
         ("tsdf_integrate_warped rigid", warped("rigid")),
+        ("tsdf_integrate_warped6 skip", warped6("skip")),
+        ("tsdf_integrate_warped6 rigid", warped6("rigid")),
         ("warp_to_live, voxels of marked bricks", lambda: A.warp_to_live(d_nodes, d_dq, d_w, k, d_pts)),
     ]
     for _, fn in items:  # warm-up
