@@ -1205,7 +1205,7 @@ int dfa_solver6_create(int max_D, int max_N, int k, dfa_solver6** out) {
     REQUIRE(s, "out of host memory");
     s->max_D = max_D, s->max_N = max_N, s->k = k, s->has_problem = false, s->node_dq = nullptr;
     std::memset(&s->v, 0, sizeof(s->v));
-    s->v.cap = DFA_SOLVE6_ROW_BLOCKS;  // = S6_MAXSLOT of solve6.hip
+    s->v.cap = DFA_SOLVE6_ROW_BLOCKS;  // = S6_MAXSLOT of solve6_internal.hpp
     const size_t N = (size_t)max_N, D = (size_t)max_D, cap = (size_t)s->v.cap;
     dfa::PlanArena& mem = s->mem;
 #define A(field, count) mem.alloc(&s->v.field, (count))
@@ -1455,7 +1455,7 @@ int dfa_solver6_get_timing(dfa_solver6* s, dfa_solve6_timing* out, dfa_stream_t 
 }
 
 const float* dfa_solver6_node_dq(const dfa_solver6* s) { return s ? s->v.dq : nullptr; }
-static_assert(DFA_SOLVE6_ROW_BLOCKS == dfa::S6_ROW_BLOCKS, "row capacity of the C ABI and of the plan (S6_MAXSLOT of solve6.hip)");
+static_assert(DFA_SOLVE6_ROW_BLOCKS == dfa::S6_ROW_BLOCKS, "row capacity of the C ABI and of the plan (S6_MAXSLOT of solve6_internal.hpp)");
 const float* dfa_solver6_matrix_blocks(const dfa_solver6* s) { return s ? s->v.bvals : nullptr; }
 const int32_t* dfa_solver6_matrix_columns(const dfa_solver6* s) { return s ? s->v.bcols : nullptr; }
 const int32_t* dfa_solver6_matrix_row_blocks(const dfa_solver6* s) { return s ? s->v.bcnt : nullptr; }
@@ -1515,7 +1515,7 @@ extern "C" __attribute__((visibility("default"))) int dfa_dev_solver_graph_ptrs(
 }
 #endif
 
-#ifdef DFA_S6_DEBUG  // development builds only: device pointers of the north-star plan (tools/_dbg*.py)
+#ifdef DFA_S6_DEBUG  // development builds only: device pointers of the north-star plan (tools/ns_plan_check.py)
 extern "C" __attribute__((visibility("default"))) int dfa_dev_solver6_ptrs(dfa_solver6* s, void** out) {
     const dfa::Solve6View& v = s->v;
     void* p[] = {v.utab, v.pair_ptr, v.pair_list, v.bcnt, v.bfu, (void*)v.node_ptr, (void*)v.node_list, v.bcols, v.bvals, v.g,

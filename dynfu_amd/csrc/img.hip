@@ -1,7 +1,7 @@
 // img.hip — depth pre-processing kernels of the reference's src/kfusion/cuda/imgproc.cu for gfx950:
 // bilateral filter (:8-52), depth truncation (:60-79), depth pyramid (:84-124), normals + depth mask
-// (:129-183), 2x2 down-samplers (:258-311, :314-358).  (compute_dists lives in tsdf.hip,
-// computePointNormals in solve6.hip.)
+// (:129-183), points + normals of a depth frame (:187-215), 2x2 down-samplers (:258-311, :314-358).  (compute_dists
+// lives in tsdf.hip.)
 //
 // All of them are small image passes (VGA: 0.3 M pixels; a launch is a few microseconds), one lane per
 // output pixel with the reference's arithmetic: integer window sums, IEEE fp32 without contraction.  The
@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_math.hpp"
+#include "dq_device.hpp"  // cross
 #include "kernels.hpp"
 
 namespace dfa {
@@ -134,6 +135,33 @@ __global__ __launch_bounds__(256) void mask_depth_kernel(const float* __restrict
     if (nx != nx) pix(depth, depth_step, y, x) = 0;  // :165-166
 }
 
+// kfusion::device::computePointNormals (src/kfusion/cuda/imgproc.cu:187-215)
+__global__ __launch_bounds__(256) void points_normals_kernel(const uint16_t* __restrict__ depth, int depth_step, int cols,
+                                                             int rows, float finvx, float finvy, float cx, float cy,
+                                                             float* __restrict__ points, int points_step,
+                                                             float* __restrict__ normals, int normals_step) {
+    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
+    if (x >= cols || y >= rows) return;
+    const float qnan = __uint_as_float(0x7fffffffu);  // numeric_limits<float>::quiet_NaN(), temp_utils.hpp:21
+    float4 P = make_float4(qnan, qnan, qnan, qnan), Nn = P;  // :195-196
+    if (x < cols - 1 && y < rows - 1) {                      // :198
+        const uint16_t* d0 = (const uint16_t*)((const char*)depth + (size_t)y * depth_step);
+        const uint16_t* d1 = (const uint16_t*)((const char*)depth + (size_t)(y + 1) * depth_step);
+        const float z00 = d0[x] * 0.001f, z01 = d0[x + 1] * 0.001f, z10 = d1[x] * 0.001f;
+        if (z00 * z01 * z10 != 0.f) {  // :206
+            // Reprojector device.hpp:50-54: x = z * (u - cx) * finv.x
+            const f3 v00 = mk3(z00 * ((float)x - cx) * finvx, z00 * ((float)y - cy) * finvy, z00);
+            const f3 v01 = mk3(z01 * ((float)(x + 1) - cx) * finvx, z01 * ((float)y - cy) * finvy, z01);
+            const f3 v10 = mk3(z10 * ((float)x - cx) * finvx, z10 * ((float)(y + 1) - cy) * finvy, z10);
+            const f3 n   = normalized(cross(v01 - v00, v10 - v00));
+            Nn = make_float4(-n.x, -n.y, -n.z, 0.f);  // :212
+            P  = make_float4(v00.x, v00.y, v00.z, 0.f);
+        }
+    }
+    *reinterpret_cast<float4*>((char*)points + (size_t)y * points_step + 16 * (size_t)x)   = P;
+    *reinterpret_cast<float4*>((char*)normals + (size_t)y * normals_step + 16 * (size_t)x) = Nn;
+}
+
 __device__ __forceinline__ float4 ld4(const float* base, int step, int y, int x) {
     return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + (size_t)y * step + 16 * (size_t)x);
 }
@@ -220,6 +248,15 @@ hipError_t launch_normals_mask_depth(uint16_t* depth, int depth_step, int cols, 
     normals_kernel<<<img_grid(cols, rows), 256, 0, s>>>(depth, depth_step, cols, rows, 1.f / fx, 1.f / fy, cx, cy, normals,
                                                         normals_step);
     mask_depth_kernel<<<img_grid(cols, rows), 256, 0, s>>>(normals, normals_step, depth, depth_step, cols, rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_points_normals(const uint16_t* depth, int depth_step, int cols, int rows, float fx, float fy, float cx,
+                                 float cy, float* points, int points_step, float* normals, int normals_step,
+                                 hipStream_t st) {
+    dim3 grid((cols + 31) / 32, (rows + 7) / 8);
+    points_normals_kernel<<<grid, 256, 0, st>>>(depth, depth_step, cols, rows, 1.f / fx, 1.f / fy, cx, cy, points,
+                                                points_step, normals, normals_step);
     return hipGetLastError();
 }
 

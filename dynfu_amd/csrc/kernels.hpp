@@ -177,6 +177,9 @@ hipError_t launch_depth_pyr(const uint16_t* src, int src_step, int cols, int row
                             float sigma_depth, hipStream_t s);
 hipError_t launch_normals_mask_depth(uint16_t* depth, int depth_step, int cols, int rows, float fx, float fy, float cx,
                                      float cy, float* normals, int normals_step, hipStream_t s);
+hipError_t launch_points_normals(const uint16_t* depth, int depth_step, int cols, int rows, float fx, float fy, float cx,
+                                 float cy, float* points, int points_step, float* normals, int normals_step,
+                                 hipStream_t st);
 hipError_t launch_resize_depth_normals(const uint16_t* dsrc, int dsrc_step, const float* nsrc, int nsrc_step, int cols,
                                        int rows, uint16_t* ddst, int ddst_step, float* ndst, int ndst_step, hipStream_t s);
 hipError_t launch_resize_points_normals(const float* vsrc, int vsrc_step, const float* nsrc, int nsrc_step, int cols,
@@ -191,7 +194,7 @@ hipError_t launch_icp_sums(bool depth_variant, const void* curr, int curr_step, 
 
 
 // Several kernels publish partial results with write-through stores and then arrive at a ticket / raise a flag word, ordering
-// the two by `s_waitcnt vmcnt(0)` (solve_linearise.hip: linearise tail; solve_pcg_team.hip; solve6.hip: linearise tail).  That is an ordering
+// the two by `s_waitcnt vmcnt(0)` (solve_linearise.hip: linearise tail; solve_pcg_team.hip; solve6_linearise.hip: linearise tail).  That is an ordering
 // on gfx9 parts only, where stores count in vmcnt; gfx10 and later track them in vscnt.  This library is built for gfx950.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__) && !defined(__gfx90a__)
 #error "dynfu_amd orders published stores with s_waitcnt vmcnt(0): gfx90a / gfx942 / gfx950 only"

@@ -1,5 +1,42 @@
-// solve6.hpp — device-side view of a north-star (6-DoF) solver plan and the launchers of
-// solve6.hip (internal).  Formulas: DESIGN.md §4.5; CPU statement: oracle/solve6_oracle.c.
+// solve6.hpp — device-side view of a north-star (6-DoF) solver plan and the launchers of the NORTH-STAR solve on gfx950
+// (internal): 6-DoF twist per deformation node, dual-quaternion blend of the k nearest nodes with normalised weights,
+// projective point-to-plane data term against the live vertex / normal maps, ARAP-style edge regulariser, Gauss-Newton
+// with a block-Jacobi (6x6) preconditioned CG on the block-sparse normal equations.  One translation unit per stage:
+//   solve6_graph.hip      vertex order, normalised weights, regularisation graph, node -> rows lists   (once per frame)
+//   solve6_pattern.hip    block-row pattern, pair lists by slot, work units of the assembly            (once per frame)
+//   solve6_linearise.hip  data rows and regularisation edges, energy, Gauss-Newton stopping rule; s6_forcing
+//   solve6_assemble.hip   normal equations: block rows, gradient, inverse diagonal blocks, start of the PCG
+//   solve6_pcg.hip        PCG, one launch per iteration
+//   solve6_update.hip     start of a solve, the step applied to the node transforms, the solve's own warp
+// solve6_internal.hpp holds what several units share; the blend itself is blend6_device.hpp (shared with the warped TSDF
+// sweep).
+//
+// Not in the reference's code: BASELINE.json:north_star / SURVEY.md App. B.2 ask for it, DESIGN.md
+// §4.5 fixes the formulas, oracle/solve6_oracle.c states them on the CPU in double precision.  The
+// reference pieces this follows where they apply: the point-to-plane row [s x n, n | n.(d - s)] and
+// the nearest-pixel projective lookup of the rigid ICP (src/kfusion/cuda/proj_icp.cu:72-98,343-350),
+// the RBF weight (src/dynfu/utils/node.cpp:29-36), the Tukey / Huber weights
+// (src/dynfu/utils/opt_solver.cpp:204-268), w_reg^2 = lambda / (D k) (opt_solver.cpp:30).
+//
+// Once per frame (s6_build_graph): the vertex sort by nearest node, k-NN rows with normalised weights in that order, the
+// regularisation graph, the node -> rows transpositions, and (s6_launch_pattern) the block row pattern of the normal matrix
+// — sorted lists: reproducible sums — with, per node, the pair lists by slot and the work units of its assembly.
+// Once per solve: s6_begin — the caller's transforms, a cleared state block, g^_i = T_i(g_i) and M_i (the node's twist as
+// dual-quaternion increments: s6_node_now) of every node.
+// Per Gauss-Newton iteration (all launches on one stream, nothing returns to the host):
+//   s6_linearise  nlin + nreg workgroups.  The first nlin, one lane per vertex: blend, project, gate, residual, Tukey
+//                 weight; the row's 6-vector for neighbour j factors as f_j M_j l — l (8 numbers) and the k scalars f are
+//                 written as one record per vertex.  The other nreg, one lane per regularisation edge.  Every workgroup
+//                 leaves its share of the energy; gn_tol > 0: the last one to arrive sums them and decides (s6_decide)
+//   s6_assemble   one workgroup per node: streams the node's rows, accumulates the 8x8 moments sum rho f_a f_b l l^T per
+//                 column slot, a lane per work unit (no atomics), then H_ab = M_a S_ab M_b^T, the regulariser, damping,
+//                 the inverse of the diagonal block, the gradient and the PCG's start; one workgroup more: the energy's
+//                 sum and bookkeeping when the linearisation has not done them (gn_tol <= 0)
+//   s6_pcg_step   ONE launch per PCG iteration (Chronopoulos-Gear form), one wave per block row; replayed as a HIP
+//                 graph.  Scalars are re-summed from per-workgroup partials by every workgroup (deterministic).
+//   s6_update     T_i <- twist about g^_i applied on the left (or, after a rejected step, the transforms before it), and
+//                 g^_i, M_i at the new transform for the next linearisation
+// gn_tol > 0: a closing s6_linearise and an s6_update that applies nothing check the solve's last step.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -178,8 +215,5 @@ hipError_t s6_update(const Solve6View& s, Solve6State* state, int launched, int 
                      hipStream_t st);
 hipError_t s6_pcg_n(const Solve6View& s, Solve6State* state, int launches, hipStream_t st);
 hipError_t s6_warp(const Solve6View& s, const float* dq, float* out_v, float* out_n, hipStream_t st);
-hipError_t launch_points_normals(const uint16_t* depth, int depth_step, int cols, int rows, float fx, float fy, float cx,
-                                 float cy, float* points, int points_step, float* normals, int normals_step,
-                                 hipStream_t st);
 
 }  // namespace dfa

@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256) void sort_node_lists_kernel(const int32_t* __r
 // ------------------------------------------------------------------------------------------
 // launchers
 
-// node -> (row, slot) lists of any R x k index array (shared with solve6.hip)
+// node -> (row, slot) lists of any R x k index array (shared with solve6_graph.hip)
 hipError_t solve_transpose_graph(const int32_t* ridx, size_t total, int D, int32_t* blk_hist, int32_t* node_ptr,
                                  uint32_t* node_list, hipStream_t st) {
     const size_t lds = sizeof(int32_t) * (size_t)D;

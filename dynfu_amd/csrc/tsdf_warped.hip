@@ -397,7 +397,7 @@ hipError_t launch_tsdf_integrate_warped6(const uint16_t* dists, int dists_step, 
         if (grid) integrate_warped6_kernel<KK, true><<<g3, block, 0, s>>>(a, f, node_pos, node_dq, node_w, D, k, rigid ? 1 : 0, bricks, gv);  \
         else integrate_warped6_kernel<KK, false><<<g3, block, 0, s>>>(a, f, node_pos, node_dq, node_w, D, k, rigid ? 1 : 0, bricks, gv);      \
     } while (0)
-    if (k <= 4) WARPED6(4);  // (as K6DISPATCH of solve6.hip)
+    if (k <= 4) WARPED6(4);  // (as K6DISPATCH of solve6_internal.hpp)
     else WARPED6(8);
 #undef WARPED6
     return hipGetLastError();

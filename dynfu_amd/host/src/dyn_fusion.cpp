@@ -323,7 +323,7 @@ void DynFusion::keepCanonicalMesh(const float* to_canonical_frame) {
 }
 
 // The mesh moves as the canonical cloud does: by the blend of the solve that fitted the transforms.  Reference mode:
-// Warpfield::warpToLive.  North-star mode: the solve's own warp (solve6.hip, s6_warp) on a plan that holds the mesh as its
+// Warpfield::warpToLive.  North-star mode: the solve's own warp (solve6_update.hip, s6_warp) on a plan that holds the mesh as its
 // cloud and never solves — the frame's plan is not touched, so a frame cannot notice the view.
 std::shared_ptr<dynfu::Frame> DynFusion::warpCanonicalMesh() {
     if (!dynfuParams.model_view) throw dfa::Error(DFA_ERR_INVALID, "DynFusion::renderWarpedModel: DynFuParams::model_view is off");

@@ -1,7 +1,7 @@
 """Independent float64 statement of ONE linearisation of the north-star (6-DoF) solve: the block normal matrix H, the
 right-hand side g, the energy, the association of every vertex, per-entry error budgets, and the statement's own solution
 x* of H x = g.  Written from the formulas of DESIGN_NOTES.md §4.5 ("Energy") and include/dynfu_amd.h, not from
-dynfu_amd/csrc/solve6.hip or oracle/solve6_oracle.c:
+dynfu_amd/csrc/solve6_*.hip or oracle/solve6_oracle.c:
 
 * unknown: per node i a twist xi_i = (omega, v) about the node's current position g^_i = T_i(g_i), applied on the left:
   r <- q(omega) r, t <- Exp(omega)(t - g^) + g^ + v.  To first order r gains 1/2 omega^ r and the dual part d = 1/2 t^ r gains

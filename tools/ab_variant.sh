@@ -1,6 +1,7 @@
 #!/bin/bash
 # Builds dynfu_amd/build/libdynfu_amd_<tag>.so with one source (or `all`) recompiled under extra flags (compile-time A/B):
-#   bash tools/ab_variant.sh s6t solve6.hip -DDFA_S6_TIMING      then      DFA_LIB_PATH=dynfu_amd/build/libdynfu_amd_s6t.so python ...
+#   bash tools/ab_variant.sh s6t solve6_assemble.hip -DDFA_S6_TIMING      then      DFA_LIB_PATH=dynfu_amd/build/libdynfu_amd_s6t.so python ...
+#     (solve6_assemble.hip for tools/ns_assemble_phases.py, solve6_pattern.hip for tools/ns_pattern_phases.py; `all` serves both)
 #   bash tools/ab_variant.sh prof all -DDFA_PCG_PROFILE -DDFA_DEV_AB
 # Sources and flags come from dynfu_amd/build.py (one owner).
 set -e

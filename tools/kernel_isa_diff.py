@@ -8,13 +8,13 @@ once comments, debug lines and symbol names are stripped.  No GPU needed.  Exit 
 the sets of kernels differ or a kernel appears twice on one side (a differing ISA alone is reported, not failed,
 unless --require-identical).
 
-    python tools/kernel_isa_diff.py PARENT_CHECKOUT BRANCH_CHECKOUT --file solve6.hip [--drop-arg KERNEL:INDEX]
+    python tools/kernel_isa_diff.py PARENT_CHECKOUT BRANCH_CHECKOUT --file solve6_assemble.hip [--drop-arg KERNEL:INDEX]
     python tools/kernel_isa_diff.py PARENT_CHECKOUT BRANCH_CHECKOUT --parent-files solve.hip \
-        --branch-files solve_graph.hip,solve_linearise.hip,... [--define NAME ...] [--require-identical]
+        --branch-files solve_graph.hip,solve_linearise.hip,... [--define NAME[=VALUE] ...] [--require-identical]
 
 --file names one file, the same on both sides.  --parent-files / --branch-files name a comma-separated list per side
 (code that moved between files): each side's kernels are the union over its files.
---define NAME adds -DNAME to every compilation (repeatable).
+--define NAME or NAME=VALUE adds -DNAME / -DNAME=VALUE to every compilation (repeatable).
 --drop-arg pcg_paired_kernel:1 matches kernels of the two sides whose template argument lists differ by the one
 argument a change removed (index into the parent's list).
 """
@@ -111,7 +111,7 @@ def main():
     ap.add_argument("--file", help="one file of csrc/, the same on both sides")
     ap.add_argument("--parent-files", help="comma-separated; instead of --file for the parent")
     ap.add_argument("--branch-files", help="comma-separated; instead of --file for the branch")
-    ap.add_argument("--define", action="append", default=[], metavar="NAME")
+    ap.add_argument("--define", action="append", default=[], metavar="NAME[=VALUE]")
     ap.add_argument("--drop-arg", action="append", default=[])
     ap.add_argument("--require-identical", action="store_true", help="a differing ISA fails too")
     a = ap.parse_args()

@@ -1,4 +1,4 @@
-"""dev (GPU; a -DDFA_S6_TIMING build): per-workgroup phase clocks of one s6_assemble2 launch.
+"""dev (GPU; a -DDFA_S6_TIMING build of solve6_assemble.hip, which exports dfa_dev_s6_timing): per-workgroup phase clocks of one s6_assemble2 launch.
 usage: DFA_EXTRA_CXXFLAGS=-DDFA_S6_TIMING python -c 'from dynfu_amd import build as B; B.build()'; python tools/ns_assemble_phases.py C3"""
 import ctypes as C
 import os

@@ -1,4 +1,4 @@
-"""dev (GPU; a -DDFA_S6_TIMING build): per-workgroup phase clocks of s6_pattern_kernel (once per frame).  usage: ... C3"""
+"""dev (GPU; a -DDFA_S6_TIMING build of solve6_pattern.hip, which exports dfa_dev_s6_pattern_timing): per-workgroup phase clocks of s6_pattern_kernel (once per frame).  usage: ... C3"""
 import ctypes as C
 import os
 import sys
@@ -23,8 +23,8 @@ for _ in range(3):
 torch.cuda.synchronize()
 n = min(D, 16384)
 buf = np.zeros((n, 16), np.uint64)
-L.dfa_dev_s6_timing.argtypes = [C.c_void_p, C.c_int]
-assert L.dfa_dev_s6_timing(buf.ctypes.data, n) == 0
+L.dfa_dev_s6_pattern_timing.argtypes = [C.c_void_p, C.c_int]
+assert L.dfa_dev_s6_pattern_timing(buf.ctypes.data, n) == 0
 t = buf.astype(np.float64)
 names = ["sort + deal", "hash the neighbours", "rank the columns", "split by slot", "work units", "(end)"]
 tot = t[:, 10]
