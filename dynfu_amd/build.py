@@ -18,7 +18,8 @@ OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libdynfu_amd.so")
 SOURCES = ["tsdf.hip", "tsdf_warped.hip", "warp.hip", "solve_graph.hip", "solve_linearise.hip", "solve_assemble.hip", "solve_pcg.hip",
            "solve_pcg_launched.hip", "solve_pcg_team.hip", "solve6_graph.hip", "solve6_pattern.hip", "solve6_linearise.hip",
-           "solve6_assemble.hip", "solve6_pcg.hip", "solve6_update.hip", "mc.hip", "extract.hip", "img.hip", "render.hip", "raster.hip", "icp.hip", "points.hip", "capi.cpp"]
+           "solve6_assemble.hip", "solve6_pcg.hip", "solve6_update.hip", "mc.hip", "extract.hip", "img.hip", "render.hip", "raster.hip", "icp.hip", "points.hip",
+           "capi.cpp", "capi_tsdf.cpp", "capi_image.cpp", "capi_warp.cpp", "capi_solver.cpp", "capi_solver6.cpp"]
 ARCH = "gfx950"
 EXTRA = os.environ.get("DFA_EXTRA_CXXFLAGS", "").split()
 FLAGS = EXTRA + ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall", "-Wno-unused-function",

@@ -1,0 +1,110 @@
+// capi_internal.hpp — what the units of the C ABI layer (capi*.cpp) share: the error state and its macros, the argument
+// checks and the node-grid scratch that more than one of them uses.  Host-only; the buffer itself is defined in capi.cpp.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <vector>
+
+#include "../../include/dynfu_amd.h"
+#include "kernels.hpp"
+#include "device_memory.hpp"
+
+#pragma GCC visibility push(hidden)  // internal to the library: nothing here joins its exported symbols
+namespace dfa {
+namespace capi {
+
+// ONE per thread for all the units (capi.cpp): what dfa_last_error returns.  __thread, not thread_local: behind an extern
+// thread_local the compiler calls an initialisation function that may exist elsewhere, through a weak reference that a
+// hidden symbol of a shared library cannot leave unresolved (the call lands on the library's load address)
+extern __thread char g_err[512];
+
+inline int fail(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+inline int hip_fail(hipError_t e, const char* what) {
+    return fail(e == hipErrorNoDevice ? DFA_ERR_NO_GPU : DFA_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+}
+
+#define REQUIRE(cond, msg) \
+    if (!(cond)) return fail(DFA_ERR_INVALID, "%s: %s", __func__, msg)
+// (`text` is what a failure reports: a call that moved into a helper keeps the words it failed under before)
+#define HIP_TRY_AS(expr, text)                         \
+    do {                                               \
+        hipError_t e_ = (expr);                        \
+        if (e_ != hipSuccess) return hip_fail(e_, text); \
+    } while (0)
+#define HIP_TRY(expr) HIP_TRY_AS(expr, #expr)
+
+inline hipStream_t S(dfa_stream_t s) { return (hipStream_t)s; }
+
+inline bool volume_args_ok(const void* vol, int X, int Y, int Z) { return vol && X > 0 && Y > 0 && Z > 0; }
+
+// device scratch of one uniform grid (warp.hip): the node grid of the k-NN searches and, with more cells, the grid part
+// of dfa_correspond's point grid.  (Declared in a named namespace: stream_scratch<GridScratch> is ONE table per process,
+// whichever unit asks for it; a type of an anonymous namespace would be another type, and another grid, in every unit.)
+struct GridScratch {
+    DeviceBuffer<dfa::KnnGridDesc> desc;
+    DeviceBuffer<int32_t> cell_count, cell_start, node_cell;
+    DeviceBuffer<float4> sorted;
+    dfa::KnnGridView v{};  // the buffers as the kernels take them
+    void release() {
+        desc.release(), cell_count.release(), cell_start.release(), node_cell.release(), sorted.release();
+        v = dfa::KnnGridView{};
+    }
+    hipError_t reserve(size_t cells, size_t points, size_t headroom) {
+        hipError_t e;
+        if ((e = desc.reserve(1)) || (e = cell_count.reserve(cells)) || (e = cell_start.reserve(cells + 1)) ||
+            (e = node_cell.reserve(points, headroom)) || (e = sorted.reserve(points, headroom)))
+            release();  // (nothing half-allocated stays behind a failure)
+        else v = dfa::KnnGridView{desc.data, cell_count.data, cell_start.data, node_cell.data, sorted.data};
+        return e;
+    }
+    // a warp field grows by a few nodes per frame: a quarter of headroom, so that growing (hipFree waits for the
+    // device, and a fresh hipMalloc costs milliseconds) happens a handful of times in a sequence, not every frame
+    hipError_t reserve(int D) { return reserve(dfa::KNN_GRID_MAX_CELLS, (size_t)D, (size_t)D / 4 + 64); }
+};
+
+// exhaustive scan below this many distance evaluations (grid build = 4 small launches)
+// the uniform-grid k-NN (three small launches to build, ~40 us) against the exhaustive scan: worth it for many queries, and for
+// ANY number of queries over a large node set — a dozen new nodes against 8.5 k existing ones is one workgroup scanning them
+// all, 0.86 ms in the adaptor's 512^3 sequence
+inline bool want_grid(int D, long n_query) { return D >= 64 && ((long)D * n_query >= (1L << 22) || D >= 1024); }
+
+// the grid of a search over D points where it pays (built in the stream's scratch), null where the exhaustive scan does
+inline int scratch_grid(const float* pos, int D, long n_query, hipStream_t st, const dfa::KnnGridView** grid) {
+    *grid = nullptr;
+    if (!want_grid(D, n_query)) return DFA_OK;
+    GridScratch& gs = stream_scratch<GridScratch>(st);
+    HIP_TRY(gs.reserve(D));
+    HIP_TRY(dfa::knn_grid_build(gs.v, pos, D, st));
+    *grid = &gs.v;
+    return DFA_OK;
+}
+
+// behind the field list of a plan: the arena's first failure as the C ABI reports it
+inline int plan_status(const dfa::PlanArena& mem) { return mem.ok() ? DFA_OK : hip_fail(mem.error, mem.what); }
+inline int plan_grid(GridScratch& grid, int max_D) {
+    const hipError_t e = grid.reserve(max_D);
+    return e == hipSuccess ? DFA_OK : hip_fail(e, "hipMalloc (node grid)");
+}
+
+// the sum of a plan's per-row count array (D device ints, D > 0), read back with a blocking copy
+inline hipError_t row_count_sum(const int32_t* counts, int D, long long* sum) {
+    std::vector<int32_t> cnt((size_t)D);
+    const hipError_t e = hipMemcpy(cnt.data(), counts, sizeof(int32_t) * cnt.size(), hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
+        for (int32_t c : cnt) *sum += c;
+    return e;
+}
+
+}  // namespace capi
+}  // namespace dfa
+#pragma GCC visibility pop

@@ -1,4 +1,4 @@
-// device_memory.hpp — the owners of the C ABI layer's device memory (host-only; included by capi.cpp and tsdf.hip):
+// device_memory.hpp — the owners of the C ABI layer's device memory (host-only; included by the capi*.cpp units through capi_internal.hpp, and by tsdf.hip):
 // grow-only scratch buffers and their per-stream table, the arena of a solver plan, the pool of timing events.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -6,7 +6,7 @@
 // their completion events — never of how far the device happens to have got: the same sequence of solves gets the same
 // budgets in every run.
 //
-// This header decides; capi.cpp keeps every HIP call.  Per solve:
+// This header decides; capi_solver6.cpp keeps every HIP call.  Per solve:
 //     b = start(adaptive, key)
 //     for f in [b.fold_from, b.fold_to):  wait for the completion event of slot f % S6_RING;  fold(its mirror slot)
 //     if (b.reset) forget(b.n)

@@ -347,7 +347,7 @@ __global__ __launch_bounds__(256) void raycast_tally_kernel(const RaycastArgs a,
 }
 
 // ------------------------------------------------------------------------------------------
-// host-side launchers (called by the C ABI, capi.cpp)
+// host-side launchers (called by the C ABI, capi_tsdf.cpp)
 
 static inline hipError_t launch_status() { return hipGetLastError(); }
 

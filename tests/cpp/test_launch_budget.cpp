@@ -1,5 +1,5 @@
 // test_launch_budget.cpp — the adaptive launch budget of the north-star solve (dynfu_amd/csrc/launch_budget.hpp) on the
-// CPU: no HIP, no library.  `Plan` below is the host side of dfa_solver6_solve around the budget (capi.cpp) with a model
+// CPU: no HIP, no library.  `Plan` below is the host side of dfa_solver6_solve around the budget (capi_solver6.cpp) with a model
 // of the device and of the pinned mirror: a solve's counts reach its mirror slot when the host waits for its completion
 // event and no sooner (`late`: the host as far ahead as the ring allows) or at once (`!late`).  The model keeps, per slot,
 // the solve it was last zeroed for, and fails when a slot is written or read for another solve than that.
@@ -35,7 +35,7 @@ struct Plan {
     }
     void wait(u64 f) { ++waits, finish(f); }  // hipEventSynchronize(done_ev[f % S6_RING])
 
-    // one solve as capi.cpp drives it -> the launches of each of its PCGs
+    // one solve as capi_solver6.cpp drives it -> the launches of each of its PCGs
     Counts solve(bool adaptive, const BudgetKey& key, const Counts& device_counts, int cap = CAP) {
         const LaunchBudget::Start b = budget.start(adaptive, key);
         ASSERT_EQ(b.n, (u64)counts.size());

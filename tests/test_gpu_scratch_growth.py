@@ -163,6 +163,68 @@ def test_tsdf_extract_cloud(A, spheres):
     _grown_equals_fresh(call, spheres[32], spheres[64])
 
 
+def _warp_nodes(D):
+    """D nodes on the sphere of the `spheres` volumes (volume frame, metres) with small general transforms"""
+    import warp_statement as WS
+    rng = np.random.default_rng(D)
+    n = rng.standard_normal((D, 3))
+    n /= np.linalg.norm(n, axis=1, keepdims=True)
+    pos = synth.SPHERE_C - np.array(synth.VOLUME_POSE_T) + synth.SPHERE_R * n
+    dq = WS.dq_from_euler(*rng.uniform(-0.1, 0.1, (3, D)), *rng.uniform(-0.03, 0.03, (3, D))).reshape(D, 8)
+    return tuple(dev(a.astype(np.float32)) for a in (pos, dq, rng.uniform(0.2, 0.5, D)))
+
+
+@pytest.fixture(scope="module")
+def warped(A, spheres):
+    """(call, args): the next 64 x 48 depth frame fused into a copy of the dim^3 sphere through D nodes, k = 4, with a fresh
+    occupancy map -> the volume words and the map; six = dfa_tsdf_integrate_warped6 with an identity vol2node"""
+    import torch
+    cfg = _image_cfg(64, 48)
+    intr = synth.intrinsics(cfg)
+    dists = torch.empty((48, 64), dtype=torch.uint16, device="cuda")
+    A.compute_dists(dev(synth.depth_frame(cfg, 1)), dists, *intr)
+    identity = aff12(np.eye(3), [0, 0, 0])
+
+    def args(dim, D):  # (64 nodes and more are searched through the node grid)
+        return (spheres[dim][0],) + _warp_nodes(D)
+
+    def call(six, start, nodes, dq, w):
+        dim = start.shape[0]
+        voxel, trunc, vol2cam, _, _ = synth.volume_params(dict(dim=dim))
+        vol = start.clone()
+        occ = A.tsdf_occupancy(vol)
+        if six:
+            A.tsdf_integrate_warped6(vol, dists, voxel, trunc, synth.MAX_WEIGHT, identity, vol2cam, *intr, nodes, dq, w, 4, occupancy=occ)
+        else:
+            A.tsdf_integrate_warped(vol, dists, voxel, trunc, synth.MAX_WEIGHT, vol2cam, *intr, nodes, dq, w, 4, occupancy=occ)
+        h, o = host(vol, np.uint32), host(occ)
+        assert (h != host(start, np.uint32)).any() and o.any()
+        return [h, o]
+
+    return call, args
+
+
+@pytest.mark.parametrize("six", [False, True], ids=["tsdf_integrate_warped", "tsdf_integrate_warped6"])
+def test_tsdf_integrate_warped(warped, six):
+    call, args = warped
+    _grown_equals_fresh(lambda *a: call(six, *a), args(32, 64), args(64, 256))
+
+
+def test_node_grid_shared_by_knn_and_tsdf_integrate_warped(A, warped):
+    """one GridScratch per stream whichever entry point builds it: knn (1 024 nodes, the smallest set 256 queries send to
+    the grid), the warped sweep over 64 nodes, the same knn again"""
+    call, args = warped
+    knn = ("knn", _cloud(1024, 1024), dev(np.full(1024, 0.1, np.float32)), _cloud(256, 3), 4)
+
+    def either(kind, *a):
+        if kind == "warped":
+            return call(False, *a)
+        idx, w = A.knn(*a)
+        return [host(idx), host(w)]
+
+    _grown_equals_fresh(either, knn, ("warped",) + args(32, 64))
+
+
 def test_compact_points(A):
     def args(n):
         rng = np.random.default_rng(n)

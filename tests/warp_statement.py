@@ -24,7 +24,7 @@ D_LIST = (2, 63, 64, 300, 1024, 2048)
 
 
 def want_grid(D, n):
-    """csrc/capi.cpp: the uniform-grid search is taken for D >= 64 and (D * n >= 2^22 or D >= 1024)"""
+    """csrc/capi_internal.hpp: the uniform-grid search is taken for D >= 64 and (D * n >= 2^22 or D >= 1024)"""
     return D >= 64 and (D * n >= (1 << 22) or D >= 1024)
 
 

@@ -9,10 +9,10 @@ tag=$1; src=$2; shift 2
 R=$(cd $(dirname $0)/.. && pwd)
 B=$R/dynfu_amd/build
 CC="/opt/rocm/bin/hipcc $(cd $R && python3 -c 'from dynfu_amd import build as B; print(" ".join(B.FLAGS))')"
-SRCS=$(cd $R && python3 -c 'from dynfu_amd import build as B; print(" ".join(s.rsplit(".", 1)[0] for s in B.SOURCES))')
+SRCS=$(cd $R && python3 -c 'from dynfu_amd import build as B; print(" ".join(B.SOURCES))')
 objs=""
-for o in $SRCS; do
-  f=$o.hip; x=""; if [ $o == capi ]; then f=capi.cpp; x="-x hip"; fi
+for f in $SRCS; do
+  o=${f%.*}; x=""; if [[ $f == *.cpp ]]; then x="-x hip"; fi
   if [ "$src" == all ] || [ "$f" == "$src" ]; then
     $CC "$@" $x -c $R/dynfu_amd/csrc/$f -o $B/${o}_$tag.o &
     objs="$objs $B/${o}_$tag.o"
