@@ -13,6 +13,8 @@ SYMBOLS = [
     "dfa_calc_dqb", "dfa_unsupported_vertices", "dfa_icp_sums", "dfa_repack_points", "dfa_compact_points", "dfa_transform_points", "dfa_warp_to_live_graph",
     "dfa_correspond", "dfa_marching_cubes", "dfa_mc_default_tables",
     "dfa_tsdf_occupancy_bytes", "dfa_tsdf_clear_occ", "dfa_tsdf_integrate_occ", "dfa_tsdf_clear_integrate_occ", "dfa_tsdf_clear_integrate_known_occ", "dfa_tsdf_integrate_warped", "dfa_tsdf_integrate_warped6", "dfa_marching_cubes_occ", "dfa_marching_cubes_indexed",
+    "dfa_knn_field_create", "dfa_knn_field_destroy", "dfa_knn_field_build", "dfa_knn_field_append", "dfa_knn_field_info", "dfa_knn_field_lookup",
+    "dfa_tsdf_integrate_warped_field", "dfa_tsdf_integrate_warped6_field",
     "dfa_depth_bilateral_filter", "dfa_depth_truncate", "dfa_depth_build_pyramid", "dfa_compute_normals_mask_depth",
     "dfa_resize_depth_normals", "dfa_resize_points_normals",
     "dfa_compute_points_normals", "dfa_solver6_create", "dfa_solver6_destroy", "dfa_solver6_set_problem",
@@ -65,8 +67,17 @@ class _Solve6Timing(C.Structure):
                 ("gn_iterations", C.c_int), ("matrix_blocks", C.c_longlong)]
 
 
+class _KnnFieldDesc(C.Structure):
+    """dfa_knn_field_desc"""
+    _fields_ = [("D", C.c_int32), ("k", C.c_int32), ("stored_bricks", C.c_int64), ("total_bricks", C.c_int64), ("bytes", C.c_uint64)]
+
+
 class DynfuAmdError(RuntimeError):
     pass
+
+
+class CapacityError(DynfuAmdError):
+    """DFA_ERR_CAPACITY (3)"""
 
 
 class SolveParams(C.Structure):
@@ -147,7 +158,7 @@ def load(path=None):
     L.dfa_abi_struct_size.argtypes = [i]
     if L.dfa_abi_version() != ABI_VERSION:
         raise DynfuAmdError("%s implements ABI version %d, this binding expects %d" % (p, L.dfa_abi_version(), ABI_VERSION))
-    for sid, mirror in enumerate((SolveParams, _SolveStats, _SolveTiming, Solve6Params, _Solve6Stats, _Solve6Timing)):
+    for sid, mirror in enumerate((SolveParams, _SolveStats, _SolveTiming, Solve6Params, _Solve6Stats, _Solve6Timing, _KnnFieldDesc)):
         if L.dfa_abi_struct_size(sid) != C.sizeof(mirror):
             raise DynfuAmdError("struct %d: the library assumes %d bytes, the ctypes mirror %s has %d"
                                 % (sid, L.dfa_abi_struct_size(sid), mirror.__name__, C.sizeof(mirror)))
@@ -159,6 +170,15 @@ def load(path=None):
     L.dfa_tsdf_integrate_occ.argtypes = integ[:-1] + [vp, vp]
     L.dfa_tsdf_integrate_warped.argtypes = integ[:8] + [vp] + integ[8:-1] + [vp, vp, vp, i, i, i, vp]
     L.dfa_tsdf_integrate_warped6.argtypes = integ[:8] + [vp] + integ[8:11] + [vp] + integ[11:-1] + [vp, vp, vp, i, i, i, vp]
+    L.dfa_tsdf_integrate_warped_field.argtypes = L.dfa_tsdf_integrate_warped.argtypes[:-1] + [vp, vp]
+    L.dfa_tsdf_integrate_warped6_field.argtypes = L.dfa_tsdf_integrate_warped6.argtypes[:-1] + [vp, vp]
+    L.dfa_knn_field_create.argtypes = [i, i, i, vp, i, vp, C.c_size_t, C.POINTER(vp)]
+    L.dfa_knn_field_destroy.argtypes = [vp]
+    L.dfa_knn_field_destroy.restype = None
+    L.dfa_knn_field_build.argtypes = [vp, vp, vp, i, vp]
+    L.dfa_knn_field_append.argtypes = [vp, vp, vp, i, vp]
+    L.dfa_knn_field_info.argtypes = [vp, C.POINTER(_KnnFieldDesc)]
+    L.dfa_knn_field_lookup.argtypes = [vp, vp, i, vp, vp]
     L.dfa_tsdf_clear_integrate_occ.argtypes = integ[:-1] + [vp, vp]
     L.dfa_tsdf_clear_integrate_known_occ.argtypes = integ[:-1] + [vp, vp]
     L.dfa_tsdf_clear_occ.argtypes = [vp, i, i, i, vp, vp]
@@ -251,7 +271,7 @@ def version():
 
 def _check(rc):
     if rc != 0:
-        raise DynfuAmdError("dynfu_amd error %d: %s" % (rc, load().dfa_last_error().decode()))
+        raise (CapacityError if rc == 3 else DynfuAmdError)("dynfu_amd error %d: %s" % (rc, load().dfa_last_error().decode()))
 
 
 def _torch():
@@ -345,10 +365,11 @@ WARPED_MODES = {"skip": 0, "rigid": 1}  # DFA_WARPED_SKIP, DFA_WARPED_RIGID
 
 
 def tsdf_integrate_warped(vol, dists, voxel_size, trunc, max_weight, vol2cam, fx, fy, cx, cy, node_pos, node_dq, node_w, k,
-                          unsupported="skip", occupancy=None):
+                          unsupported="skip", occupancy=None, field=None):
     """dfa_tsdf_integrate_warped: tsdf_integrate with every voxel taken through the warp field first (nodes in the volume's
     metric frame: node_pos (D, 3), node_dq (D, 8), node_w (D,), all three None for no nodes).  A voxel no node supports is left
-    alone (unsupported="skip") or integrated where it stands ("rigid")."""
+    alone (unsupported="skip") or integrated where it stands ("rigid").  field: a KnnField of this volume, k and node set —
+    the neighbours are read from it instead of searched (dfa_tsdf_integrate_warped_field), the result is the same bits."""
     torch = _torch()
     if unsupported not in WARPED_MODES:
         raise DynfuAmdError("unsupported must be 'skip' or 'rigid', got %r" % (unsupported,))
@@ -356,18 +377,21 @@ def tsdf_integrate_warped(vol, dists, voxel_size, trunc, max_weight, vol2cam, fx
     rows, cols = dists.shape
     D = 0 if node_pos is None else int(node_pos.shape[0])
     f32 = torch.float32
-    _check(load().dfa_tsdf_integrate_warped(_dev(dists, torch.uint16, "dists"), dists.stride(0) * 2, cols, rows, _dev(vol), X, Y, Z,
-                                            _dev(occupancy, torch.uint8, "occupancy"), _farr(voxel_size, 3), trunc, max_weight,
-                                            _aff12(vol2cam), fx, fy, cx, cy, _dev(node_pos, f32, "node_pos") if D else None,
-                                            _dev(node_dq, f32, "node_dq") if D else None, _dev(node_w, f32, "node_w") if D else None,
-                                            D, k, WARPED_MODES[unsupported], _stream()))
+    L = load()
+    fn, extra = (L.dfa_tsdf_integrate_warped, ()) if field is None else (L.dfa_tsdf_integrate_warped_field, (field._handle(),))
+    _check(fn(_dev(dists, torch.uint16, "dists"), dists.stride(0) * 2, cols, rows, _dev(vol), X, Y, Z,
+              _dev(occupancy, torch.uint8, "occupancy"), _farr(voxel_size, 3), trunc, max_weight,
+              _aff12(vol2cam), fx, fy, cx, cy, _dev(node_pos, f32, "node_pos") if D else None,
+              _dev(node_dq, f32, "node_dq") if D else None, _dev(node_w, f32, "node_w") if D else None,
+              D, k, WARPED_MODES[unsupported], *extra, _stream()))
 
 
 def tsdf_integrate_warped6(vol, dists, voxel_size, trunc, max_weight, vol2node, node2cam, fx, fy, cx, cy, node_pos, node_dq, node_w, k,
-                           unsupported="skip", occupancy=None):
+                           unsupported="skip", occupancy=None, field=None):
     """dfa_tsdf_integrate_warped6: tsdf_integrate_warped through the north-star (6-DoF) warp field.  The nodes live in their
     own frame: vol2node takes a voxel there, node2cam takes the blended point to this frame's camera (12 floats each, or None
-    for the identity).  A supported voxel moves as Solver6.warp_with moves a vertex at its node-frame position; k is 1..8."""
+    for the identity).  A supported voxel moves as Solver6.warp_with moves a vertex at its node-frame position; k is 1..8.
+    field: a KnnField created with this vol2node (dfa_tsdf_integrate_warped6_field): no search, the same bits."""
     torch = _torch()
     if unsupported not in WARPED_MODES:
         raise DynfuAmdError("unsupported must be 'skip' or 'rigid', got %r" % (unsupported,))
@@ -375,13 +399,75 @@ def tsdf_integrate_warped6(vol, dists, voxel_size, trunc, max_weight, vol2node, 
     rows, cols = dists.shape
     D = 0 if node_pos is None else int(node_pos.shape[0])
     f32 = torch.float32
-    _check(load().dfa_tsdf_integrate_warped6(_dev(dists, torch.uint16, "dists"), dists.stride(0) * 2, cols, rows, _dev(vol), X, Y, Z,
-                                             _dev(occupancy, torch.uint8, "occupancy"), _farr(voxel_size, 3), trunc, max_weight,
-                                             None if vol2node is None else _aff12(vol2node),
-                                             None if node2cam is None else _aff12(node2cam), fx, fy, cx, cy,
-                                             _dev(node_pos, f32, "node_pos") if D else None,
-                                             _dev(node_dq, f32, "node_dq") if D else None, _dev(node_w, f32, "node_w") if D else None,
-                                             D, k, WARPED_MODES[unsupported], _stream()))
+    L = load()
+    fn, extra = (L.dfa_tsdf_integrate_warped6, ()) if field is None else (L.dfa_tsdf_integrate_warped6_field, (field._handle(),))
+    _check(fn(_dev(dists, torch.uint16, "dists"), dists.stride(0) * 2, cols, rows, _dev(vol), X, Y, Z,
+              _dev(occupancy, torch.uint8, "occupancy"), _farr(voxel_size, 3), trunc, max_weight,
+              None if vol2node is None else _aff12(vol2node),
+              None if node2cam is None else _aff12(node2cam), fx, fy, cx, cy,
+              _dev(node_pos, f32, "node_pos") if D else None,
+              _dev(node_dq, f32, "node_dq") if D else None, _dev(node_w, f32, "node_w") if D else None,
+              D, k, WARPED_MODES[unsupported], *extra, _stream()))
+
+
+class KnnField:
+    """dfa_knn_field: the neighbour rows of a volume's voxels, searched once and kept (include/dynfu_amd.h).  dims = (X, Y, Z);
+    vol2node: 12 floats or None.  build / append take node_pos (D, 3) and node_w (D,) float32 CUDA tensors (None, None: no
+    nodes); append's arrays hold the old nodes, unchanged, followed by the new ones.  A build or append beyond max_bytes raises
+    CapacityError.  Calls run on torch's current stream."""
+
+    def __init__(self, dims, voxel_size, k, vol2node=None, max_bytes=0):
+        self._L = load()
+        self.dims, self.k = tuple(int(d) for d in dims), int(k)
+        h = C.c_void_p()
+        _check(self._L.dfa_knn_field_create(self.dims[0], self.dims[1], self.dims[2], _farr(voxel_size, 3), self.k,
+                                            None if vol2node is None else _aff12(vol2node), max_bytes, C.byref(h)))
+        self._h = h
+
+    def _handle(self):
+        if self._h is None:
+            raise DynfuAmdError("the KnnField is closed")
+        return self._h
+
+    def _nodes(self, node_pos, node_w):
+        f32 = _torch().float32
+        D = 0 if node_pos is None else int(node_pos.shape[0])
+        if D and int(node_w.shape[0]) != D:
+            raise DynfuAmdError("node_pos and node_w disagree on the number of nodes")
+        return (_dev(node_pos, f32, "node_pos") if D else None, _dev(node_w, f32, "node_w") if D else None, D)
+
+    def build(self, node_pos, node_w):
+        _check(self._L.dfa_knn_field_build(self._handle(), *self._nodes(node_pos, node_w), _stream()))
+
+    def append(self, node_pos, node_w):
+        _check(self._L.dfa_knn_field_append(self._handle(), *self._nodes(node_pos, node_w), _stream()))
+
+    def info(self):
+        """dict(D, k, stored_bricks, total_bricks, bytes)"""
+        d = _KnnFieldDesc()
+        _check(self._L.dfa_knn_field_info(self._handle(), C.byref(d)))
+        return {n: int(getattr(d, n)) for n, _ in _KnnFieldDesc._fields_}
+
+    def lookup(self, voxels):
+        """voxels: (n, 3) int32 CUDA tensor of (x, y, z) -> (n, k) int32 rows, -1 where the voxel is not stored"""
+        torch = _torch()
+        if voxels.dim() != 2 or voxels.shape[1] != 3 or not voxels.is_contiguous():
+            raise DynfuAmdError("voxels must be a contiguous (n, 3) tensor")
+        n = int(voxels.shape[0])
+        out = torch.empty((n, self.k), dtype=torch.int32, device=voxels.device)
+        _check(self._L.dfa_knn_field_lookup(self._handle(), _dev(voxels, torch.int32, "voxels"), n, _dev(out), _stream()))
+        return out
+
+    def close(self):
+        if self._h is not None:
+            self._L.dfa_knn_field_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def tsdf_clear_integrate(vol, dists, voxel_size, trunc, max_weight, vol2cam, fx, fy, cx, cy, occupancy=None, occupancy_known=False):

@@ -16,10 +16,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libdynfu_amd.so")
-SOURCES = ["tsdf.hip", "tsdf_warped.hip", "warp.hip", "solve_graph.hip", "solve_linearise.hip", "solve_assemble.hip", "solve_pcg.hip",
+SOURCES = ["tsdf.hip", "tsdf_warped.hip", "knn_field.hip", "warp.hip", "solve_graph.hip", "solve_linearise.hip", "solve_assemble.hip", "solve_pcg.hip",
            "solve_pcg_launched.hip", "solve_pcg_team.hip", "solve6_graph.hip", "solve6_pattern.hip", "solve6_linearise.hip",
            "solve6_assemble.hip", "solve6_pcg.hip", "solve6_update.hip", "mc.hip", "extract.hip", "img.hip", "render.hip", "raster.hip", "icp.hip", "points.hip",
-           "capi.cpp", "capi_tsdf.cpp", "capi_image.cpp", "capi_warp.cpp", "capi_solver.cpp", "capi_solver6.cpp"]
+           "capi.cpp", "capi_tsdf.cpp", "capi_field.cpp", "capi_image.cpp", "capi_warp.cpp", "capi_solver.cpp", "capi_solver6.cpp"]
 ARCH = "gfx950"
 EXTRA = os.environ.get("DFA_EXTRA_CXXFLAGS", "").split()
 FLAGS = EXTRA + ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall", "-Wno-unused-function",
@@ -143,12 +143,14 @@ def build_cpp_tests(force=False, verbose=False):
                         ("test_host_dynfusion", ["host", "oracle"]), ("test_host_icp", ["host"]),
                         ("test_tsdf_classify", ["oracle", "ieee"]), ("test_launch_budget", []), ("test_host_io", ["host"]), ("test_host_kinfu", ["host"]),
                         ("test_host_extract", ["host"]), ("test_host_render", ["host"]), ("test_host_mc_indexed", ["host"]), ("test_host_mesh_view", ["host"]),
-                        ("test_host_tsdf_warped", ["host"]), ("test_host_tsdf_warped6", ["host"])):
+                        ("test_host_tsdf_warped", ["host"]), ("test_host_tsdf_warped6", ["host"]),
+                        ("test_knn_field_size", []), ("test_host_knn_field", ["host"])):
         src = os.path.join(tdir, name + ".cpp")
         exe = os.path.join(out, name)
         if not os.path.exists(src):  # a tests/ tree from before this program was added: the rest still builds
             continue
-        deps = [src, os.path.join(tdir, "minitest.hpp"), host, os.path.join(CSRC, "tsdf_classify.hpp"), os.path.join(CSRC, "launch_budget.hpp")]
+        deps = [src, os.path.join(tdir, "minitest.hpp"), host, os.path.join(CSRC, "tsdf_classify.hpp"), os.path.join(CSRC, "launch_budget.hpp"),
+                os.path.join(CSRC, "warped_bricks.hpp")]
         if force or _stale(exe, deps):
             cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-I" + inc, src, "-o", exe]
             if "ieee" in needs:  # CPU model of a kernel: same arithmetic contract as the oracle, hardware fma

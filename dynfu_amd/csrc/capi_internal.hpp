@@ -89,6 +89,19 @@ inline int scratch_grid(const float* pos, int D, long n_query, hipStream_t st, c
     return DFA_OK;
 }
 
+// the search of the warped integrations and of the k-NN field (every voxel of a brick searches): the node grid for 64 nodes
+// and more — wherever it is exact and cheaper than a scan of all the nodes —, built in the stream's scratch; null: the scan
+inline int warped_node_grid(const float* node_pos, int D, hipStream_t st, const dfa::KnnGridView** grid) {
+    *grid = nullptr;
+    if (D >= 64) {
+        GridScratch& gs = stream_scratch<GridScratch>(st);
+        HIP_TRY(gs.reserve(D));
+        HIP_TRY(dfa::knn_grid_build(gs.v, node_pos, D, st));
+        *grid = &gs.v;
+    }
+    return DFA_OK;
+}
+
 // behind the field list of a plan: the arena's first failure as the C ABI reports it
 inline int plan_status(const dfa::PlanArena& mem) { return mem.ok() ? DFA_OK : hip_fail(mem.error, mem.what); }
 inline int plan_grid(GridScratch& grid, int max_D) {

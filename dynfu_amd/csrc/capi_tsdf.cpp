@@ -41,14 +41,7 @@ int warped_scratch(int X, int Y, int Z, const float* node_pos, int D, dfa_stream
     HIP_TRY(ws.bricks.reserve(dfa::warped_brick_count(X, Y, Z)));
     HIP_TRY(ws.wmax.reserve(1));
     *scratch = &ws;
-    *grid    = nullptr;
-    if (D >= 64) {
-        GridScratch& gs = stream_scratch<GridScratch>(S(stream));
-        HIP_TRY(gs.reserve(D));
-        HIP_TRY(dfa::knn_grid_build(gs.v, node_pos, D, S(stream)));
-        *grid = &gs.v;
-    }
-    return DFA_OK;
+    return warped_node_grid(node_pos, D, S(stream), grid);
 }
 
 }  // namespace

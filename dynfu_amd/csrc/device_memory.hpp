@@ -33,6 +33,23 @@ struct DeviceBuffer {
         else data = nullptr;
         return e;
     }
+    // as reserve, but the first `keep` elements survive the move (copied on `s`, which is waited for before the old
+    // block goes); after a failed allocation the buffer is what it was
+    hipError_t grow_keep(size_t count, size_t keep, size_t headroom, hipStream_t s) {
+        if (count <= cap) return hipSuccess;
+        T* fresh     = nullptr;
+        hipError_t e = hipMalloc((void**)&fresh, sizeof(T) * (count + headroom));
+        if (e != hipSuccess) return e;
+        if (keep) e = hipMemcpyAsync(fresh, data, sizeof(T) * keep, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hipFree(fresh);
+            return e;
+        }
+        (void)hipFree(data);
+        data = fresh, cap = count + headroom;
+        return hipSuccess;
+    }
 };
 
 // Scratch of the entry points that have no plan to keep it in (dfa_knn, dfa_warp_to_live, dfa_correspond,

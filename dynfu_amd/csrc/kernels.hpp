@@ -97,6 +97,40 @@ hipError_t launch_tsdf_integrate_warped6(const uint16_t* dists, int dists_step, 
                                          const float* node_dq, const float* node_w, int D, int k, bool rigid,
                                          const KnnGridView* grid, uint8_t* bricks, float* wmax, hipStream_t s);
 
+// knn_field.hip — the k-NN field of a volume (dfa_knn_field_*): per stored brick (the 64 x 4 x 1 voxels of the warped sweeps)
+// one record of k slots x 256 int32 ids, slot-major — ids[(record k + slot) 256 + voxel of the brick] —, a table brick ->
+// record (-1: not stored) and the list record -> brick.  A brick is stored when a node's OWN radius reaches its box.
+struct KnnFieldView {
+    int X, Y, Z, k;
+    float vs[3];
+    int has_frame;  // vol2node given: the search position is c = R_n v + t_n
+    float vol2node[12], node2vol[12], stretch, tmax;  // (warped6_frame's)
+    int32_t* table;   // knn_field_bricks(X, Y, Z)
+    int32_t* coords;  // per record: its brick's index in the table
+    int32_t* ids;     // records x k x 256
+};
+// Step 1 of an extension by the nodes [first, D): the bricks they reach that the table does not hold yet, counted.  marks:
+// one byte per brick; offsets: bricks + 1 ints (on return the exclusive scan of the new bricks' flags); chunk_sums:
+// mc_scan_chunks(bricks) ints; total: one device int, the number of new bricks.  Writes scratch only.
+hipError_t launch_knn_field_count(const KnnFieldView& f, const float* node_pos, const float* node_w, int first, int D,
+                                  uint8_t* marks, int32_t* offsets, int32_t* chunk_sums, int32_t* total, hipStream_t s);
+// Step 2: the new bricks become records [records, records + fresh) with a search over all D nodes (grid: the node grid or
+// null = scan), and every voxel of the records [0, records) merges the nodes [D_old, D) into its list.
+hipError_t launch_knn_field_extend(const KnnFieldView& f, const float* node_pos, int D_old, int D, size_t records, size_t fresh,
+                                   const int32_t* offsets, const KnnGridView* grid, hipStream_t s);
+hipError_t launch_knn_field_lookup(const KnnFieldView& f, const int32_t* voxels, int n, int32_t* out_idx, hipStream_t s);
+// the two warped sweeps with the neighbours read from the field (records: the number of stored bricks)
+hipError_t launch_tsdf_integrate_warped_field(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol,
+                                              uint8_t* occ, float trunc_dist, int max_weight, const float vol2cam[12], float fx,
+                                              float fy, float cx, float cy, const float* node_pos, const float* node_dq,
+                                              const float* node_w, bool rigid, const KnnFieldView& f, size_t records,
+                                              hipStream_t s);
+hipError_t launch_tsdf_integrate_warped6_field(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol,
+                                               uint8_t* occ, float trunc_dist, int max_weight, const float* node2cam, float fx,
+                                               float fy, float cx, float cy, const float* node_pos, const float* node_dq,
+                                               const float* node_w, bool rigid, const KnnFieldView& f, size_t records,
+                                               hipStream_t s);
+
 hipError_t launch_correspond_projective(const float* verts, const float* normals, int n, const float* vmap, int vmap_step,
                                         const float* nmap, int nmap_step, int cols, int rows, float fx, float fy, float cx,
                                         float cy, float dist_thres, float min_cosine, float* out_v, float* out_n,

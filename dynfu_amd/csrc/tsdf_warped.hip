@@ -33,15 +33,11 @@
 #include "kernels.hpp"
 #include "knn_device.hpp"
 #include "tsdf_integrate_device.hpp"
+#include "warped_mark_device.hpp"
 
 namespace dfa {
 
-// A brick, in voxels.  One slice deep: a lane's voxels are searched one after the other, and the searches of a brick far from
-// the nodes are long (shells beyond the 3 x 3 x 3 block), so deeper bricks are fewer, longer workgroups with a long tail —
-// measured at 512^3, 2 048 nodes, k = 8 (tools/warped_integrate_timing.py, SKIP mode): 8 slices 9.39 ms, 4: 7.80, 2: 6.98,
-// 1: 4.47.  The code below holds for any depth that divides the occupancy box's 8.
-constexpr int WBX = 64, WBY = 4, WBZ = 1;
-
+// (the brick, 64 x 4 x 1 voxels: warped_bricks.hpp, shared with the k-NN field of knn_field.hip)
 size_t warped_brick_count(int X, int Y, int Z) {
     return (size_t)((X + WBX - 1) / WBX) * (size_t)((Y + WBY - 1) / WBY) * (size_t)((Z + WBZ - 1) / WBZ);
 }
@@ -62,43 +58,7 @@ __global__ __launch_bounds__(1024) void node_wmax_kernel(const float* __restrict
     }
 }
 
-// The bricks whose box of voxel POSITIONS comes within r of the point g (volume frame), marked by the 64 lanes of one wave.
-// The candidate range is widened by a voxel either side.
-__device__ __forceinline__ void mark_bricks_near(const float (&g)[3], float r, int X, int Y, int Z, float vsx, float vsy,
-                                                 float vsz, uint8_t* __restrict__ bricks) {
-    const float vs[3] = {vsx, vsy, vsz};
-    const int dim[3]  = {X, Y, Z};
-    const int bs[3]   = {WBX, WBY, WBZ};
-    int b0[3], nb[3];
-    for (int c = 0; c < 3; ++c) {
-        // voxel indices whose position can lie in [g - r, g + r]; the clamps also make the conversions safe (a NaN or an
-        // infinite radius ends as the whole axis)
-        const float inv = 1.f / fabsf(vs[c]);
-        float lo = (g[c] - r) * inv - 1.f, hi = (g[c] + r) * inv + 1.f;
-        if (vs[c] < 0.f) {
-            const float t = -lo;
-            lo = -hi, hi = t;
-        }
-        if (!(lo >= 0.f)) lo = 0.f;
-        if (!(hi <= (float)(dim[c] - 1))) hi = (float)(dim[c] - 1);
-        if (lo > hi) return;  // (uniform) the node is farther than w_max from the volume along this axis
-        b0[c] = (int)lo / bs[c];
-        nb[c] = (int)hi / bs[c] - b0[c] + 1;
-    }
-    const int nbx = (X + WBX - 1) / WBX, nby = (Y + WBY - 1) / WBY;
-    const long total = (long)nb[0] * nb[1] * nb[2];
-    for (long i = threadIdx.x; i < total; i += 64) {
-        const int b[3] = {b0[0] + (int)(i % nb[0]), b0[1] + (int)((i / nb[0]) % nb[1]), b0[2] + (int)(i / ((long)nb[0] * nb[1]))};
-        float d2 = 0.f;
-        for (int c = 0; c < 3; ++c) {
-            // the brick's first and last voxel position on this axis
-            const float pa = (float)(b[c] * bs[c]) * vs[c], pb = (float)min(b[c] * bs[c] + bs[c] - 1, dim[c] - 1) * vs[c];
-            const float d  = fmaxf(fmaxf(fminf(pa, pb) - g[c], g[c] - fmaxf(pa, pb)), 0.f);
-            d2 += d * d;
-        }
-        if (!(d2 > r * r)) bricks[((size_t)b[2] * nby + b[1]) * nbx + b[0]] = 1;  // (racing stores of the same byte)
-    }
-}
+// (mark_bricks_near — the bricks within r of a point, marked by one wave: warped_mark_device.hpp)
 
 // One wave per node: the bricks whose box of voxel POSITIONS comes within w_max of the node.  Conservative: the radius
 // is widened by 1e-3 relative and a millionth of the largest coordinate in play (the positions, differences and roots of

@@ -10,6 +10,7 @@
 // plus fuse(): the TSDF steps of operator() (:58,:108-115 — dists, clear, integrate) on a caller-
 // owned kfusion::cuda::TsdfVolume.  Vertices come from the caller (marching cubes is a later row).
 #pragma once
+#include <cstddef>
 #include <memory>
 #include <vector>
 
@@ -69,6 +70,15 @@ struct DynFuParams {  // dyn_fusion.hpp:25-42
     // (TsdfVolume::integrateWarped6; the node frame is frame 0's camera).  Off, nothing of this runs; on or off every other
     // output of a frame is the same, bit for bit.
     bool north_star_fuse_canonical = false;
+    // Extension — the canonical fusion without its per-voxel search.  With fuse_canonical or north_star_fuse_canonical (alone
+    // it means nothing: the constructor throws dfa::Error) the canonical volume gets a k-NN field when it is created
+    // (TsdfVolume::buildKnnField over frame 0's nodes), and before every warped integrate the field is brought up to date when
+    // the warp field holds more nodes than it does (TsdfVolume::appendKnnField: Warpfield::update only ever appends).  The
+    // canonical volume is the one the searching calls fuse, bit for bit.  fuse_knn_field_max_bytes bounds the field's rows
+    // (0: no cap): when a build or append would exceed it the field is dropped and the sequence goes on searching.  Off,
+    // nothing of this runs.
+    bool fuse_knn_field = false;
+    size_t fuse_knn_field_max_bytes = 0;
 };
 
 struct dfa_solver6;  // include/dynfu_amd.h
@@ -165,7 +175,9 @@ private:
     std::shared_ptr<dynfu::Frame> extractSurface(int frame_id, bool with_normals);
     bool northStarFrame(const kfusion::cuda::Depth& depth);  // operator() in north-star mode
     std::shared_ptr<kfusion::cuda::TsdfVolume> canonical_volume_;  // fuse_canonical, north_star_fuse_canonical
+    bool knn_field_dropped_ = false;  // fuse_knn_field: the field exceeded fuse_knn_field_max_bytes and is not tried again
     void createCanonicalVolume();  // frame 0: a copy of the live volume
+    void syncKnnField();           // fuse_knn_field: the canonical volume's field built, or appended to, for the nodes as they are
     kfusion::cuda::Cloud live_points_;
     kfusion::cuda::Normals live_normals_;
     // model_view: the canonical mesh (frame 0) as a frame for Warpfield::warpToLive and as float4 vertices + indices, the

@@ -7,8 +7,11 @@
 // Not provided: get,setGridOrigin (not on the DynFusion path).
 #pragma once
 #include <algorithm>
+#include <memory>
 
 #include <kfusion/types.hpp>
+
+struct dfa_knn_field;  // include/dynfu_amd.h
 
 namespace kfusion {
 namespace cuda {
@@ -32,15 +35,28 @@ class TsdfVolume {
     // handle is alive all make it unknown until the next clear / fused sweep by a sole owner.
     CudaData occ_;
     mutable bool occ_known_ = false;  // (mutable: copying a volume makes the SOURCE's map unknown too)
+    // The k-NN field of the volume (dynfu_amd.h: dfa_knn_field_*), when one has been built: the neighbour rows of the voxels,
+    // which integrateWarped / integrateWarped6 read instead of searching while the field matches their call.  What it was
+    // created for is kept beside the handle; copies of the object share it (it depends on the geometry, not on the voxels).
+    struct KnnFieldState {
+        std::shared_ptr<dfa_knn_field> handle;
+        Vec3i dims;
+        Vec3f voxel;
+        int k = 0;
+        bool has_frame = false;
+        float vol2node[12] = {};
+    } field_;
+    // the field when it serves a call with this k, node count and frame (vol2node: null for integrateWarped), else null
+    const dfa_knn_field* matchingField(int k, int D, const float* vol2node) const;
     bool soleOwner() const { return blob_.unique() && occ_.unique(); }
     bool mapTrusted() const { return occ_known_ && soleOwner(); }
 
 public:
     // --- construction / storage -----------------------------------------------------------------------------
     explicit TsdfVolume(const Vec3i& dims) { cfg_.dims = dims, create(dims); }
-    TsdfVolume(const TsdfVolume& o) : cfg_(o.cfg_), blob_(o.blob_), occ_(o.occ_) { o.occ_known_ = false; }
+    TsdfVolume(const TsdfVolume& o) : cfg_(o.cfg_), blob_(o.blob_), occ_(o.occ_), field_(o.field_) { o.occ_known_ = false; }
     TsdfVolume& operator=(const TsdfVolume& o) {
-        if (this != &o) cfg_ = o.cfg_, blob_ = o.blob_, occ_ = o.occ_, occ_known_ = false, o.occ_known_ = false;
+        if (this != &o) cfg_ = o.cfg_, blob_ = o.blob_, occ_ = o.occ_, field_ = o.field_, occ_known_ = false, o.occ_known_ = false;
         return *this;
     }
     virtual ~TsdfVolume() {}
@@ -72,6 +88,19 @@ public:
     void integrateWarped6(const Dists& dists, const Affine3f& camera_pose, const Intr& intr, const Affine3f& node_frame_pose,
                           const float* node_pos, const float* node_dq, const float* node_w, int D, int k,
                           UnsupportedMode mode = UnsupportedMode::Skip);
+    // The k-NN field (dfa_knn_field_*): the neighbours of every voxel near a node searched once — buildKnnField — and brought
+    // up to date when nodes have been appended — appendKnnField: the arrays hold the old nodes, unchanged, followed by the new
+    // ones —, so that integrateWarped / integrateWarped6 with the same k, node count and (integrateWarped6: node_frame_pose
+    // given here) frame run without their search: the same voxels and map, bit for bit.  A call the field does not match
+    // searches as before.  max_bytes bounds the rows (0: no cap); a build or append that would exceed it drops the field and
+    // returns false.  The field belongs to the volume's dimensions, size and pose as they are now.  Extension of the
+    // reference's interface.
+    bool buildKnnField(const float* node_pos, const float* node_w, int D, int k, const Affine3f* node_frame_pose = nullptr,
+                       size_t max_bytes = 0);
+    bool appendKnnField(const float* node_pos, const float* node_w, int D_new);
+    void dropKnnField() { field_ = KnnFieldState(); }
+    const dfa_knn_field* knnField() const { return field_.handle.get(); }
+    int knnFieldNodes() const;  // the node count of the field's rows (0 without a field)
     // the voxels of another volume of the same dimensions, copied (a copy of the OBJECT shares them); the map comes along
     // when the source's is trusted.  Extension of the reference's interface.
     void copyVoxelsFrom(const TsdfVolume& src);

@@ -51,6 +51,8 @@ DynFusion::DynFusion(const DynFuParams& params) : kfusion::KinFu(params.kinfuPar
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: fuse_canonical is a reference-mode extension (north_star blends otherwise, in the camera frame: north_star_fuse_canonical)");
     if (params.north_star_fuse_canonical && !params.north_star)
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_fuse_canonical needs north_star (reference mode: fuse_canonical)");
+    if (params.fuse_knn_field && !params.fuse_canonical && !params.north_star_fuse_canonical)
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion: fuse_knn_field serves the canonical fusion (fuse_canonical or north_star_fuse_canonical)");
     solverParams.numIter       = 24;  // dyn_fusion.cpp:183-189
     solverParams.nonLinearIter = 16;
     solverParams.linearIter    = 256;
@@ -207,6 +209,26 @@ void DynFusion::createCanonicalVolume() {
     canonical_volume_->setRaycastStepFactor(tsdf().getRaycastStepFactor());
     canonical_volume_->setGradientDeltaFactor(tsdf().getGradientDeltaFactor());
     canonical_volume_->copyVoxelsFrom(tsdf());
+    knn_field_dropped_ = false;
+    if (dynfuParams.fuse_knn_field) syncKnnField();
+}
+
+// fuse_knn_field, before a warped integrate (and at frame 0): the canonical volume's k-NN field over the nodes as they are
+// now — built when there is none yet, appended to when the warp field has grown (Warpfield::update only appends).  Beyond
+// fuse_knn_field_max_bytes the field is dropped for good and the integrations search.
+void DynFusion::syncKnnField() {
+    if (knn_field_dropped_) return;
+    const Warpfield::DeviceNodeView nodes = warpfield->deviceNodes(false);
+    kfusion::cuda::TsdfVolume& vol        = *canonical_volume_;
+    bool ok = true;
+    if (!vol.knnField()) {
+        const dfa::Affine3f camera;  // north-star mode: the node frame is frame 0's camera, which stays at the origin
+        ok = vol.buildKnnField(nodes.pos, nodes.w, nodes.D, dynfuParams.north_star ? std::min(warpfield->getKnn(), 8) : warpfield->getKnn(),
+                               dynfuParams.north_star ? &camera : nullptr, dynfuParams.fuse_knn_field_max_bytes);
+    } else if (vol.knnFieldNodes() < nodes.D) {
+        ok = vol.appendKnnField(nodes.pos, nodes.w, nodes.D);
+    }
+    if (!ok) knn_field_dropped_ = true;
 }
 
 bool DynFusion::operator()(const kfusion::cuda::Depth& depth) {
@@ -234,6 +256,7 @@ bool DynFusion::operator()(const kfusion::cuda::Depth& depth) {
     warpCanonicalToLiveOpt(camera);      // :140
     clk.mark("warpCanonicalToLiveOpt");
     if (dynfuParams.fuse_canonical) {  // step 4 of :39-47: this frame's depth into the canonical volume, through the solved field
+        if (dynfuParams.fuse_knn_field) syncKnnField();
         const Warpfield::DeviceNodeView nodes = warpfield->deviceNodes();
         canonical_volume_->integrateWarped(dists_, camera, p.intr, nodes.pos, nodes.dq, nodes.w, nodes.D, warpfield->getKnn());
         clk.mark("integrateWarped");
@@ -283,6 +306,7 @@ bool DynFusion::northStarFrame(const kfusion::cuda::Depth& depth) {
     if (dynfuParams.north_star_fuse_canonical) {
         // this frame's depth into the canonical volume through the solved field: the nodes hold the solved transforms now, and
         // the field has not grown yet.  The node frame is frame 0's camera — `camera`: it stays at the origin
+        if (dynfuParams.fuse_knn_field) syncKnnField();
         const Warpfield::DeviceNodeView nodes = warpfield->deviceNodes();
         canonical_volume_->integrateWarped6(dists_, camera, p.intr, camera, nodes.pos, nodes.dq, nodes.w, nodes.D,
                                             std::min(warpfield->getKnn(), 8));

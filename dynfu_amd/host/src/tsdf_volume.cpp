@@ -1,6 +1,7 @@
 // tsdf_volume.cpp — kfusion::cuda::TsdfVolume on the dynfu_amd C ABI
 // (host logic follows src/kfusion/tsdf_volume.cpp:18-129; kernels are in libdynfu_amd.so).
 #include <algorithm>
+#include <cstring>
 
 #include <hip/hip_runtime.h>
 #include <kfusion/cuda/tsdf_volume.hpp>
@@ -58,12 +59,20 @@ void TsdfVolume::integrateWarped(const Dists& dists, const Affine3f& camera_pose
     float aff[12];
     vol2cam.to12(aff);
     const Vec3f vsz = getVoxelSize();
+    const int unsupported = mode == UnsupportedMode::Rigid ? DFA_WARPED_RIGID : DFA_WARPED_SKIP;
     // (the call only ADDS to the map, as the accumulating sweep does: it has to be right before)
-    dfa::check(dfa_tsdf_integrate_warped(dists.ptr(), (int)dists.step(), dists.cols(), dists.rows(), blob_.ptr<uint32_t>(), cfg_.dims[0],
-                                         cfg_.dims[1], cfg_.dims[2], mapTrusted() ? occ_.ptr<uint8_t>() : nullptr, vsz.v, cfg_.trunc,
-                                         cfg_.max_weight, aff, intr.fx, intr.fy, intr.cx, intr.cy, node_pos, node_dq, node_w, D, k,
-                                         mode == UnsupportedMode::Rigid ? DFA_WARPED_RIGID : DFA_WARPED_SKIP, nullptr),
-               "TsdfVolume::integrateWarped");
+    if (const dfa_knn_field* field = matchingField(k, D, nullptr))  // the neighbours are known: no search
+        dfa::check(dfa_tsdf_integrate_warped_field(dists.ptr(), (int)dists.step(), dists.cols(), dists.rows(), blob_.ptr<uint32_t>(),
+                                                   cfg_.dims[0], cfg_.dims[1], cfg_.dims[2], mapTrusted() ? occ_.ptr<uint8_t>() : nullptr,
+                                                   vsz.v, cfg_.trunc, cfg_.max_weight, aff, intr.fx, intr.fy, intr.cx, intr.cy, node_pos,
+                                                   node_dq, node_w, D, k, unsupported, field, nullptr),
+                   "TsdfVolume::integrateWarped (k-NN field)");
+    else
+        dfa::check(dfa_tsdf_integrate_warped(dists.ptr(), (int)dists.step(), dists.cols(), dists.rows(), blob_.ptr<uint32_t>(), cfg_.dims[0],
+                                             cfg_.dims[1], cfg_.dims[2], mapTrusted() ? occ_.ptr<uint8_t>() : nullptr, vsz.v, cfg_.trunc,
+                                             cfg_.max_weight, aff, intr.fx, intr.fy, intr.cx, intr.cy, node_pos, node_dq, node_w, D, k,
+                                             unsupported, nullptr),
+                   "TsdfVolume::integrateWarped");
     dfa::device_synchronize();  // (as integrate())
 }
 
@@ -75,13 +84,62 @@ void TsdfVolume::integrateWarped6(const Dists& dists, const Affine3f& camera_pos
     (node_frame_pose.inv() * cfg_.pose).to12(vol2node);
     (camera_pose.inv() * node_frame_pose).to12(node2cam);
     const Vec3f vsz = getVoxelSize();
+    const int unsupported = mode == UnsupportedMode::Rigid ? DFA_WARPED_RIGID : DFA_WARPED_SKIP;
     // (the call only ADDS to the map, as the accumulating sweep does: it has to be right before)
-    dfa::check(dfa_tsdf_integrate_warped6(dists.ptr(), (int)dists.step(), dists.cols(), dists.rows(), blob_.ptr<uint32_t>(), cfg_.dims[0],
-                                          cfg_.dims[1], cfg_.dims[2], mapTrusted() ? occ_.ptr<uint8_t>() : nullptr, vsz.v, cfg_.trunc,
-                                          cfg_.max_weight, vol2node, node2cam, intr.fx, intr.fy, intr.cx, intr.cy, node_pos, node_dq,
-                                          node_w, D, k, mode == UnsupportedMode::Rigid ? DFA_WARPED_RIGID : DFA_WARPED_SKIP, nullptr),
-               "TsdfVolume::integrateWarped6");
+    if (const dfa_knn_field* field = matchingField(k, D, vol2node))  // the neighbours are known: no search
+        dfa::check(dfa_tsdf_integrate_warped6_field(dists.ptr(), (int)dists.step(), dists.cols(), dists.rows(), blob_.ptr<uint32_t>(),
+                                                    cfg_.dims[0], cfg_.dims[1], cfg_.dims[2], mapTrusted() ? occ_.ptr<uint8_t>() : nullptr,
+                                                    vsz.v, cfg_.trunc, cfg_.max_weight, vol2node, node2cam, intr.fx, intr.fy, intr.cx,
+                                                    intr.cy, node_pos, node_dq, node_w, D, k, unsupported, field, nullptr),
+                   "TsdfVolume::integrateWarped6 (k-NN field)");
+    else
+        dfa::check(dfa_tsdf_integrate_warped6(dists.ptr(), (int)dists.step(), dists.cols(), dists.rows(), blob_.ptr<uint32_t>(), cfg_.dims[0],
+                                              cfg_.dims[1], cfg_.dims[2], mapTrusted() ? occ_.ptr<uint8_t>() : nullptr, vsz.v, cfg_.trunc,
+                                              cfg_.max_weight, vol2node, node2cam, intr.fx, intr.fy, intr.cx, intr.cy, node_pos, node_dq,
+                                              node_w, D, k, unsupported, nullptr),
+                   "TsdfVolume::integrateWarped6");
     dfa::device_synchronize();  // (as integrate())
+}
+
+// ---- the k-NN field
+bool TsdfVolume::buildKnnField(const float* node_pos, const float* node_w, int D, int k, const Affine3f* node_frame_pose, size_t max_bytes) {
+    KnnFieldState f;
+    f.dims = cfg_.dims, f.voxel = getVoxelSize(), f.k = k, f.has_frame = node_frame_pose != nullptr;
+    if (node_frame_pose) (node_frame_pose->inv() * cfg_.pose).to12(f.vol2node);  // as integrateWarped6 forms it
+    dfa_knn_field* h = nullptr;
+    dfa::check(dfa_knn_field_create(f.dims[0], f.dims[1], f.dims[2], f.voxel.v, k, f.has_frame ? f.vol2node : nullptr, max_bytes, &h),
+               "TsdfVolume::buildKnnField");
+    f.handle.reset(h, dfa_knn_field_destroy);
+    field_ = KnnFieldState();
+    const int rc = dfa_knn_field_build(h, node_pos, node_w, D, nullptr);
+    if (rc == DFA_ERR_CAPACITY) return false;  // (the field is dropped: the integrations search)
+    dfa::check(rc, "TsdfVolume::buildKnnField");
+    field_ = f;
+    return true;
+}
+
+bool TsdfVolume::appendKnnField(const float* node_pos, const float* node_w, int D_new) {
+    if (!field_.handle) throw dfa::Error(DFA_ERR_INVALID, "TsdfVolume::appendKnnField: the volume has no k-NN field");
+    const int rc = dfa_knn_field_append(field_.handle.get(), node_pos, node_w, D_new, nullptr);
+    if (rc == DFA_ERR_CAPACITY) return dropKnnField(), false;
+    dfa::check(rc, "TsdfVolume::appendKnnField");
+    return true;
+}
+
+int TsdfVolume::knnFieldNodes() const {
+    if (!field_.handle) return 0;
+    dfa_knn_field_desc d;
+    dfa::check(dfa_knn_field_info(field_.handle.get(), &d), "TsdfVolume::knnFieldNodes");
+    return d.D;
+}
+
+const dfa_knn_field* TsdfVolume::matchingField(int k, int D, const float* vol2node) const {
+    const KnnFieldState& f = field_;
+    const Vec3f vsz        = getVoxelSize();
+    if (!f.handle || f.k != k || f.has_frame != (vol2node != nullptr) || knnFieldNodes() != D) return nullptr;
+    if (std::memcmp(f.dims.v, cfg_.dims.v, sizeof(f.dims.v)) != 0 || std::memcmp(f.voxel.v, vsz.v, sizeof(vsz.v)) != 0) return nullptr;
+    if (vol2node && std::memcmp(f.vol2node, vol2node, sizeof(f.vol2node)) != 0) return nullptr;
+    return f.handle.get();
 }
 
 void TsdfVolume::copyVoxelsFrom(const TsdfVolume& src) {

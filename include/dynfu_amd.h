@@ -43,7 +43,7 @@ enum {
     DFA_OK           = 0,
     DFA_ERR_INVALID  = 1, /* bad argument (null pointer, non-positive size, unsupported k, ...) */
     DFA_ERR_HIP      = 2, /* a HIP runtime call or kernel launch failed */
-    DFA_ERR_CAPACITY = 3, /* a solver plan is too small for the problem handed to it */
+    DFA_ERR_CAPACITY = 3, /* a solver plan is too small for the problem handed to it; a k-NN field would exceed its max_bytes */
     DFA_ERR_NO_GPU   = 4  /* no HIP device visible */
 };
 
@@ -63,7 +63,8 @@ enum {
     DFA_STRUCT_SOLVE_TIMING  = 2, /* dfa_solve_timing  */
     DFA_STRUCT_SOLVE6_PARAMS = 3, /* dfa_solve6_params */
     DFA_STRUCT_SOLVE6_STATS  = 4, /* dfa_solve6_stats  */
-    DFA_STRUCT_SOLVE6_TIMING = 5  /* dfa_solve6_timing */
+    DFA_STRUCT_SOLVE6_TIMING = 5, /* dfa_solve6_timing */
+    DFA_STRUCT_KNN_FIELD_DESC = 6 /* dfa_knn_field_desc */
 };
 int dfa_abi_version(void);
 size_t dfa_abi_struct_size(int struct_id);
@@ -429,6 +430,71 @@ int dfa_tsdf_integrate_warped6(const uint16_t* dists, int dists_step, int cols, 
                                const float vol2node[12] /* may be NULL: identity */, const float node2cam[12] /* may be NULL: identity */,
                                float fx, float fy, float cx, float cy, const float* node_pos, const float* node_dq,
                                const float* node_w, int D, int k /* 1..8 */, int unsupported_mode, dfa_stream_t stream);
+
+/* k-NN field of a volume: the neighbour rows of the volume's voxels searched once and kept, so that the two warped
+ * integrations above can run without their per-voxel search (dfa_tsdf_integrate_warped_field / _warped6_field below) — what
+ * dfa_warp_to_live_graph is to dfa_warp_to_live.  The voxels never move and a warp field only ever appends nodes
+ * (Warpfield::update), so a row stays valid until nodes are appended, and dfa_knn_field_append brings it up to date.
+ *
+ * A field is an opaque, caller-owned object (as dfa_solver) that belongs to a volume geometry (X, Y, Z, voxel_size), a k
+ * (1..16), an optional rigid vol2node (NULL: identity; the rule of dfa_tsdf_integrate_warped6, refused when not rigid) and
+ * the node set (node_pos, node_w, D) of its last build / append.  It does not depend on the node transforms.
+ *   - The row of voxel (x, y, z): the first k ids of dfa_knn's contract at the voxel's search position — v = (x, y, z) *
+ *     voxel_size (float32 products), or c = R_n v + t_n with vol2node, by the expressions of the integrations —, int32,
+ *     ascending by (distance, index), -1 padded when D < k.
+ *   - Rows are stored per BRICK of 64 x 4 x 1 voxels (the workgroup of the warped sweeps): a brick is stored when its box of
+ *     voxel positions comes within a node's own radius of that node (widened as the sweeps' pre-pass widens), which holds
+ *     every voxel the support rule of dfa_unsupported_vertices can pass.  Every voxel of a stored brick keeps its full row,
+ *     supported or not; voxels of a partial brick beyond the volume's edge hold -1.  stored bricks x 256 x k x 4 bytes.
+ *   - max_bytes (0: no cap) bounds the rows' bytes: a build or append that would exceed it returns DFA_ERR_CAPACITY and has
+ *     written nothing — the field is then empty (build) or what it was (append).
+ * dfa_knn_field_create makes no HIP call.  Calls on one field are ordered by the caller (one stream, or synchronised); the
+ * node grid of a build / append is scratch of the stream, the rows are the field's.  build and append wait on the stream
+ * once, to read the number of bricks to store.  Node radii are > 0, as in the integrations.
+ *
+ * dfa_knn_field_build   discards what the field held, then marks, sizes and searches (the node grid for D >= 64, a scan of
+ *                       all nodes below, as the integrations).  D == 0 with NULL arrays is valid: an empty field.
+ * dfa_knn_field_append  nodes [D_field, D_new) are new; nodes below D_field are UNCHANGED — a contract the call cannot
+ *                       check.  D_new < D_field: DFA_ERR_INVALID; D_new == D_field: nothing happens.  The result is the
+ *                       field dfa_knn_field_build gives on all D_new nodes, id for id: bricks stored now for the first time
+ *                       are searched over all D_new nodes, every row stored before takes the top k by (distance, index) of
+ *                       itself and the new nodes (distances recomputed from the same float32 positions: exact).
+ * dfa_knn_field_info    the host-side description below.
+ * dfa_knn_field_lookup  the rows of n voxels (voxels: n x 3 int32 (x, y, z), device; out_idx: n x k int32, device); a row of
+ *                       -1 for a voxel outside the volume or in a brick that is not stored. */
+typedef struct dfa_knn_field dfa_knn_field;
+typedef struct dfa_knn_field_desc {
+    int32_t D, k;          /* nodes the rows were searched over; ids per row */
+    int64_t stored_bricks; /* bricks with a record                           */
+    int64_t total_bricks;  /* bricks of the volume                           */
+    uint64_t bytes;        /* stored_bricks x 256 x k x 4                    */
+} dfa_knn_field_desc;
+int dfa_knn_field_create(int X, int Y, int Z, const float voxel_size[3], int k, const float vol2node[12] /* may be NULL: identity */,
+                         size_t max_bytes /* 0: no cap */, dfa_knn_field** out);
+void dfa_knn_field_destroy(dfa_knn_field* field);
+int dfa_knn_field_build(dfa_knn_field* field, const float* node_pos, const float* node_w, int D, dfa_stream_t stream);
+int dfa_knn_field_append(dfa_knn_field* field, const float* node_pos, const float* node_w, int D_new, dfa_stream_t stream);
+int dfa_knn_field_info(const dfa_knn_field* field, dfa_knn_field_desc* info);
+int dfa_knn_field_lookup(const dfa_knn_field* field, const int32_t* voxels, int n, int32_t* out_idx, dfa_stream_t stream);
+
+/* dfa_tsdf_integrate_warped / dfa_tsdf_integrate_warped6 with every voxel's neighbours read from a field instead of
+ * searched: the same support rule, blend, update, store rule and occupancy rule on the same values — the volume and the
+ * occupancy map are those of the call without a field, bit for bit.  DFA_WARPED_SKIP launches one workgroup per stored
+ * brick; DFA_WARPED_RIGID covers every brick, bricks that are not stored taking p = v (p = c).  Refused with
+ * DFA_ERR_INVALID before any HIP call: a field whose geometry (X, Y, Z, voxel_size), k or D differ from the call's; a field
+ * with a vol2node handed to dfa_tsdf_integrate_warped_field; a vol2node that differs from the field's in any of its 12
+ * floats (NULL matches a field created with NULL only).  The node arrays are those of the field's last build / append. */
+int dfa_tsdf_integrate_warped_field(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* volume, int X, int Y, int Z,
+                                    uint8_t* occupancy, const float voxel_size[3], float trunc_dist, int max_weight,
+                                    const float vol2cam[12], float fx, float fy, float cx, float cy, const float* node_pos,
+                                    const float* node_dq, const float* node_w, int D, int k, int unsupported_mode,
+                                    const dfa_knn_field* field, dfa_stream_t stream);
+int dfa_tsdf_integrate_warped6_field(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* volume, int X, int Y, int Z,
+                                     uint8_t* occupancy, const float voxel_size[3], float trunc_dist, int max_weight,
+                                     const float vol2node[12] /* may be NULL: identity */, const float node2cam[12] /* may be NULL: identity */,
+                                     float fx, float fy, float cx, float cy, const float* node_pos, const float* node_dq,
+                                     const float* node_w, int D, int k /* 1..8 */, int unsupported_mode, const dfa_knn_field* field,
+                                     dfa_stream_t stream);
 
 /* Point-cloud plumbing between the seams (no arithmetic, bit copies).  The reference moves clouds between its
  * stages as pcl::PointCloud objects on the host; with the clouds resident in HBM the same two steps are:
