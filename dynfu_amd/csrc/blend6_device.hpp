@@ -1,7 +1,7 @@
 // blend6_device.hpp — the north-star (6-DoF) blend of a point's k nearest nodes, shared by its two users: the solve and its
 // warp (solve6_graph.hip: s6_permute normalises the weights once per plan; solve6_linearise.hip, solve6_update.hip:
 // s6_linearise and s6_warp blend) and the warped TSDF
-// sweep of tsdf_warped6.hip (one search, normalisation and blend per voxel).  Weights are the radial basis weights divided
+// sweep (warped_sweep_device.hpp: NorthStarWarp, one normalisation and blend per voxel).  Weights are the radial basis weights divided
 // by their row sum; a neighbour takes part when its id is >= 0 and its normalised weight is not 0; every transform is taken
 // to the hemisphere of the first such neighbour; a = sum w~ s r, b = sum w~ s d; the point is (a c a* + 2 b a*) / |a|^2.
 #pragma once

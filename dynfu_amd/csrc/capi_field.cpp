@@ -1,6 +1,6 @@
 // capi_field.cpp — C ABI (include/dynfu_amd.h), the k-NN field of a volume: dfa_knn_field_* and the two warped
 // integrations served from a field.  Argument checks, the field's memory and launcher calls only (capi_internal.hpp); the
-// kernels are in knn_field.hip, the size arithmetic in warped_bricks.hpp.
+// field's kernels are in knn_field.hip, the sweeps in tsdf_warped.hip, the size arithmetic in warped_bricks.hpp.
 #include <algorithm>
 #include <cstring>
 
@@ -34,8 +34,7 @@ namespace {
 // what the cached integrations require of a field, beyond the checks of the uncached calls
 int field_matches(const char* fn, const dfa_knn_field* f, int X, int Y, int Z, const float voxel_size[3], int k, int D,
                   const float* vol2node, bool reference_mode) {
-#define MATCH(cond, msg) \
-    if (!(cond)) return fail(DFA_ERR_INVALID, "%s: %s", fn, msg)
+#define MATCH(cond, msg) REQUIRE_AS(fn, cond, msg)
     MATCH(f, "null field");
     MATCH(f->v.X == X && f->v.Y == Y && f->v.Z == Z && std::memcmp(f->v.vs, voxel_size, sizeof(float) * 3) == 0,
           "the field belongs to another volume geometry");
@@ -156,17 +155,11 @@ int dfa_tsdf_integrate_warped_field(const uint16_t* dists, int dists_step, int c
                                     const float vol2cam[12], float fx, float fy, float cx, float cy, const float* node_pos,
                                     const float* node_dq, const float* node_w, int D, int k, int unsupported_mode,
                                     const dfa_knn_field* field, dfa_stream_t stream) {
-    REQUIRE(volume_args_ok(volume, X, Y, Z), "bad volume");
-    REQUIRE(dists && cols > 0 && rows > 0 && dists_step >= cols * 2, "bad dists image");
-    REQUIRE(voxel_size && vol2cam, "null parameter block");
-    REQUIRE(trunc_dist > 0.f, "trunc_dist must be positive");
-    REQUIRE(max_weight >= 0 && max_weight <= 65535, "max_weight must fit the 16-bit weight");
-    REQUIRE(D >= 0, "negative node count");
-    REQUIRE(D == 0 || (node_pos && node_dq && node_w), "nodes without positions, transforms or radii");
-    REQUIRE(k >= 1 && k <= DFA_MAX_KNN, "k out of range 1..16");
-    REQUIRE(unsupported_mode == DFA_WARPED_SKIP || unsupported_mode == DFA_WARPED_RIGID, "unknown unsupported_mode");
-    if (int rc = field_matches(__func__, field, X, Y, Z, voxel_size, k, D, nullptr, true)) return rc;
+    if (int rc = warped_args_ok(__func__, true, dists, dists_step, cols, rows, volume, X, Y, Z, voxel_size, vol2cam, trunc_dist,
+                                max_weight, node_pos, node_dq, node_w, D, k, unsupported_mode))
+        return rc;
     const bool rigid = unsupported_mode == DFA_WARPED_RIGID;
+    if (int rc = field_matches(__func__, field, X, Y, Z, voxel_size, k, D, nullptr, true)) return rc;
     if (D == 0 && !rigid) return DFA_OK;  // no node supports anything: every voxel is left alone
     dfa_knn_field* f = const_cast<dfa_knn_field*>(field);
     HIP_TRY(dfa::launch_tsdf_integrate_warped_field(dists, dists_step, cols, rows, volume, occupancy, trunc_dist, max_weight, vol2cam,
@@ -180,17 +173,11 @@ int dfa_tsdf_integrate_warped6_field(const uint16_t* dists, int dists_step, int 
                                      const float vol2node[12], const float node2cam[12], float fx, float fy, float cx, float cy,
                                      const float* node_pos, const float* node_dq, const float* node_w, int D, int k,
                                      int unsupported_mode, const dfa_knn_field* field, dfa_stream_t stream) {
-    REQUIRE(volume_args_ok(volume, X, Y, Z), "bad volume");
-    REQUIRE(dists && cols > 0 && rows > 0 && dists_step >= cols * 2, "bad dists image");
-    REQUIRE(voxel_size, "null parameter block");
-    REQUIRE(trunc_dist > 0.f, "trunc_dist must be positive");
-    REQUIRE(max_weight >= 0 && max_weight <= 65535, "max_weight must fit the 16-bit weight");
-    REQUIRE(D >= 0, "negative node count");
-    REQUIRE(D == 0 || (node_pos && node_dq && node_w), "nodes without positions, transforms or radii");
-    REQUIRE(k >= 1 && k <= 8, "k out of range 1..8");
-    REQUIRE(unsupported_mode == DFA_WARPED_SKIP || unsupported_mode == DFA_WARPED_RIGID, "unknown unsupported_mode");
-    if (int rc = field_matches(__func__, field, X, Y, Z, voxel_size, k, D, vol2node, false)) return rc;
+    if (int rc = warped_args_ok(__func__, false, dists, dists_step, cols, rows, volume, X, Y, Z, voxel_size, nullptr, trunc_dist,
+                                max_weight, node_pos, node_dq, node_w, D, k, unsupported_mode))
+        return rc;
     const bool rigid = unsupported_mode == DFA_WARPED_RIGID;
+    if (int rc = field_matches(__func__, field, X, Y, Z, voxel_size, k, D, vol2node, false)) return rc;
     if (D == 0 && !rigid) return DFA_OK;  // no node supports anything: every voxel is left alone
     dfa_knn_field* f = const_cast<dfa_knn_field*>(field);
     HIP_TRY(dfa::launch_tsdf_integrate_warped6_field(dists, dists_step, cols, rows, volume, occupancy, trunc_dist, max_weight, node2cam,

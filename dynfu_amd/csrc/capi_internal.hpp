@@ -33,8 +33,10 @@ inline int hip_fail(hipError_t e, const char* what) {
     return fail(e == hipErrorNoDevice ? DFA_ERR_NO_GPU : DFA_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
 }
 
-#define REQUIRE(cond, msg) \
-    if (!(cond)) return fail(DFA_ERR_INVALID, "%s: %s", __func__, msg)
+// (a check shared by several public functions reports under the name of the one that was called: `fn`, its __func__)
+#define REQUIRE_AS(fn, cond, msg) \
+    if (!(cond)) return fail(DFA_ERR_INVALID, "%s: %s", fn, msg)
+#define REQUIRE(cond, msg) REQUIRE_AS(__func__, cond, msg)
 // (`text` is what a failure reports: a call that moved into a helper keeps the words it failed under before)
 #define HIP_TRY_AS(expr, text)                         \
     do {                                               \
@@ -46,6 +48,25 @@ inline int hip_fail(hipError_t e, const char* what) {
 inline hipStream_t S(dfa_stream_t s) { return (hipStream_t)s; }
 
 inline bool volume_args_ok(const void* vol, int X, int Y, int Z) { return vol && X > 0 && Y > 0 && Z > 0; }
+
+// The argument checks the four warped integrations open with (dfa_tsdf_integrate_warped, _warped6 and their _field forms), in
+// one order and one wording, under the called function's name.  reference_mode: vol2cam belongs to the parameter block and k
+// goes up to DFA_MAX_KNN; otherwise (north-star) vol2cam is not looked at and k goes up to 8.
+inline int warped_args_ok(const char* fn, bool reference_mode, const uint16_t* dists, int dists_step, int cols, int rows,
+                          const uint32_t* volume, int X, int Y, int Z, const float* voxel_size, const float* vol2cam,
+                          float trunc_dist, int max_weight, const float* node_pos, const float* node_dq, const float* node_w, int D,
+                          int k, int unsupported_mode) {
+    REQUIRE_AS(fn, volume_args_ok(volume, X, Y, Z), "bad volume");
+    REQUIRE_AS(fn, dists && cols > 0 && rows > 0 && dists_step >= cols * 2, "bad dists image");
+    REQUIRE_AS(fn, voxel_size && (vol2cam || !reference_mode), "null parameter block");
+    REQUIRE_AS(fn, trunc_dist > 0.f, "trunc_dist must be positive");
+    REQUIRE_AS(fn, max_weight >= 0 && max_weight <= 65535, "max_weight must fit the 16-bit weight");
+    REQUIRE_AS(fn, D >= 0, "negative node count");
+    REQUIRE_AS(fn, D == 0 || (node_pos && node_dq && node_w), "nodes without positions, transforms or radii");
+    REQUIRE_AS(fn, k >= 1 && k <= (reference_mode ? DFA_MAX_KNN : 8), reference_mode ? "k out of range 1..16" : "k out of range 1..8");
+    REQUIRE_AS(fn, unsupported_mode == DFA_WARPED_SKIP || unsupported_mode == DFA_WARPED_RIGID, "unknown unsupported_mode");
+    return DFA_OK;
+}
 
 // device scratch of one uniform grid (warp.hip): the node grid of the k-NN searches and, with more cells, the grid part
 // of dfa_correspond's point grid.  (Declared in a named namespace: stream_scratch<GridScratch> is ONE table per process,

@@ -2,6 +2,7 @@
 // integrations, marching cubes and the point-cloud extraction, with the scratch each keeps per stream.  Argument checks
 // and launcher calls only (capi_internal.hpp); the kernels are in tsdf.hip, tsdf_warped.hip, mc.hip and extract.hip.
 #include "capi_internal.hpp"
+#include "warped_bricks.hpp"
 
 using namespace dfa::capi;
 using dfa::DeviceBuffer;
@@ -38,7 +39,8 @@ struct WarpedScratch {
 int warped_scratch(int X, int Y, int Z, const float* node_pos, int D, dfa_stream_t stream, WarpedScratch** scratch,
                    const dfa::KnnGridView** grid) {
     WarpedScratch& ws = stream_scratch<WarpedScratch>(S(stream));
-    HIP_TRY(ws.bricks.reserve(dfa::warped_brick_count(X, Y, Z)));
+    // (the words this reservation failed under while the count had a name of its own)
+    HIP_TRY_AS(ws.bricks.reserve(dfa::knn_field_bricks(X, Y, Z)), "ws.bricks.reserve(dfa::warped_brick_count(X, Y, Z))");
     HIP_TRY(ws.wmax.reserve(1));
     *scratch = &ws;
     return warped_node_grid(node_pos, D, S(stream), grid);
@@ -323,15 +325,9 @@ int dfa_tsdf_integrate_warped(const uint16_t* dists, int dists_step, int cols, i
                               const float vol2cam[12], float fx, float fy, float cx, float cy, const float* node_pos,
                               const float* node_dq, const float* node_w, int D, int k, int unsupported_mode,
                               dfa_stream_t stream) {
-    REQUIRE(volume_args_ok(volume, X, Y, Z), "bad volume");
-    REQUIRE(dists && cols > 0 && rows > 0 && dists_step >= cols * 2, "bad dists image");
-    REQUIRE(voxel_size && vol2cam, "null parameter block");
-    REQUIRE(trunc_dist > 0.f, "trunc_dist must be positive");
-    REQUIRE(max_weight >= 0 && max_weight <= 65535, "max_weight must fit the 16-bit weight");
-    REQUIRE(D >= 0, "negative node count");
-    REQUIRE(D == 0 || (node_pos && node_dq && node_w), "nodes without positions, transforms or radii");
-    REQUIRE(k >= 1 && k <= DFA_MAX_KNN, "k out of range 1..16");
-    REQUIRE(unsupported_mode == DFA_WARPED_SKIP || unsupported_mode == DFA_WARPED_RIGID, "unknown unsupported_mode");
+    if (int rc = warped_args_ok(__func__, true, dists, dists_step, cols, rows, volume, X, Y, Z, voxel_size, vol2cam, trunc_dist,
+                                max_weight, node_pos, node_dq, node_w, D, k, unsupported_mode))
+        return rc;
     const bool rigid = unsupported_mode == DFA_WARPED_RIGID;
     if (D == 0 && !rigid) return DFA_OK;  // no node supports anything: every voxel is left alone
     WarpedScratch* ws;
@@ -348,18 +344,12 @@ int dfa_tsdf_integrate_warped6(const uint16_t* dists, int dists_step, int cols, 
                                const float vol2node[12], const float node2cam[12], float fx, float fy, float cx, float cy,
                                const float* node_pos, const float* node_dq, const float* node_w, int D, int k,
                                int unsupported_mode, dfa_stream_t stream) {
-    REQUIRE(volume_args_ok(volume, X, Y, Z), "bad volume");
-    REQUIRE(dists && cols > 0 && rows > 0 && dists_step >= cols * 2, "bad dists image");
-    REQUIRE(voxel_size, "null parameter block");
-    REQUIRE(trunc_dist > 0.f, "trunc_dist must be positive");
-    REQUIRE(max_weight >= 0 && max_weight <= 65535, "max_weight must fit the 16-bit weight");
-    REQUIRE(D >= 0, "negative node count");
-    REQUIRE(D == 0 || (node_pos && node_dq && node_w), "nodes without positions, transforms or radii");
-    REQUIRE(k >= 1 && k <= 8, "k out of range 1..8");
-    REQUIRE(unsupported_mode == DFA_WARPED_SKIP || unsupported_mode == DFA_WARPED_RIGID, "unknown unsupported_mode");
+    if (int rc = warped_args_ok(__func__, false, dists, dists_step, cols, rows, volume, X, Y, Z, voxel_size, nullptr, trunc_dist,
+                                max_weight, node_pos, node_dq, node_w, D, k, unsupported_mode))
+        return rc;
+    const bool rigid = unsupported_mode == DFA_WARPED_RIGID;
     float node2vol[12], stretch, tmax;
     REQUIRE(dfa::warped6_frame(vol2node, node2vol, &stretch, &tmax), "vol2node must be rigid");
-    const bool rigid = unsupported_mode == DFA_WARPED_RIGID;
     if (D == 0 && !rigid) return DFA_OK;  // no node supports anything: every voxel is left alone
     WarpedScratch* ws;
     const dfa::KnnGridView* grid;

@@ -30,6 +30,12 @@ struct Aff3 {
     float m[9];
     float t[3];
 };
+// (host) the 12 floats of the C ABI, R row-major then t; null: the identity
+inline Aff3 aff3_from(const float* a) {
+    Aff3 A{{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, {0.f, 0.f, 0.f}};
+    for (int i = 0; a && i < 12; ++i) (i < 9 ? A.m[i] : A.t[i - 9]) = a[i];
+    return A;
+}
 __device__ __forceinline__ f3 mul(const Mat3& R, f3 v) {
     return mk3(dot(mk3(R.m[0], R.m[1], R.m[2]), v), dot(mk3(R.m[3], R.m[4], R.m[5]), v),
                dot(mk3(R.m[6], R.m[7], R.m[8]), v));

@@ -78,9 +78,9 @@ hipError_t launch_warp_to_live(const float* node_pos, const float* node_dq, cons
                                const float* verts, const float* normals, int N, float* out_verts, float* out_normals,
                                const KnnGridView* grid, hipStream_t s);
 
-// tsdf_warped.hip — a depth frame integrated through the warp field (dfa_tsdf_integrate_warped).  bricks: warped_brick_count
-// bytes and wmax: one float, both device scratch of the call; grid: the node grid (knn_grid_build) or null = scan all nodes
-size_t warped_brick_count(int X, int Y, int Z);
+// tsdf_warped.hip — a depth frame integrated through the warp field, the four sweeps: searching (here) and served from a k-NN
+// field (below, behind KnnFieldView).  dfa_tsdf_integrate_warped: bricks: knn_field_bricks(X, Y, Z) bytes (warped_bricks.hpp)
+// and wmax: one float, both device scratch of the call; grid: the node grid (knn_grid_build) or null = scan all nodes
 hipError_t launch_tsdf_integrate_warped(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol, int X, int Y,
                                         int Z, uint8_t* occ, const float voxel_size[3], float trunc_dist, int max_weight,
                                         const float vol2cam[12], float fx, float fy, float cx, float cy, const float* node_pos,
@@ -97,7 +97,7 @@ hipError_t launch_tsdf_integrate_warped6(const uint16_t* dists, int dists_step, 
                                          const float* node_dq, const float* node_w, int D, int k, bool rigid,
                                          const KnnGridView* grid, uint8_t* bricks, float* wmax, hipStream_t s);
 
-// knn_field.hip — the k-NN field of a volume (dfa_knn_field_*): per stored brick (the 64 x 4 x 1 voxels of the warped sweeps)
+// knn_field.hip — the k-NN field of a volume (dfa_knn_field_*: stored set, search, merge, lookup): per stored brick (the 64 x 4 x 1 voxels of the warped sweeps)
 // one record of k slots x 256 int32 ids, slot-major — ids[(record k + slot) 256 + voxel of the brick] —, a table brick ->
 // record (-1: not stored) and the list record -> brick.  A brick is stored when a node's OWN radius reaches its box.
 struct KnnFieldView {
@@ -119,7 +119,7 @@ hipError_t launch_knn_field_count(const KnnFieldView& f, const float* node_pos, 
 hipError_t launch_knn_field_extend(const KnnFieldView& f, const float* node_pos, int D_old, int D, size_t records, size_t fresh,
                                    const int32_t* offsets, const KnnGridView* grid, hipStream_t s);
 hipError_t launch_knn_field_lookup(const KnnFieldView& f, const int32_t* voxels, int n, int32_t* out_idx, hipStream_t s);
-// the two warped sweeps with the neighbours read from the field (records: the number of stored bricks)
+// tsdf_warped.hip — the two warped sweeps with the neighbours read from the field (records: the number of stored bricks)
 hipError_t launch_tsdf_integrate_warped_field(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol,
                                               uint8_t* occ, float trunc_dist, int max_weight, const float vol2cam[12], float fx,
                                               float fy, float cx, float cy, const float* node_pos, const float* node_dq,

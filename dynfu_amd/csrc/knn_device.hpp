@@ -1,7 +1,7 @@
 // knn_device.hpp — device side of the exact k-NN searches over the node grid, shared by the kernels of warp.hip and the
 // fused graph-build kernel of solve_graph.hip: the sorted candidate list, the distance expression, the one-lane-per-query grid
 // search (knn_grid_query) and the one-wave-per-query search (knn_wave_search) — and what a point does with its neighbour list:
-// the ordered blend (calc_dqb) and the support rule (support_min), shared with tsdf_warped.hip.  The grid itself is built in warp.hip.
+// the ordered blend (calc_dqb) and the support rule (support_min), shared with the warped sweeps (warped_sweep_device.hpp) and the k-NN field (knn_field.hip).  The grid itself is built in warp.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,5 +1,5 @@
 // tsdf_integrate_device.hpp — the per-voxel TSDF update of tsdf_volume.cu:65-91, shared by the sweeps of tsdf.hip (voxel
-// positions by the reference's running addition) and the warped sweep of tsdf_warped.hip (voxel positions through the
+// positions by the reference's running addition) and the warped sweeps of tsdf_warped.hip (warped_sweep_device.hpp: voxel positions through the
 // warp field): the argument block, the projector's divisions, the distance of one voxel and its running average.
 #pragma once
 #include <hip/hip_runtime.h>

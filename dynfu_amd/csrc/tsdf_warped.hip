@@ -1,46 +1,37 @@
 // tsdf_warped.hip — non-rigid TSDF fusion on gfx950: one depth frame integrated into the canonical volume THROUGH the warp
 // field (DynamicFusion's "dense non-rigid surface fusion"; the reference lists the step and never does it,
-// src/dynfu/dyn_fusion.cpp:39-47, :107-116).
+// src/dynfu/dyn_fusion.cpp:39-47, :107-116).  All four sweeps and their launchers: through the reference-mode or the north-star
+// (6-DoF) warp field, with a search per voxel or served from the k-NN field of knn_field.hip.
 //
-// Per voxel: v = (x, y, z) * voxel_size; its k nearest nodes (knn_device.hpp, dfa_knn's contract); the support rule of
-// Warpfield::getUnsupportedVertices (support_min); a supported voxel moves to p = dq_transform(calcDQB(v), v) — the
-// reference-mode blend of Warpfield::warpToLive (calc_dqb) —, an unsupported one is left alone (DFA_WARPED_SKIP) or stays at
-// p = v (DFA_WARPED_RIGID); from vc = R p + t on, the reference's integrate (tsdf_integrate_device.hpp: voxel_tsdf,
-// voxel_update<false>), unchanged.
+// Per voxel (warped_sweep_device.hpp, the one body of the four): v = (x, y, z) * voxel_size; its k nearest nodes
+// (knn_device.hpp, dfa_knn's contract); the support rule of Warpfield::getUnsupportedVertices (support_min); a supported voxel
+// moves to p = dq_transform(calcDQB(v), v) — the reference-mode blend of Warpfield::warpToLive (calc_dqb) — or by the blend of
+// blend6_device.hpp in the nodes' own frame, an unsupported one is left alone (DFA_WARPED_SKIP) or stays at p = v
+// (DFA_WARPED_RIGID); from the camera frame on, the reference's integrate (tsdf_integrate_device.hpp), unchanged.
 //
-// Layout.  A search per voxel is the cost of this first form, so the voxels that cannot be supported never search:
+// Layout.  A search per voxel is the cost of the searching form, so the voxels that cannot be supported never search:
 //   * a BRICK is the footprint of one workgroup of the sweep, 64 x 4 x 1 voxels (two occupancy boxes wide, two high:
 //     kernels.hpp OccDims).  A pre-pass (one wave per node) marks every brick whose box lies within w_max — the
-//     largest node radius — of the node, by byte stores of 1.  No node within w_max of a voxel means every quotient
-//     |v - g| / w >= |v - g| / w_max >= 1: the marked bricks are a superset of the bricks with a supported voxel;
+//     largest node radius — of the node, by byte stores of 1 (warped_mark_device.hpp): the marked bricks are a superset of
+//     the bricks with a supported voxel;
 //   * an unmarked brick does no search: it returns at once in SKIP mode (no memory touched) and takes p = v in RIGID mode;
 //   * a marked brick: one lane per voxel, a wave along x (its loads and stores are 256-byte row segments; the load is
-//     issued before the search), then the search, the rule, the blend and the update.  A voxel is stored only when the
-//     update changed it.
+//     issued before the search), then the search, the rule, the blend and the update.
+// The cached form reads the list the field stores for the voxel where the searching form searches; its bricks are the
+// field's stored ones (SKIP: one workgroup per stored brick and no other; RIGID: every brick, the table says which are stored).
 // Node radii are positive (a radius <= 0 has no meaning in the support rule).  No fused contraction beyond the fmaf()s of
 // the shared headers, no fast-math; vector stores only.
-//
-// The second half of the file is the same sweep for the north-star (6-DoF) warp field (dfa_tsdf_integrate_warped6): nodes in
-// their own frame, the blend of blend6_device.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 
-#include "blend6_device.hpp"
-#include "device_math.hpp"
-#include "dq_device.hpp"
 #include "kernels.hpp"
-#include "knn_device.hpp"
-#include "tsdf_integrate_device.hpp"
+#include "knn_field_device.hpp"
 #include "warped_mark_device.hpp"
+#include "warped_sweep_device.hpp"
 
 namespace dfa {
-
-// (the brick, 64 x 4 x 1 voxels: warped_bricks.hpp, shared with the k-NN field of knn_field.hip)
-size_t warped_brick_count(int X, int Y, int Z) {
-    return (size_t)((X + WBX - 1) / WBX) * (size_t)((Y + WBY - 1) / WBY) * (size_t)((Z + WBZ - 1) / WBZ);
-}
 
 // ------------------------------------------------------------------------------------------ support pre-pass
 // the largest node radius (NaN radii are ignored: fmaxf)
@@ -58,90 +49,108 @@ __global__ __launch_bounds__(1024) void node_wmax_kernel(const float* __restrict
     }
 }
 
-// (mark_bricks_near — the bricks within r of a point, marked by one wave: warped_mark_device.hpp)
-
-// One wave per node: the bricks whose box of voxel POSITIONS comes within w_max of the node.  Conservative: the radius
-// is widened by 1e-3 relative and a millionth of the largest coordinate in play (the positions, differences and roots of
-// the support rule are rounded at 1e-7 relative), the candidate range by a voxel either side.
+// One wave per node: the bricks whose box of voxel POSITIONS comes within w_max of the node (mark_radius, mark_bricks_near).
 __global__ __launch_bounds__(64) void mark_bricks_kernel(const float* __restrict__ node_pos, int D,
                                                          const float* __restrict__ wmax, int X, int Y, int Z, float vsx,
                                                          float vsy, float vsz, uint8_t* __restrict__ bricks) {
     const int node = blockIdx.x;
     if (node >= D) return;
     const float g[3] = {node_pos[3 * (size_t)node], node_pos[3 * (size_t)node + 1], node_pos[3 * (size_t)node + 2]};
-    const float ext  = fmaxf(fmaxf(fabsf(vsx) * (float)X, fabsf(vsy) * (float)Y), fabsf(vsz) * (float)Z);
-    const float r = *wmax * 1.001f + 1e-6f * fmaxf(ext, fmaxf(fmaxf(fabsf(g[0]), fabsf(g[1])), fabsf(g[2])));
+    const float ext  = volume_extent(X, Y, Z, vsx, vsy, vsz);
+    const float r    = mark_radius(*wmax, mk3(g[0], g[1], g[2]), ext);
     mark_bricks_near(g, r, X, Y, Z, vsx, vsy, vsz, bricks);
 }
 
-// ------------------------------------------------------------------------------------------ the sweep
-// block = (64, 4): a wave spans 64 voxels in x, the block 4 rows in y, a lane WBZ voxels in z — one brick per workgroup.
-// GRID: the neighbours come from the node grid (knn_grid_query); otherwise (few nodes) from a scan of all of them.
+// As mark_bricks_kernel for nodes of the north-star warp field, each taken back to the volume's frame (node2vol =
+// vol2node^-1) first (mark_radius_framed).
+__global__ __launch_bounds__(64) void mark_bricks6_kernel(const float* __restrict__ node_pos, int D,
+                                                          const float* __restrict__ wmax, const Aff3 node2vol, int has_frame,
+                                                          float stretch, float tmax, int X, int Y, int Z, float vsx, float vsy,
+                                                          float vsz, uint8_t* __restrict__ bricks) {
+    const int node = blockIdx.x;
+    if (node >= D) return;
+    const f3 gn = mk3(node_pos[3 * (size_t)node], node_pos[3 * (size_t)node + 1], node_pos[3 * (size_t)node + 2]);
+    const f3 gv = has_frame ? mulR(node2vol, gn) + mk3(node2vol.t[0], node2vol.t[1], node2vol.t[2]) : gn;
+    const float g[3] = {gv.x, gv.y, gv.z};
+    const float ext  = volume_extent(X, Y, Z, vsx, vsy, vsz);
+    const float r    = mark_radius_framed(*wmax, gn, gv, ext, stretch, tmax);
+    mark_bricks_near(g, r, X, Y, Z, vsx, vsy, vsz, bricks);
+}
+
+// ------------------------------------------------------------------------------------------ the sweeps
+// block = (64, 4), one brick per workgroup: each kernel finds its brick, says where the neighbours come from and which warp
+// moves a supported voxel, and runs warped_sweep_brick.  K holds k: 4, 8 or 16 in reference mode, 4 or 8 (k = 1..8) for the
+// north-star field.
+
+// (uniform) the pre-pass's mark of this workgroup's brick: a brick no node marked holds no supported voxel
+__device__ __forceinline__ bool brick_marked(const uint8_t* __restrict__ bricks) {
+    return bricks[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] != 0;
+}
+
+// the transforms of the north-star sweep
+struct Warped6Frames {
+    Aff3 vol2node, node2cam;  // read only where the flag below is set
+    int has_vol2node, has_node2cam;
+};
+
 template <int K, bool GRID>
 __global__ __launch_bounds__(256) void integrate_warped_kernel(const IntegrateArgs a, const float* __restrict__ node_pos,
                                                                const float* __restrict__ node_dq,
                                                                const float* __restrict__ node_w, int D, int k, int rigid,
                                                                const uint8_t* __restrict__ bricks, KnnGridView grid) {
-    // (uniform) a brick no node marked holds no supported voxel
-    const bool marked = bricks[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] != 0;
+    const bool marked = brick_marked(bricks);
     if (!marked && !rigid) return;
-    const int x = blockIdx.x * WBX + threadIdx.x;
-    const int y = blockIdx.y * WBY + threadIdx.y;
-    if (x >= a.X || y >= a.Y) return;
-    const int z0 = blockIdx.z * WBZ;
-    const int nz = min(WBZ, a.Z - z0);
-
-    const size_t slice = (size_t)a.X * a.Y;
-    uint32_t* ptr      = a.vol + (size_t)x + (size_t)a.X * y + slice * z0;
-    uint32_t cur[WBZ];
-#pragma unroll
-    for (int u = 0; u < WBZ; ++u) cur[u] = u < nz ? ptr[slice * u] : 0u;
-
-    KnnGridDesc g{};
-    if (GRID && marked) g = *grid.desc;
-    const f3 t = mk3(a.vol2cam.t[0], a.vol2cam.t[1], a.vol2cam.t[2]);
-    bool any   = false;  // an update happened: the voxel may hold a weight now
-    for (int u = 0; u < nz; ++u) {
-        const f3 v = mk3((float)x * a.vsx, (float)y * a.vsy, (float)(z0 + u) * a.vsz);  // the voxel's corner (tsdf_volume.cu:60), by multiplication
-        f3 p       = v;
-        bool go    = rigid != 0;
-        if (marked) {
-            KnnList<K> best;
-            if (GRID) {
-                knn_grid_query<K>(g, grid.cell_start, grid.sorted, v, best);
-            } else {
-                best.init();
-                for (int j = 0; j < D; ++j) best.push(dist2(v, node_pos[3 * j], node_pos[3 * j + 1], node_pos[3 * j + 2]), j);
-            }
-            if (support_min<K>(best, k, node_pos, node_w, v) < 1.f) {  // Warpfield::getUnsupportedVertices' rule
-                p  = dq_transform(calc_dqb<K>(best, k, node_pos, node_dq, node_w, v), v);  // Warpfield::warpToLive, vertex only
-                go = true;
-            }
-        }
-        if (!go) continue;
-        const f3 vc = mulR(a.vol2cam, p) + t;
-        float tsdf;
-        if (!voxel_tsdf(a, vc, tsdf)) continue;
-        const uint32_t upd = voxel_update<false>(a, cur[u], tsdf);
-        if (upd != cur[u]) ptr[slice * u] = upd;
-        any = true;
-    }
-    if (a.occ) {
-        // the two occupancy boxes a wave's row crosses (32 voxels each): lanes 0 and 32 write theirs when a lane of that half
-        // updated a voxel.  Both bits: the update may have left a negative distance.  Rows y and y + 1 share a byte and store
-        // the same value.
-        const unsigned long long m = __ballot(any);
-        if ((threadIdx.x & 31) == 0 && ((m >> threadIdx.x) & 0xffffffffull) != 0ull)
-            a.occ[(size_t)(x / 32) + (size_t)a.ox * ((size_t)(y / 2) + (size_t)a.oy * (size_t)(z0 / 8))] = 3;
-    }
+    SearchedNeighbours<K, GRID> nb{marked, node_pos, D, grid};
+    const ReferenceWarp warp(a.vol2cam);
+    warped_sweep_brick<K>(a, rigid, nb, warp, k, node_pos, node_dq, node_w);
 }
 
-// ------------------------------------------------------------------------------------------ launcher
-hipError_t launch_tsdf_integrate_warped(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol, int X, int Y,
-                                        int Z, uint8_t* occ, const float voxel_size[3], float trunc_dist, int max_weight,
-                                        const float vol2cam[12], float fx, float fy, float cx, float cy, const float* node_pos,
-                                        const float* node_dq, const float* node_w, int D, int k, bool rigid,
-                                        const KnnGridView* grid, uint8_t* bricks, float* wmax, hipStream_t s) {
+template <int K, bool GRID>
+__global__ __launch_bounds__(256) void integrate_warped6_kernel(const IntegrateArgs a, const Warped6Frames f,
+                                                                const float* __restrict__ node_pos,
+                                                                const float* __restrict__ node_dq,
+                                                                const float* __restrict__ node_w, int D, int k, int rigid,
+                                                                const uint8_t* __restrict__ bricks, KnnGridView grid) {
+    const bool marked = brick_marked(bricks);
+    if (!marked && !rigid) return;
+    SearchedNeighbours<K, GRID> nb{marked, node_pos, D, grid};
+    const NorthStarWarp warp{f.vol2node, f.has_vol2node, f.node2cam, f.has_node2cam};
+    warped_sweep_brick<K>(a, rigid, nb, warp, k, node_pos, node_dq, node_w);
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void integrate_warped_field_kernel(const IntegrateArgs a, const FieldGeom g,
+                                                                     const float* __restrict__ node_pos,
+                                                                     const float* __restrict__ node_dq,
+                                                                     const float* __restrict__ node_w, int rigid,
+                                                                     const int32_t* __restrict__ table,
+                                                                     const int32_t* __restrict__ coords,
+                                                                     const int32_t* __restrict__ ids) {
+    StoredNeighbours<K> nb(field_brick(g, table, coords, !rigid), ids, g.k);
+    const ReferenceWarp warp(a.vol2cam);
+    warped_sweep_brick<K>(a, rigid, nb, warp, g.k, node_pos, node_dq, node_w);
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void integrate_warped6_field_kernel(const IntegrateArgs a, const FieldGeom g, const Aff3 node2cam,
+                                                                      int has_node2cam, const float* __restrict__ node_pos,
+                                                                      const float* __restrict__ node_dq,
+                                                                      const float* __restrict__ node_w, int rigid,
+                                                                      const int32_t* __restrict__ table,
+                                                                      const int32_t* __restrict__ coords,
+                                                                      const int32_t* __restrict__ ids) {
+    StoredNeighbours<K> nb(field_brick(g, table, coords, !rigid), ids, g.k);
+    const NorthStarWarp warp{g.vol2node, g.has_frame, node2cam, has_node2cam};
+    warped_sweep_brick<K>(a, rigid, nb, warp, g.k, node_pos, node_dq, node_w);
+}
+
+// ------------------------------------------------------------------------------------------ launchers
+namespace {
+
+// the argument block of a warped sweep; vol2cam null: the identity (the sweep's frames are elsewhere and it is not read)
+IntegrateArgs warped_args(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol, int X, int Y, int Z, uint8_t* occ,
+                          const float voxel_size[3], float trunc_dist, int max_weight, const float* vol2cam, float fx, float fy,
+                          float cx, float cy) {
     IntegrateArgs a;
     a.dists = dists, a.dists_step = dists_step, a.cols = cols, a.rows = rows;
     a.vol = vol, a.X = X, a.Y = Y, a.Z = Z;
@@ -151,40 +160,38 @@ hipError_t launch_tsdf_integrate_warped(const uint16_t* dists, int dists_step, i
     a.trunc      = trunc_dist;
     a.trunc_inv  = 1.f / trunc_dist;  // tsdf_volume.cu:106
     a.max_weight = max_weight;
-    for (int i = 0; i < 9; ++i) a.vol2cam.m[i] = vol2cam[i];
-    for (int i = 0; i < 3; ++i) a.vol2cam.t[i] = vol2cam[9 + i];
+    a.vol2cam    = aff3_from(vol2cam);
     a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy;
     a.zchunk = WBZ;
+    return a;
+}
 
-    hipError_t e = hipMemsetAsync(bricks, 0, warped_brick_count(X, Y, Z), s);
+// the grid of a cached sweep.  SKIP: one workgroup per stored brick.  RIGID: every brick.
+dim3 field_sweep_grid(const KnnFieldView& f, bool rigid, size_t records) {
+    return rigid ? brick_grid(f.X, f.Y, f.Z) : dim3((unsigned)records);
+}
+
+}  // namespace
+
+hipError_t launch_tsdf_integrate_warped(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol, int X, int Y,
+                                        int Z, uint8_t* occ, const float voxel_size[3], float trunc_dist, int max_weight,
+                                        const float vol2cam[12], float fx, float fy, float cx, float cy, const float* node_pos,
+                                        const float* node_dq, const float* node_w, int D, int k, bool rigid,
+                                        const KnnGridView* grid, uint8_t* bricks, float* wmax, hipStream_t s) {
+    const IntegrateArgs a = warped_args(dists, dists_step, cols, rows, vol, X, Y, Z, occ, voxel_size, trunc_dist, max_weight, vol2cam,
+                                        fx, fy, cx, cy);
+    hipError_t e = hipMemsetAsync(bricks, 0, knn_field_bricks(X, Y, Z), s);
     if (e != hipSuccess) return e;
     if (D > 0) {
         node_wmax_kernel<<<1, 1024, 0, s>>>(node_w, D, wmax);
         mark_bricks_kernel<<<D, 64, 0, s>>>(node_pos, D, wmax, X, Y, Z, a.vsx, a.vsy, a.vsz, bricks);
     }
-    dim3 block(WBX, WBY), g3((X + WBX - 1) / WBX, (Y + WBY - 1) / WBY, (Z + WBZ - 1) / WBZ);
+    const dim3 block(WBX, WBY), g3 = brick_grid(X, Y, Z);
     const KnnGridView gv = grid ? *grid : KnnGridView{};
-#define WARPED(KK)                                                                                                                   \
-    do {                                                                                                                             \
-        if (grid) integrate_warped_kernel<KK, true><<<g3, block, 0, s>>>(a, node_pos, node_dq, node_w, D, k, rigid ? 1 : 0, bricks, gv);  \
-        else integrate_warped_kernel<KK, false><<<g3, block, 0, s>>>(a, node_pos, node_dq, node_w, D, k, rigid ? 1 : 0, bricks, gv);      \
-    } while (0)
-    if (k <= 4) WARPED(4);
-    else if (k <= 8) WARPED(8);
-    else WARPED(16);
-#undef WARPED
+    if (grid) KDISPATCH16(k, integrate_warped_kernel<KK, true><<<g3, block, 0, s>>>(a, node_pos, node_dq, node_w, D, k, rigid ? 1 : 0, bricks, gv));
+    else KDISPATCH16(k, integrate_warped_kernel<KK, false><<<g3, block, 0, s>>>(a, node_pos, node_dq, node_w, D, k, rigid ? 1 : 0, bricks, gv));
     return hipGetLastError();
 }
-
-// ------------------------------------------------------------------------------------------ the north-star sweep
-// dfa_tsdf_integrate_warped6: the same bricks, pre-pass idea, occupancy rule and store rule with the north-star (6-DoF)
-// blend of blend6_device.hpp.  North-star nodes live in the camera frame of frame 0, not in the volume's, so a voxel is
-// taken to the node frame first: c = R_n v + t_n (vol2node), the search, the support rule and the blend happen at c, and
-// the blended point goes on to the camera by node2cam.  Either transform may be absent (identity: no product is made).
-struct Warped6Frames {
-    Aff3 vol2node, node2cam;  // read only where the flag below is set
-    int has_vol2node, has_node2cam;
-};
 
 // vol2node checked and inverted on the host, in double: false when |R^T R - I| exceeds 1e-3 in some entry (the pre-pass
 // measures distances in the volume's frame, so the product has to keep them).  node2vol: the inverse, rounded to float;
@@ -222,144 +229,57 @@ bool warped6_frame(const float* vol2node, float node2vol[12], float* stretch, fl
     return true;
 }
 
-// One wave per node, as mark_bricks_kernel, with the node taken back to the volume's frame (node2vol = vol2node^-1) first.
-// A supported voxel has |c - g| < w <= w_max in the node frame, hence |v - g'| <= stretch w_max in the volume's, up to
-// the rounding of the two products: c = R_n v + t_n in the sweep and g' = R' g + t' here, each a few ulp of the
-// coordinates that enter it.  The radius is widened by the 1e-3 relative of mark_bricks_kernel times the stretch, and by a
-// millionth of the SUM of the coordinates in play in either frame: the volume's extent (twice: |R_n v| reaches sqrt 3 of
-// it), the node's coordinates in both frames and the translation.
-__global__ __launch_bounds__(64) void mark_bricks6_kernel(const float* __restrict__ node_pos, int D,
-                                                          const float* __restrict__ wmax, const Aff3 node2vol, int has_frame,
-                                                          float stretch, float tmax, int X, int Y, int Z, float vsx, float vsy,
-                                                          float vsz, uint8_t* __restrict__ bricks) {
-    const int node = blockIdx.x;
-    if (node >= D) return;
-    const f3 gn = mk3(node_pos[3 * (size_t)node], node_pos[3 * (size_t)node + 1], node_pos[3 * (size_t)node + 2]);
-    const f3 gv = has_frame ? mulR(node2vol, gn) + mk3(node2vol.t[0], node2vol.t[1], node2vol.t[2]) : gn;
-    const float g[3] = {gv.x, gv.y, gv.z};
-    const float ext  = fmaxf(fmaxf(fabsf(vsx) * (float)X, fabsf(vsy) * (float)Y), fabsf(vsz) * (float)Z);
-    const float L    = 2.f * ext + fmaxf(fmaxf(fabsf(gn.x), fabsf(gn.y)), fabsf(gn.z)) +
-                    fmaxf(fmaxf(fabsf(gv.x), fabsf(gv.y)), fabsf(gv.z)) + tmax;
-    const float r = *wmax * 1.001f * stretch + 1e-6f * L;
-    mark_bricks_near(g, r, X, Y, Z, vsx, vsy, vsz, bricks);
-}
-
-// block = (64, 4), one brick per workgroup, GRID as in integrate_warped_kernel.  K is 4 or 8 (k = 1..8).
-template <int K, bool GRID>
-__global__ __launch_bounds__(256) void integrate_warped6_kernel(const IntegrateArgs a, const Warped6Frames f,
-                                                                const float* __restrict__ node_pos,
-                                                                const float* __restrict__ node_dq,
-                                                                const float* __restrict__ node_w, int D, int k, int rigid,
-                                                                const uint8_t* __restrict__ bricks, KnnGridView grid) {
-    // (uniform) a brick no node marked holds no supported voxel
-    const bool marked = bricks[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] != 0;
-    if (!marked && !rigid) return;
-    const int x = blockIdx.x * WBX + threadIdx.x;
-    const int y = blockIdx.y * WBY + threadIdx.y;
-    if (x >= a.X || y >= a.Y) return;
-    const int z0 = blockIdx.z * WBZ;
-    const int nz = min(WBZ, a.Z - z0);
-
-    const size_t slice = (size_t)a.X * a.Y;
-    uint32_t* ptr      = a.vol + (size_t)x + (size_t)a.X * y + slice * z0;
-    uint32_t cur[WBZ];
-#pragma unroll
-    for (int u = 0; u < WBZ; ++u) cur[u] = u < nz ? ptr[slice * u] : 0u;
-
-    KnnGridDesc g{};
-    if (GRID && marked) g = *grid.desc;
-    bool any = false;  // an update happened: the voxel may hold a weight now
-    for (int u = 0; u < nz; ++u) {
-        const f3 v = mk3((float)x * a.vsx, (float)y * a.vsy, (float)(z0 + u) * a.vsz);  // the voxel's corner, by multiplication
-        // (uniform) the voxel in the node frame
-        const f3 c = f.has_vol2node ? mulR(f.vol2node, v) + mk3(f.vol2node.t[0], f.vol2node.t[1], f.vol2node.t[2]) : v;
-        f3 p       = c;
-        bool go    = rigid != 0;
-        if (marked) {
-            KnnList<K> best;
-            if (GRID) {
-                knn_grid_query<K>(g, grid.cell_start, grid.sorted, c, best);
-            } else {
-                best.init();
-                for (int j = 0; j < D; ++j) best.push(dist2(c, node_pos[3 * j], node_pos[3 * j + 1], node_pos[3 * j + 2]), j);
-            }
-            if (support_min<K>(best, k, node_pos, node_w, c) < 1.f) {  // Warpfield::getUnsupportedVertices' rule, at c
-                // the plan's graph row of a vertex at c (dfa_knn's ids and weights, s6_permute's normalisation), then
-                // s6_warp_kernel's rule
-                int id[K];
-                float wn[K];
-                knn_ids_weights<K>(best, k, node_pos, node_w, true, c, id, wn);
-                float sum = 0.f;
-#pragma unroll
-                for (int j = 0; j < K; ++j) sum = weight_sum_add(sum, &wn[j], j < k);
-#pragma unroll
-                for (int j = 0; j < K; ++j) wn[j] = normalised_weight(&wn[j], sum);
-                Blend<K> B;
-                blend<K>(node_dq, id, wn, k, B);
-                if (B.m > 0.f) p = blend_point<K>(B, c);
-                go = true;
-            }
-        }
-        if (!go) continue;
-        // (uniform) on to the camera
-        const f3 vc = f.has_node2cam ? mulR(f.node2cam, p) + mk3(f.node2cam.t[0], f.node2cam.t[1], f.node2cam.t[2]) : p;
-        float tsdf;
-        if (!voxel_tsdf(a, vc, tsdf)) continue;
-        const uint32_t upd = voxel_update<false>(a, cur[u], tsdf);
-        if (upd != cur[u]) ptr[slice * u] = upd;
-        any = true;
-    }
-    if (a.occ) {
-        // as integrate_warped_kernel: lanes 0 and 32 write the occupancy box of their half of the row when it updated a voxel
-        const unsigned long long m = __ballot(any);
-        if ((threadIdx.x & 31) == 0 && ((m >> threadIdx.x) & 0xffffffffull) != 0ull)
-            a.occ[(size_t)(x / 32) + (size_t)a.ox * ((size_t)(y / 2) + (size_t)a.oy * (size_t)(z0 / 8))] = 3;
-    }
-}
-
 hipError_t launch_tsdf_integrate_warped6(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol, int X, int Y,
                                          int Z, uint8_t* occ, const float voxel_size[3], float trunc_dist, int max_weight,
                                          const float* vol2node, const float* node2cam, const float node2vol[12], float stretch,
                                          float tmax, float fx, float fy, float cx, float cy, const float* node_pos,
                                          const float* node_dq, const float* node_w, int D, int k, bool rigid,
                                          const KnnGridView* grid, uint8_t* bricks, float* wmax, hipStream_t s) {
-    IntegrateArgs a;
-    a.dists = dists, a.dists_step = dists_step, a.cols = cols, a.rows = rows;
-    a.vol = vol, a.X = X, a.Y = Y, a.Z = Z;
-    const OccDims od = occ_dims(X, Y, Z);
-    a.occ = occ, a.ox = od.ox, a.oy = od.oy, a.occ_known = 0;
-    a.vsx = voxel_size[0], a.vsy = voxel_size[1], a.vsz = voxel_size[2];
-    a.trunc      = trunc_dist;
-    a.trunc_inv  = 1.f / trunc_dist;  // tsdf_volume.cu:106
-    a.max_weight = max_weight;
-    a.vol2cam    = Aff3{{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, {0.f, 0.f, 0.f}};  // (not read: the frames are in f)
-    a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy;
-    a.zchunk = WBZ;
-    Warped6Frames f{a.vol2cam, a.vol2cam, vol2node ? 1 : 0, node2cam ? 1 : 0};
-    Aff3 back = a.vol2cam;
-    for (int i = 0; i < 12; ++i) {
-        if (vol2node) (i < 9 ? f.vol2node.m[i] : f.vol2node.t[i - 9]) = vol2node[i];
-        if (node2cam) (i < 9 ? f.node2cam.m[i] : f.node2cam.t[i - 9]) = node2cam[i];
-        (i < 9 ? back.m[i] : back.t[i - 9]) = node2vol[i];
-    }
-
-    hipError_t e = hipMemsetAsync(bricks, 0, warped_brick_count(X, Y, Z), s);
+    const IntegrateArgs a = warped_args(dists, dists_step, cols, rows, vol, X, Y, Z, occ, voxel_size, trunc_dist, max_weight, nullptr,
+                                        fx, fy, cx, cy);  // (vol2cam is not read: the frames are in f)
+    const Warped6Frames f{aff3_from(vol2node), aff3_from(node2cam), vol2node ? 1 : 0, node2cam ? 1 : 0};
+    hipError_t e = hipMemsetAsync(bricks, 0, knn_field_bricks(X, Y, Z), s);
     if (e != hipSuccess) return e;
     if (D > 0) {
         node_wmax_kernel<<<1, 1024, 0, s>>>(node_w, D, wmax);
-        mark_bricks6_kernel<<<D, 64, 0, s>>>(node_pos, D, wmax, back, vol2node ? 1 : 0, stretch, tmax, X, Y, Z, a.vsx, a.vsy,
-                                             a.vsz, bricks);
+        mark_bricks6_kernel<<<D, 64, 0, s>>>(node_pos, D, wmax, aff3_from(node2vol), vol2node ? 1 : 0, stretch, tmax, X, Y, Z, a.vsx,
+                                             a.vsy, a.vsz, bricks);
     }
-    dim3 block(WBX, WBY), g3((X + WBX - 1) / WBX, (Y + WBY - 1) / WBY, (Z + WBZ - 1) / WBZ);
+    const dim3 block(WBX, WBY), g3 = brick_grid(X, Y, Z);
     const KnnGridView gv = grid ? *grid : KnnGridView{};
-#define WARPED6(KK)                                                                                                                     \
-    do {                                                                                                                                \
-        if (grid) integrate_warped6_kernel<KK, true><<<g3, block, 0, s>>>(a, f, node_pos, node_dq, node_w, D, k, rigid ? 1 : 0, bricks, gv);  \
-        else integrate_warped6_kernel<KK, false><<<g3, block, 0, s>>>(a, f, node_pos, node_dq, node_w, D, k, rigid ? 1 : 0, bricks, gv);      \
-    } while (0)
-    if (k <= 4) WARPED6(4);  // (as K6DISPATCH of solve6_internal.hpp)
-    else WARPED6(8);
-#undef WARPED6
+    if (grid) KDISPATCH8(k, integrate_warped6_kernel<KK, true><<<g3, block, 0, s>>>(a, f, node_pos, node_dq, node_w, D, k, rigid ? 1 : 0, bricks, gv));
+    else KDISPATCH8(k, integrate_warped6_kernel<KK, false><<<g3, block, 0, s>>>(a, f, node_pos, node_dq, node_w, D, k, rigid ? 1 : 0, bricks, gv));
+    return hipGetLastError();
+}
+
+// the two sweeps with the neighbours read from the field f (records: its stored bricks; none in SKIP mode: nothing to do)
+hipError_t launch_tsdf_integrate_warped_field(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol,
+                                              uint8_t* occ, float trunc_dist, int max_weight, const float vol2cam[12], float fx,
+                                              float fy, float cx, float cy, const float* node_pos, const float* node_dq,
+                                              const float* node_w, bool rigid, const KnnFieldView& f, size_t records,
+                                              hipStream_t s) {
+    if (!rigid && records == 0) return hipSuccess;
+    const IntegrateArgs a = warped_args(dists, dists_step, cols, rows, vol, f.X, f.Y, f.Z, occ, f.vs, trunc_dist, max_weight, vol2cam,
+                                        fx, fy, cx, cy);
+    const FieldGeom g = field_geom(f);
+    const dim3 block(WBX, WBY), g3 = field_sweep_grid(f, rigid, records);
+    KDISPATCH16(f.k, integrate_warped_field_kernel<KK><<<g3, block, 0, s>>>(a, g, node_pos, node_dq, node_w, rigid ? 1 : 0, f.table,
+                                                                             f.coords, f.ids));
+    return hipGetLastError();
+}
+
+hipError_t launch_tsdf_integrate_warped6_field(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol,
+                                               uint8_t* occ, float trunc_dist, int max_weight, const float* node2cam, float fx,
+                                               float fy, float cx, float cy, const float* node_pos, const float* node_dq,
+                                               const float* node_w, bool rigid, const KnnFieldView& f, size_t records,
+                                               hipStream_t s) {
+    if (!rigid && records == 0) return hipSuccess;
+    const IntegrateArgs a = warped_args(dists, dists_step, cols, rows, vol, f.X, f.Y, f.Z, occ, f.vs, trunc_dist, max_weight, nullptr,
+                                        fx, fy, cx, cy);  // (vol2cam is not read: the frames are the field's and node2cam)
+    const FieldGeom g = field_geom(f);
+    const dim3 block(WBX, WBY), g3 = field_sweep_grid(f, rigid, records);
+    KDISPATCH8(f.k, integrate_warped6_field_kernel<KK><<<g3, block, 0, s>>>(a, g, aff3_from(node2cam), node2cam ? 1 : 0, node_pos, node_dq,
+                                                                             node_w, rigid ? 1 : 0, f.table, f.coords, f.ids));
     return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
-// warped_bricks.hpp — the brick of the warped TSDF sweeps (tsdf_warped.hip) and of the k-NN field (knn_field.hip), and the
-// field's size arithmetic.  Host-only code: no HIP header, plain g++ compiles it (tests/cpp/test_knn_field_size.cpp
-// drives the arithmetic on the CPU).
+// warped_bricks.hpp — the brick of the warped TSDF sweeps (tsdf_warped.hip) and of the k-NN field (knn_field.hip), the
+// field's size arithmetic and the launchers' dispatch over K.  Host-only code: no HIP header, plain g++ compiles it
+// (tests/cpp/test_knn_field_size.cpp drives the arithmetic on the CPU).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -36,3 +36,23 @@ inline bool knn_field_fits(size_t records, int k, size_t max_bytes) {
 }
 
 }  // namespace dfa
+
+// ---- the dispatch of the launchers over K (tsdf_warped.hip, knn_field.hip): a statement that names KK, with KK the
+// smallest of {4, 8, 16} — {4, 8} — that holds k (as K6DISPATCH of solve6_internal.hpp, for kernel templates with further
+// parameters):  KDISPATCH16(k, kernel<KK, true><<<...>>>(...));
+#define KDISPATCH_AS_(value, ...)  \
+    {                              \
+        constexpr int KK = value;  \
+        __VA_ARGS__;               \
+    }
+#define KDISPATCH16(k, ...)                               \
+    do {                                                  \
+        if ((k) <= 4) KDISPATCH_AS_(4, __VA_ARGS__)       \
+        else if ((k) <= 8) KDISPATCH_AS_(8, __VA_ARGS__)  \
+        else KDISPATCH_AS_(16, __VA_ARGS__)               \
+    } while (0)
+#define KDISPATCH8(k, ...)                           \
+    do {                                             \
+        if ((k) <= 4) KDISPATCH_AS_(4, __VA_ARGS__)  \
+        else KDISPATCH_AS_(8, __VA_ARGS__)           \
+    } while (0)

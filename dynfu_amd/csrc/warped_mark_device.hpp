@@ -1,8 +1,10 @@
 // warped_mark_device.hpp — the brick marking shared by the support pre-pass of the warped sweeps (tsdf_warped.hip: every
-// node at the largest radius) and the stored set of the k-NN field (knn_field.hip: every node at its own radius).
+// node at the largest radius) and the stored set of the k-NN field (knn_field.hip: every node at its own radius): the bricks
+// near a point, and the ONE statement of how far "near" has to reach for the marked set to be a superset.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "device_math.hpp"
 #include "warped_bricks.hpp"
 
 namespace dfa {
@@ -43,6 +45,32 @@ __device__ __forceinline__ void mark_bricks_near(const float (&g)[3], float r, i
         }
         if (!(d2 > r * r)) bricks[((size_t)b[2] * nby + b[1]) * nbx + b[0]] = 1;  // (racing stores of the same byte)
     }
+}
+
+// ---- the marking radius.  A voxel at v is supported by the node at g with reach w when |v - g| < w in float arithmetic
+// (w: the largest node radius for the sweeps' pre-pass — no node within w_max of a voxel means every quotient
+// |v - g| / w >= |v - g| / w_max >= 1 —, the node's own radius for the field).  The radius r handed to mark_bricks_near must
+// not be smaller than any |v - g| the support rule can accept.
+
+// the longest edge of the volume, in metres
+__device__ __forceinline__ float volume_extent(int X, int Y, int Z, float vsx, float vsy, float vsz) {
+    return fmaxf(fmaxf(fabsf(vsx) * (float)X, fabsf(vsy) * (float)Y), fabsf(vsz) * (float)Z);
+}
+__device__ __forceinline__ float max_abs(f3 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fabsf(v.z)); }
+
+// A node in the volume's frame.  Conservative: the reach is widened by 1e-3 relative and a millionth of the largest
+// coordinate in play (the positions, differences and roots of the support rule are rounded at 1e-7 relative).
+__device__ __forceinline__ float mark_radius(float w, f3 g, float ext) { return w * 1.001f + 1e-6f * fmaxf(ext, max_abs(g)); }
+
+// A node at gn in a node frame, taken back to gv = R' gn + t' in the volume's (node2vol = vol2node^-1; stretch and tmax:
+// warped6_frame's).  A supported voxel has |c - gn| < w in the node frame, hence |v - gv| <= stretch w in the volume's, up to
+// the rounding of the two products: c = R_n v + t_n in the sweep and gv = R' gn + t' in the marking kernel, each a few ulp of
+// the coordinates that enter it.  The reach is widened by the 1e-3 relative of mark_radius times the stretch, and by a
+// millionth of the SUM of the coordinates in play in either frame: the volume's extent (twice: |R_n v| reaches sqrt 3 of
+// it), the node's coordinates in both frames and the translation.
+__device__ __forceinline__ float mark_radius_framed(float w, f3 gn, f3 gv, float ext, float stretch, float tmax) {
+    const float L = 2.f * ext + max_abs(gn) + max_abs(gv) + tmax;
+    return w * 1.001f * stretch + 1e-6f * L;
 }
 
 }  // namespace dfa

@@ -12,7 +12,8 @@ import tsdf_warped_cases as CS
 WITH_NODES = [n for n in CS.CASES if CS.CASES[n][1] > 0]
 # bricks that must be stored / bricks of the volume, per case (on all of them: exactly the bricks with a supported voxel)
 MUST_STORE = {"main_skip": (230, 256), "main_rigid_junk": (228, 256), "odd_scan": (422, 440), "odd_grid_rigid": (432, 440),
-              "k16": (234, 256), "padded": (7, 28), "thin": (10, 12), "thin_padded": (6, 12)}
+              "k16": (234, 256), "padded": (7, 28), "thin": (10, 12), "thin_padded": (6, 12),
+              "tiny_k4_grid": (26, 28), "tiny_k16_scan": (28, 28)}
 
 
 @pytest.mark.parametrize("name", WITH_NODES)

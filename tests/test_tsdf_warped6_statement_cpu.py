@@ -132,7 +132,7 @@ def test_undecided_share(name):
 def test_cases_cover_the_matrix():
     vals = list(C6.CASES.values())
     assert {v[0] for v in vals} == {(32, 32, 32), (50, 38, 44), (9, 7, 14), (1, 2, 12)}
-    assert {(v[1], v[2]) for v in vals} == {(300, 8), (63, 4), (2, 8), (1024, 8), (0, 8)}
+    assert {(v[1], v[2]) for v in vals} == {(300, 8), (63, 4), (2, 8), (1024, 8), (0, 8), (64, 3)}
     assert {v[3] for v in vals} == {"identity", "general"} and {v[4] for v in vals} == {W6.SKIP, W6.RIGID}
     assert {v[5] for v in vals} == {"empty", "junk"} and {v[6] for v in vals} == {"volume", "posed", "moved"}
     c = C6.case("big_moved")

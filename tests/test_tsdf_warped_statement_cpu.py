@@ -94,7 +94,7 @@ def test_undecided_share(name):
 def test_cases_cover_every_shape_and_mode():
     vals = list(CS.CASES.values())
     assert {v[0] for v in vals} == {(32, 32, 32), (50, 38, 44), (9, 7, 14), (1, 2, 12)}
-    assert {(v[1], v[2]) for v in vals} == {(300, 8), (63, 4), (2, 8), (1024, 16), (0, 8)}
+    assert {(v[1], v[2]) for v in vals} == {(300, 8), (63, 4), (2, 8), (1024, 16), (0, 8), (64, 4), (63, 16)}
     assert {v[3] for v in vals} == {"identity", "general"} and {v[4] for v in vals} == {WST.SKIP, WST.RIGID}
     assert {v[5] for v in vals} == {"empty", "junk"}
     junk = CS.case("main_rigid_junk")["vol"] >> 16

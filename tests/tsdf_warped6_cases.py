@@ -11,7 +11,8 @@ frame set-up — the nodes of the north-star warp field live in a frame of their
             frame 0.
 
 The matrix holds tsdf_warped_cases' four volumes ((32, 32, 32), (50, 38, 44), (9, 7, 14), (1, 2, 12): see there why), the
-(D, k) pairs (300, 8), (63, 4), (2, 8), (1024, 8), (0, 8) — k <= 8 here —, identity and general node transforms, both modes, an
+(D, k) pairs (300, 8), (63, 4), (2, 8), (1024, 8), (0, 8), (64, 3) — k <= 8 here; the last is k <= 4 with the node grid, which
+starts at D = 64 —, identity and general node transforms, both modes, an
 empty and a junk starting volume.  "antipodal" is "main_posed_rigid_junk" with every second node's dual quaternion negated:
 q and -q are the same motion, and the statement's volume must be the same, exactly.
 """
@@ -39,6 +40,7 @@ CASES = {
     "no_nodes_skip":          ((9, 7, 14),      0, 8, "identity", W6.SKIP,  "junk",  "posed"),
     "no_nodes_rigid":         ((32, 32, 32),    0, 8, "identity", W6.RIGID, "junk",  "posed"),
     "antipodal":              ((32, 32, 32),  300, 8, "general",  W6.RIGID, "junk",  "posed"),
+    "tiny_k3_grid_moved":     ((9, 7, 14),     64, 3, "general",  W6.SKIP,  "junk",  "moved"),
 }
 MAIN = ("main_volume_skip", "main_posed_rigid_junk", "odd_scan_moved", "odd_grid_rigid_posed", "big_moved")
 ANTIPODAL_OF = {"antipodal": "main_posed_rigid_junk"}

@@ -1,11 +1,13 @@
 """The cases of the warped-integrate tests, shared by the CPU statement tests and the -m gpu tests: a sphere in front of a
 back wall seen by a camera tilted about y, deformation nodes on the sphere, and the statement's answer computed once per case.
 
-Between them the cases hold four volumes, the five (D, k) pairs, identity and general node transforms, both
+Between them the cases hold four volumes, seven (D, k) pairs, identity and general node transforms, both
 modes, an empty and a junk starting volume.  The shapes are small on purpose: the odd volumes exercise partial bricks in
 x and y ((50, 38, 44): no multiple of the 64 x 4 x 1 brick; (9, 7, 14) and (1, 2, 12): less than one brick wide), (32, 32, 32)
 and (50, 38, 44) have several bricks in y and z, D = 63 takes the scan of all nodes and D >= 64 the node grid, D = 2 < k gives
-padded lists.
+padded lists.  The two "tiny" cases close the list of kernel instantiations: k <= 4 with the node grid (D = 64, the first
+size that takes it) and k = 16 with the scan.  case() seeds a case by its place in sorted(CASES): a new name has to sort
+after the last one, or every case behind it silently gets other inputs.
 """
 import functools
 
@@ -32,6 +34,8 @@ CASES = {
     "thin_padded":      ((1, 2, 12),      2,  8, "general",  WST.SKIP,  "empty"),
     "no_nodes_skip":    ((9, 7, 14),      0,  8, "identity", WST.SKIP,  "junk"),
     "no_nodes_rigid":   ((32, 32, 32),    0,  8, "identity", WST.RIGID, "junk"),
+    "tiny_k4_grid":     ((9, 7, 14),     64,  4, "general",  WST.RIGID, "junk"),
+    "tiny_k16_scan":    ((9, 7, 14),     63, 16, "general",  WST.SKIP,  "junk"),
 }
 MAIN = ("main_skip", "main_rigid_junk", "odd_scan", "odd_grid_rigid", "k16")  # the cases of the vacuity guard
 

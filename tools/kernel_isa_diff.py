@@ -64,7 +64,8 @@ def bodies(asm):
         lines = []
         for ln in m.group(2).splitlines():
             ln = ln.split(";")[0].rstrip()
-            if not ln.strip() or re.match(r"\s*\.(loc|file|cfi_\w+)\b", ln):
+            # (.section / .text: where the NEXT symbol of the file goes — it changes with what follows the kernel in its file)
+            if not ln.strip() or re.match(r"\s*\.(loc|file|cfi_\w+|section|text)\b", ln):
                 continue
             ln = re.sub(r"_Z\w+", "SYM", ln)
             ln = re.sub(r"\.L(BB|tmp|func_\w+?)\d+(_\d+)?", lambda g: ".L" + g.group(1) + (g.group(2) or ""), ln)

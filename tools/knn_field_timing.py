@@ -3,7 +3,8 @@ calls, in ONE run: the set-up of tools/warped_integrate_timing.py — 512^3 with
 (dynfu_amd/synth.py: the C2 scene; the nodes in the volume's frame for dfa_tsdf_integrate_warped, in the camera frame with
 vol2node = the volume's pose for dfa_tsdf_integrate_warped6), each node with a translation of up to a centimetre.
 
-Items: the four searching calls (two warp fields x SKIP / RIGID), the four cached ones, dfa_tsdf_integrate of the same frame
+Items: the four searching calls (two warp fields x SKIP / RIGID), the four cached ones (all eight calls run kernels of
+csrc/tsdf_warped.hip over the one body of csrc/warped_sweep_device.hpp; build and append are csrc/knn_field.hip), dfa_tsdf_integrate of the same frame
 and dfa_warp_to_live_graph over the voxels of the stored bricks (the blend from stored ids, one point per lane, nothing
 else) as yardsticks.  They alternate inside every window, after a warm-up of each; per item the median over the windows
 [min, max].  Then, one call per window each: dfa_knn_field_build of both fields, and dfa_knn_field_append of the last 16

@@ -19,12 +19,12 @@ import torch
 import dynfu_amd as A
 from dynfu_amd import synth
 
-BRICK = (64, 4, 1)  # csrc/tsdf_warped.hip: WBX, WBY, WBZ
+BRICK = (64, 4, 1)  # csrc/warped_bricks.hpp: WBX, WBY, WBZ
 
 
 def marked_bricks(dim, voxel, nodes, w_max):
     """the bricks whose box of voxel positions comes within w_max of a node (csrc/tsdf_warped.hip: mark_bricks_kernel,
-    without its rounding margins): bool (bz, by, bx)"""
+    without the rounding margins of csrc/warped_mark_device.hpp: mark_radius): bool (bz, by, bx)"""
     nb = [-(-dim // b) for b in BRICK]
     lo = [np.arange(n) * b * voxel for n, b in zip(nb, BRICK)]
     hi = [np.minimum(np.arange(n) * b + b - 1, dim - 1) * voxel for n, b in zip(nb, BRICK)]
