@@ -477,26 +477,23 @@ __global__ __launch_bounds__(NT) void pcg_paired_kernel(SolveView s, SolveState*
                     acc[0]         = fmaf(v3, g3, fmaf(v2, g2, fmaf(v1, g1, fmaf(v0, g0, acc[0]))));
                 }
             };
-            // row A: slots [0, nA) upwards; row B: slots [E - nB, E) from the top (nA, nB even, wave-uniform).
-            // (8 gathers in flight per step measured no faster: the loop is bound by LDS bank conflicts — a
-            // random 4-byte gather costs ~6.5 clocks per wave instruction against 2 conflict-free.)
+            // row A: slots [0, nA) upwards; row B: slots [E - nB, E) from the top (nA, nB even, wave-uniform).  A row's
+            // two-slot remainder is a branch of ITS OWN step, at that step's constant slots: placed behind the break, the
+            // remainders of all steps are merged into one block that reads mval at a merged index, and the compiler
+            // keeps a second copy of the array in scratch memory for it (DESIGN_NOTES, compiler note).
+            // (More gathers in flight per step measured slower, profiles/r10_pcg_gather.md: with rows A and B swept together,
+            // 8 ds_read_b32 ahead of the first wait, the C2 frame is 2.6 % longer than with 4.)
 #pragma unroll
             for (int q0 = 0; q0 < E; q0 += 4) {
-                if (q0 + 4 <= nA[j]) {
-                    slots4(q0, aA[j]);
-                } else {
-                    if (q0 + 2 <= nA[j]) slots2(q0, aA[j]);
-                    break;
-                }
+                if (q0 >= nA[j]) break;
+                if (q0 + 4 <= nA[j]) slots4(q0, aA[j]);
+                else slots2(q0, aA[j]);
             }
 #pragma unroll
-            for (int q0 = E - 4; q0 >= 0; q0 -= 4) {
-                if (q0 >= E - nB[j]) {
-                    slots4(q0, aB[j]);
-                } else {
-                    if (q0 + 2 >= E - nB[j]) slots2(q0 + 2, aB[j]);
-                    break;
-                }
+            for (int q0 = 0; q0 < E; q0 += 4) {
+                if (q0 >= nB[j]) break;
+                if (q0 + 4 <= nB[j]) slots4(E - 4 - q0, aB[j]);
+                else slots2(E - 2 - q0, aB[j]);
             }
         }
     };
