@@ -15,7 +15,7 @@
 
 namespace dfa {
 
-// The adaptors pass dfa_solve_params / dfa_solve6_params / ..._stats by pointer: a libdynfu_amd.so built from another
+// The adaptors pass dfa_solve_params / dfa_solve6_params / ..._stats / dfa_knn_field_desc by pointer: a libdynfu_amd.so built from another
 // header would read or write past them.  Checked once, on the first checked call.
 static void require_matching_abi() {
     static const bool ok = [] {
@@ -23,8 +23,10 @@ static void require_matching_abi() {
             throw Error(DFA_ERR_INVALID, "libdynfu_amd.so implements ABI version " + std::to_string(dfa_abi_version()) +
                                              ", the host adaptors were built against " + std::to_string(DFA_ABI_VERSION));
         const size_t mine[] = {sizeof(dfa_solve_params), sizeof(dfa_solve_stats), sizeof(dfa_solve_timing),
-                               sizeof(dfa_solve6_params), sizeof(dfa_solve6_stats), sizeof(dfa_solve6_timing)};
-        for (int id = 0; id < 6; ++id)
+                               sizeof(dfa_solve6_params), sizeof(dfa_solve6_stats), sizeof(dfa_solve6_timing),
+                               sizeof(dfa_knn_field_desc)};  // (in the order of the header's DFA_STRUCT_* ids)
+        static_assert(DFA_STRUCT_KNN_FIELD_DESC + 1 == sizeof(mine) / sizeof(mine[0]), "one size per DFA_STRUCT_* id");
+        for (int id = 0; id < (int)(sizeof(mine) / sizeof(mine[0])); ++id)
             if (dfa_abi_struct_size(id) != mine[id])
                 throw Error(DFA_ERR_INVALID, "libdynfu_amd.so and the host adaptors disagree on the size of struct " + std::to_string(id));
         return true;

@@ -71,6 +71,22 @@ def test_unknown_struct_id_has_size_zero(lib):
     assert lib.dfa_last_error() == CASES["capi_tsdf.cpp"][1]
 
 
+def test_every_struct_id_of_the_header_has_a_size(lib):
+    """the DFA_STRUCT_* enum of include/dynfu_amd.h, read from the header: ids 0 .. n-1 without a gap, each with a non-zero
+    size in the library, and the first id past the enum with none"""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(root, "include", "dynfu_amd.h")).read(), flags=re.S)
+    ids = {name: int(val) for name, val in re.findall(r"\b(DFA_STRUCT_[A-Z0-9_]+)\s*=\s*(\d+)", src)}
+    assert "DFA_STRUCT_KNN_FIELD_DESC" in ids and sorted(ids.values()) == list(range(len(ids))), ids
+    for name, sid in ids.items():
+        assert lib.dfa_abi_struct_size(sid) > 0, name
+    assert lib.dfa_abi_struct_size(len(ids)) == 0, "the library knows a struct id the header does not declare"
+    # the k-NN field's description: two ints, two 64-bit counts and the byte count (the mirror of dynfu_amd/_lib.py)
+    assert lib.dfa_abi_struct_size(ids["DFA_STRUCT_KNN_FIELD_DESC"]) == 4 + 4 + 8 + 8 + 8
+
+
 def test_error_buffer_is_per_thread(lib):
     """a failing call in a second thread leaves this thread's last message as it was"""
     assert _null_volume(lib) == DFA_ERR_INVALID

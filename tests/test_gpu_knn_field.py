@@ -1,15 +1,20 @@
 """-m gpu tests of the k-NN field (dfa_knn_field_*) and of the warped integrations served from it, on the cases of
-tests/tsdf_warped_cases.py and tests/tsdf_warped6_cases.py.
+tests/tsdf_warped_cases.py, tests/tsdf_warped6_cases.py and tests/knn_field_cases.py.
 
 No tolerance anywhere: the rows are the statement's (tests/knn_field_statement.py: warp_statement.knn, exact with ties), a field
 that was appended to is the field built in one go, id for id, and a cached integration leaves the volume and the occupancy
 map of the uncached call, bit for bit.  One cached result per case file also goes through the uncached tests' bar against
-the numpy statement, which ties the chain to the statement and not only to the sibling kernel."""
+the numpy statement, which ties the chain to the statement and not only to the sibling kernel.
+
+In a node frame (the cases of tests/tsdf_warped6_cases.py and tests/knn_field_cases.py) the rows are the statement's wherever the
+k + 1 nearest nodes are more than the statement's own float32 deviation apart, and a valid list at the few voxels where they are
+not; the stored set lies between the statement's lower and upper bound (profiles/knn_field_node_frame.md: the figures)."""
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
+import knn_field_cases as KC  # noqa: E402
 import knn_field_statement as KS  # noqa: E402
 import tsdf_warped6_cases as C6  # noqa: E402
 import tsdf_warped_cases as CS  # noqa: E402
@@ -95,6 +100,93 @@ def test_lookup_is_the_statement(A, name):
                         [2 ** 31 - 1, 0, 0], [0, -2 ** 31, 0], [X - 1, Y - 1, Z - 1]], np.int32)
     got = host(f.lookup(dev(outside)))
     assert (got[:-1] == -1).all() and np.array_equal(got[-1], rows[Z - 1, Y - 1, X - 1])
+    f.close()
+
+
+def check_against_statement(f, c, s, label):
+    """every row of the field f, its stored set and its info() against the statement s of the inputs c -> the rows"""
+    rows = lookup_all(f, c["dims"])
+    has = rows[..., 0] >= 0  # (D > 0: every voxel of a stored brick has a nearest node)
+    stored = KS.stored_bricks(rows, s)
+    assert np.array_equal(has, stored[s["brick"]]), "a brick is stored as a whole or not at all"
+    bad_rows, differ = KS.check_rows(rows, s, stored)
+    info = f.info()
+    print("%s: %d of %d bricks stored, %d must be, %d may be; %d bytes; rho %.3g, %d voxels ambiguous, %d of them with another row "
+          "than the float32 statement's" % (label, int(stored.sum()), len(stored), int(s["must"].sum()), int(s["may"].sum()), info["bytes"],
+                                            s["rho"], int(s["ambiguous"].sum()), differ))
+    assert KS.check_stored(stored, s) == []
+    assert bad_rows == []
+    assert (rows[~has] == -1).all(), "rows of voxels that are not stored"
+    assert info == dict(D=s["D"], k=c["k"], stored_bricks=int(stored.sum()), total_bricks=len(stored),
+                        bytes=int(stored.sum()) * 256 * c["k"] * 4)
+    return rows
+
+
+SIX_WITH_NODES = [n for n in C6.CASES if C6.CASES[n][1] > 0]
+LAST = KC.RADII_SPECIAL["last"]
+#             kind     name  k     D (None: all)
+NODE_FRAME = [("six", n, None, None) for n in SIX_WITH_NODES] + [("field", "turned", None, None)] + \
+             [("field", n, None, D) for n in KC.RADII for D in (LAST, None)] + [("field", n, k, None) for n in KC.TIES for k in KC.CASES[n][0]]
+
+
+@pytest.mark.parametrize("kind,name,k,D", NODE_FRAME)
+def test_lookup_is_the_statement_in_a_node_frame(A, kind, name, k, D):
+    """rows exact at decided voxels and valid at ambiguous ones (knn_field_statement.check_rows), the stored set between its
+    lower and its upper bound.  The radii cases also on their first 69 nodes, without the infinite / NaN radius that stores
+    every brick.  A NaN radius is not refused: the build stores every brick, as field_mark_kernel's comment says"""
+    c, s = KS.inputs(name, kind, k), KS.case(name, D, kind, k)
+    X, Y, Z = c["dims"]
+    f, _ = make_field(A, c, [s["D"]])
+    rows = check_against_statement(f, c, s, "%s %s k = %d D = %d" % (kind, name, c["k"], s["D"]))
+    if s["every_brick"] or np.isinf(s["node_w"]).any():
+        assert f.info()["stored_bricks"] == f.info()["total_bricks"] and f.info()["bytes"] == len(s["must"]) * 256 * c["k"] * 4
+    outside = np.array([[-1, 0, 0], [X, 0, 0], [0, -1, 0], [0, Y, 0], [0, 0, -1], [0, 0, Z], [X + 63, Y + 3, Z], [-64, -4, -1],
+                        [2 ** 31 - 1, 0, 0], [0, -2 ** 31, 0], [X - 1, Y - 1, Z - 1]], np.int32)
+    got = host(f.lookup(dev(outside)))
+    assert (got[:-1] == -1).all() and np.array_equal(got[-1], rows[Z - 1, Y - 1, X - 1])
+    f.close()
+
+
+D_TIES = 111
+APPENDS = [("six", "main_posed_rigid_junk", None, [2, 63, 64, 300]),  # padded lists (D < k), then the scan, then the node grid
+           ("six", "odd_scan_moved", None, [0, 63]),                  # an empty field first
+           ("six", "tiny_k3_grid_moved", None, [1, 64]),
+           ("field", "turned", None, [150, 300])] + \
+          [("field", n, k, steps) for n in KC.TIES for k in KC.CASES[n][0]
+           for steps in ([1, 50, 63, 64, D_TIES], [64, D_TIES - KC.LATTICE_DUPLICATES, D_TIES])]  # ... the last step: the duplicates alone
+
+
+@pytest.mark.parametrize("kind,name,k,steps", APPENDS)
+def test_append_equals_build_in_a_node_frame(A, kind, name, k, steps):
+    """id for id at every intermediate step, with no allowance: both fields saw the same float positions.  On the tie cases the
+    merge meets candidates at the distance of list entries (and, with the duplicates, at the position of one)"""
+    c = KS.inputs(name, kind, k)
+    assert steps[-1] == c["D"]
+    for upto in range(1, len(steps)):
+        part = steps[:upto + 1]
+        built, _ = make_field(A, c, [part[-1]])
+        grown, _ = make_field(A, c, part)
+        a, b = lookup_all(built, c["dims"]), lookup_all(grown, c["dims"])
+        print("%s %s k = %d %s: %d rows differ" % (kind, name, c["k"], part, int((a != b).any(-1).sum())))
+        assert np.array_equal(a, b), part
+        assert built.info() == grown.info()
+        if part[-1] == c["D"]:
+            check_against_statement(grown, c, KS.case(name, None, kind, k), "%s %s grown" % (kind, name))
+        built.close(), grown.close()
+
+
+@pytest.mark.parametrize("name", ["turned", "radii_posed"])
+def test_a_field_grown_then_used(A, name):
+    """the new geometries through the sweeps: a field built on half the nodes and appended to serves dfa_tsdf_integrate_warped6_field;
+    the volume is the searching call's bit for bit, and passes the uncached tests' bar against the numpy statement"""
+    import test_gpu_tsdf_warped6 as T6
+    c = KC.warped6_case(name)
+    want = integrate(A, "six", c)
+    f, _ = make_field(A, c, [c["D"] // 2, c["D"]])
+    got = integrate(A, "six", c, field=f)
+    print("%s: %d voxels differ of %d; %d changed by the call" % (name, int((got != want).sum()), want.size, int((want != c["vol"]).sum())))
+    assert np.array_equal(got, want)
+    T6.check(got, c)
     f.close()
 
 

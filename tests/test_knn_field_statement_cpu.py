@@ -1,12 +1,17 @@
 """CPU checks of the k-NN field's statement (tests/knn_field_statement.py) against itself on the cases of
 tests/tsdf_warped_cases.py — every brick that holds a supported voxel must be stored, and the cases exercise stored and
-unstored bricks and both branches of the support rule —, and of the C calls' argument checks, which come before any HIP call."""
+unstored bricks and both branches of the support rule —; of the statement in a node frame (tests/tsdf_warped6_cases.py,
+tests/knn_field_cases.py): the measured deviation behind rho, the share of ambiguous voxels, the tie density of the tie cases, the
+order of the stored set's bounds, and that check_rows / check_stored flag planted defects and nothing else; and of the C calls'
+argument checks, which come before any HIP call."""
 import ctypes
 
 import numpy as np
 import pytest
 
+import knn_field_cases as KC
 import knn_field_statement as KS
+import tsdf_warped6_cases as C6
 import tsdf_warped_cases as CS
 
 WITH_NODES = [n for n in CS.CASES if CS.CASES[n][1] > 0]
@@ -59,6 +64,179 @@ def test_must_store_by_hand():
         m = KS.must_store((70, 5, 2), [0.5] * 3, np.array([[40.0, 0, 0]], np.float32), np.array([radius], np.float32)).reshape(2, 2, 2)
         got = sorted((int(x), int(y), int(z)) for z, y, x in zip(*np.nonzero(m)))
         assert got == sorted(want), (radius, got)
+
+
+# ------------------------------------------------------------------------------------------ the statement in a node frame
+SIX_WITH_NODES = [n for n in C6.CASES if C6.CASES[n][1] > 0]
+EVERY = [("ref", n, None) for n in WITH_NODES] + [("six", n, None) for n in SIX_WITH_NODES] + \
+        [("field", n, k) for n in KC.CASES for k in KC.CASES[n][0]]
+FRAMED = [(kind, n, k) for kind, n, k in EVERY if (kind == "six" and C6.CASES[n][6] != "volume") or (kind == "field" and KC.CASES[n][1])]
+
+
+def test_every_framed_case_has_its_constant():
+    assert sorted(KS.FIELD_DEVIATION) == sorted({(kind, n) for kind, n, _ in FRAMED})
+
+
+@pytest.mark.parametrize("kind,name,k", FRAMED)
+def test_deviation_and_ambiguous_share_of_a_framed_case(kind, name, k):
+    """rho is measured again and stays within the recorded constant; at most 2 % of the voxels are ambiguous"""
+    s = KS.case(name, kind=kind, k=k)
+    share = float(s["ambiguous"].mean())
+    print("%s %s k = %d: max |d32 - d64| = %.3e m (recorded %.1e), rho = %.3e m, %d of %d voxels ambiguous (%.3f %%), %.1f %% with a tie" %
+          (kind, name, s["k"], s["deviation"], KS.FIELD_DEVIATION[kind, name], s["rho"], int(s["ambiguous"].sum()), s["ambiguous"].size,
+           100 * share, 100 * float(KS.case_pairs(name, None, kind, k)["tie"].mean())))
+    assert s["deviation"] <= KS.FIELD_DEVIATION[kind, name]
+    assert share <= KS.AMBIGUOUS_CAP
+    if name in KC.TIES:
+        assert s["rho"] == 0.0 and not s["ambiguous"].any(), "an exact frame: every voxel is decided, ties included"
+    else:
+        assert s["rho"] == 2 * s["deviation"] > 0
+
+
+@pytest.mark.parametrize("kind,name,k", EVERY)
+def test_bounds_of_the_stored_set_are_ordered(kind, name, k):
+    """the voxel rule's set lies within the box rule's (no frame), and the lower bound within the upper one"""
+    s, held = KS.case(name, kind=kind, k=k), KS.case_pairs(name, None, kind, k)["must_voxel"]
+    print("%s %s: %d bricks hold a supported voxel, %d must be stored, %d may be, of %d" %
+          (kind, name, int(held.sum()), int(s["must"].sum()), int(s["may"].sum()), len(s["must"])))
+    assert not (held & ~s["must"]).any() and (not s["framed"] or np.array_equal(held, s["must"]))
+    assert not (s["must"] & ~s["may"]).any()
+    assert s["framed"] or not s["ambiguous"].any()
+
+
+@pytest.mark.parametrize("name,k", [(n, k) for n in KC.TIES for k in KC.CASES[n][0]])
+def test_tie_cases_have_ties(name, k):
+    c, s = KC.case(name, k), KS.case(name, kind="field", k=k)
+    _, c32, c64 = KS.positions(c["dims"], c["voxel_size"], c["vol2node"])
+    density = float(KS.case_pairs(name, None, "field", k)["tie"].mean())
+    print("%s k = %d: D = %d, %.1f %% of the voxels have an exact tie among their k + 1 nearest" % (name, k, c["D"], 100 * density))
+    assert density >= 0.25
+    assert np.array_equal(c32.astype(np.float64), c64), "the frame is exact in float32"
+    assert 100 < c["D"] < 128 and len(np.unique(c["nodes"], axis=0)) == c["D"] - KC.LATTICE_DUPLICATES
+    assert np.array_equal(c["nodes"][-3:], c["nodes"][[5, 40, 77]])
+    # exact arithmetic: the float32 squared distances are the fp64 ones
+    q = c32[::97]
+    d = q[:, None, :] - c["nodes"][None]
+    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    e = c64[::97, None, :] - c["nodes"].astype(np.float64)[None]
+    assert np.array_equal(d2.astype(np.float64), (e * e).sum(-1))
+
+
+def test_radii_cases_are_what_they_say():
+    S = KC.RADII_SPECIAL
+    for name in ("radii", "radii_nan"):
+        c = KC.case(name)
+        w, g, edge = c["node_w"], c["nodes"], 1.0
+        assert w[S["zero"]] == 0 and w[S["negative"]] < 0 and g[S["far_outside"]][0] - edge >= 10 * edge
+        assert -w[S["half_outside"]] < g[S["half_outside"]][0] < 0
+        assert np.array_equal(g[S["far_corner"]], (np.array(c["dims"], np.float32) - 1) * c["voxel_size"])
+        assert (np.isnan(w).sum(), np.isinf(w).sum()) == ((1, 0) if name == "radii_nan" else (0, 1))
+        whole, part = KS.case(name, kind="field"), KS.case(name, D=S["last"], kind="field")
+        assert whole["may"].all() and whole["every_brick"] == (name == "radii_nan")
+        assert part["must"].any() and not part["may"].all() and not part["every_brick"], "without the last node the others decide"
+    assert KS.case("radii", kind="field")["must"].all(), "an infinite radius supports every voxel"
+
+
+def test_the_turned_frame_is_far_from_the_existing_ones():
+    c = KC.case("turned")
+    R, t = c["vol2node"][:9].reshape(3, 3).astype(np.float64), c["vol2node"][9:]
+    assert abs(np.arccos((np.trace(R) - 1) / 2) - 2.6) < 1e-6 and np.abs(t).max() == 5.0 and t[0] == 3.0
+    s = KS.case("turned", kind="field")
+    assert s["must"].any() and not s["may"].all()
+
+
+def test_the_warped6_statement_holds_its_bound_on_the_new_cases():
+    """tsdf_warped6_statement.WARPED6_DEVIATION was measured on tsdf_warped6_cases; the two cases that go through
+    dfa_tsdf_integrate_warped6 here stay within it, so test_gpu_tsdf_warped6.check applies to them as it stands"""
+    import tsdf_warped6_statement as W6
+    for name in ("turned", "radii_posed"):
+        c = KC.warped6_case(name)
+        with np.errstate(all="ignore"):
+            dev = W6.deviation(c["vol"].shape, c["voxel_size"], c["vol2node"], c["node2cam"], c["nodes"], c["node_dq"], c["node_w"], c["k"],
+                               c["mode"])
+        print("%s: |vc32 - vc64| / L = %.3e" % (name, dev))
+        assert dev <= W6.WARPED6_DEVIATION
+        assert c["ref"]["updated"].any() and c["ref"]["supported"].any()
+
+
+def answer(s, stored=None):
+    """the statement's own answer as a lookup of every voxel would return it: its rows in the bricks `stored` (default: the ones
+    that must be), -1 elsewhere"""
+    stored = s["must"] if stored is None else stored
+    return np.where(stored[s["brick"]][..., None], s["rows"], -1).astype(np.int32), stored.copy()
+
+
+def flagged(got, stored, s):
+    bad, _ = KS.check_rows(got, s, stored)
+    return bad + KS.check_stored(stored, s)
+
+
+def test_the_comparison_catches_planted_defects():
+    import tsdf_warped6_statement as W6
+    import warp_statement as WS
+    s, c = KS.case("turned", kind="field"), KC.case("turned")
+    X, Y, Z = c["dims"]
+    k = c["k"]
+    clean, stored = answer(s)
+    assert flagged(clean, stored, s) == [], "nothing on the statement's own answer"
+    for kind, name, kk in (("ref", "main_skip", None), ("six", "big_moved", None), ("field", "ties_lattice", 8), ("field", "radii_nan", None)):
+        t = KS.case(name, kind=kind, k=kk)
+        assert flagged(*answer(t, t["may"] if t["every_brick"] else None), t) == [], name
+    has = stored[s["brick"]]
+    z, y, x = (int(a[7]) for a in np.nonzero(has & ~s["ambiguous"]))  # a decided voxel of a stored brick
+    # 1. two adjacent ids swapped at a decided voxel
+    got = clean.copy()
+    got[z, y, x, [2, 3]] = got[z, y, x, [3, 2]]
+    assert flagged(got, stored, s)
+    # 2. one id replaced by the (k + 1)-th nearest
+    _, c32, _ = KS.positions(c["dims"], c["voxel_size"], c["vol2node"])
+    flat = (z * Y + y) * X + x
+    got = clean.copy()
+    got[z, y, x, k - 1] = WS.knn(c["nodes"], c32[flat:flat + 1], k + 1)[0, k]
+    assert flagged(got, stored, s)
+    # 3. the frame ignored: rows searched at v;  4. its translation dropped: rows searched at R v
+    v = KS.positions(c["dims"], c["voxel_size"])[1]
+    turn_only = np.concatenate([c["vol2node"][:9], np.zeros(3, np.float32)])
+    for where in (v, W6.apply32(turn_only, v)):
+        got = np.where(has[..., None], WS.knn(c["nodes"], where, k).reshape(Z, Y, X, k), -1).astype(np.int32)
+        assert flagged(got, stored, s)
+    # 5. tie order reversed at a tied voxel of ties_lattice
+    t, tc = KS.case("ties_lattice", kind="field", k=4), KC.case("ties_lattice", 4)
+    tclean, tstored = answer(t)
+    tz, ty, tx = 2, 2, 30
+    row = tclean[tz, ty, tx]
+    d = np.array([tx, ty, tz], np.float32) * tc["voxel_size"] - tc["nodes"][row]
+    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    j = int(np.flatnonzero(np.diff(d2) == 0)[0])
+    assert row[j] < row[j + 1], "equal distances: the lower index first"
+    got = tclean.copy()
+    got[tz, ty, tx, [j, j + 1]] = row[[j + 1, j]]
+    assert flagged(got, tstored, t)
+    # 6. one must-store brick removed
+    b = int(np.flatnonzero(s["must"])[11])
+    fewer = stored.copy()
+    fewer[b] = False
+    assert flagged(answer(s, fewer)[0], fewer, s)
+    # 7. every brick stored
+    every = np.ones_like(stored)
+    assert not s["may"].all() and flagged(answer(s, every)[0], every, s)
+    # the allowance at an ambiguous voxel is for the near-tie alone: the two ids that are within 2 rho of each other may come in
+    # either order, an id from farther away may not
+    az, ay, ax = (int(a[0]) for a in np.nonzero(has & s["ambiguous"]))
+    e = s["c64"][(az * Y + ay) * X + ax] - c["nodes"][clean[az, ay, ax]].astype(np.float64)
+    near = np.flatnonzero(np.diff(np.sqrt((e * e).sum(-1))) <= 2 * s["rho"])
+    if len(near):  # (the near-tie may also be between the k-th and the (k + 1)-th nearest)
+        j = int(near[0])
+        got = clean.copy()
+        got[az, ay, ax, [j, j + 1]] = clean[az, ay, ax, [j + 1, j]]
+        assert flagged(got, stored, s) == []
+    got = clean.copy()
+    far = int(np.setdiff1d(s["rows"][Z - 1 - az, Y - 1 - ay, X - 1 - ax], clean[az, ay, ax])[0])  # a neighbour of the opposite voxel
+    got[az, ay, ax, 0] = far
+    assert flagged(got, stored, s)
+    got = clean.copy()
+    got[az, ay, ax, 1] = got[az, ay, ax, 0]
+    assert flagged(got, stored, s), "an id twice"
 
 
 # ------------------------------------------------------------------------------------------ the C calls' validation
