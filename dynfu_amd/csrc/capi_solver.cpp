@@ -17,6 +17,7 @@ struct dfa_solver {
     int max_D, max_N, k;
     size_t max_R;
     int ell_cap;
+    int asm_resident = 0;      // workgroups of the in-flight assembly the device holds at once (solve_assemble_resident_blocks)
     dfa::SolveView v;          // pointers into `mem`
     dfa::SolveState* state;    // device
     double* cost_partials;     // device
@@ -68,6 +69,7 @@ int dfa_solver_create(int max_D, int max_N, int k, dfa_solver** out) {
     s->max_D = max_D, s->max_N = max_N, s->k = k;
     s->max_R       = (size_t)max_N + (size_t)max_D * k;
     s->ell_cap     = 256;
+    s->asm_resident = dfa::solve_assemble_resident_blocks(k);
     s->has_problem = false;
     s->timing      = false;
     {
@@ -288,7 +290,7 @@ int dfa_solver_solve(dfa_solver* s, const dfa_solve_params* p, dfa_stream_t stre
                                          p->gn_tol, p->tukey_offset, p->psi_data, w_reg_sq, with_huber ? p->psi_reg : 0.f, nullptr, st));
             huber_done |= with_huber;
             const int ev = bracket_open(s, st);
-            HIP_TRY(dfa::solve_assemble(v, s->state, gn == 0 && p->nonlinear_iter > 1, w_reg_sq, st));
+            HIP_TRY(dfa::solve_assemble(v, s->state, gn == 0 && p->nonlinear_iter > 1, w_reg_sq, s->asm_resident, st));
             if (int rc = run_pcg(ev)) return rc;
         }
     }

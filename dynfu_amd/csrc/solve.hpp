@@ -179,8 +179,13 @@ hipError_t solve_huber(const SolveView& s, float psi_reg, hipStream_t st);
 hipError_t solve_reset(const SolveView& s, SolveState* state, unsigned int* ticket, int nticket, hipStream_t st);
 // w_reg_sq: the weight of the regularisation rows — with 1 (the data rows) the bound of an addend's magnitude, which sets the
 // scale of the assembly's fixed-point sums
+// resident_blocks: solve_assemble_resident_blocks of the plan's k — a plan of at most that many nodes walks its lists in
+// flight (assemble_kernel, solve_assemble.hip)
 hipError_t solve_assemble(const SolveView& s, SolveState* state, int save_base /* g, t -> g_base, t_base */, float w_reg_sq,
-                          hipStream_t st);
+                          int resident_blocks, hipStream_t st);
+// workgroups of the in-flight assembly the device holds at once (CUs x the occupancy the runtime reports; 0: this k has the
+// plain loop only).  A runtime query: asked once per plan, not per launch.
+int solve_assemble_resident_blocks(int k);
 // inner Gauss-Newton iteration of an outer iteration whose robust weights are frozen: the energy is linear least squares,
 // so the matrix of the outer iteration's first linearisation still holds and the new right-hand side is
 // g = g_base - A (t - t_base) — one sparse matrix-vector product instead of a linearisation and an assembly

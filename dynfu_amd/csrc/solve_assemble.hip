@@ -7,6 +7,7 @@
 
 #include <algorithm>
 
+#include "dev_switch.hpp"
 #include "device_math.hpp"
 #include "solve.hpp"
 #include "solve_internal.hpp"
@@ -72,7 +73,82 @@ extern "C" __attribute__((visibility("default"))) int dfa_dev_asm_timing(unsigne
 }
 #endif
 
+// One list entry of node a — slot `slot` of a row whose record is (idx, w, et = (e.x, e.y, e.z, tau)): its share of the gradient
+// and of the diagonal into the thread's registers, its off-diagonal pairs into the hash.
 template <int K>
+__device__ __forceinline__ void assemble_entry(int a, int slot, const int (&idx)[K], const float (&w)[K], float4 et, float up, int* key,
+                                               long long* val, int* ovf, float& gx, float& gy, float& gz, float& dsum) {
+    float wa = 0.f;
+#pragma unroll
+    for (int j = 0; j < K; ++j) wa = (j == slot) ? w[j] : wa;
+    const float tw = et.w * wa;
+    gx += tw * et.x, gy += tw * et.y, gz += tw * et.z;
+    if (et.w == 0.f) return;
+    // first probe of all k columns read together (keys never change once set): the common
+    // case "column already present" costs one LDS read + one fire-and-forget ds_add instead
+    // of a returning CAS per column
+    // (measured and not kept, tools/ref_assemble_phases.py at C4 / C3: every lane taking its columns in the order
+    // (lane + t) mod K, so that a step's adds spread over K addresses — 149 / 86 us against 141 / 81, the selects cost
+    // more than the conflicts)
+    uint32_t h0[K];
+    int k0[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        h0[j] = ((uint32_t)idx[j] * 2654435761u) >> (32 - 9);
+        k0[j] = key[h0[j]];
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const int b = idx[j];
+        if (b < 0) continue;
+        const float v = tw * w[j];
+        if (b == a) {  // the diagonal is hit by every row: kept in a register
+            dsum += v;
+            continue;
+        }
+        if (k0[j] == b) {  // the column is in the table where its first probe looks: nearly every pair after the first rows
+            fixed_add(&val[h0[j]], v, up);
+            continue;
+        }
+        uint32_t h = h0[j];
+        int cur    = k0[j];
+#pragma unroll 1
+        for (int probes = 0;; ++probes) {
+            if (cur == -1) cur = atomicCAS(&key[h], -1, b), cur = cur == -1 ? b : cur;
+            if (cur == b) {
+                fixed_add(&val[h], v, up);
+                break;
+            }
+            if (probes >= HASH) {
+                *ovf = 1;
+                break;
+            }
+            h   = (h + 1) & HASH_MASK;
+            cur = key[h];
+        }
+    }
+}
+
+// A node's list is walked in one of two forms, T the template's choice:
+//   T == 1  the plain loop: a thread's entries one after the other, each a chain node_list[p] -> row record -> hash adds.
+//           With its ~36 registers the most workgroups are resident, which is what counts where a grid runs in several
+//           rounds (measured at C4 / C3, tools/ref_assemble_phases.py: a thread's rows 2 or 4 at a time with their loads
+//           in flight together — a workgroup lives 18 us instead of 23 but fewer are resident: 140-163 / 81-91 us
+//           against 141 / 81).
+//   T > 1   the list in flight: a thread's entries in chunks of T (256 T entries per workgroup and chunk) — the T
+//           node_list entries together (addresses clamped into the list, entries past its end masked), then the T row
+//           records together, and only then the hash work, in the order p, p + 256, ... of the plain loop, so that every
+//           float sum of a thread sees the same addends in the same order (the fixed-point sums do not depend on order).
+//           The first chunk's entries are asked for in front of the hash initialisation, which they do not depend on.
+//           For a grid that is resident in ONE round (solve_assemble_resident_blocks; C2: 2 048 workgroups = 256 CUs x 8),
+//           where the launch lasts as long as its slowest workgroup and a list of ~520 entries (C2: 302 ... 651) is
+//           1 + 2 dependent round trips instead of 1 + 2 x 3.  It must stay within 64 VGPRs: the residency of the plain loop
+//           (K = 4, T = 3: 64 VGPRs, no scratch, 8 waves per SIMD; it is launched for k == K only, so that the record is
+//           its three 16-byte loads and nothing else of load_record).  Measured at C2: 114.3 -> 99.4 us per frame of five
+//           launches, a workgroup's list + hash phase 11.1 -> 9.4 us (profiles/r11_assembly_in_flight.md; the same
+//           profile shows a fifth of the C2 grid starting only when the first workgroups leave, in either form, whatever
+//           the occupancy query says: not explained yet).
+template <int K, int T>
 __global__ __launch_bounds__(256) void assemble_kernel(SolveView s, SolveState* __restrict__ st, int save_base, float amax_unset) {
     __shared__ int key[HASH];
     __shared__ long long val[2 * HASH];  // [0, HASH): sums of the non-negative addends, [HASH, 2 HASH): of the negative ones' magnitudes
@@ -89,6 +165,13 @@ __global__ __launch_bounds__(256) void assemble_kernel(SolveView s, SolveState* 
     long long t0_ = clock64(), t1_, t2_, t3_, t4_;
     const unsigned long long w0_ = wall_clock64();
 #endif
+    const int beg = s.node_ptr[a], end = s.node_ptr[a + 1];
+    const float amax_st = st->amax;
+    [[maybe_unused]] uint32_t ent[T];
+    if constexpr (T > 1) {  // (an empty list reads entry 0 of the array, which every plan has, and uses nothing of it)
+#pragma unroll
+        for (int t = 0; t < T; ++t) ent[t] = s.node_list[max(min(beg + 256 * t + (int)threadIdx.x, end - 1), 0)];
+    }
     for (int i = threadIdx.x; i < HASH; i += 256) key[i] = -1, val[i] = val[i + HASH] = 0ll;
     if (threadIdx.x == 0) ovf = 0;
     __syncthreads();
@@ -96,66 +179,38 @@ __global__ __launch_bounds__(256) void assemble_kernel(SolveView s, SolveState* 
     t1_ = clock64();
 #endif
 
-    const int beg = s.node_ptr[a], end = s.node_ptr[a + 1];
-    const FixedScale fx = fixed_scale_for_rows(solve_fixed_scale(st->amax > 0.f ? st->amax : amax_unset), end - beg);
+    const FixedScale fx = fixed_scale_for_rows(solve_fixed_scale(amax_st > 0.f ? amax_st : amax_unset), end - beg);
     float gx = 0.f, gy = 0.f, gz = 0.f, dsum = 0.f;
-    for (int p = beg + (int)threadIdx.x; p < end; p += 256) {
-        const uint32_t e = s.node_list[p];
-        const size_t r   = e / (uint32_t)s.k;
-        const int slot   = (int)(e - (uint32_t)r * (uint32_t)s.k);
-        int idx[K];
-        float w[K];
-        const float4 et = load_record<K>(s, r, idx, w);  // (e.x, e.y, e.z, tau)
-        float wa = 0.f;
+    if constexpr (T > 1) {
+        SolveView sk = s;  // (this form is launched for k == K only: the record's 16-byte loads and nothing else of load_record)
+        sk.k         = K;
+        for (int base = beg + (int)threadIdx.x; base - (int)threadIdx.x < end; base += 256 * T) {
+            if (base - (int)threadIdx.x != beg) {
 #pragma unroll
-        for (int j = 0; j < K; ++j) wa = (j == slot) ? w[j] : wa;
-        const float tw = et.w * wa;
-        gx += tw * et.x, gy += tw * et.y, gz += tw * et.z;
-        if (et.w != 0.f) {
-            // first probe of all k columns read together (keys never change once set): the common
-            // case "column already present" costs one LDS read + one fire-and-forget ds_add instead
-            // of a returning CAS per column
-            // (measured and not kept, tools/ref_assemble_phases.py at C4 / C3: every lane taking its columns in the order
-            // (lane + t) mod K, so that a step's adds spread over K addresses — 149 / 86 us against 141 / 81, the selects cost
-            // more than the conflicts; a thread's rows 2 or 4 at a time with their loads in flight together — a workgroup
-            // lives 18 us instead of 23 but fewer are resident: 140-163 / 81-91 us)
-            uint32_t h0[K];
-            int k0[K];
+                for (int t = 0; t < T; ++t) ent[t] = s.node_list[min(base + 256 * t, end - 1)];
+            }
+            int slot[T], idx[T][K];
+            float w[T][K];
+            float4 et[T];
 #pragma unroll
-            for (int j = 0; j < K; ++j) {
-                h0[j] = ((uint32_t)idx[j] * 2654435761u) >> (32 - 9);
-                k0[j] = key[h0[j]];
+            for (int t = 0; t < T; ++t) {
+                const size_t r = ent[t] / (uint32_t)K;
+                slot[t]        = (int)(ent[t] - (uint32_t)r * (uint32_t)K);
+                et[t]          = load_record<K>(sk, r, idx[t], w[t]);  // (e.x, e.y, e.z, tau)
             }
 #pragma unroll
-            for (int j = 0; j < K; ++j) {
-                const int b = idx[j];
-                if (b < 0) continue;
-                const float v = tw * w[j];
-                if (b == a) {  // the diagonal is hit by every row: kept in a register
-                    dsum += v;
-                    continue;
-                }
-                if (k0[j] == b) {  // the column is in the table where its first probe looks: nearly every pair after the first rows
-                    fixed_add(&val[h0[j]], v, fx.up);
-                    continue;
-                }
-                uint32_t h = h0[j];
-                int cur    = k0[j];
-#pragma unroll 1
-                for (int probes = 0;; ++probes) {
-                    if (cur == -1) cur = atomicCAS(&key[h], -1, b), cur = cur == -1 ? b : cur;
-                    if (cur == b) {
-                        fixed_add(&val[h], v, fx.up);
-                        break;
-                    }
-                    if (probes >= HASH) {
-                        ovf = 1;
-                        break;
-                    }
-                    h   = (h + 1) & HASH_MASK;
-                    cur = key[h];
-                }
-            }
+            for (int t = 0; t < T; ++t)
+                if (base + 256 * t < end) assemble_entry<K>(a, slot[t], idx[t], w[t], et[t], fx.up, key, val, &ovf, gx, gy, gz, dsum);
+        }
+    } else {
+        for (int p = beg + (int)threadIdx.x; p < end; p += 256) {
+            const uint32_t e = s.node_list[p];
+            const size_t r   = e / (uint32_t)s.k;
+            const int slot   = (int)(e - (uint32_t)r * (uint32_t)s.k);
+            int idx[K];
+            float w[K];
+            const float4 et = load_record<K>(s, r, idx, w);  // (e.x, e.y, e.z, tau)
+            assemble_entry<K>(a, slot, idx, w, et, fx.up, key, val, &ovf, gx, gy, gz, dsum);
         }
     }
     // the diagonal: one add per wave into its (pre-inserted) slot
@@ -380,14 +435,50 @@ __global__ __launch_bounds__(256) void assemble_det_kernel(SolveView s, SolveSta
 // ------------------------------------------------------------------------------------------
 // launcher
 
-hipError_t solve_assemble(const SolveView& s, SolveState* state, int save_base, float w_reg_sq, hipStream_t st) {
+// entries of a thread in flight together, per template K (1: that K has the plain loop only).  K = 8 and 16 hold 16 and 28
+// record words per entry: two entries in flight cost them waves (K = 8: 52 -> 76 VGPRs, 8 -> 6 waves per SIMD; K = 16:
+// 85 -> 130, 5 -> 3), so they keep the plain loop.
+constexpr int asm_chunk(int K) { return K == 4 ? 3 : 1; }
+
+template <int K>
+static int resident_blocks_of() {
+    if (asm_chunk(K) == 1) return 0;
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, assemble_kernel<K, asm_chunk(K)>, 256, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;  // (unknown: the plain loop)
+    }
+    return cus * per_cu;
+}
+
+int solve_assemble_resident_blocks(int k) {
+    return k <= 4 ? resident_blocks_of<4>() : k <= 8 ? resident_blocks_of<8>() : resident_blocks_of<16>();
+}
+
+template <int K>
+static void launch_assemble(const SolveView& s, SolveState* state, int save_base, float amax_unset, bool in_flight, hipStream_t st) {
+    if (asm_chunk(K) > 1 && in_flight && s.k == K) assemble_kernel<K, asm_chunk(K)><<<s.D, 256, 0, st>>>(s, state, save_base, amax_unset);
+    else assemble_kernel<K, 1><<<s.D, 256, 0, st>>>(s, state, save_base, amax_unset);
+}
+
+hipError_t solve_assemble(const SolveView& s, SolveState* state, int save_base, float w_reg_sq, int resident_blocks, hipStream_t st) {
     // The rows carry w_reg^2 as their tau; the scale of the fixed-point sums comes from SolveState::amax, which the
     // re-weighting linearisation in front of this launch has found.  Should no such linearisation have stored one (amax is
     // still the 0 of solve_reset — nothing in the driver does that today), the sums take the bound every addend obeys,
     // max(1, w_reg^2), instead of a grid for addends of 1e-30 that the first real one would overflow.
     const float amax_unset = std::max(1.0f, w_reg_sq);
     if (s.deterministic) KDISPATCH(assemble_det_kernel, s.k, <<<s.D, 256, 0, st>>>(s, state, save_base, amax_unset));
-    else KDISPATCH(assemble_kernel, s.k, <<<s.D, 256, 0, st>>>(s, state, save_base, amax_unset));
+    else {
+        // the list in flight only where the whole grid is resident in one round; larger plans keep the plain loop, which
+        // won there (assemble_kernel).  DFA_ASM_IN_FLIGHT=0 / 1 (development builds): one form for every plan (A/B, tests).
+        bool in_flight  = s.D <= resident_blocks;
+        const int force = dev_env_int("DFA_ASM_IN_FLIGHT", -1);
+        if (force >= 0) in_flight = force != 0;
+        if (s.k <= 4) launch_assemble<4>(s, state, save_base, amax_unset, in_flight, st);
+        else if (s.k <= 8) launch_assemble<8>(s, state, save_base, amax_unset, in_flight, st);
+        else launch_assemble<16>(s, state, save_base, amax_unset, in_flight, st);
+    }
     return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 // and an assembly while the robust weights are frozen.
 #include <hip/hip_runtime.h>
 
+#include "dev_switch.hpp"
 #include "dq_device.hpp"
 #include "solve.hpp"
 #include "solve_internal.hpp"
@@ -21,13 +22,11 @@ namespace dfa {
 //       release/acquire around a ticket counter) adds the partials in index order (deterministic)
 //       and runs the Gauss-Newton control logic — no separate control launch.
 
+// (the row's own data — graph slots n, w, canonical point c, live point l — is the caller's: already in registers)
 template <int K>
-__device__ __forceinline__ float tukey_weight(const SolveView& s, size_t v, float tukey_offset, float psi_data) {
-    const f3 c = mk3(s.canon[3 * v], s.canon[3 * v + 1], s.canon[3 * v + 2]);
-    DQ sum     = dq_identity();
-    int n[K];
-    float w[K];
-    load_row_graph<K>(s, v, n, w);
+__device__ __forceinline__ float tukey_weight_of(const SolveView& s, const int (&n)[K], const float (&w)[K], f3 c, f3 l, float tukey_offset,
+                                                 float psi_data) {
+    DQ sum = dq_identity();
     // the neighbours' translations and transforms four at a time, by unconditional loads (an absent neighbour reads node 0
     // and is skipped): loads inside the `if` were k dependent round trips
 #pragma unroll
@@ -49,7 +48,7 @@ __device__ __forceinline__ float tukey_weight(const SolveView& s, size_t v, floa
         }
     }
     const f3 warped = dq_transform(dq_normalize(sum), c);
-    const float ex = s.live[3 * v] - warped.x, ey = s.live[3 * v + 1] - warped.y, ez = s.live[3 * v + 2] - warped.z;
+    const float ex = l.x - warped.x, ey = l.y - warped.y, ez = l.z - warped.z;
     // calcTukeyBiweight (:204-212)
     const float d = sqrtf(ex * ex + ey * ey + ez * ez) / tukey_offset;
     if (d < psi_data) {
@@ -57,6 +56,15 @@ __device__ __forceinline__ float tukey_weight(const SolveView& s, size_t v, floa
         return (float)(q * q);
     }
     return 0.f;
+}
+template <int K>
+__device__ __forceinline__ float tukey_weight(const SolveView& s, size_t v, float tukey_offset, float psi_data) {
+    const f3 c = mk3(s.canon[3 * v], s.canon[3 * v + 1], s.canon[3 * v + 2]);
+    int n[K];
+    float w[K];
+    load_row_graph<K>(s, v, n, w);
+    const f3 l = mk3(s.live[3 * v], s.live[3 * v + 1], s.live[3 * v + 2]);
+    return tukey_weight_of<K>(s, n, w, c, l, tukey_offset, psi_data);
 }
 
 // Huber weights (opt_solver.cpp:233-268): computed for interface parity, energy.t:70 never uses them
@@ -94,7 +102,60 @@ struct LineariseArgs {
 constexpr int LIN_SHARDS     = 32;    // ticket counters: one device-scope atomic costs ~11 ns when
 constexpr int LIN_MAX_BLOCKS = 1024;  // serialised on one word, so arrivals are sharded 2-level
 
+// What a row's arithmetic reads of the row itself — graph slots, right-hand side, and for its robust weight the canonical
+// and the live point (data rows of a re-weighting linearisation) or the stored weight — asked for together, ahead of the
+// gathers (translations, transforms) that depend on the slots.
 template <int K>
+struct LinRow {
+    int n[K];
+    float w[K];
+    float bx, by, bz, tau;
+    f3 c, l;
+};
+template <int K>
+__device__ __forceinline__ void lin_row_load(const SolveView& s, size_t r, int update_weights, LinRow<K>& q) {
+    load_row_graph<K>(s, r, q.n, q.w);
+    q.bx = s.rb[3 * r], q.by = s.rb[3 * r + 1], q.bz = s.rb[3 * r + 2];
+    q.tau = 0.f, q.c = q.l = mk3(0.f, 0.f, 0.f);
+    if (!update_weights) q.tau = s.rtau[r];
+    else if (r < (size_t)s.N) {
+        q.c = mk3(s.canon[3 * r], s.canon[3 * r + 1], s.canon[3 * r + 2]);
+        q.l = mk3(s.live[3 * r], s.live[3 * r + 1], s.live[3 * r + 2]);
+    }
+}
+// ... and the row's arithmetic, as the plain loop of linearise_kernel does it: weight, residual into the record's tail,
+// the row's share of the cost added to c, its largest matrix addend into amax
+template <int K>
+__device__ __forceinline__ void lin_row_finish(const SolveView& s, size_t r, const LineariseArgs& a, const LinRow<K>& q, double& c, float& amax) {
+    float tau = q.tau;
+    if (a.update_weights) {
+        tau       = r < (size_t)s.N ? tukey_weight_of<K>(s, q.n, q.w, q.c, q.l, a.tukey_offset, a.psi_data) : a.w_reg_sq;
+        s.rtau[r] = tau;
+    }
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    float tx[K], ty[K], tz[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const int nn = q.n[j] >= 0 ? q.n[j] : 0;
+        tx[j] = s.t[3 * nn], ty[j] = s.t[3 * nn + 1], tz[j] = s.t[3 * nn + 2];
+    }
+    float wm = 0.f;
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+        if (q.n[j] >= 0) sx += q.w[j] * tx[j], sy += q.w[j] * ty[j], sz += q.w[j] * tz[j], wm = fmaxf(wm, fabsf(q.w[j]));
+    amax = fmaxf(amax, tau * wm * wm);
+    const float ex = q.bx - sx, ey = q.by - sy, ez = q.bz - sz;
+    *(float4*)(s.re + r * (size_t)solve_rec_words(s.k) + solve_rec_tail(s.k)) = make_float4(ex, ey, ez, tau);
+    c += (double)tau * ((double)ex * ex + (double)ey * ey + (double)ez * ez);
+}
+
+// TWO: a thread's first two rows with the second row's own loads (lin_row_load) ahead of the first row's arithmetic.  The
+// grid is capped at LIN_MAX_BLOCKS x 256 threads — raising the cap would regroup the cost's partial sums — so a plan of
+// more rows than that (C2: 262 144 data rows fill it, the 8 192 regularisation rows are a second trip of blocks 0-31) took
+// that trip's loads only when the first row was finished: a dependent round trip in front of the last workgroup's serial
+// tail, which the assembly behind this launch waits for.  Same row -> thread mapping, same order of a thread's adds into
+// c and amax: the same bits (tests/test_gpu_linearise_two_rows.py).  Third and later trips: the plain loop.
+template <int K, bool TWO>
 __global__ __launch_bounds__(256) void linearise_kernel(SolveView s, SolveState* __restrict__ st,
                                                         double* __restrict__ cost_partials,
                                                         unsigned int* __restrict__ ticket /*[LIN_SHARDS+1]*/,
@@ -122,7 +183,20 @@ __global__ __launch_bounds__(256) void linearise_kernel(SolveView s, SolveState*
     const size_t R = (size_t)s.N + (size_t)s.D * s.k;
     double c       = 0.0;
     float amax     = 0.f;  // re-weighting linearisations: the largest addend tau w_a w_b any row brings to the normal matrix
-    for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r < R; r += (size_t)gridDim.x * blockDim.x) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    size_t r_first      = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if constexpr (TWO) {
+        if (r_first < R) {
+            const size_t r1 = r_first + stride;
+            LinRow<K> q0, q1;
+            lin_row_load<K>(s, r_first, a.update_weights, q0);
+            if (r1 < R) lin_row_load<K>(s, r1, a.update_weights, q1);
+            lin_row_finish<K>(s, r_first, a, q0, c, amax);
+            if (r1 < R) lin_row_finish<K>(s, r1, a, q1, c, amax);
+            r_first = r1 + stride;  // (past R if there was no second row)
+        }
+    }
+    for (size_t r = r_first; r < R; r += stride) {
         float tau;
         if (a.update_weights) {
             tau       = r < (size_t)s.N ? tukey_weight<K>(s, r, a.tukey_offset, a.psi_data) : a.w_reg_sq;
@@ -238,12 +312,28 @@ int solve_residual_blocks(const SolveView& s) {
     return (int)(nb < (size_t)LIN_MAX_BLOCKS ? nb : (size_t)LIN_MAX_BLOCKS);
 }
 
+// which template K takes the two-row form: where its second row's registers leave the kernel's waves per SIMD as they are
+constexpr bool lin_two_rows(int K) { return K == 4; }
+
+template <int K>
+static void launch_linearise(const SolveView& s, SolveState* state, double* cost_partials, unsigned int* ticket, const LineariseArgs& a,
+                             int nb, hipStream_t st) {
+#ifdef DFA_DEV_AB  // DFA_LIN_TWO_ROWS=0 / 1 (development builds): either form for every k (A/B, tests)
+    if (dev_env_int("DFA_LIN_TWO_ROWS", lin_two_rows(K)) != 0) linearise_kernel<K, true><<<nb, 256, 0, st>>>(s, state, cost_partials, ticket, a);
+    else linearise_kernel<K, false><<<nb, 256, 0, st>>>(s, state, cost_partials, ticket, a);
+#else
+    linearise_kernel<K, lin_two_rows(K)><<<nb, 256, 0, st>>>(s, state, cost_partials, ticket, a);
+#endif
+}
+
 hipError_t solve_linearise(const SolveView& s, SolveState* state, double* cost_partials, unsigned int* ticket,
                            int update_weights, int mode, float gn_tol, float tukey_offset, float psi_data,
                            float w_reg_sq, float huber_psi, long long* iters_total, hipStream_t st) {
     const int nb = solve_residual_blocks(s);
     LineariseArgs a{update_weights, mode, gn_tol, tukey_offset, psi_data, w_reg_sq, iters_total, huber_psi};
-    KDISPATCH(linearise_kernel, s.k, <<<nb, 256, 0, st>>>(s, state, cost_partials, ticket, a));
+    if (s.k <= 4) launch_linearise<4>(s, state, cost_partials, ticket, a, nb, st);
+    else if (s.k <= 8) launch_linearise<8>(s, state, cost_partials, ticket, a, nb, st);
+    else launch_linearise<16>(s, state, cost_partials, ticket, a, nb, st);
     return hipGetLastError();
 }
 
