@@ -9,7 +9,7 @@ _LIB = None
 # every symbol include/dynfu_amd.h declares (tests/test_capi_symbols.py checks the .so exports them)
 SYMBOLS = [
     "dfa_last_error", "dfa_version", "dfa_abi_version", "dfa_abi_struct_size", "dfa_compute_dists", "dfa_tsdf_clear", "dfa_tsdf_integrate",
-    "dfa_tsdf_clear_integrate", "dfa_tsdf_raycast_points", "dfa_tsdf_raycast_depth", "dfa_tsdf_raycast_tally", "dfa_tsdf_raycast_render", "dfa_render_image_points", "dfa_render_image_depth", "dfa_render_tangent_colors", "dfa_mesh_rasterize", "dfa_tsdf_vertex_normals", "dfa_tsdf_extract_cloud", "dfa_tsdf_extract_cloud_occ", "dfa_tsdf_extract_normals", "dfa_correspond_projective", "dfa_knn", "dfa_warp_to_live",
+    "dfa_tsdf_clear_integrate", "dfa_tsdf_raycast_points", "dfa_tsdf_raycast_depth", "dfa_tsdf_raycast_tally", "dfa_tsdf_raycast_render", "dfa_render_image_points", "dfa_render_image_depth", "dfa_render_tangent_colors", "dfa_mesh_rasterize", "dfa_visible_vertices", "dfa_tsdf_vertex_normals", "dfa_tsdf_extract_cloud", "dfa_tsdf_extract_cloud_occ", "dfa_tsdf_extract_normals", "dfa_correspond_projective", "dfa_knn", "dfa_warp_to_live",
     "dfa_calc_dqb", "dfa_unsupported_vertices", "dfa_icp_sums", "dfa_repack_points", "dfa_compact_points", "dfa_transform_points", "dfa_warp_to_live_graph",
     "dfa_correspond", "dfa_marching_cubes", "dfa_mc_default_tables",
     "dfa_tsdf_occupancy_bytes", "dfa_tsdf_clear_occ", "dfa_tsdf_integrate_occ", "dfa_tsdf_clear_integrate_occ", "dfa_tsdf_clear_integrate_known_occ", "dfa_tsdf_integrate_warped", "dfa_tsdf_integrate_warped6", "dfa_marching_cubes_occ", "dfa_marching_cubes_indexed",
@@ -18,7 +18,7 @@ SYMBOLS = [
     "dfa_depth_bilateral_filter", "dfa_depth_truncate", "dfa_depth_build_pyramid", "dfa_compute_normals_mask_depth",
     "dfa_resize_depth_normals", "dfa_resize_points_normals",
     "dfa_compute_points_normals", "dfa_solver6_create", "dfa_solver6_destroy", "dfa_solver6_set_problem",
-    "dfa_solver6_solve", "dfa_solver6_set_node_transforms", "dfa_solver6_node_dq", "dfa_solver6_warp", "dfa_solver6_warp_with", "dfa_solver6_get_stats",
+    "dfa_solver6_solve", "dfa_solver6_set_node_transforms", "dfa_solver6_set_vertex_mask", "dfa_solver6_node_dq", "dfa_solver6_warp", "dfa_solver6_warp_with", "dfa_solver6_get_stats",
     "dfa_solver6_enable_timing", "dfa_solver6_get_timing", "dfa_solver6_matrix_blocks", "dfa_solver6_matrix_columns",
     "dfa_solver6_matrix_row_blocks", "dfa_solver6_gradient", "dfa_solver6_step", "dfa_solver6_data_graph", "dfa_solver6_reg_graph",
     "dfa_solver_create", "dfa_solver_destroy", "dfa_solver_set_problem", "dfa_solver_solve", "dfa_solver_set_deterministic", "dfa_solver_matrix_entries", "dfa_solver_matrix_row_lengths", "dfa_solver_gradient",
@@ -193,6 +193,7 @@ def load(path=None):
     L.dfa_render_image_depth.argtypes = [vp, i, vp, i, i, i, f, f, f, f, vp, vp, i, vp]
     L.dfa_render_tangent_colors.argtypes = [vp, i, i, i, vp, i, vp]
     L.dfa_mesh_rasterize.argtypes = [vp, vp, i, vp, i, vp, f, f, f, f, f, i, i, vp, vp, i, vp, i, vp]
+    L.dfa_visible_vertices.argtypes = [vp, i, i, vp, i, i, i, f, f, f, f, f, vp, vp, vp]
     L.dfa_tsdf_vertex_normals.argtypes = [vp, i, i, i, vp, f, vp, i, vp, vp]
     L.dfa_tsdf_extract_cloud.argtypes = [vp, i, i, i, vp, vp, vp, i, vp, vp]
     L.dfa_tsdf_extract_cloud_occ.argtypes = [vp, vp, i, i, i, vp, vp, vp, i, vp, vp]
@@ -212,6 +213,7 @@ def load(path=None):
     L.dfa_solver6_destroy.restype = None
     L.dfa_solver6_set_problem.argtypes = [vp, vp, vp, vp, i, vp, vp, i, vp]
     L.dfa_solver6_set_node_transforms.argtypes = [vp, vp]
+    L.dfa_solver6_set_vertex_mask.argtypes = [vp, vp, vp]
     L.dfa_solver6_solve.argtypes = [vp, vp, i, vp, i, i, i, f, f, f, f, C.POINTER(Solve6Params), vp]
     L.dfa_solver6_node_dq.argtypes = [vp]
     L.dfa_solver6_node_dq.restype = vp
@@ -574,6 +576,26 @@ def mesh_rasterize(vertices, normals, indices, world2cam, fx, fy, cx, cy, z_near
                                      points.stride(0) * 4 if points is not None else 0,
                                      _dev(out_normals, torch.float32, "out_normals"),
                                      out_normals.stride(0) * 4 if out_normals is not None else 0, _stream()))
+
+
+def visible_vertices(vertices, model_points, fx, fy, cx, cy, z_tol, count=False):
+    """dfa_visible_vertices: vertices (N, 3) or (N, 4) float32 in the camera frame against model_points ((rows, cols, 4)
+    float32, a row stride makes a pitched map; misses are NaN) -> flags (N,) uint8, 1 where the model does not lie in front
+    of the vertex by more than z_tol; with count=True (flags, count) with the number of set flags as a one-element int32
+    CUDA tensor."""
+    torch = _torch()
+    if vertices.dim() != 2 or vertices.shape[1] not in (3, 4) or not vertices.is_contiguous():
+        raise DynfuAmdError("vertices must be a contiguous (N, 3) or (N, 4) float32 tensor")
+    if model_points.dim() != 3 or model_points.shape[2] != 4 or model_points.stride(2) != 1 or model_points.stride(1) != 4:
+        raise DynfuAmdError("model_points must be a (rows, cols, 4) float32 tensor of packed float4 pixels")
+    N, stride = int(vertices.shape[0]), int(vertices.shape[1])
+    rows, cols = int(model_points.shape[0]), int(model_points.shape[1])
+    flags = torch.empty((N,), dtype=torch.uint8, device="cuda")
+    n = torch.empty((1,), dtype=torch.int32, device="cuda") if count else None
+    _check(load().dfa_visible_vertices(_dev(vertices, torch.float32, "vertices") if N else None, stride, N,
+                                       _dev(model_points, torch.float32, "model_points"), model_points.stride(0) * 4, cols, rows,
+                                       fx, fy, cx, cy, z_tol, _dev(flags) if N else None, _dev(n), _stream()))
+    return (flags, n) if count else flags
 
 
 def tsdf_raycast_tally(vol, voxel_size, trunc, cam2vol, Rinv, fx, fy, cx, cy, step_factor, delta_factor, cols, rows,
@@ -997,6 +1019,17 @@ class Solver6:
         """the same graphs, new starting transforms (dfa_solver6_set_node_transforms)"""
         self._keep = self._keep[:1] + (node_dq,) + self._keep[2:]
         _check(self._L.dfa_solver6_set_node_transforms(self._h, _dev(node_dq, _torch().float32, "node_dq")))
+
+    def set_vertex_mask(self, mask):
+        """dfa_solver6_set_vertex_mask: mask (N,) uint8 or bool in the vertex order of set_problem, non-zero = the vertex may
+        take a data row; None removes the mask.  The plan copies it: the tensor is free again once the stream has passed."""
+        torch = _torch()
+        if mask is not None:
+            if mask.dtype == torch.bool:
+                mask = mask.view(torch.uint8)
+            if self._keep is not None and (tuple(mask.shape) != (self.N,) or not mask.is_contiguous()):  # (no problem: the library says so)
+                raise DynfuAmdError("mask must be a contiguous (%d,) uint8 or bool tensor" % self.N)
+        _check(self._L.dfa_solver6_set_vertex_mask(self._h, _dev(mask, torch.uint8, "mask"), _stream()))
 
     def solve(self, vmap, nmap, fx, fy, cx, cy, params):
         f32 = _torch().float32

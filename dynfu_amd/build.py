@@ -18,7 +18,7 @@ OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libdynfu_amd.so")
 SOURCES = ["tsdf.hip", "tsdf_warped.hip", "knn_field.hip", "warp.hip", "solve_graph.hip", "solve_linearise.hip", "solve_assemble.hip", "solve_pcg.hip",
            "solve_pcg_launched.hip", "solve_pcg_team.hip", "solve6_graph.hip", "solve6_pattern.hip", "solve6_linearise.hip",
-           "solve6_assemble.hip", "solve6_pcg.hip", "solve6_update.hip", "mc.hip", "extract.hip", "img.hip", "render.hip", "raster.hip", "icp.hip", "points.hip",
+           "solve6_assemble.hip", "solve6_pcg.hip", "solve6_update.hip", "mc.hip", "extract.hip", "img.hip", "render.hip", "raster.hip", "visibility.hip", "icp.hip", "points.hip",
            "capi.cpp", "capi_tsdf.cpp", "capi_field.cpp", "capi_image.cpp", "capi_warp.cpp", "capi_solver.cpp", "capi_solver6.cpp"]
 ARCH = "gfx950"
 EXTRA = os.environ.get("DFA_EXTRA_CXXFLAGS", "").split()
@@ -142,7 +142,7 @@ def build_cpp_tests(force=False, verbose=False):
     for name, needs in (("test_host_dq", []), ("test_host_solver", ["host"]), ("test_host_tsdf", ["host", "oracle"]),
                         ("test_host_dynfusion", ["host", "oracle"]), ("test_host_icp", ["host"]),
                         ("test_tsdf_classify", ["oracle", "ieee"]), ("test_launch_budget", []), ("test_host_io", ["host"]), ("test_host_kinfu", ["host"]),
-                        ("test_host_extract", ["host"]), ("test_host_render", ["host"]), ("test_host_mc_indexed", ["host"]), ("test_host_mesh_view", ["host"]),
+                        ("test_host_extract", ["host"]), ("test_host_render", ["host"]), ("test_host_mc_indexed", ["host"]), ("test_host_mesh_view", ["host"]), ("test_host_visible_term", ["host"]),
                         ("test_host_tsdf_warped", ["host"]), ("test_host_tsdf_warped6", ["host"]),
                         ("test_knn_field_size", []), ("test_host_knn_field", ["host"])):
         src = os.path.join(tdir, name + ".cpp")

@@ -1,6 +1,6 @@
-// capi_image.cpp — C ABI (include/dynfu_amd.h), the image seams: shading, the mesh rasteriser, the depth filters and
-// resizes, vertex / normal maps and the rigid-ICP sums.  Argument checks and launcher calls only (capi_internal.hpp); the
-// kernels are in render.hip, raster.hip, img.hip and icp.hip.
+// capi_image.cpp — C ABI (include/dynfu_amd.h), the image seams: shading, the mesh rasteriser, the visibility of a cloud
+// against a model map, the depth filters and resizes, vertex / normal maps and the rigid-ICP sums.  Argument checks and
+// launcher calls only (capi_internal.hpp); the kernels are in render.hip, raster.hip, visibility.hip, img.hip and icp.hip.
 #include "capi_internal.hpp"
 
 using namespace dfa::capi;
@@ -9,6 +9,7 @@ using dfa::stream_scratch;
 
 namespace {
 struct IcpScratch : DeviceBuffer<float> {};        // partial sums of dfa_icp_sums
+struct VisScratch : DeviceBuffer<int32_t> {};      // per-workgroup counts of dfa_visible_vertices
 }  // namespace
 
 extern "C" {
@@ -76,6 +77,27 @@ int dfa_mesh_rasterize(const float* vertices, const float* normals, int N, const
     REQUIRE(!out_normals || (((uintptr_t)out_normals | (uintptr_t)normals_step) & 15) == 0, "normal rows must be 16-byte aligned");
     HIP_TRY(dfa::launch_mesh_rasterize(vertices, normals, N, indices, T, world2cam, fx, fy, cx, cy, z_near, cols, rows, zbuffer,
                                        points, points_step, out_normals, normals_step, S(stream)));
+    return DFA_OK;
+}
+
+int dfa_visible_vertices(const float* vertices, int stride, int N, const float* model_points, int points_step, int cols, int rows,
+                         float fx, float fy, float cx, float cy, float z_tol, uint8_t* flags, int32_t* count,
+                         dfa_stream_t stream) {
+    REQUIRE(N >= 0, "negative vertex count");
+    REQUIRE(stride == 3 || stride == 4, "stride must be 3 or 4 floats");
+    REQUIRE(N == 0 || (vertices && flags), "null vertices / flags");
+    REQUIRE(model_points, "null model map");
+    REQUIRE(cols > 0 && rows > 0, "non-positive image size");
+    REQUIRE(points_step >= cols * 16, "row step smaller than a float4 row");
+    REQUIRE((((uintptr_t)model_points | (uintptr_t)points_step) & 3) == 0, "model map rows must be 4-byte aligned");
+    int32_t* partial = nullptr;
+    if (count && N > 0) {
+        VisScratch& scratch = stream_scratch<VisScratch>(S(stream));
+        HIP_TRY(scratch.reserve((size_t)dfa::visible_blocks(N)));
+        partial = scratch.data;
+    }
+    HIP_TRY(dfa::launch_visible_vertices(vertices, stride, N, model_points, points_step, cols, rows, fx, fy, cx, cy, z_tol, flags,
+                                         count, partial, S(stream)));
     return DFA_OK;
 }
 

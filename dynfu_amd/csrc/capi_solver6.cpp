@@ -34,6 +34,10 @@ struct dfa_solver6 {
     bool timing = false;  // hipEvent brackets around linearise / assemble / PCG of every Gauss-Newton iteration
     dfa::EventPool ev;  // 4 per Gauss-Newton iteration
     int pcg_key_D = -1;  // node count the captured PCG graphs were recorded for
+    // dfa_solver6_set_vertex_mask: the plan's copy of the caller's mask in its sorted order (max_N bytes, allocated on first
+    // use); has_mask: the linearisations read it
+    uint8_t* vmask = nullptr;
+    bool has_mask  = false;
 };
 
 namespace {
@@ -187,6 +191,21 @@ int dfa_solver6_set_problem(dfa_solver6* s, const float* node_pos, const float* 
     HIP_TRY(dfa::launch_knn(node_pos, node_w, D, node_pos, D, kreg, s->raw_reg, nullptr, grid, S(stream)));
     HIP_TRY(dfa::s6_build_graph(v, s->state, canon_vertices, canon_normals, s->raw_w, s->raw_reg, kreg, S(stream)));
     s->has_problem = true;
+    s->has_mask    = false;  // a mask belongs to the vertex order it was given in
+    return DFA_OK;
+}
+
+int dfa_solver6_set_vertex_mask(dfa_solver6* s, const uint8_t* mask, dfa_stream_t stream) {
+    REQUIRE(s && s->has_problem, "no problem set");
+    s->has_mask = false;
+    if (!mask) return DFA_OK;
+    if (!s->vmask) {
+        s->mem.alloc(&s->vmask, (size_t)s->max_N);
+        const int rc = plan_status(s->mem);
+        if (rc != DFA_OK) return rc;
+    }
+    HIP_TRY(dfa::s6_gather_mask(s->v, mask, s->vmask, S(stream)));
+    s->has_mask = true;
     return DFA_OK;
 }
 
@@ -217,6 +236,7 @@ int dfa_solver6_solve(dfa_solver6* s, const float* live_vertex_map, int vertex_s
     const bool early = p.gn_tol > 0.f;
     dfa::Solve6Image img{live_vertex_map, live_normal_map, vertex_step, normal_step, cols, rows, fx, fy, cx, cy};
     hipStream_t st = S(stream);
+    const uint8_t* vmask = s->has_mask ? s->vmask : nullptr;
     s->ev.rewind();
     HIP_TRY(dfa::s6_begin(s->v, s->state, s->node_dq, early ? p.num_iter * p.gn_iter : 0, st));
     s->last_launches = 0;
@@ -253,7 +273,7 @@ int dfa_solver6_solve(dfa_solver6* s, const float* live_vertex_map, int vertex_s
             // gn_tol > 0: the launch's last workgroup applies the stopping rule on the device — launches behind the end of an
             // outer iteration return at entry (nothing comes back to the host: the launches of the whole solve are enqueued
             // regardless)
-            HIP_TRY(dfa::s6_linearise(s->v, s->state, img, p, gn == 0, gi, gn, 0, st));
+            HIP_TRY(dfa::s6_linearise(s->v, s->state, img, p, gn == 0, gi, gn, 0, vmask, st));
             mark();
             HIP_TRY(dfa::s6_assemble(s->v, s->state, p, gn, st));
             mark();
@@ -269,7 +289,7 @@ int dfa_solver6_solve(dfa_solver6* s, const float* live_vertex_map, int vertex_s
     if (early && p.num_iter * p.gn_iter > 0) {
         // the last step of the solve, if its outer iteration ran to the cap: one closing linearisation decides whether it stays
         const int gi = p.num_iter * p.gn_iter;
-        HIP_TRY(dfa::s6_linearise(s->v, s->state, img, p, 0, gi, p.gn_iter, 1, st));
+        HIP_TRY(dfa::s6_linearise(s->v, s->state, img, p, 0, gi, p.gn_iter, 1, vmask, st));
         HIP_TRY(dfa::s6_update(s->v, s->state, 0, p.linear_iter, nullptr, gi, 0, st));
     }
     if (mirror_slot) HIP_TRY(hipEventRecord(s->done_ev[b.slot], st));

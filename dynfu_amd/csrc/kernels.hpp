@@ -202,6 +202,12 @@ hipError_t launch_mesh_rasterize(const float* vertices, const float* normals, in
                                  int rows, uint64_t* zbuffer, float* points, int points_step, float* out_normals,
                                  int normals_step, hipStream_t s);
 
+// visibility.hip — a cloud's vertices against a model point map (dfa_visible_vertices).  partial: visible_blocks(n) ints of
+// device scratch, needed when count is given
+int visible_blocks(int n);
+hipError_t launch_visible_vertices(const float* vertices, int stride, int n, const float* model_points, int points_step, int cols,
+                                   int rows, float fx, float fy, float cx, float cy, float z_tol, uint8_t* flags, int32_t* count,
+                                   int32_t* partial, hipStream_t s);
 
 // img.hip
 hipError_t launch_bilateral(const uint16_t* src, int src_step, uint16_t* dst, int dst_step, int cols, int rows, int ksz,

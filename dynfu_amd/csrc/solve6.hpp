@@ -190,8 +190,11 @@ hipError_t s6_begin(const Solve6View& s, Solve6State* state, const float* node_d
 // gn_tol > 0: the launch also sums the energy and applies the Gauss-Newton stopping rule for history slot gi (gn_in_outer:
 // index inside the outer iteration; closing: the check of the solve's last step) — by its last workgroup, which every other
 // workgroup's partial sums reach through write-through stores
+// vmask: the plan's vertex mask in its sorted order (s6_gather_mask) or null — a vertex with a zero byte takes no data row
 hipError_t s6_linearise(const Solve6View& s, Solve6State* state, const Solve6Image& img, const Solve6Params& p,
-                        int update_weights, int gi, int gn_in_outer, int closing, hipStream_t st);
+                        int update_weights, int gi, int gn_in_outer, int closing, const uint8_t* vmask, hipStream_t st);
+// out[v] = mask[vperm[v]] != 0: a caller's per-vertex mask (N bytes, the caller's vertex order) in the plan's order
+hipError_t s6_gather_mask(const Solve6View& s, const uint8_t* mask, uint8_t* out, hipStream_t st);
 // gn_in_outer: index of the Gauss-Newton iteration inside its outer iteration (selects the PCG tolerance of the forcing schedule)
 hipError_t s6_assemble(const Solve6View& s, Solve6State* state, const Solve6Params& p, int gn_in_outer, hipStream_t st);
 struct S6Forcing {  // what the assembly launch (gn_tol > 0: the linearisation) leaves in the state block for the PCG that follows

@@ -1,6 +1,7 @@
 // solve6_graph.hip — once per frame of the north-star solve (formulation and launch list: solve6.hpp): the solver's
 // vertex order (by nearest node, by index inside a node), the normalised weights, the regularisation graph and the three
-// node -> rows transpositions; s6_build_graph ends in the pattern's two launches (solve6_pattern.hip).
+// node -> rows transpositions; s6_build_graph ends in the pattern's two launches (solve6_pattern.hip).  Also here, because
+// it goes through that vertex order: s6_gather_mask, a caller's vertex mask brought into it.
 #include <hip/hip_runtime.h>
 
 #include "solve.hpp"  // solve_transpose_graph
@@ -101,7 +102,21 @@ __global__ __launch_bounds__(256) void s6_reg_graph_kernel(const int32_t* __rest
 
 __global__ void s6_pattern_reset_kernel(Solve6State* st) { st->overflow = 0, st->max_row_blocks = 0; }
 
+// a caller's per-vertex mask brought into the solver's vertex order (what s6_warp does the other way round): a lane per
+// sorted position, bytes normalised to 0 / 1
+__global__ __launch_bounds__(256) void s6_gather_mask_kernel(const uint32_t* __restrict__ vperm, int N,
+                                                             const uint8_t* __restrict__ mask, uint8_t* __restrict__ out) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v < N) out[v] = mask[vperm[v]] != 0;
+}
+
 }  // namespace
+
+hipError_t s6_gather_mask(const Solve6View& s, const uint8_t* mask, uint8_t* out, hipStream_t st) {
+    if (s.N == 0) return hipSuccess;
+    s6_gather_mask_kernel<<<(s.N + 255) / 256, 256, 0, st>>>(s.vperm, s.N, mask, out);
+    return hipGetLastError();
+}
 
 hipError_t s6_build_graph(const Solve6View& s, Solve6State* state, const float* canon_user, const float* canon_n_user,
                           const float* raw_w, const int32_t* raw_reg, int kreg, hipStream_t st) {

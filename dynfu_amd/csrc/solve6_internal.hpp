@@ -162,7 +162,7 @@ constexpr int S6_UNITS = 256;           // work units of a node's assembly = thr
 
 }  // namespace
 
-// a kernel template by the smaller K in {4, 8} that holds the plan's k  [used by: _graph, _linearise, _update]
+// a kernel template by the smaller K in {4, 8} that holds the plan's k  [used by: _graph, _update; _linearise, whose kernel has a second template argument, spells the same choice out]
 #define K6DISPATCH(kernel, k, ...)            \
     do {                                      \
         if ((k) <= 4) kernel<4> __VA_ARGS__;  \

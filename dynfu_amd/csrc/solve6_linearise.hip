@@ -90,11 +90,20 @@ __device__ __forceinline__ void s6_linearise_tail(const Solve6View& s, Solve6Sta
     if (threadIdx.x == 0) s6_decide(st, d);
 }
 
-// blocks [0, nlin): the data term, a lane per vertex; blocks from nlin on: the regulariser, a lane per edge
-template <int K>
+// may vertex v (the plan's sorted order) take a data row?  Without a mask: always; with one: where its byte is set
+__device__ __forceinline__ bool s6_unmasked(int) { return true; }
+__device__ __forceinline__ bool s6_unmasked(int v, const uint8_t* vmask) { return vmask[v] != 0; }
+
+// blocks [0, nlin): the data term, a lane per vertex; blocks from nlin on: the regulariser, a lane per edge.
+// MASKED: the plan has a vertex mask (dfa_solver6_set_vertex_mask) and the launch one argument more, the mask in the plan's
+// sorted order — a zero byte sends the vertex down the path of a vertex without association: a record of zeros, no energy,
+// not counted, its rho left alone.  The instantiations without MASKED have no such argument (Mask is empty) and are the
+// code they were before the mask existed.
+template <int K, bool MASKED, class... Mask>
 __global__ __launch_bounds__(256) void s6_linearise_kernel(Solve6View s, Solve6State* st, Solve6Image img,
                                                            Solve6Params prm, int update_w, int nlin, float wreg2, int gate,
-                                                           const S6Decide dec) {
+                                                           const S6Decide dec, Mask... vmask) {
+    static_assert(sizeof...(Mask) == (MASKED ? 1 : 0), "the mask pointer is the masked instantiation's argument alone");
     if (gate && st->gn_stop) return;  // (uniform) the outer iteration has ended: nothing to linearise, nothing to decide
     if ((int)blockIdx.x >= nlin) {  // (uniform)
         const int e = ((int)blockIdx.x - nlin) * 256 + (int)threadIdx.x;
@@ -134,7 +143,7 @@ __global__ __launch_bounds__(256) void s6_linearise_kernel(Solve6View s, Solve6S
         blend<K>(s.dq, idx, wn, k, B);
         const f3 c = mk3(s.canon[3 * (size_t)v], s.canon[3 * (size_t)v + 1], s.canon[3 * (size_t)v + 2]);
         f3 p = c, nl = mk3(0.f, 0.f, 0.f);
-        if (B.m > 0.f) {
+        if (B.m > 0.f && s6_unmasked(v, vmask...)) {
             p = blend_point<K>(B, c);
             if (p.z > 0.f) {
                 // nearest pixel (proj_icp.cu:80-86 uses __float2int_rn)
@@ -225,7 +234,7 @@ __device__ __forceinline__ double s6_reg_edge(const Solve6View& s, int e, float 
 }  // namespace
 
 hipError_t s6_linearise(const Solve6View& s, Solve6State* state, const Solve6Image& img, const Solve6Params& p,
-                        int update_weights, int gi, int gn_in_outer, int closing, hipStream_t st) {
+                        int update_weights, int gi, int gn_in_outer, int closing, const uint8_t* vmask, hipStream_t st) {
     // (g^, M of the nodes and the cleared cost accumulators come from the launch that produced the transforms:
     // s6_begin / s6_update)
     const float wreg2 = p.lambda / ((float)s.D * (float)s.k);
@@ -233,7 +242,15 @@ hipError_t s6_linearise(const Solve6View& s, Solve6State* state, const Solve6Ima
     // gn_tol > 0: a linearisation that does not open an outer iteration is skipped once that iteration has ended
     const int gate = p.gn_tol > 0.f && !update_weights;
     const S6Decide dec{p.gn_tol > 0.f ? 1 : 0, gi, gn_in_outer, closing, p.gn_tol, s6_forcing(p, gn_in_outer)};
-    K6DISPATCH(s6_linearise_kernel, s.k, <<<nlin + nreg, 256, 0, st>>>(s, state, img, p, update_weights, nlin, wreg2, gate, dec));
+    // (K6DISPATCH's choice of K, by hand: the kernel has a second template argument)
+    const dim3 grid(nlin + nreg), block(256);
+    if (vmask) {
+        if (s.k <= 4) s6_linearise_kernel<4, true><<<grid, block, 0, st>>>(s, state, img, p, update_weights, nlin, wreg2, gate, dec, vmask);
+        else s6_linearise_kernel<8, true><<<grid, block, 0, st>>>(s, state, img, p, update_weights, nlin, wreg2, gate, dec, vmask);
+    } else {
+        if (s.k <= 4) s6_linearise_kernel<4, false><<<grid, block, 0, st>>>(s, state, img, p, update_weights, nlin, wreg2, gate, dec);
+        else s6_linearise_kernel<8, false><<<grid, block, 0, st>>>(s, state, img, p, update_weights, nlin, wreg2, gate, dec);
+    }
     return hipGetLastError();
 }
 

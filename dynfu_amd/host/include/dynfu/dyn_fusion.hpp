@@ -79,6 +79,18 @@ struct DynFuParams {  // dyn_fusion.hpp:25-42
     // nothing of this runs.
     bool fuse_knn_field = false;
     size_t fuse_knn_field_max_bytes = 0;
+    // Extension — the north-star data term over the visible surface of the model only (needs north_star AND model_view:
+    // otherwise the constructor throws dfa::Error).  Every frame after the first, between initializeProblemInstance and the
+    // solve: the canonical mesh is warped by the node transforms the solve starts from and rasterised from the frame's camera
+    // (renderWarpedModel's path without the shading: getWarpedModelMaps() holds the maps afterwards), the canonical cloud is
+    // warped by the same transforms on the solver's plan, and the vertices the model's surface hides
+    // (kfusion::cuda::visibleVertices) take no data row in that frame's solve (NorthStarSolver::setVertexMask).
+    // visibility_z_tol: how far behind the rasterised surface a vertex may lie and still count as seen, in metres; 0 = two
+    // voxels of the volume's largest voxel edge — the cloud's vertices are vertices of the rasterised mesh, and the depth
+    // interpolated under a vertex's pixel differs from the vertex's own by at most one cell's extent, sqrt(3) voxels.
+    // Off, nothing of this runs and a frame's outputs are what they were, bit for bit.
+    bool north_star_visible_only = false;
+    float visibility_z_tol       = 0.f;
 };
 
 struct dfa_solver6;  // include/dynfu_amd.h
@@ -127,6 +139,9 @@ public:
     double northStarInitialCost() const { return ns_initial_cost_; }
     double northStarFinalCost() const { return ns_final_cost_; }
     long long northStarValidRows() const { return ns_valid_rows_; }
+    // north_star_visible_only: canonical vertices the last frame's solve could take data rows from (one small read from the
+    // device); -1 before the first such frame, or with the switch off
+    long long northStarVisibleVertices() const;
 
     void init(dfa::PointCloud<dfa::PointXYZ>& canonicalVertices, dfa::PointCloud<dfa::Normal>& canonicalNormals);
     void initCanonicalFrame(dfa::PointCloud<dfa::PointXYZ>& vertices, dfa::PointCloud<dfa::Normal>& normals);
@@ -197,6 +212,13 @@ private:
     std::vector<float> mesh_nodes_built_pos_, mesh_nodes_built_w_;
     kfusion::cuda::Cloud model_points_;
     kfusion::cuda::Normals model_normals_;
+    // the warped mesh as float4 vertices / normals rasterised into model_points_ / model_normals_ / model_zbuffer_
+    // (renderWarpedModel's first half; north_star_visible_only runs it alone)
+    void rasterizeWarpedModel();
+    // north_star_visible_only: the frame's flags (one per canonical vertex) and their count, on the device
+    dfa::DeviceArray<unsigned char> visible_flags_;
+    dfa::DeviceArray<int> visible_count_;
+    bool visible_counted_ = false;
 };
 
 // DynFuApp::execute of the reference's demo (src/apps/demo.cpp:68-124) without its windows and command line: every

@@ -53,6 +53,15 @@ public:
     // the canonical frame of the problem warped by the solved transforms (dual-quaternion blend, as the solve models
     // it); stays in HBM
     std::shared_ptr<dynfu::Frame> warpCanonicalToLive();
+    // ... warped by the transforms the solve STARTS from (the nodes' as initializeProblemInstance found them): the same
+    // blend, no solve needed (dfa_solver6_warp_with).  Vertices only, packed N x 3
+    dfa::DeviceArray<float> warpCanonicalByStart();
+
+    // Which canonical vertices may take a data row in the solveAll calls that follow (dfa_solver6_set_vertex_mask): one byte
+    // per vertex of the canonical frame, in its order, non-zero = may.  Every initializeProblemInstance starts without a
+    // mask; the bytes are copied by the work the call enqueues.
+    void setVertexMask(const dfa::DeviceArray<unsigned char>& mask);
+    void clearVertexMask();
 
     double initialCost() const { return initial_cost_; }
     double finalCost() const { return final_cost_; }

@@ -19,5 +19,12 @@ void rasterizeMesh(const dfa::DeviceArray<dfa::PointXYZ>& vertices, const dfa::D
                    const dfa::DeviceArray<int>& indices, const Affine3f& world2cam, const Intr& intr, int cols, int rows,
                    float z_near, Cloud& points, Normals& normals_out, dfa::DeviceArray<uint64_t>& zbuffer);
 
+// dfa_visible_vertices: n vertices in the camera frame, `stride` floats apart (3: a dynfu::Frame's packed arrays, the
+// north-star warp's output; 4: float4 clouds), against the point map of the model's visible surface — rasterizeMesh's or
+// TsdfVolume::raycast's, NaN where nothing is seen.  flags (created at n bytes) gets 1 where the model does not lie in front
+// of the vertex by more than z_tol, 0 elsewhere; count (optional, created at one int, stays on the device): the set flags.
+void visibleVertices(const float* vertices, int stride, size_t n, const Cloud& model_points, const Intr& intr, float z_tol,
+                     dfa::DeviceArray<unsigned char>& flags, dfa::DeviceArray<int>* count = nullptr);
+
 }  // namespace cuda
 }  // namespace kfusion

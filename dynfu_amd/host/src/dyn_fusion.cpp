@@ -53,6 +53,8 @@ DynFusion::DynFusion(const DynFuParams& params) : kfusion::KinFu(params.kinfuPar
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_fuse_canonical needs north_star (reference mode: fuse_canonical)");
     if (params.fuse_knn_field && !params.fuse_canonical && !params.north_star_fuse_canonical)
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: fuse_knn_field serves the canonical fusion (fuse_canonical or north_star_fuse_canonical)");
+    if (params.north_star_visible_only && !(params.north_star && params.model_view))
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_visible_only needs north_star and model_view (the rasterised canonical mesh is what hides a vertex)");
     solverParams.numIter       = 24;  // dyn_fusion.cpp:183-189
     solverParams.nonLinearIter = 16;
     solverParams.linearIter    = 256;
@@ -299,6 +301,21 @@ bool DynFusion::northStarFrame(const kfusion::cuda::Depth& depth) {
                            dynfuParams.lambda, dynfuParams.psi_reg);
     solver.initializeProblemInstance(canonicalFrame);
     clk.mark("  initializeProblemInstance");
+    if (dynfuParams.north_star_visible_only) {
+        // the model as the solve finds it: mesh and cloud warped by the transforms the solve starts from, the mesh rasterised
+        // from this frame's camera; a vertex behind the rasterised surface takes no data row
+        rasterizeWarpedModel();
+        const dfa::DeviceArray<float> start = solver.warpCanonicalByStart();
+        float z_tol = dynfuParams.visibility_z_tol;
+        if (z_tol == 0.f) {
+            const kfusion::Vec3f vs = tsdf().getVoxelSize();
+            z_tol = 2.f * std::max(vs[0], std::max(vs[1], vs[2]));
+        }
+        kfusion::cuda::visibleVertices(start.ptr(), 3, canonicalFrame->size(), model_points_, p.intr, z_tol, visible_flags_, &visible_count_);
+        solver.setVertexMask(visible_flags_);
+        visible_counted_ = true;
+        clk.mark("  visible vertices");
+    }
     kfusion::cuda::computePointNormals(p.intr, depth_filtered_, live_points_, live_normals_);
     solver.solveAll(live_points_, live_normals_, p.intr);
     clk.mark("  solveAll");
@@ -382,7 +399,14 @@ std::shared_ptr<dynfu::Frame> DynFusion::warpCanonicalMesh() {
     return dynfu::Frame::fromDevice(0, ov, on, n);
 }
 
-void DynFusion::renderWarpedModel(kfusion::cuda::Image& image, int flag) {
+long long DynFusion::northStarVisibleVertices() const {
+    if (!visible_counted_) return -1;
+    std::vector<int> n;
+    visible_count_.download(n);  // (a blocking copy on the default stream: behind the frame's work)
+    return n.empty() ? -1 : n[0];
+}
+
+void DynFusion::rasterizeWarpedModel() {
     const auto warped = warpCanonicalMesh();
     const kfusion::KinFuParams& p = params_;
     const dynfu::Frame::DeviceView w = warped->device();
@@ -394,6 +418,11 @@ void DynFusion::renderWarpedModel(kfusion::cuda::Image& image, int flag) {
     const dfa::Affine3f world2cam = dynfuParams.north_star ? dfa::Affine3f() : getCameraPose().inv() * tsdf().getPose();
     kfusion::cuda::rasterizeMesh(warped_vertices_, warped_normals_, canonical_mesh_.indices, world2cam, p.intr, p.cols, p.rows,
                                  dynfuParams.model_view_z_near, model_points_, model_normals_, model_zbuffer_);
+}
+
+void DynFusion::renderWarpedModel(kfusion::cuda::Image& image, int flag) {
+    rasterizeWarpedModel();
+    const kfusion::KinFuParams& p = params_;
     image.create(p.rows, flag != 3 ? p.cols : p.cols * 2);  // as KinFu::renderImage
     if (flag == 2) kfusion::cuda::renderTangentColors(model_normals_, image);
     else if (flag != 3) kfusion::cuda::renderImage(model_points_, model_normals_, p.intr, p.light_pose, image);

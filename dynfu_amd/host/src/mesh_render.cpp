@@ -23,5 +23,16 @@ void rasterizeMesh(const dfa::DeviceArray<dfa::PointXYZ>& vertices, const dfa::D
                "rasterizeMesh");
 }
 
+void visibleVertices(const float* vertices, int stride, size_t n, const Cloud& model_points, const Intr& intr, float z_tol,
+                     dfa::DeviceArray<unsigned char>& flags, dfa::DeviceArray<int>* count) {
+    if (n > 0x7fffffffu) throw dfa::Error(DFA_ERR_INVALID, "visibleVertices: more than 2^31 - 1 vertices");
+    if (flags.size() != n) flags.create(n);
+    if (count && count->size() != 1) count->create(1);
+    dfa::check(dfa_visible_vertices(vertices, stride, (int)n, (const float*)model_points.ptr(), (int)model_points.step(),
+                                    model_points.cols(), model_points.rows(), intr.fx, intr.fy, intr.cx, intr.cy, z_tol,
+                                    flags.ptr(), count ? count->ptr() : nullptr, nullptr),
+               "visibleVertices");
+}
+
 }  // namespace cuda
 }  // namespace kfusion

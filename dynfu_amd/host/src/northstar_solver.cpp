@@ -95,6 +95,8 @@ void NorthStarSolver::initializeProblemInstance(const std::shared_ptr<dynfu::Fra
                 b.canon_n.ptr() == I.canon_n.ptr()) {
                 I.node_pos = b.node_pos, I.node_w = b.node_w;  // shared: the plan reads them
                 dfa::check(dfa_solver6_set_node_transforms(I.plan, I.node_dq.ptr()), "NorthStarSolver: set_node_transforms");
+                // a mask stays across set_node_transforms, and the plan may have served another solver: a frame starts without
+                dfa::check(dfa_solver6_set_vertex_mask(I.plan, nullptr, nullptr), "NorthStarSolver: set_vertex_mask");
                 return;
             }
         }
@@ -163,6 +165,27 @@ void NorthStarSolver::solveAll(const kfusion::cuda::Cloud& vmap, const kfusion::
         nodes[i]->setTransformation(std::make_shared<DualQuaternion<float>>(dfa::quaternion<float>(q[0], q[1], q[2], q[3]),
                                                                             dfa::quaternion<float>(q[4], q[5], q[6], q[7])));
     }
+}
+
+dfa::DeviceArray<float> NorthStarSolver::warpCanonicalByStart() {
+    Impl& I = *impl;
+    if (!I.plan) throw dfa::Error(DFA_ERR_INVALID, "warpCanonicalByStart before initializeProblemInstance");
+    dfa::DeviceArray<float> ov(3 * (size_t)I.N);
+    if (I.N) dfa::check(dfa_solver6_warp_with(I.plan, I.node_dq.ptr(), ov.ptr(), nullptr, nullptr), "NorthStarSolver::warpCanonicalByStart");
+    return ov;
+}
+
+void NorthStarSolver::setVertexMask(const dfa::DeviceArray<unsigned char>& mask) {
+    Impl& I = *impl;
+    if (!I.plan) throw dfa::Error(DFA_ERR_INVALID, "setVertexMask before initializeProblemInstance");
+    if (mask.size() != (size_t)I.N) throw dfa::Error(DFA_ERR_INVALID, "NorthStarSolver::setVertexMask: one byte per canonical vertex");
+    if (I.N) dfa::check(dfa_solver6_set_vertex_mask(I.plan, mask.ptr(), nullptr), "NorthStarSolver::setVertexMask");
+}
+
+void NorthStarSolver::clearVertexMask() {
+    Impl& I = *impl;
+    if (!I.plan) throw dfa::Error(DFA_ERR_INVALID, "clearVertexMask before initializeProblemInstance");
+    dfa::check(dfa_solver6_set_vertex_mask(I.plan, nullptr, nullptr), "NorthStarSolver::clearVertexMask");
 }
 
 std::shared_ptr<dynfu::Frame> NorthStarSolver::warpCanonicalToLive() {

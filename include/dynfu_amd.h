@@ -247,6 +247,27 @@ int dfa_mesh_rasterize(const float* vertices, const float* normals /* may be NUL
                        int cols, int rows, uint64_t* zbuffer, float* points, int points_step, float* out_normals,
                        int normals_step, dfa_stream_t stream);
 
+/* Visibility of a cloud against a model point map (no reference counterpart; DynamicFusion's data term sums over the visible
+ * points of the warped model): flags[i] = 1 where the camera can see vertex i, 0 where the model's surface lies in front of it.
+ *   vertices: N vertices in the camera frame, `stride` floats apart (device): 3 — what dfa_solver6_warp and
+ *     dfa_solver6_warp_with write — or 4, the float4 clouds.
+ *   model_points: float4 point map in that frame with its row step in bytes, quiet NaN where nothing is seen —
+ *     dfa_mesh_rasterize's or dfa_tsdf_raycast_points'.  Only read; bytes of a row beyond its last pixel are not looked at.
+ *   flags: N bytes (device).  count: one device int32 or NULL: the number of set flags, the same in every run.
+ * One lane per vertex (x, y, z), float32, in this order:
+ *   1. x, y or z not finite, or z <= 0: flag 0.
+ *   2. qx = x / z, qy = y / z, correctly rounded.
+ *   3. u = fmaf(fx, qx, cx), v = fmaf(fy, qy, cy).
+ *   4. ru = rintf(u), rv = rintf(v); unless 0 <= ru <= cols - 1 and 0 <= rv <= rows - 1 (compared as floats): flag 0.
+ *   5. M = model_points[rv][ru]; M.x is NaN: flag 1 — nothing of the model covers that pixel, so nothing occludes the vertex.
+ *   6. Otherwise flag = z <= M.z + z_tol (one addition, one comparison).
+ * The arithmetic is stated in csrc/visibility.hip and tests/visibility_statement.py.  One launch (two with count) on
+ * `stream`; the host does not wait, and nothing is allocated beyond the stream's scratch (the workgroups' counts).
+ * N == 0 succeeds and writes count = 0. */
+int dfa_visible_vertices(const float* vertices, int stride /* floats per vertex: 3 or 4 */, int N, const float* model_points,
+                         int points_step, int cols, int rows, float fx, float fy, float cx, float cy, float z_tol,
+                         uint8_t* flags /* N */, int32_t* count /* device, may be NULL */, dfa_stream_t stream);
+
 
 /* ===================================================================================== */
 /* Depth pre-processing seam — replaces the image kernels of kfusion::device declared in    */
@@ -805,6 +826,16 @@ int dfa_solver6_set_problem(dfa_solver6* s, const float* node_pos, const float* 
  * set_problem).  What a per-frame caller does instead of rebuilding k-NN, transposition and pair lists (~0.5 ms at 232 k
  * vertices) when nothing they depend on has moved. */
 int dfa_solver6_set_node_transforms(dfa_solver6* s, const float* node_dq);
+/* Which vertices may take a data row in the solves that follow — dfa_visible_vertices' flags, say, so that the data term runs
+ * over the visible surface of the model only.
+ * mask: N bytes (device), the caller's vertex order of the last dfa_solver6_set_problem; non-zero = the vertex may take a
+ * data row.  Read by the work this call enqueues only.  NULL: no mask.  Stays across dfa_solver6_set_node_transforms;
+ * dfa_solver6_set_problem removes it.
+ * The plan keeps its own copy in its sorted order (max_N bytes, allocated by the first call that gives a mask).  A masked-out
+ * vertex takes the path of a vertex without association in every linearisation that follows: a record of zeros, no energy, not
+ * counted in valid_*, its robust weight left alone.  The graphs, the block pattern of the normal matrix, dfa_solver6_warp and
+ * dfa_solver6_warp_with do not change: a masked vertex still warps.  Without a dfa_solver6_set_problem: DFA_ERR_INVALID. */
+int dfa_solver6_set_vertex_mask(dfa_solver6* s, const uint8_t* mask, dfa_stream_t stream);
 /* live maps: float4 pixels in the camera frame (the canonical cloud and the nodes are in the same
  * frame), NaN where undefined — dfa_compute_points_normals or dfa_tsdf_raycast_points output */
 int dfa_solver6_solve(dfa_solver6* s, const float* live_vertex_map, int vertex_step, const float* live_normal_map,

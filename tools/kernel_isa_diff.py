@@ -17,6 +17,8 @@ unless --require-identical).
 --define NAME or NAME=VALUE adds -DNAME / -DNAME=VALUE to every compilation (repeatable).
 --drop-arg pcg_paired_kernel:1 matches kernels of the two sides whose template argument lists differ by the one
 argument a change removed (index into the parent's list).
+--drop-branch-arg s6_linearise_kernel:1:false does the same for an argument a change ADDED: the branch's instantiations
+whose argument at that index has that value lose it before the names are matched (the others stay "only in branch").
 """
 import argparse
 import os
@@ -96,10 +98,12 @@ def compile_side(checkout, files, extra, out):
 
 
 def drop(name, rules):
-    for kern, idx in rules:
+    for kern, idx, *value in rules:
         m = re.match(r"(%s)<(.*)>$" % re.escape(kern), name)
         if m:
             args = [a.strip() for a in m.group(2).split(",")]
+            if value and args[idx] != value[0]:  # (a rule with a value only meets the instantiations that have it)
+                continue
             del args[idx]
             return "%s<%s>" % (m.group(1), ", ".join(args))
     return name
@@ -114,9 +118,11 @@ def main():
     ap.add_argument("--branch-files", help="comma-separated; instead of --file for the branch")
     ap.add_argument("--define", action="append", default=[], metavar="NAME[=VALUE]")
     ap.add_argument("--drop-arg", action="append", default=[])
+    ap.add_argument("--drop-branch-arg", action="append", default=[], metavar="KERNEL:INDEX:VALUE")
     ap.add_argument("--require-identical", action="store_true", help="a differing ISA fails too")
     a = ap.parse_args()
     rules = [(r.split(":")[0], int(r.split(":")[1])) for r in a.drop_arg]
+    rules_b = [(r.split(":")[0], int(r.split(":")[1]), r.split(":")[2]) for r in a.drop_branch_arg]
     if not (a.file or (a.parent_files and a.branch_files)):
         ap.error("--file, or --parent-files and --branch-files")
     pfiles = (a.parent_files or a.file).split(",")
@@ -129,6 +135,7 @@ def main():
             kp, twice_p = compile_side(a.parent, pfiles, defines + extra, os.path.join(tmp, "p"))
             kb, twice_b = compile_side(a.branch, bfiles, defines + extra, os.path.join(tmp, "b"))
         kp = {drop(k, rules): v for k, v in kp.items()}
+        kb = {drop(k, rules_b): v for k, v in kb.items()}
         print("\n### %s build%s of %s: %d kernels (parent), %d (branch)\n" % (label, "".join(" " + d for d in defines), what, len(kp), len(kb)))
         for side, twice in (("parent", twice_p), ("branch", twice_b)):
             for k in twice:
