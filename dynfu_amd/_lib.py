@@ -12,7 +12,7 @@ SYMBOLS = [
     "dfa_tsdf_clear_integrate", "dfa_tsdf_raycast_points", "dfa_tsdf_raycast_depth", "dfa_tsdf_raycast_tally", "dfa_tsdf_raycast_render", "dfa_render_image_points", "dfa_render_image_depth", "dfa_render_tangent_colors", "dfa_mesh_rasterize", "dfa_visible_vertices", "dfa_tsdf_vertex_normals", "dfa_tsdf_extract_cloud", "dfa_tsdf_extract_cloud_occ", "dfa_tsdf_extract_normals", "dfa_correspond_projective", "dfa_knn", "dfa_warp_to_live",
     "dfa_calc_dqb", "dfa_unsupported_vertices", "dfa_icp_sums", "dfa_repack_points", "dfa_compact_points", "dfa_transform_points", "dfa_warp_to_live_graph",
     "dfa_correspond", "dfa_marching_cubes", "dfa_mc_default_tables",
-    "dfa_tsdf_occupancy_bytes", "dfa_tsdf_clear_occ", "dfa_tsdf_integrate_occ", "dfa_tsdf_clear_integrate_occ", "dfa_tsdf_clear_integrate_known_occ", "dfa_tsdf_integrate_warped", "dfa_tsdf_integrate_warped6", "dfa_marching_cubes_occ", "dfa_marching_cubes_indexed",
+    "dfa_tsdf_occupancy_bytes", "dfa_tsdf_clear_occ", "dfa_tsdf_integrate_occ", "dfa_tsdf_clear_integrate_occ", "dfa_tsdf_clear_integrate_known_occ", "dfa_tsdf_integrate_warped", "dfa_tsdf_integrate_warped6", "dfa_marching_cubes_occ", "dfa_marching_cubes_indexed", "dfa_marching_cubes_indexed_min_weight",
     "dfa_knn_field_create", "dfa_knn_field_destroy", "dfa_knn_field_build", "dfa_knn_field_append", "dfa_knn_field_info", "dfa_knn_field_lookup",
     "dfa_tsdf_integrate_warped_field", "dfa_tsdf_integrate_warped6_field",
     "dfa_depth_bilateral_filter", "dfa_depth_truncate", "dfa_depth_build_pyramid", "dfa_compute_normals_mask_depth",
@@ -229,6 +229,7 @@ def load(path=None):
     L.dfa_marching_cubes.argtypes = [vp, i, i, i, vp, vp, vp, vp, i, vp, vp]
     L.dfa_marching_cubes_occ.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, i, vp, vp]
     L.dfa_marching_cubes_indexed.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, i, vp, i, vp, vp]
+    L.dfa_marching_cubes_indexed_min_weight.argtypes = [vp, vp, i, i, i, vp, vp, vp, i, vp, i, vp, i, vp, vp]
     L.dfa_mc_default_tables.argtypes = [vp, vp]
     L.dfa_icp_sums.argtypes = [i, vp, i, vp, i, vp, i, vp, i, i, i, vp, f, f, f, f, f, f, vp, vp, vp]
     L.dfa_calc_dqb.argtypes = [vp, vp, vp, i, i, vp, i, vp, vp]
@@ -701,21 +702,25 @@ def marching_cubes(vol, cell_size, tri_table, num_verts_table, max_vertices, occ
     return pts, total
 
 
-def marching_cubes_indexed(vol, cell_size, tri_table, num_verts_table, max_vertices, max_indices, occupancy=None):
+def marching_cubes_indexed(vol, cell_size, tri_table, num_verts_table, max_vertices, max_indices, occupancy=None, min_weight=1):
     """dfa_marching_cubes_indexed: the surface as an indexed mesh.  Returns (vertices (max_vertices, 4) float32 CUDA tensor —
     every crossed lattice edge once, in ascending 3 * voxel + axis —, indices (max_indices,) int32 CUDA tensor — the vertex
     of every soup vertex of marching_cubes, same order —, totals int32 CUDA tensor of 2 elements: vertices, indices).  The
-    buffers hold the mesh only when neither total exceeds its capacity; zero capacities count only."""
+    buffers hold the mesh only when neither total exceeds its capacity; zero capacities count only.
+    min_weight other than 1: dfa_marching_cubes_indexed_min_weight — a voxel counts as observed from that weight on."""
     torch = _torch()
     X, Y, Z = _vol_dims(vol)
     verts = torch.empty((max(max_vertices, 1), 4), dtype=torch.float32, device=vol.device)
     idx = torch.empty((max(max_indices, 1),), dtype=torch.int32, device=vol.device)
     totals = torch.zeros((2,), dtype=torch.int32, device=vol.device)
-    _check(load().dfa_marching_cubes_indexed(
-        _dev(vol), None if occupancy is None else _dev(occupancy, torch.uint8, "occupancy"), X, Y, Z, _farr(cell_size, 3),
-        _dev(tri_table, torch.int32, "tri_table"), _dev(num_verts_table, torch.int32, "num_verts_table"),
-        _dev(verts) if max_vertices > 0 else None, max_vertices, _dev(idx) if max_indices > 0 else None, max_indices,
-        _dev(totals), _stream()))
+    head = (_dev(vol), None if occupancy is None else _dev(occupancy, torch.uint8, "occupancy"), X, Y, Z, _farr(cell_size, 3),
+            _dev(tri_table, torch.int32, "tri_table"), _dev(num_verts_table, torch.int32, "num_verts_table"))
+    tail = (_dev(verts) if max_vertices > 0 else None, max_vertices, _dev(idx) if max_indices > 0 else None, max_indices,
+            _dev(totals), _stream())
+    if min_weight == 1:
+        _check(load().dfa_marching_cubes_indexed(*head, *tail))
+    else:
+        _check(load().dfa_marching_cubes_indexed_min_weight(*head, int(min_weight), *tail))
     return verts, idx, totals
 
 

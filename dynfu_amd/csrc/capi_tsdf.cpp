@@ -247,24 +247,49 @@ int dfa_marching_cubes_occ(const uint32_t* volume, const uint8_t* occupancy, int
                                  total_vertices, occupancy, stream);
 }
 
+// min_weight 0: the plain call (no floor); fn: the entry point a refusal names
+static int marching_cubes_indexed_common(const char* fn, const uint32_t* volume, const uint8_t* occupancy, int X, int Y, int Z,
+                                         const float cell_size[3], const int32_t* tri_table, const int32_t* num_verts_table,
+                                         int min_weight, float* out_vertices, int max_vertices, int32_t* out_indices,
+                                         int max_indices, int32_t* totals, dfa_stream_t stream) {
+    REQUIRE_AS(fn, volume && X >= 2 && Y >= 2 && Z >= 2, "bad volume");
+    REQUIRE_AS(fn, cell_size && tri_table && num_verts_table, "null parameter block / case tables");
+    REQUIRE_AS(fn, max_vertices >= 0 && (max_vertices == 0 || out_vertices), "bad vertex buffer");
+    REQUIRE_AS(fn, max_indices >= 0 && (max_indices == 0 || out_indices), "bad index buffer");
+    REQUIRE_AS(fn, ((uintptr_t)out_vertices & 15) == 0, "out_vertices must be 16-byte aligned");
+    REQUIRE_AS(fn, totals, "null totals");
+    REQUIRE_AS(fn, (long)X * Y * Z / 64 < (1L << 31), "volume too large");
+    const long nsegs = dfa::mci_segments(X, Y, Z);
+    McIndexedScratch& scratch = stream_scratch<McIndexedScratch>(S(stream));
+    HIP_TRY(scratch.reserve(nsegs));
+    if (min_weight == 0) {
+        HIP_TRY(dfa::launch_marching_cubes_indexed(volume, X, Y, Z, cell_size, tri_table, num_verts_table, out_vertices,
+                                                   max_vertices, out_indices, max_indices, totals, scratch.vert.seg_off.data,
+                                                   scratch.idx_off.data, scratch.vert.chunk_sums.data, occupancy, S(stream)));
+    } else {
+        HIP_TRY(dfa::launch_marching_cubes_indexed_min_weight(volume, X, Y, Z, cell_size, tri_table, num_verts_table, min_weight,
+                                                              out_vertices, max_vertices, out_indices, max_indices, totals,
+                                                              scratch.vert.seg_off.data, scratch.idx_off.data,
+                                                              scratch.vert.chunk_sums.data, occupancy, S(stream)));
+    }
+    return DFA_OK;
+}
+
 int dfa_marching_cubes_indexed(const uint32_t* volume, const uint8_t* occupancy, int X, int Y, int Z, const float cell_size[3],
                                const int32_t* tri_table, const int32_t* num_verts_table, float* out_vertices,
                                int max_vertices, int32_t* out_indices, int max_indices, int32_t* totals,
                                dfa_stream_t stream) {
-    REQUIRE(volume && X >= 2 && Y >= 2 && Z >= 2, "bad volume");
-    REQUIRE(cell_size && tri_table && num_verts_table, "null parameter block / case tables");
-    REQUIRE(max_vertices >= 0 && (max_vertices == 0 || out_vertices), "bad vertex buffer");
-    REQUIRE(max_indices >= 0 && (max_indices == 0 || out_indices), "bad index buffer");
-    REQUIRE(((uintptr_t)out_vertices & 15) == 0, "out_vertices must be 16-byte aligned");
-    REQUIRE(totals, "null totals");
-    REQUIRE((long)X * Y * Z / 64 < (1L << 31), "volume too large");
-    const long nsegs = dfa::mci_segments(X, Y, Z);
-    McIndexedScratch& scratch = stream_scratch<McIndexedScratch>(S(stream));
-    HIP_TRY(scratch.reserve(nsegs));
-    HIP_TRY(dfa::launch_marching_cubes_indexed(volume, X, Y, Z, cell_size, tri_table, num_verts_table, out_vertices,
-                                               max_vertices, out_indices, max_indices, totals, scratch.vert.seg_off.data,
-                                               scratch.idx_off.data, scratch.vert.chunk_sums.data, occupancy, S(stream)));
-    return DFA_OK;
+    return marching_cubes_indexed_common(__func__, volume, occupancy, X, Y, Z, cell_size, tri_table, num_verts_table, 0, out_vertices,
+                                         max_vertices, out_indices, max_indices, totals, stream);
+}
+
+int dfa_marching_cubes_indexed_min_weight(const uint32_t* volume, const uint8_t* occupancy, int X, int Y, int Z,
+                                          const float cell_size[3], const int32_t* tri_table, const int32_t* num_verts_table,
+                                          int min_weight, float* out_vertices, int max_vertices, int32_t* out_indices,
+                                          int max_indices, int32_t* totals, dfa_stream_t stream) {
+    REQUIRE(min_weight >= 1 && min_weight <= 65535, "min_weight outside 1..65535 (the weight is 16 bits; 0 would admit unobserved voxels)");
+    return marching_cubes_indexed_common(__func__, volume, occupancy, X, Y, Z, cell_size, tri_table, num_verts_table, min_weight,
+                                         out_vertices, max_vertices, out_indices, max_indices, totals, stream);
 }
 
 // -------------------------------------------------------------- TSDF seam: point-cloud extraction

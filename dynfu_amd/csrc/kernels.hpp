@@ -169,6 +169,12 @@ hipError_t launch_marching_cubes_indexed(const uint32_t* vol, int X, int Y, int 
                                          int max_vertices, int32_t* out_indices, int max_indices, int32_t* totals,
                                          int32_t* voff, int32_t* ioff, int32_t* chunk_sums, const uint8_t* occ,
                                          hipStream_t s);
+// ... with a weight floor (dfa_marching_cubes_indexed_min_weight): a voxel counts as observed from min_weight (1..65535) on
+hipError_t launch_marching_cubes_indexed_min_weight(const uint32_t* vol, int X, int Y, int Z, const float cell_size[3],
+                                                    const int32_t* tri_table, const int32_t* num_verts_table,
+                                                    int min_weight, float* out_vertices, int max_vertices,
+                                                    int32_t* out_indices, int max_indices, int32_t* totals, int32_t* voff,
+                                                    int32_t* ioff, int32_t* chunk_sums, const uint8_t* occ, hipStream_t s);
 void mc_default_tables(int32_t tri_table[256 * 16], int32_t num_verts_table[256]);
 // exclusive scan of n segment counts in place (counts: n + 1 entries; counts[n] and *total (device, optional) receive the
 // sum; chunk_sums: mc_scan_chunks(n) entries) — marching cubes' step 2, shared with the point-cloud extraction

@@ -386,17 +386,31 @@ struct IdxArgs {
     int ox, oy, oz;
 };
 
+// dfa_marching_cubes_indexed_min_weight: the same kernels in their FLOOR form.  A voxel counts as observed from the weight
+// `min_weight` (1..65535) on; the one place that looks at a weight is voxel_bits, so everything built from the W masks —
+// valid cubes, the cubes around an owned edge — follows.  The plain form carries no floor: its arguments and its
+// instructions are those it had before there was one.
+template <bool FLOOR>
+struct IdxArgsT : IdxArgs {};
+template <>
+struct IdxArgsT<true> : IdxArgs {
+    uint32_t min_weight;
+};
+
 constexpr uint32_t IDX_OWN = 0x1eu;  // a lane's own voxels in a row mask
 
-// bit 0: weight != 0, bit 8: distance < 0
-__device__ __forceinline__ uint32_t voxel_bits(uint32_t v) {
+// bit 0: weight != 0 (FLOOR: weight >= min_weight), bit 8: distance < 0
+__device__ __forceinline__ uint32_t voxel_bits(const IdxArgsT<false>&, uint32_t v) {
     return ((v >> 16) != 0u ? 1u : 0u) | (half_bits_to_float(v & 0xffffu) < 0.f ? 0x100u : 0u);
+}
+__device__ __forceinline__ uint32_t voxel_bits(const IdxArgsT<true>& a, uint32_t v) {
+    return ((v >> 16) >= a.min_weight ? 1u : 0u) | (half_bits_to_float(v & 0xffffu) < 0.f ? 0x100u : 0u);
 }
 
 // NR consecutive rows y .. y + NR - 1 (NR <= 4) of slice z as masks; rows, slices and voxels that do not exist (y or z
 // may be -1 or past the end) give zeros: weight 0.  The three voxels around the segment come by ONE load for all rows.
-template <int NR>
-__device__ __forceinline__ void load_row_bits(const IdxArgs& a, int seg, int y, int z, uint32_t* W, uint32_t* N) {
+template <int NR, bool FLOOR>
+__device__ __forceinline__ void load_row_bits(const IdxArgsT<FLOOR>& a, int seg, int y, int z, uint32_t* W, uint32_t* N) {
     const int lane = threadIdx.x & 63, xs = seg * 256, x0 = xs + lane * 4;
     const bool z_ok = z >= 0 && z < a.Z;
     uint32_t own[NR];
@@ -416,14 +430,14 @@ __device__ __forceinline__ void load_row_bits(const IdxArgs& a, int seg, int y, 
                 if (x0 + 3 < a.X) v3 = p[3];
             }
         }
-        own[r] = voxel_bits(v0) | voxel_bits(v1) << 1 | voxel_bits(v2) << 2 | voxel_bits(v3) << 3;
+        own[r] = voxel_bits(a, v0) | voxel_bits(a, v1) << 1 | voxel_bits(a, v2) << 2 | voxel_bits(a, v3) << 3;
     }
     uint32_t extra = 0u;  // lane 4 r + k: row r, voxel xs - 1 (k = 0), xs + 256 (1), xs + 257 (2)
     {
         const int r = lane >> 2, k = lane & 3, yy = y + r;
         const int x = k == 0 ? xs - 1 : xs + 255 + k;
         if (r < NR && k < 3 && z_ok && yy >= 0 && yy < a.Y && x >= 0 && x < a.X)
-            extra = voxel_bits(a.vol[(size_t)x + (size_t)a.X * ((size_t)yy + (size_t)a.Y * (size_t)z)]);
+            extra = voxel_bits(a, a.vol[(size_t)x + (size_t)a.X * ((size_t)yy + (size_t)a.Y * (size_t)z)]);
     }
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
@@ -467,7 +481,8 @@ __device__ __forceinline__ int mask_case(uint32_t a0, uint32_t a1, uint32_t b0, 
 
 // count sweep: per segment the vertices it owns (vcount) and the soup vertices of its cubes (icount).  A wave marches
 // along z over MC_ROWS rows and keeps the masks of slices z - 1, z, z + 1, rows y - 1 .. y + MC_ROWS.
-__global__ __launch_bounds__(256) void mci_count_kernel(const IdxArgs a, int32_t* __restrict__ vcount,
+template <bool FLOOR>
+__global__ __launch_bounds__(256) void mci_count_kernel(const IdxArgsT<FLOOR> a, int32_t* __restrict__ vcount,
                                                         int32_t* __restrict__ icount) {
     __shared__ uint8_t ntri_lds[256];
     __shared__ int wave_work[4];
@@ -560,7 +575,8 @@ struct IdxTriStage {
 };
 
 // vertices of one segment in key order: lanes first own voxels (edge masks, wave prefix sum, the list), then VERTICES
-__device__ __forceinline__ void emit_vertices_segment(const IdxArgs& a, IdxVertStage& st, long s, int begin, int count,
+template <bool FLOOR>
+__device__ __forceinline__ void emit_vertices_segment(const IdxArgsT<FLOOR>& a, IdxVertStage& st, long s, int begin, int count,
                                                       float4* __restrict__ out, int max_vertices) {
     const int seg = (int)(s % a.nseg);
     const long yz = s / a.nseg;
@@ -604,7 +620,8 @@ __device__ __forceinline__ void emit_vertices_segment(const IdxArgs& a, IdxVertS
     __builtin_amdgcn_wave_barrier();
 }
 
-__global__ __launch_bounds__(256) void mci_emit_vertices_kernel(const IdxArgs a, const int32_t* __restrict__ voff,
+template <bool FLOOR>
+__global__ __launch_bounds__(256) void mci_emit_vertices_kernel(const IdxArgsT<FLOOR> a, const int32_t* __restrict__ voff,
                                                                 float4* __restrict__ out, int max_vertices,
                                                                 long nsegs_total) {
     __shared__ IdxVertStage stage[4];
@@ -627,7 +644,8 @@ __global__ __launch_bounds__(256) void mci_emit_vertices_kernel(const IdxArgs a,
 
 // indices of one segment's cubes, in the soup's order.  The edges of the cubes of row (y, z) have their lower voxels in the
 // rows (y .. y + 1, z .. z + 1), at x .. x + 1: this segment's voxels and the first one of the next segment.
-__device__ __forceinline__ void emit_indices_segment(const IdxArgs& a, const uint8_t* __restrict__ tri_lds,
+template <bool FLOOR>
+__device__ __forceinline__ void emit_indices_segment(const IdxArgsT<FLOOR>& a, const uint8_t* __restrict__ tri_lds,
                                                      const uint8_t* __restrict__ nv_lds, IdxTriStage& st, long s, int begin,
                                                      int count, const int32_t* __restrict__ voff, int32_t* __restrict__ out,
                                                      int max_indices) {
@@ -724,7 +742,8 @@ __device__ __forceinline__ void emit_indices_segment(const IdxArgs& a, const uin
     __builtin_amdgcn_wave_barrier();
 }
 
-__global__ __launch_bounds__(256) void mci_emit_indices_kernel(const IdxArgs a, const int32_t* __restrict__ ioff,
+template <bool FLOOR>
+__global__ __launch_bounds__(256) void mci_emit_indices_kernel(const IdxArgsT<FLOOR> a, const int32_t* __restrict__ ioff,
                                                                const int32_t* __restrict__ voff, int32_t* __restrict__ out,
                                                                int max_indices, long nsegs_total) {
     __shared__ uint8_t tri_lds[256 * 16], nv_lds[256];
@@ -757,12 +776,13 @@ __global__ __launch_bounds__(256) void mci_emit_indices_kernel(const IdxArgs a, 
 
 long mci_segments(int X, int Y, int Z) { return (long)((X + 255) / 256) * Y * Z; }
 
-hipError_t launch_marching_cubes_indexed(const uint32_t* vol, int X, int Y, int Z, const float cell_size[3],
-                                         const int32_t* tri_table, const int32_t* num_verts_table, float* out_vertices,
-                                         int max_vertices, int32_t* out_indices, int max_indices, int32_t* totals,
-                                         int32_t* voff, int32_t* ioff, int32_t* chunk_sums, const uint8_t* occ,
-                                         hipStream_t s) {
-    IdxArgs a;
+namespace {
+
+template <bool FLOOR>
+hipError_t launch_mci(IdxArgsT<FLOOR> a, const uint32_t* vol, int X, int Y, int Z, const float cell_size[3],
+                      const int32_t* tri_table, const int32_t* num_verts_table, float* out_vertices, int max_vertices,
+                      int32_t* out_indices, int max_indices, int32_t* totals, int32_t* voff, int32_t* ioff,
+                      int32_t* chunk_sums, const uint8_t* occ, hipStream_t s) {
     a.vol = vol, a.X = X, a.Y = Y, a.Z = Z;
     a.vec4 = (X % 4 == 0) && (((uintptr_t)vol & 15) == 0);
     const OccDims od = occ_dims(X, Y, Z);
@@ -781,15 +801,38 @@ hipError_t launch_marching_cubes_indexed(const uint32_t* vol, int X, int Y, int 
     if (e != hipSuccess) return e;
     if ((e = hipMemsetAsync(ioff, 0, sizeof(int32_t) * (size_t)(nsegs + 1), s)) != hipSuccess) return e;
     dim3 block(64, 4), grid(a.nseg, (Y + 4 * MC_ROWS - 1) / (4 * MC_ROWS), (Z + zchunk - 1) / zchunk);
-    mci_count_kernel<<<grid, block, 0, s>>>(a, voff, ioff);
+    mci_count_kernel<FLOOR><<<grid, block, 0, s>>>(a, voff, ioff);
     launch_segment_scan(voff, nsegs, chunk_sums, totals, s);
     launch_segment_scan(ioff, nsegs, chunk_sums, totals + 1, s);
     const unsigned eblocks = (unsigned)std::min<long>((nsegs + 3) / 4, 8192);
     if (out_vertices && max_vertices > 0)
-        mci_emit_vertices_kernel<<<eblocks, block, 0, s>>>(a, voff, (float4*)out_vertices, max_vertices, nsegs);
+        mci_emit_vertices_kernel<FLOOR><<<eblocks, block, 0, s>>>(a, voff, (float4*)out_vertices, max_vertices, nsegs);
     if (out_indices && max_indices > 0)
-        mci_emit_indices_kernel<<<eblocks, block, 0, s>>>(a, ioff, voff, out_indices, max_indices, nsegs);
+        mci_emit_indices_kernel<FLOOR><<<eblocks, block, 0, s>>>(a, ioff, voff, out_indices, max_indices, nsegs);
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_marching_cubes_indexed(const uint32_t* vol, int X, int Y, int Z, const float cell_size[3],
+                                         const int32_t* tri_table, const int32_t* num_verts_table, float* out_vertices,
+                                         int max_vertices, int32_t* out_indices, int max_indices, int32_t* totals,
+                                         int32_t* voff, int32_t* ioff, int32_t* chunk_sums, const uint8_t* occ,
+                                         hipStream_t s) {
+    return launch_mci(IdxArgsT<false>{}, vol, X, Y, Z, cell_size, tri_table, num_verts_table, out_vertices, max_vertices,
+                      out_indices, max_indices, totals, voff, ioff, chunk_sums, occ, s);
+}
+
+// (the occupancy map's bit 0 marks boxes with a non-zero weight: a superset of the boxes with a weight at or above a floor)
+hipError_t launch_marching_cubes_indexed_min_weight(const uint32_t* vol, int X, int Y, int Z, const float cell_size[3],
+                                                    const int32_t* tri_table, const int32_t* num_verts_table,
+                                                    int min_weight, float* out_vertices, int max_vertices,
+                                                    int32_t* out_indices, int max_indices, int32_t* totals, int32_t* voff,
+                                                    int32_t* ioff, int32_t* chunk_sums, const uint8_t* occ, hipStream_t s) {
+    IdxArgsT<true> a{};
+    a.min_weight = (uint32_t)min_weight;
+    return launch_mci(a, vol, X, Y, Z, cell_size, tri_table, num_verts_table, out_vertices, max_vertices, out_indices,
+                      max_indices, totals, voff, ioff, chunk_sums, occ, s);
 }
 
 long mc_segments(int X, int Y, int Z, bool vec4) {

@@ -91,6 +91,27 @@ struct DynFuParams {  // dyn_fusion.hpp:25-42
     // Off, nothing of this runs and a frame's outputs are what they were, bit for bit.
     bool north_star_visible_only = false;
     float visibility_z_tol       = 0.f;
+    // Extension — voxels no node supports are integrated where they stand (TsdfVolume::UnsupportedMode::Rigid) instead of left
+    // alone, in fuse_canonical's and north_star_fuse_canonical's warped integrations, with or without fuse_knn_field (without
+    // one of the two fusion switches the constructor throws dfa::Error).  Without it the canonical volume only ever changes
+    // inside the support of the nodes it already has.  Off, the integrations are what they were.
+    bool fuse_unsupported_rigid = false;
+    // Extension — the GROWING canonical model (needs north_star AND north_star_fuse_canonical: otherwise the
+    // constructor throws dfa::Error; reference mode keeps frame 0's cloud).  Frame 0: the canonical cloud is the welded vertex
+    // set of the volume (MarchingCubes::runIndexed, gradient normals) instead of the triangle soup.  Every later frame, after
+    // the solve and the warped integration: getCanonicalWarpedToLive() is the cloud the solve used, warped; then the cloud is
+    // re-extracted from the canonical volume — runIndexed with the weight floor canonical_min_weight, normals from the
+    // canonical volume, to the camera frame as frame 0's — and replaces getCanonicalFrame() (an empty extraction keeps the old
+    // cloud: regrowSkippedFrames() counts those); Warpfield::update then seeds nodes where the NEW cloud, in canonical space,
+    // has no support (instead of where the warped old one has none), and the nodes it appends start from the north-star blend
+    // of the nodes before them, not from update's calcDQB (which composes its k neighbours' transforms: fine at the edge of
+    // the support, a metre off for a seed half a model away).  With model_view the kept mesh is replaced by the same
+    // extraction — getCanonicalMesh()'s views then hold until the next frame —, so north_star_visible_only tests the regrown
+    // cloud against the regrown surface.  The next frame's solve, node insertion, model view and visibility test see what the
+    // fusion added.  canonical_min_weight (1..65535): what one frame touched once (weight 1) stays out at the default, 2.
+    // Off, nothing of this runs and a frame's outputs are what they were, bit for bit.
+    bool north_star_regrow_canonical = false;
+    int canonical_min_weight         = 2;
 };
 
 struct dfa_solver6;  // include/dynfu_amd.h
@@ -151,6 +172,12 @@ public:
     void addLiveFrame(int frameID, std::shared_ptr<dynfu::Frame> frame);
     void warpCanonicalToLiveOpt(dfa::Affine3f affine);
     std::shared_ptr<dynfu::Frame> getCanonicalWarpedToLive();
+    // the canonical cloud the NEXT frame's solve starts from (frame 0's; with north_star_regrow_canonical the last
+    // re-extraction), and its size
+    std::shared_ptr<dynfu::Frame> getCanonicalFrame() { return canonicalFrame; }
+    size_t canonicalVertexCount() const { return canonicalFrame ? canonicalFrame->size() : 0; }
+    // north_star_regrow_canonical: frames whose re-extraction was empty (the cloud before it was kept)
+    int regrowSkippedFrames() const { return regrow_skipped_; }
 
     // private in the reference (dyn_fusion.hpp:86-89); public here so that it can be tested alone
     std::shared_ptr<dynfu::Frame> findCorrespondingFrame(dfa::PointCloud<dfa::PointXYZ> canonicalVertices,
@@ -198,6 +225,15 @@ private:
     // model_view: the canonical mesh (frame 0) as a frame for Warpfield::warpToLive and as float4 vertices + indices, the
     // buffers behind them, and what the last renderWarpedModel made
     void keepCanonicalMesh(const float* to_canonical_frame /* 12 floats, or null: the volume's frame */);
+    // the welded mesh of a volume at a weight floor (in mesh_vertex_buffer_ / mesh_index_buffer_) and its vertices with
+    // gradient normals as a frame; null when there is no surface.  keepCanonicalMesh's extraction, and the regrown model's
+    std::shared_ptr<dynfu::Frame> extractWeldedModel(const kfusion::cuda::TsdfVolume& volume, int min_weight, const float* to_frame,
+                                                     kfusion::cuda::MarchingCubes::IndexedMesh& mesh);
+    kfusion::cuda::TsdfVolume::UnsupportedMode unsupportedMode() const;  // fuse_unsupported_rigid
+    int regrow_skipped_ = 0;
+    // north_star_regrow_canonical: the nodes appended since there were `nodes_before` start from the north-star blend of the
+    // nodes before them (Warpfield::update's calcDQB composes its k neighbours' transforms: see dyn_fusion.cpp)
+    void startNewNodesFromBlend(size_t nodes_before);
     std::shared_ptr<dynfu::Frame> canonical_mesh_frame_;
     kfusion::cuda::MarchingCubes::IndexedMesh canonical_mesh_;
     dfa::DeviceArray<kfusion::cuda::MarchingCubes::PointType> mesh_vertex_buffer_, warped_vertices_;
@@ -208,6 +244,8 @@ private:
     // node set has grown; the arrays it borrows, and the node set they were built from
     std::shared_ptr<dfa_solver6> mesh_plan_;
     int mesh_plan_D_ = 0;
+    size_t mesh_plan_N_ = 0;        // the plan's vertex capacity
+    bool mesh_plan_stale_ = false;  // the kept mesh was replaced after the plan's last set_problem
     dfa::DeviceArray<float> mesh_node_pos_, mesh_node_w_, mesh_node_dq_;
     std::vector<float> mesh_nodes_built_pos_, mesh_nodes_built_w_;
     kfusion::cuda::Cloud model_points_;

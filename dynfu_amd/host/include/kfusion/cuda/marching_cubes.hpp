@@ -42,12 +42,14 @@ public:
     // NON-owning views of what was written; when the mesh does not fit one of the buffers BOTH views are empty and
     // totalUniqueVertices() / totalVertices() say what the buffers need.  Uses the volume's occupancy map when it is
     // trusted.  ONE host synchronisation, to size the views.
+    // min_weight other than 1: dfa_marching_cubes_indexed_min_weight — a voxel counts as observed from that weight on (the
+    // extraction for a volume that accumulates frames: what one frame touched once stays out at 2).
     struct IndexedMesh {
         dfa::DeviceArray<PointType> vertices;
         dfa::DeviceArray<int> indices;
     };
     IndexedMesh runIndexed(const TsdfVolume& volume, dfa::DeviceArray<PointType>& vertex_buffer,
-                           dfa::DeviceArray<int>& index_buffer);
+                           dfa::DeviceArray<int>& index_buffer, int min_weight = 1);
 
     // distinct vertices the last runIndexed() found (totalVertices(): the indices = run()'s vertices)
     int totalUniqueVertices() const { return last_unique_; }

@@ -68,7 +68,8 @@ public:
     // marching cubes of the current volume in KinFu::convertToMesh's layout (:236-262)
     std::shared_ptr<dfa::PolygonMesh> extractMesh();
     // the same surface with every vertex once (MarchingCubes::runIndexed, dfa::convertToIndexedMesh): a fifth of the points
-    std::shared_ptr<dfa::PolygonMesh> extractIndexedMesh();
+    // (min_weight: MarchingCubes::runIndexed's weight floor)
+    std::shared_ptr<dfa::PolygonMesh> extractIndexedMesh(int min_weight = 1);
 
 protected:  // as in the reference (kinfu.hpp:88-108): DynFusion derives from this class and drives these directly
     struct Frame {

@@ -55,6 +55,14 @@ DynFusion::DynFusion(const DynFuParams& params) : kfusion::KinFu(params.kinfuPar
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: fuse_knn_field serves the canonical fusion (fuse_canonical or north_star_fuse_canonical)");
     if (params.north_star_visible_only && !(params.north_star && params.model_view))
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_visible_only needs north_star and model_view (the rasterised canonical mesh is what hides a vertex)");
+    if (params.fuse_unsupported_rigid && !params.fuse_canonical && !params.north_star_fuse_canonical)
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion: fuse_unsupported_rigid serves the canonical fusion (fuse_canonical or north_star_fuse_canonical)");
+    if (params.north_star_regrow_canonical && !params.north_star)
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_regrow_canonical needs north_star (reference mode keeps frame 0's cloud)");
+    if (params.north_star_regrow_canonical && !params.north_star_fuse_canonical)
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_regrow_canonical needs north_star_fuse_canonical (the canonical volume is what the cloud is re-extracted from)");
+    if (params.north_star_regrow_canonical && (params.canonical_min_weight < 1 || params.canonical_min_weight > 65535))
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion: canonical_min_weight outside 1..65535");
     solverParams.numIter       = 24;  // dyn_fusion.cpp:183-189
     solverParams.nonLinearIter = 16;
     solverParams.linearIter    = 256;
@@ -65,6 +73,11 @@ DynFusion::DynFusion(const DynFuParams& params) : kfusion::KinFu(params.kinfuPar
 DynFusion::~DynFusion() = default;
 
 DynFuParams& DynFusion::params() { return dynfuParams; }
+
+kfusion::cuda::TsdfVolume::UnsupportedMode DynFusion::unsupportedMode() const {
+    return dynfuParams.fuse_unsupported_rigid ? kfusion::cuda::TsdfVolume::UnsupportedMode::Rigid
+                                              : kfusion::cuda::TsdfVolume::UnsupportedMode::Skip;
+}
 
 void DynFusion::init(dfa::PointCloud<dfa::PointXYZ>& canonicalVertices, dfa::PointCloud<dfa::Normal>& canonicalNormals) {
     initCanonicalFrame(canonicalVertices, canonicalNormals);
@@ -260,7 +273,7 @@ bool DynFusion::operator()(const kfusion::cuda::Depth& depth) {
     if (dynfuParams.fuse_canonical) {  // step 4 of :39-47: this frame's depth into the canonical volume, through the solved field
         if (dynfuParams.fuse_knn_field) syncKnnField();
         const Warpfield::DeviceNodeView nodes = warpfield->deviceNodes();
-        canonical_volume_->integrateWarped(dists_, camera, p.intr, nodes.pos, nodes.dq, nodes.w, nodes.D, warpfield->getKnn());
+        canonical_volume_->integrateWarped(dists_, camera, p.intr, nodes.pos, nodes.dq, nodes.w, nodes.D, warpfield->getKnn(), unsupportedMode());
         clk.mark("integrateWarped");
     }
     warpfield->update(getCanonicalWarpedToLive());    // :142
@@ -278,6 +291,19 @@ bool DynFusion::northStarFrame(const kfusion::cuda::Depth& depth) {
     const dfa::Affine3f camera;  // the camera stays at the origin, as in the reference's operator() (:100-105)
     if (frame_counter_ == 0) {
         tsdf().integrate(dists_, camera, p.intr);
+        if (dynfuParams.north_star_regrow_canonical) {
+            // the canonical cloud is the WELDED vertex set (frame 0 holds weight 1 only: no floor), and with model_view the
+            // kept mesh is the cloud's mesh; every later frame replaces both from the canonical volume
+            float aff[12];
+            (camera.inv() * tsdf().getPose()).to12(aff);
+            kfusion::cuda::MarchingCubes::IndexedMesh mesh;
+            auto welded = extractWeldedModel(tsdf(), 1, aff, mesh);
+            if (!welded) throw dfa::Error(DFA_ERR_INVALID, "DynFusion (north-star mode): the first frame has no surface");
+            initFromFrame(welded);
+            if (dynfuParams.model_view) canonical_mesh_frame_ = welded, canonical_mesh_ = mesh;
+            createCanonicalVolume();
+            return ++frame_counter_, false;
+        }
         auto vol_frame = extractSurface(0, true);  // volume frame, normals from the TSDF gradient
         const size_t n = vol_frame->size();
         if (n == 0) throw dfa::Error(DFA_ERR_INVALID, "DynFusion (north-star mode): the first frame has no surface");
@@ -326,13 +352,76 @@ bool DynFusion::northStarFrame(const kfusion::cuda::Depth& depth) {
         if (dynfuParams.fuse_knn_field) syncKnnField();
         const Warpfield::DeviceNodeView nodes = warpfield->deviceNodes();
         canonical_volume_->integrateWarped6(dists_, camera, p.intr, camera, nodes.pos, nodes.dq, nodes.w, nodes.D,
-                                            std::min(warpfield->getKnn(), 8));
+                                            std::min(warpfield->getKnn(), 8), unsupportedMode());
         clk.mark("integrateWarped6");
     }
-    canonicalFrameWarpedToLive = solver.warpCanonicalToLive();
+    canonicalFrameWarpedToLive = solver.warpCanonicalToLive();  // the cloud the solve used
+    if (dynfuParams.north_star_regrow_canonical) {
+        // the canonical model grows: the cloud (and the kept mesh) of the next frame is the canonical volume's surface as it is
+        // now, from the voxels seen canonical_min_weight times, and the field is extended where THAT cloud — in canonical
+        // space — has no support.  An empty extraction keeps the old model.
+        float aff[12];
+        (camera.inv() * tsdf().getPose()).to12(aff);
+        kfusion::cuda::MarchingCubes::IndexedMesh mesh;
+        if (auto grown = extractWeldedModel(*canonical_volume_, dynfuParams.canonical_min_weight, aff, mesh)) {
+            canonicalFrame = grown;
+            if (dynfuParams.model_view) canonical_mesh_frame_ = grown, canonical_mesh_ = mesh, mesh_plan_stale_ = true;
+        } else {
+            ++regrow_skipped_;
+        }
+        clk.mark("warp + regrow");
+        const size_t nodes_before = warpfield->nodesRef().size();
+        warpfield->update(canonicalFrame);
+        startNewNodesFromBlend(nodes_before);
+        clk.mark("warpfield->update");
+        return ++frame_counter_, true;
+    }
     warpfield->update(canonicalFrameWarpedToLive);
     clk.mark("warp + warpfield->update");
     return ++frame_counter_, true;
+}
+
+// north_star_regrow_canonical: the transforms the nodes Warpfield::update has just appended start from.  update gives a new
+// node calcDQB of the field before it — the reference's blend, a PRODUCT of the k neighbours' weighted transforms, which
+// composes them: harmless for the translations of a few millimetres it was written for and for seeds at the edge of the
+// support, but a seed of the regrown cloud may lie half a model away from the nearest node, and the north-star nodes hold
+// whole rigid transforms: k of them composed threw the new part of the model a metre off on the half-sphere sequence of
+// tests/cpp/test_host_regrow.cpp.  Here a new node takes what the north-star blend (csrc/blend6_device.hpp) gives a point
+// at its position from the nodes that existed before: the k nearest, radial basis weights normalised, every transform in the
+// hemisphere of the nearest, real and dual parts summed and divided by the real part's norm.  Host arithmetic in double over
+// the handful of new nodes; the weights are taken relative to the nearest node's, so that no distance underflows them all.
+void DynFusion::startNewNodesFromBlend(size_t nodes_before) {
+    const auto& nodes = warpfield->nodesRef();
+    if (nodes_before == 0 || nodes.size() <= nodes_before) return;
+    std::vector<float> pos, w, dq;
+    warpfield->hostArrays(pos, w, dq);
+    const int k = (int)std::min<size_t>((size_t)std::min(warpfield->getKnn(), 8), nodes_before);
+    std::vector<std::pair<double, size_t>> near(nodes_before);
+    for (size_t i = nodes_before; i < nodes.size(); ++i) {
+        for (size_t j = 0; j < nodes_before; ++j) {
+            const double dx = (double)pos[3 * i] - pos[3 * j], dy = (double)pos[3 * i + 1] - pos[3 * j + 1],
+                         dz = (double)pos[3 * i + 2] - pos[3 * j + 2];
+            near[j] = {dx * dx + dy * dy + dz * dz, j};
+        }
+        std::partial_sort(near.begin(), near.begin() + k, near.end());  // ascending distance, ties to the lower index
+        double e[8], e_max = -1e300, a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
+        for (int q = 0; q < k; ++q) {
+            const double r = (double)w[near[q].second];
+            e[q] = -near[q].first / (2 * r * r), e_max = std::max(e_max, e[q]);
+        }
+        const float* first = &dq[8 * near[0].second];
+        for (int q = 0; q < k; ++q) {
+            const float* t = &dq[8 * near[q].second];
+            const double dot = (double)t[0] * first[0] + (double)t[1] * first[1] + (double)t[2] * first[2] + (double)t[3] * first[3];
+            const double wt = std::exp(e[q] - e_max) * (dot < 0 ? -1.0 : 1.0);
+            for (int c = 0; c < 4; ++c) a[c] += wt * t[c], b[c] += wt * t[4 + c];
+        }
+        const double norm = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2] + a[3] * a[3]);
+        if (!(norm > 0)) continue;  // (opposite rotations cancelling exactly: the node keeps update's transform)
+        nodes[i]->setTransformation(std::make_shared<DualQuaternion<float>>(
+            dfa::quaternion<float>((float)(a[0] / norm), (float)(a[1] / norm), (float)(a[2] / norm), (float)(a[3] / norm)),
+            dfa::quaternion<float>((float)(b[0] / norm), (float)(b[1] / norm), (float)(b[2] / norm), (float)(b[3] / norm))));
+    }
 }
 
 // ------------------------------------------------------------------------- the view of the canonical model
@@ -340,27 +429,39 @@ bool DynFusion::northStarFrame(const kfusion::cuda::Depth& depth) {
 // frame 0, model_view: the volume just fused as a welded mesh with normals from the TSDF gradient, moved to the frame of the
 // canonical cloud exactly as the cloud is (north-star mode: the camera frame)
 void DynFusion::keepCanonicalMesh(const float* to_canonical_frame) {
-    auto mesh = mc_->runIndexed(tsdf(), mesh_vertex_buffer_, mesh_index_buffer_);
+    kfusion::cuda::MarchingCubes::IndexedMesh mesh;
+    auto frame = extractWeldedModel(tsdf(), 1, to_canonical_frame, mesh);
+    if (!frame) throw dfa::Error(DFA_ERR_INVALID, "DynFusion (model_view): the first frame has no surface");
+    canonical_mesh_frame_ = frame;
+    canonical_mesh_       = mesh;
+}
+
+// `volume` as a welded mesh (views of mesh_vertex_buffer_ / mesh_index_buffer_: the mesh extracted before is overwritten) from
+// the voxels of weight >= min_weight, and its vertices with normals from the TSDF gradient as a frame, both moved by
+// `to_frame` (12 floats, or null).  Null when the volume has no such surface: the buffers are then untouched.
+std::shared_ptr<dynfu::Frame> DynFusion::extractWeldedModel(const kfusion::cuda::TsdfVolume& volume, int min_weight,
+                                                            const float* to_frame,
+                                                            kfusion::cuda::MarchingCubes::IndexedMesh& mesh) {
+    mesh = mc_->runIndexed(volume, mesh_vertex_buffer_, mesh_index_buffer_, min_weight);
     if (mesh.vertices.empty() && mc_->totalUniqueVertices() > 0) {  // it did not fit the default buffers: size them and run again
         mesh_vertex_buffer_.create((size_t)mc_->totalUniqueVertices());
         mesh_index_buffer_.create((size_t)mc_->totalVertices());
-        mesh = mc_->runIndexed(tsdf(), mesh_vertex_buffer_, mesh_index_buffer_);
+        mesh = mc_->runIndexed(volume, mesh_vertex_buffer_, mesh_index_buffer_, min_weight);
     }
     const size_t n = mesh.vertices.size();
-    if (n == 0) throw dfa::Error(DFA_ERR_INVALID, "DynFusion (model_view): the first frame has no surface");
+    if (n == 0) return nullptr;
     dfa::DeviceArray<dfa::Normal> normals4;
-    mc_->computeNormals(tsdf(), mesh.vertices, normals4);
+    mc_->computeNormals(volume, mesh.vertices, normals4);
     dfa::DeviceArray<float> v3(3 * n), n3(3 * n);
     dfa::check(dfa_repack_points((const float*)mesh.vertices.ptr(), 4, v3.ptr(), 3, (int)n, 0.f, nullptr), "DynFusion: mesh vertices");
     dfa::check(dfa_repack_points((const float*)normals4.ptr(), 4, n3.ptr(), 3, (int)n, 0.f, nullptr), "DynFusion: mesh normals");
-    if (to_canonical_frame) {
-        dfa::check(dfa_transform_points(v3.ptr(), (int)n, to_canonical_frame, 1, v3.ptr(), nullptr), "DynFusion: mesh vertices to the camera frame");
-        dfa::check(dfa_transform_points(n3.ptr(), (int)n, to_canonical_frame, 0, n3.ptr(), nullptr), "DynFusion: mesh normals to the camera frame");
+    if (to_frame) {
+        dfa::check(dfa_transform_points(v3.ptr(), (int)n, to_frame, 1, v3.ptr(), nullptr), "DynFusion: mesh vertices to the camera frame");
+        dfa::check(dfa_transform_points(n3.ptr(), (int)n, to_frame, 0, n3.ptr(), nullptr), "DynFusion: mesh normals to the camera frame");
         // the float4 vertices getCanonicalMesh() hands out follow (in place: the buffer is this object's)
         dfa::check(dfa_repack_points(v3.ptr(), 3, (float*)mesh.vertices.ptr(), 4, (int)n, 1.f, nullptr), "DynFusion: mesh vertices");
     }
-    canonical_mesh_frame_ = dynfu::Frame::fromDevice(0, v3, n3, n);
-    canonical_mesh_       = mesh;
+    return dynfu::Frame::fromDevice(0, v3, n3, n);
 }
 
 // The mesh moves as the canonical cloud does: by the blend of the solve that fitted the transforms.  Reference mode:
@@ -376,14 +477,17 @@ std::shared_ptr<dynfu::Frame> DynFusion::warpCanonicalMesh() {
     const size_t n = canonical_mesh_frame_->size();
     if (D == 0) throw dfa::Error(DFA_ERR_INVALID, "DynFusion::renderWarpedModel: the warp field has no nodes");
     mesh_node_dq_.upload(dq);
-    if (!mesh_plan_ || pos != mesh_nodes_built_pos_ || w != mesh_nodes_built_w_) {
-        if (!mesh_plan_ || D > mesh_plan_D_) {
+    // (mesh_plan_stale_: north_star_regrow_canonical has replaced the mesh — the plan holds the old one's vertices)
+    if (!mesh_plan_ || mesh_plan_stale_ || pos != mesh_nodes_built_pos_ || w != mesh_nodes_built_w_) {
+        if (!mesh_plan_ || D > mesh_plan_D_ || n > mesh_plan_N_) {
             mesh_plan_.reset();
             dfa_solver6* plan = nullptr;
             const int cap = D + D / 4 + 16;  // (room for the nodes Warpfield::update adds, as NorthStarSolver sizes its plan)
-            dfa::check(dfa_solver6_create(cap, (int)n, std::min(warpfield->getKnn(), 8), &plan), "DynFusion (model_view): dfa_solver6_create");
+            // (... and, where the mesh grows from frame to frame, for the vertices the next extractions add)
+            const size_t cap_n = dynfuParams.north_star_regrow_canonical ? n + n / 4 + 1024 : n;
+            dfa::check(dfa_solver6_create(cap, (int)cap_n, std::min(warpfield->getKnn(), 8), &plan), "DynFusion (model_view): dfa_solver6_create");
             mesh_plan_ = std::shared_ptr<dfa_solver6>(plan, dfa_solver6_destroy);
-            mesh_plan_D_ = cap;
+            mesh_plan_D_ = cap, mesh_plan_N_ = cap_n;
         }
         // fresh arrays: the plan borrows them until the next set_problem
         mesh_node_pos_ = dfa::DeviceArray<float>(), mesh_node_w_ = dfa::DeviceArray<float>();
@@ -392,7 +496,7 @@ std::shared_ptr<dynfu::Frame> DynFusion::warpCanonicalMesh() {
         dfa::check(dfa_solver6_set_problem(mesh_plan_.get(), mesh_node_pos_.ptr(), mesh_node_dq_.ptr(), mesh_node_w_.ptr(), D, m.vertices,
                                            m.normals, (int)n, nullptr),
                    "DynFusion (model_view): dfa_solver6_set_problem");
-        mesh_nodes_built_pos_ = pos, mesh_nodes_built_w_ = w;
+        mesh_nodes_built_pos_ = pos, mesh_nodes_built_w_ = w, mesh_plan_stale_ = false;
     }
     dfa::DeviceArray<float> ov(3 * n), on(3 * n);
     dfa::check(dfa_solver6_warp_with(mesh_plan_.get(), mesh_node_dq_.ptr(), ov.ptr(), on.ptr(), nullptr), "DynFusion (model_view): dfa_solver6_warp_with");

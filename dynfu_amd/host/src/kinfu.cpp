@@ -106,10 +106,10 @@ std::shared_ptr<dfa::PolygonMesh> KinFu::extractMesh() {
     return std::make_shared<dfa::PolygonMesh>(dfa::convertToMesh(host));
 }
 
-std::shared_ptr<dfa::PolygonMesh> KinFu::extractIndexedMesh() {
+std::shared_ptr<dfa::PolygonMesh> KinFu::extractIndexedMesh(int min_weight) {
     dfa::DeviceArray<cuda::MarchingCubes::PointType> vertex_buffer;
     dfa::DeviceArray<int> index_buffer;
-    const auto mesh = mc_->runIndexed(*volume_, vertex_buffer, index_buffer);
+    const auto mesh = mc_->runIndexed(*volume_, vertex_buffer, index_buffer, min_weight);
     std::vector<cuda::MarchingCubes::PointType> vertices;
     std::vector<int> indices;
     if (!mesh.vertices.empty()) mesh.vertices.download(vertices), mesh.indices.download(indices);

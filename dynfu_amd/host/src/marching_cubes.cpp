@@ -52,18 +52,25 @@ dfa::DeviceArray<MarchingCubes::PointType> MarchingCubes::run(const TsdfVolume& 
 }
 
 MarchingCubes::IndexedMesh MarchingCubes::runIndexed(const TsdfVolume& volume, dfa::DeviceArray<PointType>& vertex_buffer,
-                                                     dfa::DeviceArray<int>& index_buffer) {
+                                                     dfa::DeviceArray<int>& index_buffer, int min_weight) {
     if (index_buffer.empty()) index_buffer.create(DEFAULT_TRIANGLES_BUFFER_SIZE);
     if (vertex_buffer.empty()) vertex_buffer.create(DEFAULT_TRIANGLES_BUFFER_SIZE / POINTS_PER_TRIANGLE);
     if (totals_dev_.empty()) totals_dev_.create(2);
     const Vec3i dims = volume.getDims();
     const Vec3f size = volume.getSize();
     const float cell[3] = {size[0] / dims[0], size[1] / dims[1], size[2] / dims[2]};
-    dfa::check(dfa_marching_cubes_indexed(volume.data().ptr<uint32_t>(), volume.occupancy(), dims[0], dims[1], dims[2], cell,
-                                          tri_dev_.ptr(), nverts_dev_.ptr(), (float*)vertex_buffer.ptr(),
-                                          (int)vertex_buffer.size(), index_buffer.ptr(), (int)index_buffer.size(),
-                                          totals_dev_.ptr(), nullptr),
-               "MarchingCubes::runIndexed");
+    if (min_weight == 1)
+        dfa::check(dfa_marching_cubes_indexed(volume.data().ptr<uint32_t>(), volume.occupancy(), dims[0], dims[1], dims[2], cell,
+                                              tri_dev_.ptr(), nverts_dev_.ptr(), (float*)vertex_buffer.ptr(),
+                                              (int)vertex_buffer.size(), index_buffer.ptr(), (int)index_buffer.size(),
+                                              totals_dev_.ptr(), nullptr),
+                   "MarchingCubes::runIndexed");
+    else  // (a floor outside 1..65535 is the library's to refuse)
+        dfa::check(dfa_marching_cubes_indexed_min_weight(volume.data().ptr<uint32_t>(), volume.occupancy(), dims[0], dims[1], dims[2],
+                                                         cell, tri_dev_.ptr(), nverts_dev_.ptr(), min_weight,
+                                                         (float*)vertex_buffer.ptr(), (int)vertex_buffer.size(), index_buffer.ptr(),
+                                                         (int)index_buffer.size(), totals_dev_.ptr(), nullptr),
+                   "MarchingCubes::runIndexed");
     std::vector<int> t;
     totals_dev_.download(t);  // synchronises
     last_unique_ = t[0], last_total_ = t[1];

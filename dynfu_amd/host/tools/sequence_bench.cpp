@@ -2,6 +2,11 @@
 // (src/apps/demo.cpp:90-95: upload outside, operator() inside), frame by frame, over a sequence of raw depth frames.
 //
 //   sequence_bench FRAMES.u16 W H N DIM ref|northstar [epsilon] [node_step]
+//   sequence_bench FRAMES.u16 W H N DIM northstar+fuse|northstar+fuse+rigid|northstar+regrow [epsilon] [node_step]
+//
+// The second form (tools/regrow_timing.py): the north-star sequence with north_star_fuse_canonical, with
+// fuse_unsupported_rigid added, and with north_star_regrow_canonical added to both (canonical_min_weight 2); the JSON then
+// also holds the canonical cloud's size per frame.
 //
 // FRAMES.u16: N frames of W x H little-endian uint16 millimetres, back to back (bench.py writes its synthetic
 // sequence there).  Prints one JSON object: per-frame milliseconds (the device is synchronised inside the timed region,
@@ -24,7 +29,9 @@ int main(int argc, char** argv) {
         return 2;
     }
     const int W = std::atoi(argv[2]), H = std::atoi(argv[3]), N = std::atoi(argv[4]), dim = std::atoi(argv[5]);
-    const bool ns = !std::strcmp(argv[6], "northstar");
+    const bool ns = !std::strncmp(argv[6], "northstar", 9);
+    const bool fuse = ns && std::strstr(argv[6], "+fuse"), regrow = ns && std::strstr(argv[6], "+regrow");
+    const bool rigid = regrow || (ns && std::strstr(argv[6], "+rigid"));
     std::vector<uint16_t> all((size_t)W * H * N);
     std::ifstream f(argv[1], std::ios::binary);
     if (!f.read((char*)all.data(), (std::streamsize)(all.size() * 2))) {
@@ -39,13 +46,14 @@ int main(int argc, char** argv) {
         p.intr        = k.intr;
         k.volume_dims = dfa::Vec3i(dim, dim, dim);
         p.north_star  = ns;
+        p.north_star_fuse_canonical = fuse || regrow, p.fuse_unsupported_rigid = rigid, p.north_star_regrow_canonical = regrow;
         if (argc > 7) p.epsilon = (float)std::atof(argv[7]);
         else if (ns) p.epsilon = 0.05f;
         DynFusion dynfu(p);
         dynfu.nodeStep = argc > 8 ? std::atoi(argv[8]) : 128;  // dyn_fusion.cpp:151
         kfusion::cuda::Depth depth;
         std::vector<double> ms;
-        std::vector<size_t> nodes;
+        std::vector<size_t> nodes, cloud;
         for (int i = 0; i < N; ++i) {
             depth.upload(all.data() + (size_t)i * W * H, (size_t)W * sizeof(uint16_t), H, W);  // demo.cpp:90
             (void)hipDeviceSynchronize();
@@ -54,15 +62,21 @@ int main(int argc, char** argv) {
             (void)hipDeviceSynchronize();
             ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
             nodes.push_back(dynfu.getWarpfield()->getNodes().size());
+            cloud.push_back(dynfu.canonicalVertexCount());
         }
         std::printf("{\"mode\": \"%s\", \"dim\": %d, \"width\": %d, \"height\": %d, \"frames\": %d, \"canonical_vertices\": %zu, "
                     "\"live_vertices_last\": %zu, \"nodes_first\": %zu, \"nodes_last\": %zu, \"epsilon\": %g, \"node_step\": %d",
-                    ns ? "northstar" : "ref", dim, W, H, N, dynfu.getCanonicalWarpedToLive()->size(),
+                    ns ? argv[6] : "ref", dim, W, H, N, dynfu.getCanonicalWarpedToLive()->size(),
                     dynfu.getLiveFrame() ? dynfu.getLiveFrame()->size() : (size_t)0, nodes.front(), nodes.back(), p.epsilon,
                     dynfu.nodeStep);
         if (ns)
             std::printf(", \"cost_first\": %.6g, \"cost_last\": %.6g, \"valid_rows\": %lld", dynfu.northStarInitialCost(),
                         dynfu.northStarFinalCost(), dynfu.northStarValidRows());
+        if (fuse || regrow) {
+            std::printf(", \"regrow_skipped\": %d, \"canonical_vertices_by_frame\": [", dynfu.regrowSkippedFrames());
+            for (size_t i = 0; i < cloud.size(); ++i) std::printf("%s%zu", i ? ", " : "", cloud[i]);
+            std::printf("]");
+        }
         std::printf(", \"frame_ms\": [");
         for (size_t i = 0; i < ms.size(); ++i) std::printf("%s%.4f", i ? ", " : "", ms[i]);
         std::printf("]}\n");

@@ -365,6 +365,19 @@ int dfa_marching_cubes_indexed(const uint32_t* volume, const uint8_t* occupancy 
                                float* out_vertices, int max_vertices, int32_t* out_indices, int max_indices,
                                int32_t* totals /* device, 2 ints: vertices, indices */, dfa_stream_t stream);
 
+/* ... with a WEIGHT FLOOR, for a volume that accumulates frames: a voxel counts as observed only if its 16-bit weight is
+ * >= min_weight (1..65535, anything else is DFA_ERR_INVALID).  Wherever the rule above says "non-zero weight" read
+ * "weight >= min_weight": the eight corners of a cube with triangles, the cubes around an owned edge.  The output is, bit
+ * for bit and with the same totals, dfa_marching_cubes_indexed's on a copy of the volume in which every voxel of weight
+ * < min_weight has its weight field zeroed (distance bits kept) — without the copy; min_weight = 1 is
+ * dfa_marching_cubes_indexed itself.  Occupancy map, capacities, scratch: as there (the map's weight bit marks a superset
+ * of the voxels at or above any floor). */
+int dfa_marching_cubes_indexed_min_weight(const uint32_t* volume, const uint8_t* occupancy /* may be NULL */, int X, int Y,
+                                          int Z, const float cell_size[3], const int32_t* tri_table,
+                                          const int32_t* num_verts_table, int min_weight, float* out_vertices,
+                                          int max_vertices, int32_t* out_indices, int max_indices,
+                                          int32_t* totals /* device, 2 ints: vertices, indices */, dfa_stream_t stream);
+
 /* A valid case table pair for callers that do not have the reference's (HOST buffers, 256 x 16
  * and 256 ints): derived from the face-by-face rule described in csrc/mc.hip.  Same corner / edge
  * numbering and winding as the reference's table (src/kfusion/marching_cubes.cpp:86-343) but not

@@ -105,7 +105,8 @@ def drop(name, rules):
             if value and args[idx] != value[0]:  # (a rule with a value only meets the instantiations that have it)
                 continue
             del args[idx]
-            return "%s<%s>" % (m.group(1), ", ".join(args))
+            # (a kernel that had no template arguments before the change added its first one keeps its bare name)
+            return "%s<%s>" % (m.group(1), ", ".join(args)) if args else m.group(1)
     return name
 
 
