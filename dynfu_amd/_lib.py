@@ -1,5 +1,6 @@
 """ctypes binding of include/dynfu_amd.h.  Tensors are torch CUDA tensors (device memory +
 stream plumbing only); every function launches on torch's current stream."""
+import contextlib
 import ctypes as C
 import os
 
@@ -10,7 +11,7 @@ _LIB = None
 SYMBOLS = [
     "dfa_last_error", "dfa_version", "dfa_abi_version", "dfa_abi_struct_size", "dfa_compute_dists", "dfa_tsdf_clear", "dfa_tsdf_integrate",
     "dfa_tsdf_clear_integrate", "dfa_tsdf_raycast_points", "dfa_tsdf_raycast_depth", "dfa_tsdf_raycast_tally", "dfa_tsdf_raycast_render", "dfa_render_image_points", "dfa_render_image_depth", "dfa_render_tangent_colors", "dfa_mesh_rasterize", "dfa_visible_vertices", "dfa_tsdf_vertex_normals", "dfa_tsdf_extract_cloud", "dfa_tsdf_extract_cloud_occ", "dfa_tsdf_extract_normals", "dfa_correspond_projective", "dfa_knn", "dfa_warp_to_live",
-    "dfa_calc_dqb", "dfa_unsupported_vertices", "dfa_icp_sums", "dfa_repack_points", "dfa_compact_points", "dfa_transform_points", "dfa_warp_to_live_graph",
+    "dfa_calc_dqb", "dfa_unsupported_vertices", "dfa_icp_sums", "dfa_rigid_sums_cloud", "dfa_repack_points", "dfa_compact_points", "dfa_transform_points", "dfa_warp_to_live_graph",
     "dfa_correspond", "dfa_marching_cubes", "dfa_mc_default_tables",
     "dfa_tsdf_occupancy_bytes", "dfa_tsdf_clear_occ", "dfa_tsdf_integrate_occ", "dfa_tsdf_clear_integrate_occ", "dfa_tsdf_clear_integrate_known_occ", "dfa_tsdf_integrate_warped", "dfa_tsdf_integrate_warped6", "dfa_marching_cubes_occ", "dfa_marching_cubes_indexed", "dfa_marching_cubes_indexed_min_weight",
     "dfa_knn_field_create", "dfa_knn_field_destroy", "dfa_knn_field_build", "dfa_knn_field_append", "dfa_knn_field_info", "dfa_knn_field_lookup",
@@ -232,6 +233,7 @@ def load(path=None):
     L.dfa_marching_cubes_indexed_min_weight.argtypes = [vp, vp, i, i, i, vp, vp, vp, i, vp, i, vp, i, vp, vp]
     L.dfa_mc_default_tables.argtypes = [vp, vp]
     L.dfa_icp_sums.argtypes = [i, vp, i, vp, i, vp, i, vp, i, i, i, vp, f, f, f, f, f, f, vp, vp, vp]
+    L.dfa_rigid_sums_cloud.argtypes = [vp, vp, i, i, vp, vp, i, vp, i, i, i, f, f, f, f, f, f, vp, vp, vp]
     L.dfa_calc_dqb.argtypes = [vp, vp, vp, i, i, vp, i, vp, vp]
     L.dfa_unsupported_vertices.argtypes = [vp, vp, i, i, vp, i, vp, vp]
     L.dfa_correspond.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp]
@@ -1190,3 +1192,32 @@ def icp_sums(curr, ncurr, prev, nprev, aff12, fx, fy, cx, cy, dist_thres=0.1, an
                                nprev.stride(0) * 4, cols, rows, _aff12(aff12), fx, fy, cx, cy, dist_thres, angle_thres,
                                _dev(sums), _dev(matched), _stream()))
     return sums, matched
+
+
+def rigid_sums_cloud(vertices, normals, aff, vmap, nmap, intr, dist_thresh, cos_thresh, stream=None):
+    """dfa_rigid_sums_cloud: one linearisation of the rigid Gauss-Newton of the north-star data term.  vertices (N, 3) or
+    (N, 4) float32, normals the same shape or None (no cosine gate), aff 12 floats (R row-major, then t), vmap / nmap
+    ((rows, cols, 4) float32, a row stride makes a pitched map), intr = (fx, fy, cx, cy); stream: a torch.cuda.Stream, or
+    None for the current one -> (27 sums CUDA float tensor in icp_sums' layout, matched vertices as an int: one read-back)."""
+    torch = _torch()
+    if vertices.dim() != 2 or vertices.shape[1] not in (3, 4) or not vertices.is_contiguous():
+        raise DynfuAmdError("vertices must be a contiguous (N, 3) or (N, 4) float32 tensor")
+    if normals is not None and (normals.shape != vertices.shape or not normals.is_contiguous()):
+        raise DynfuAmdError("normals must be a contiguous tensor of the vertices' shape")
+    for m, name in ((vmap, "vmap"), (nmap, "nmap")):
+        if m.dim() != 3 or m.shape[2] != 4 or m.stride(2) != 1 or m.stride(1) != 4:
+            raise DynfuAmdError("%s must be a (rows, cols, 4) float32 tensor of packed float4 pixels" % name)
+    if vmap.shape != nmap.shape:
+        raise DynfuAmdError("vmap and nmap differ in size")
+    N, stride = int(vertices.shape[0]), int(vertices.shape[1])
+    rows, cols = int(vmap.shape[0]), int(vmap.shape[1])
+    fx, fy, cx, cy = (float(v) for v in intr)
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        sums = torch.empty(27, dtype=torch.float32, device="cuda")
+        matched = torch.empty(1, dtype=torch.int32, device="cuda")
+        _check(load().dfa_rigid_sums_cloud(_dev(vertices, torch.float32, "vertices") if N else None,
+                                           _dev(normals, torch.float32, "normals") if N else None, stride, N, _aff12(aff),
+                                           _dev(vmap, torch.float32, "vmap"), vmap.stride(0) * 4,
+                                           _dev(nmap, torch.float32, "nmap"), nmap.stride(0) * 4, cols, rows, fx, fy, cx, cy,
+                                           float(dist_thresh), float(cos_thresh), _dev(sums), _dev(matched), _stream()))
+        return sums, int(matched.item())

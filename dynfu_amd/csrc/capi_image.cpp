@@ -186,6 +186,28 @@ int dfa_icp_sums(int depth_variant, const void* curr, int curr_step, const float
     return DFA_OK;
 }
 
+int dfa_rigid_sums_cloud(const float* vertices, const float* normals, int stride, int N, const float aff[12],
+                         const float* live_vertex_map, int vertex_step, const float* live_normal_map, int normal_step,
+                         int cols, int rows, float fx, float fy, float cx, float cy, float dist_thresh, float cos_thresh,
+                         float* sums27, unsigned int* matched, dfa_stream_t stream) {
+    REQUIRE(N >= 0, "negative vertex count");
+    REQUIRE(stride == 3 || stride == 4, "stride must be 3 or 4 floats");
+    REQUIRE(N == 0 || vertices, "null vertices");
+    REQUIRE(aff && live_vertex_map && live_normal_map && sums27, "null argument");
+    REQUIRE(cols > 0 && rows > 0, "bad image size");
+    REQUIRE(vertex_step >= cols * 16 && normal_step >= cols * 16, "row step smaller than a float4 row");
+    REQUIRE((((uintptr_t)live_vertex_map | (uintptr_t)live_normal_map | (uintptr_t)vertex_step | (uintptr_t)normal_step) & 15) == 0,
+            "map rows must be 16-byte aligned");
+    REQUIRE((((uintptr_t)vertices | (uintptr_t)normals) & 3) == 0, "vertices / normals must be 4-byte aligned");
+    REQUIRE(fx != 0.f && fy != 0.f && dist_thresh >= 0.f, "bad intrinsics / threshold");
+    IcpScratch& partial = stream_scratch<IcpScratch>(S(stream));
+    if (N > 0) HIP_TRY(partial.reserve(dfa::rigid_cloud_partial_floats(N)));
+    HIP_TRY(dfa::launch_rigid_sums_cloud(vertices, normals, stride, N, aff, live_vertex_map, vertex_step, live_normal_map,
+                                         normal_step, cols, rows, fx, fy, cx, cy, dist_thresh, cos_thresh, partial.data, sums27,
+                                         matched, S(stream)));
+    return DFA_OK;
+}
+
 // ------------------------------------------------------------------------ vertex / normal maps
 
 int dfa_compute_points_normals(const uint16_t* depth, int depth_step, int cols, int rows, float fx, float fy, float cx,

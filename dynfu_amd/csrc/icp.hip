@@ -6,6 +6,10 @@
 // One lane per pixel of the current frame; the 27 products are reduced per wave with DPP adds and per
 // workgroup through LDS (the reference tree-reduces 27 times through shared memory with 5 barriers each), one
 // partial per workgroup and product; a second launch adds the partials in index order in double precision.
+//
+// rigid_rows_cloud_kernel (dfa_rigid_sums_cloud; no reference counterpart) is the same linearisation over a CLOUD against
+// the live maps: one lane per vertex, the pixel rule and the gates of the north-star solve's data term
+// (solve6_linearise.hip), the same reduction and the same closing launch.
 #include <hip/hip_runtime.h>
 
 #include "device_math.hpp"
@@ -108,6 +112,82 @@ __global__ __launch_bounds__(64) void icp_final_kernel(const float* __restrict__
     if (threadIdx.x == 0) out[blockIdx.x] = (float)acc;
 }
 
+struct RigidCloudArgs {
+    const float* vertices;
+    const float* normals;  // or null: no cosine gate
+    int stride, n;
+    Aff3 aff;
+    const float* vmap;
+    const float* nmap;
+    int vstep, nstep, cols, rows;
+    float fx, fy, cx, cy, dist_thresh, cos_thresh;
+};
+
+struct __attribute__((packed, aligned(4))) Packed3 {  // one 12-byte load
+    float x, y, z;
+};
+
+// One lane per vertex c (normal n0), float32 (tests/rigid_align_statement.py states the same):
+//   s = R c + t; no row if c.x is NaN or s.z > 0 fails
+//   u = rintf(fx * (s.x / s.z) + cx), w likewise (ties to even); no row outside [0, cols) x [0, rows) (compared as floats: a
+//   NaN or an overflowed quotient is outside)
+//   L, Ln the float4 pixels of the two maps; no row if L.x or Ln.x is NaN
+//   gates: sqrtf(|s - L|^2) <= dist_thresh, and with normals dot(R n0, Ln) >= cos_thresh (signed)
+//   row (s x Ln, Ln | Ln . (L - s))
+__global__ __launch_bounds__(256) void rigid_rows_cloud_kernel(const RigidCloudArgs a, float* __restrict__ partial, int nblocks,
+                                                               unsigned int* __restrict__ matched) {
+    __shared__ float sh[4][27];
+    __shared__ unsigned int sh_count[4];
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    float row[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    bool ok = false;
+    if (i < (size_t)a.n) {
+        const Packed3 c = *reinterpret_cast<const Packed3*>(a.vertices + i * (size_t)a.stride);
+        Packed3 n0{0.f, 0.f, 0.f};
+        if (a.normals) n0 = *reinterpret_cast<const Packed3*>(a.normals + i * (size_t)a.stride);  // (uniform)
+        const f3 s = mulR(a.aff, mk3(c.x, c.y, c.z)) + mk3(a.aff.t[0], a.aff.t[1], a.aff.t[2]);
+        if (c.x == c.x && s.z > 0.f) {
+            const float u = rintf(a.fx * (s.x / s.z) + a.cx), w = rintf(a.fy * (s.y / s.z) + a.cy);
+            if (u >= 0.f && w >= 0.f && u < (float)a.cols && w < (float)a.rows) {
+                const size_t px = 16 * (size_t)(int)u;
+                // two gathers: both in flight before either is looked at
+                const float4 L  = *reinterpret_cast<const float4*>((const char*)a.vmap + (size_t)(int)w * a.vstep + px);
+                const float4 Ln = *reinterpret_cast<const float4*>((const char*)a.nmap + (size_t)(int)w * a.nstep + px);
+                if (L.x == L.x && Ln.x == Ln.x) {
+                    const f3 l = mk3(L.x, L.y, L.z), n = mk3(Ln.x, Ln.y, Ln.z);
+                    const f3 sl = s - l;
+                    ok = sqrtf(dot(sl, sl)) <= a.dist_thresh;
+                    if (ok && a.normals) ok = dot(mulR(a.aff, mk3(n0.x, n0.y, n0.z)), n) >= a.cos_thresh;
+                    if (ok) {
+                        row[0] = s.y * n.z - s.z * n.y, row[1] = s.z * n.x - s.x * n.z, row[2] = s.x * n.y - s.y * n.x;
+                        row[3] = n.x, row[4] = n.y, row[5] = n.z;
+                        row[6] = dot(n, l - s);
+                    }
+                }
+            }
+        }
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int q = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int j = r; j < 7; ++j) {
+            const float t = wave_total(row[r] * row[j]);
+            if (lane == 0) sh[wave][q] = t;
+            ++q;
+        }
+    const unsigned int cnt = (unsigned int)__popcll(__ballot(ok));  // integers: the count is exact
+    if (lane == 0) sh_count[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x < 27)
+        partial[(size_t)threadIdx.x * nblocks + blockIdx.x] = (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
+    if (threadIdx.x == 27 && matched) {
+        const unsigned int c = (sh_count[0] + sh_count[1]) + (sh_count[2] + sh_count[3]);
+        if (c) atomicAdd(matched, c);
+    }
+}
+
 }  // namespace
 
 size_t icp_partial_floats(int cols, int rows) { return (size_t)27 * ((cols + 31) / 32) * ((rows + 7) / 8); }
@@ -133,6 +213,28 @@ hipError_t launch_icp_sums(bool depth_variant, const void* curr, int curr_step, 
     }
     if (depth_variant) icp_rows_kernel<true><<<grid, 256, 0, s>>>(a, partial, nblocks, matched);
     else icp_rows_kernel<false><<<grid, 256, 0, s>>>(a, partial, nblocks, matched);
+    icp_final_kernel<<<27, 64, 0, s>>>(partial, nblocks, sums27);
+    return hipGetLastError();
+}
+
+size_t rigid_cloud_partial_floats(int n) { return (size_t)27 * (size_t)(((long)n + 255) / 256); }
+
+hipError_t launch_rigid_sums_cloud(const float* vertices, const float* normals, int stride, int n, const float aff[12],
+                                   const float* vmap, int vstep, const float* nmap, int nstep, int cols, int rows, float fx,
+                                   float fy, float cx, float cy, float dist_thresh, float cos_thresh, float* partial,
+                                   float* sums27, unsigned int* matched, hipStream_t s) {
+    if (matched) {
+        hipError_t e = hipMemsetAsync(matched, 0, sizeof(unsigned int), s);
+        if (e != hipSuccess) return e;
+    }
+    if (n <= 0) return hipMemsetAsync(sums27, 0, 27 * sizeof(float), s);
+    RigidCloudArgs a;
+    a.vertices = vertices, a.normals = normals, a.stride = stride, a.n = n;
+    a.aff  = aff3_from(aff);
+    a.vmap = vmap, a.nmap = nmap, a.vstep = vstep, a.nstep = nstep, a.cols = cols, a.rows = rows;
+    a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy, a.dist_thresh = dist_thresh, a.cos_thresh = cos_thresh;
+    const int nblocks = (int)(((long)n + 255) / 256);
+    rigid_rows_cloud_kernel<<<nblocks, 256, 0, s>>>(a, partial, nblocks, matched);
     icp_final_kernel<<<27, 64, 0, s>>>(partial, nblocks, sums27);
     return hipGetLastError();
 }

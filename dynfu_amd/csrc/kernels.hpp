@@ -237,6 +237,12 @@ hipError_t launch_icp_sums(bool depth_variant, const void* curr, int curr_step, 
                            const void* prev, int prev_step, const float* nprev, int nprev_step, int cols, int rows,
                            const float aff[12], float fx, float fy, float cx, float cy, float dist_thres, float angle_thres,
                            float* partial, float* sums27, unsigned int* matched, hipStream_t s);
+// the same sums over a cloud against the live maps (the north-star data term's association); n = 0: zeros, no kernel
+size_t rigid_cloud_partial_floats(int n);
+hipError_t launch_rigid_sums_cloud(const float* vertices, const float* normals, int stride, int n, const float aff[12],
+                                   const float* vmap, int vstep, const float* nmap, int nstep, int cols, int rows, float fx,
+                                   float fy, float cx, float cy, float dist_thresh, float cos_thresh, float* partial,
+                                   float* sums27, unsigned int* matched, hipStream_t s);
 
 
 // Several kernels publish partial results with write-through stores and then arrive at a ticket / raise a flag word, ordering

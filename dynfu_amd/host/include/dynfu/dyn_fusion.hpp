@@ -112,6 +112,17 @@ struct DynFuParams {  // dyn_fusion.hpp:25-42
     // Off, nothing of this runs and a frame's outputs are what they were, bit for bit.
     bool north_star_regrow_canonical = false;
     int canonical_min_weight         = 2;
+    // Extension — rigid pre-alignment of the warp field (needs north_star: otherwise the constructor throws
+    // dfa::Error).  Every frame after the first, between initializeProblemInstance / the live maps and the visibility test /
+    // the solve: NorthStarSolver::alignRigid estimates the rigid motion T of the model as the solve would start from it
+    // against the live depth frame — rigid_prealign_iters Gauss-Newton iterations of the solve's own data term (its pixel rule,
+    // its gates; 10 is KinFu's count at full resolution) — and composes T onto every node (Warpfield::composeRigid).  The
+    // north-star blend is left-invariant, so the solve starts from the same field moved by T, an exact warm start of the same
+    // energy, and the model view, the visibility test, the fusion and the node insertion see the aligned model.  A singular
+    // system (no overlap, an empty depth frame) skips the step for that frame: rigidSkippedFrames() counts those.  Off, or
+    // with rigid_prealign_iters = 0, nothing of this runs and a frame's outputs are what they were, bit for bit.
+    bool north_star_rigid_prealign = false;
+    int rigid_prealign_iters       = 10;
 };
 
 struct dfa_solver6;  // include/dynfu_amd.h
@@ -160,6 +171,15 @@ public:
     double northStarInitialCost() const { return ns_initial_cost_; }
     double northStarFinalCost() const { return ns_final_cost_; }
     long long northStarValidRows() const { return ns_valid_rows_; }
+    // north_star_rigid_prealign: the last frame's rigid estimate — it maps the model, warped by the transforms that frame's
+    // solve would have started from, into the live camera's frame (the identity when the step was skipped, or is off) —, the
+    // vertices that took a row in its first and its last iteration, and the frames whose system was singular
+    dfa::Affine3f northStarRigidPose() const { return rigid_pose_; }
+    struct RigidMatched {
+        long long first, last;
+    };
+    RigidMatched northStarRigidMatched() const { return RigidMatched{rigid_matched_first_, rigid_matched_last_}; }
+    int rigidSkippedFrames() const { return rigid_skipped_; }
     // north_star_visible_only: canonical vertices the last frame's solve could take data rows from (one small read from the
     // device); -1 before the first such frame, or with the switch off
     long long northStarVisibleVertices() const;
@@ -231,6 +251,10 @@ private:
                                                      kfusion::cuda::MarchingCubes::IndexedMesh& mesh);
     kfusion::cuda::TsdfVolume::UnsupportedMode unsupportedMode() const;  // fuse_unsupported_rigid
     int regrow_skipped_ = 0;
+    // north_star_rigid_prealign
+    dfa::Affine3f rigid_pose_;
+    long long rigid_matched_first_ = 0, rigid_matched_last_ = 0;
+    int rigid_skipped_ = 0;
     // north_star_regrow_canonical: the nodes appended since there were `nodes_before` start from the north-star blend of the
     // nodes before them (Warpfield::update's calcDQB composes its k neighbours' transforms: see dyn_fusion.cpp)
     void startNewNodesFromBlend(size_t nodes_before);

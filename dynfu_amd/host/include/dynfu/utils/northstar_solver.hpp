@@ -50,6 +50,21 @@ public:
     void solveAll(const kfusion::cuda::Cloud& liveVertexMap, const kfusion::cuda::Normals& liveNormalMap,
                   const kfusion::Intr& intr);
 
+    // Rigid pre-alignment (call it after initializeProblemInstance, before solveAll): the rigid Gauss-Newton
+    // of the solve's own data term.  The canonical cloud and its normals are warped once by the transforms the solve starts
+    // from (dfa_solver6_warp_with); then, `iters` times, dfa_rigid_sums_cloud with distThresh / cosThresh against the live
+    // maps, one read-back of the 27 sums and kfusion::cuda::icp_update: T <- exp(x) T, from the identity.  T maps the
+    // start-warped model into the live camera's frame.  On success T is composed onto the start transforms of the plan
+    // (dfa_solver6_set_node_transforms) and onto the shared Nodes (Warpfield::composeRigid): the north-star blend is
+    // left-invariant, so the solve starts from the same field moved by T — as do the model view, the visibility test, the
+    // fusion and the node insertion that read the Nodes.  A singular update ends the loop: T goes back to the identity,
+    // nothing is composed, the call returns false.  iters <= 0: nothing is enqueued, T is the identity, true.
+    bool alignRigid(const kfusion::cuda::Cloud& liveVertexMap, const kfusion::cuda::Normals& liveNormalMap,
+                    const kfusion::Intr& intr, int iters, dfa::Affine3f& T);
+    // vertices that took a row in the first / the last iteration of the last alignRigid (0 before it)
+    long long rigidMatchedFirst() const { return rigid_matched_first_; }
+    long long rigidMatchedLast() const { return rigid_matched_last_; }
+
     // the canonical frame of the problem warped by the solved transforms (dual-quaternion blend, as the solve models
     // it); stays in HBM
     std::shared_ptr<dynfu::Frame> warpCanonicalToLive();
@@ -84,4 +99,5 @@ private:
     int pcg_iters_        = 0;
     int pcg_short_        = 0;
     int gn_solves_ = 0, gn_rejected_ = 0;
+    long long rigid_matched_first_ = 0, rigid_matched_last_ = 0;
 };

@@ -37,6 +37,14 @@ public:
     // warp_field.cpp:64-95: insert a node per 5 cm voxel of unsupported vertices
     void update(std::shared_ptr<dynfu::Frame> frame);
 
+    // North-star mode (DESIGN.md §4.1 "Rigid pre-alignment"): every node's dg_se3 becomes dq(T) o dg_se3 — real part r_T r,
+    // dual part r_T d + d_T r, with r_T the unit quaternion of T's rotation and d_T = 1/2 t^ r_T.  The north-star blend is
+    // left-invariant, so the field then warps every point to T applied to where it warped it before.  Host arithmetic in
+    // double, rounded once to float; the device copies follow as after Node::setTransformation (the next deviceNodes()).
+    void composeRigid(const dfa::Affine3f& T);
+    // ... the same on D x 8 floats (real w,x,y,z ; dual w,x,y,z), in place
+    static void composeRigid(const dfa::Affine3f& T, float* dq, size_t D);
+
     // number of neighbours (the reference's compile-time KNN; run-time here, default 8)
     void setKnn(int k) { knn_ = k; }
     int getKnn() const { return knn_; }

@@ -63,6 +63,10 @@ DynFusion::DynFusion(const DynFuParams& params) : kfusion::KinFu(params.kinfuPar
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_regrow_canonical needs north_star_fuse_canonical (the canonical volume is what the cloud is re-extracted from)");
     if (params.north_star_regrow_canonical && (params.canonical_min_weight < 1 || params.canonical_min_weight > 65535))
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: canonical_min_weight outside 1..65535");
+    if (params.north_star_rigid_prealign && !params.north_star)
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_rigid_prealign needs north_star (reference mode has no rigid step: KinFu tracks rigidly)");
+    if (params.north_star_rigid_prealign && params.rigid_prealign_iters < 0)
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion: negative rigid_prealign_iters");
     solverParams.numIter       = 24;  // dyn_fusion.cpp:183-189
     solverParams.nonLinearIter = 16;
     solverParams.linearIter    = 256;
@@ -327,6 +331,15 @@ bool DynFusion::northStarFrame(const kfusion::cuda::Depth& depth) {
                            dynfuParams.lambda, dynfuParams.psi_reg);
     solver.initializeProblemInstance(canonicalFrame);
     clk.mark("  initializeProblemInstance");
+    const bool prealign = dynfuParams.north_star_rigid_prealign && dynfuParams.rigid_prealign_iters > 0;
+    if (prealign) {
+        // the global rigid motion first: the start transforms and the shared nodes come out composed with it, so everything
+        // below — the model view, the visibility test, the solve, the fusion — sees the aligned field
+        kfusion::cuda::computePointNormals(p.intr, depth_filtered_, live_points_, live_normals_);
+        if (!solver.alignRigid(live_points_, live_normals_, p.intr, dynfuParams.rigid_prealign_iters, rigid_pose_)) ++rigid_skipped_;
+        rigid_matched_first_ = solver.rigidMatchedFirst(), rigid_matched_last_ = solver.rigidMatchedLast();
+        clk.mark("  alignRigid");
+    }
     if (dynfuParams.north_star_visible_only) {
         // the model as the solve finds it: mesh and cloud warped by the transforms the solve starts from, the mesh rasterised
         // from this frame's camera; a vertex behind the rasterised surface takes no data row
@@ -342,7 +355,7 @@ bool DynFusion::northStarFrame(const kfusion::cuda::Depth& depth) {
         visible_counted_ = true;
         clk.mark("  visible vertices");
     }
-    kfusion::cuda::computePointNormals(p.intr, depth_filtered_, live_points_, live_normals_);
+    if (!prealign) kfusion::cuda::computePointNormals(p.intr, depth_filtered_, live_points_, live_normals_);
     solver.solveAll(live_points_, live_normals_, p.intr);
     clk.mark("  solveAll");
     ns_initial_cost_ = solver.initialCost(), ns_final_cost_ = solver.finalCost(), ns_valid_rows_ = solver.validRows();

@@ -5,11 +5,13 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <vector>
 
 #include <dfa_host/plan_cache.hpp>
+#include <kfusion/cuda/icp_update.hpp>
 #include <kfusion/cuda/imgproc.hpp>
 
 #include "../../../include/dynfu_amd.h"
@@ -53,6 +55,7 @@ struct NorthStarSolver::Impl {
     dfa::DeviceArray<float> node_pos, node_dq, node_w, canon, canon_n;  // borrowed by the plan until the next set_problem
     kfusion::cuda::Cloud vmap;
     kfusion::cuda::Normals nmap;
+    std::vector<float> host_dq;  // the start transforms as uploaded to node_dq
     int D = 0, N = 0;
     ~Impl() { plan_cache().park(plan, plan_D, plan_N, plan_k); }
 };
@@ -85,6 +88,7 @@ void NorthStarSolver::initializeProblemInstance(const std::shared_ptr<dynfu::Fra
         dfa::check(dfa_solver6_create(I.plan_D, I.plan_N, k, &I.plan), "NorthStarSolver: dfa_solver6_create");
     }
     I.node_dq.upload(dq);
+    I.host_dq = dq;
     const uint64_t nodes_hash = fnv1a(w, fnv1a(pos, 1469598103934665603ull));
     {
         std::lock_guard<std::mutex> lock(g_built_mu);
@@ -165,6 +169,44 @@ void NorthStarSolver::solveAll(const kfusion::cuda::Cloud& vmap, const kfusion::
         nodes[i]->setTransformation(std::make_shared<DualQuaternion<float>>(dfa::quaternion<float>(q[0], q[1], q[2], q[3]),
                                                                             dfa::quaternion<float>(q[4], q[5], q[6], q[7])));
     }
+}
+
+bool NorthStarSolver::alignRigid(const kfusion::cuda::Cloud& vmap, const kfusion::cuda::Normals& nmap, const kfusion::Intr& intr,
+                                 int iters, dfa::Affine3f& T) {
+    Impl& I = *impl;
+    T = dfa::Affine3f();
+    rigid_matched_first_ = rigid_matched_last_ = 0;
+    if (!I.plan) throw dfa::Error(DFA_ERR_INVALID, "alignRigid before initializeProblemInstance");
+    if (vmap.rows() != nmap.rows() || vmap.cols() != nmap.cols() || vmap.empty())
+        throw dfa::Error(DFA_ERR_INVALID, "NorthStarSolver: vertex / normal maps differ in size or are empty");
+    if (iters <= 0) return true;
+    dfa::DeviceArray<float> wv(3 * (size_t)I.N), wn(3 * (size_t)I.N);
+    if (I.N) dfa::check(dfa_solver6_warp_with(I.plan, I.node_dq.ptr(), wv.ptr(), wn.ptr(), nullptr), "NorthStarSolver::alignRigid (warp)");
+    dfa::DeviceArray<float> out(28);  // the 27 sums, then the matched count: one read-back per iteration
+    float h[28];
+    for (int it = 0; it < iters; ++it) {
+        float aff[12];
+        T.to12(aff);
+        dfa::check(dfa_rigid_sums_cloud(wv.ptr(), wn.ptr(), 3, I.N, aff, (const float*)vmap.ptr(), (int)vmap.step(),
+                                        (const float*)nmap.ptr(), (int)nmap.step(), vmap.cols(), vmap.rows(), intr.fx, intr.fy,
+                                        intr.cx, intr.cy, m_params.distThresh, m_params.cosThresh, out.ptr(),
+                                        reinterpret_cast<unsigned int*>(out.ptr() + 27), nullptr),
+                   "NorthStarSolver::alignRigid");
+        dfa_host_copy_from_device(h, out.ptr(), sizeof(h));
+        unsigned int matched;
+        std::memcpy(&matched, &h[27], sizeof(matched));
+        if (it == 0) rigid_matched_first_ = matched;
+        rigid_matched_last_ = matched;
+        if (!kfusion::cuda::icp_update(h, T)) {
+            T = dfa::Affine3f();
+            return false;
+        }
+    }
+    Warpfield::composeRigid(T, I.host_dq.data(), (size_t)I.D);
+    I.node_dq.upload(I.host_dq);
+    dfa::check(dfa_solver6_set_node_transforms(I.plan, I.node_dq.ptr()), "NorthStarSolver::alignRigid (set_node_transforms)");
+    m_warpfield.composeRigid(T);
+    return true;
 }
 
 dfa::DeviceArray<float> NorthStarSolver::warpCanonicalByStart() {

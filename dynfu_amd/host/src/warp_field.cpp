@@ -110,6 +110,58 @@ void Warpfield::syncTransforms() {
     if (!hdq.empty()) dev->dq.upload(hdq);
 }
 
+namespace {
+void qmul(const double a[4], const double b[4], double o[4]) {  // (w, x, y, z)
+    o[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
+    o[1] = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
+    o[2] = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1];
+    o[3] = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
+}
+// the unit dual quaternion (r_T, d_T) of a rigid transform: r_T from the rotation matrix by the branch with the largest
+// pivot, normalised (the matrix is a float rounding of a rotation); d_T = 1/2 t^ r_T
+void dq_of(const dfa::Affine3f& T, double r[4], double d[4]) {
+    const double m00 = T.R[0], m01 = T.R[1], m02 = T.R[2], m10 = T.R[3], m11 = T.R[4], m12 = T.R[5], m20 = T.R[6], m21 = T.R[7],
+                 m22 = T.R[8];
+    const double cand[4] = {1 + m00 + m11 + m22, 1 + m00 - m11 - m22, 1 - m00 + m11 - m22, 1 - m00 - m11 + m22};
+    int i = 0;
+    for (int j = 1; j < 4; ++j)
+        if (cand[j] > cand[i]) i = j;
+    const double h = 0.5 * std::sqrt(cand[i]), q = 4 * h;
+    if (i == 0) r[0] = h, r[1] = (m21 - m12) / q, r[2] = (m02 - m20) / q, r[3] = (m10 - m01) / q;
+    else if (i == 1) r[0] = (m21 - m12) / q, r[1] = h, r[2] = (m01 + m10) / q, r[3] = (m02 + m20) / q;
+    else if (i == 2) r[0] = (m02 - m20) / q, r[1] = (m01 + m10) / q, r[2] = h, r[3] = (m12 + m21) / q;
+    else r[0] = (m10 - m01) / q, r[1] = (m02 + m20) / q, r[2] = (m12 + m21) / q, r[3] = h;
+    const double n = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
+    for (int c = 0; c < 4; ++c) r[c] /= n;
+    const double t[4] = {0.0, T.t[0], T.t[1], T.t[2]};
+    qmul(t, r, d);
+    for (int c = 0; c < 4; ++c) d[c] *= 0.5;
+}
+}  // namespace
+
+void Warpfield::composeRigid(const dfa::Affine3f& T, float* dq, size_t D) {
+    double rT[4], dT[4];
+    dq_of(T, rT, dT);
+    for (size_t i = 0; i < D; ++i) {
+        float* q = dq + 8 * i;
+        const double r[4] = {q[0], q[1], q[2], q[3]}, d[4] = {q[4], q[5], q[6], q[7]};
+        double real[4], a[4], b[4];
+        qmul(rT, r, real), qmul(rT, d, a), qmul(dT, r, b);
+        for (int c = 0; c < 4; ++c) q[c] = (float)real[c], q[4 + c] = (float)(a[c] + b[c]);
+    }
+}
+
+void Warpfield::composeRigid(const dfa::Affine3f& T) {
+    std::vector<float> hdq;
+    pack_transforms(*nodes, hdq);
+    composeRigid(T, hdq.data(), nodes->size());
+    for (size_t i = 0; i < nodes->size(); ++i) {
+        const float* q = &hdq[8 * i];
+        (*nodes)[i]->setTransformation(std::make_shared<DualQuaternion<float>>(dfa::quaternion<float>(q[0], q[1], q[2], q[3]),
+                                                                               dfa::quaternion<float>(q[4], q[5], q[6], q[7])));
+    }
+}
+
 void Warpfield::hostArrays(std::vector<float>& pos, std::vector<float>& w, std::vector<float>& dq) {
     const NodeList& nodes = *this->nodes;
     pos.resize(3 * nodes.size()), w.resize(nodes.size());

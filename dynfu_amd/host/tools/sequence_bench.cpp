@@ -6,7 +6,8 @@
 //
 // The second form (tools/regrow_timing.py): the north-star sequence with north_star_fuse_canonical, with
 // fuse_unsupported_rigid added, and with north_star_regrow_canonical added to both (canonical_min_weight 2); the JSON then
-// also holds the canonical cloud's size per frame.
+// also holds the canonical cloud's size per frame.  "+prealign" on any northstar mode adds north_star_rigid_prealign
+// (tools/rigid_align_timing.py): the JSON then holds the frames whose alignment was skipped and the last frame's matched counts.
 //
 // FRAMES.u16: N frames of W x H little-endian uint16 millimetres, back to back (bench.py writes its synthetic
 // sequence there).  Prints one JSON object: per-frame milliseconds (the device is synchronised inside the timed region,
@@ -32,6 +33,7 @@ int main(int argc, char** argv) {
     const bool ns = !std::strncmp(argv[6], "northstar", 9);
     const bool fuse = ns && std::strstr(argv[6], "+fuse"), regrow = ns && std::strstr(argv[6], "+regrow");
     const bool rigid = regrow || (ns && std::strstr(argv[6], "+rigid"));
+    const bool prealign = ns && std::strstr(argv[6], "+prealign");
     std::vector<uint16_t> all((size_t)W * H * N);
     std::ifstream f(argv[1], std::ios::binary);
     if (!f.read((char*)all.data(), (std::streamsize)(all.size() * 2))) {
@@ -47,6 +49,7 @@ int main(int argc, char** argv) {
         k.volume_dims = dfa::Vec3i(dim, dim, dim);
         p.north_star  = ns;
         p.north_star_fuse_canonical = fuse || regrow, p.fuse_unsupported_rigid = rigid, p.north_star_regrow_canonical = regrow;
+        p.north_star_rigid_prealign = prealign;
         if (argc > 7) p.epsilon = (float)std::atof(argv[7]);
         else if (ns) p.epsilon = 0.05f;
         DynFusion dynfu(p);
@@ -72,6 +75,9 @@ int main(int argc, char** argv) {
         if (ns)
             std::printf(", \"cost_first\": %.6g, \"cost_last\": %.6g, \"valid_rows\": %lld", dynfu.northStarInitialCost(),
                         dynfu.northStarFinalCost(), dynfu.northStarValidRows());
+        if (prealign)
+            std::printf(", \"rigid_skipped\": %d, \"rigid_matched_first\": %lld, \"rigid_matched_last\": %lld", dynfu.rigidSkippedFrames(),
+                        dynfu.northStarRigidMatched().first, dynfu.northStarRigidMatched().last);
         if (fuse || regrow) {
             std::printf(", \"regrow_skipped\": %d, \"canonical_vertices_by_frame\": [", dynfu.regrowSkippedFrames());
             for (size_t i = 0; i < cloud.size(); ++i) std::printf("%s%zu", i ? ", " : "", cloud[i]);

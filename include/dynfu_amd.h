@@ -313,6 +313,21 @@ int dfa_icp_sums(int depth_variant, const void* curr, int curr_step, const float
                  float fy, float cx, float cy, float dist_thres, float angle_thres, float* sums27, unsigned int* matched,
                  dfa_stream_t stream);
 
+/* The same 27 sums, in the same layout, over a CLOUD against the live maps: one linearisation of the rigid Gauss-Newton
+ * of the north-star solve's own data term (no reference counterpart; DESIGN.md §4.1 "Rigid pre-alignment").  vertices /
+ * normals (device, N x stride floats, stride 3 or 4, the 4th float never read; normals may be NULL: no cosine gate);
+ * aff = current estimate (R row-major, then t).  Per vertex c with normal n0, float32: s = R c + t; no row if c.x is NaN
+ * or s.z > 0 fails; pixel u = rintf(fx * (s.x / s.z) + cx), w likewise (the solve's rule, ties to even), no row outside
+ * the image; L, Ln the float4 pixels of live_vertex_map / live_normal_map (row steps in bytes, >= cols * 16, maps and
+ * steps 16-byte aligned), no row if L.x or Ln.x is NaN; gates sqrtf(|s - L|^2) <= dist_thresh and, with normals,
+ * dot(R n0, Ln) >= cos_thresh (signed: back faces stay out); row (s x Ln, Ln | Ln . (L - s)).  kfusion::cuda::icp_update
+ * consumes sums27 unchanged: T <- exp(x) T.  matched (device, optional) = vertices with a row, exact.  N = 0 is valid:
+ * 27 zeros, matched 0.  The same inputs give the same bits on every call. */
+int dfa_rigid_sums_cloud(const float* vertices, const float* normals, int stride, int N, const float aff[12],
+                         const float* live_vertex_map, int vertex_step, const float* live_normal_map, int normal_step,
+                         int cols, int rows, float fx, float fy, float cx, float cy, float dist_thresh, float cos_thresh,
+                         float* sums27, unsigned int* matched, dfa_stream_t stream);
+
 /* ===================================================================================== */
 /* Marching-cubes seam — replaces kfusion::device::{bindTextures, getOccupiedVoxels,        */
 /* computeOffsetsAndTotalVertices, generateTriangles} (include/kfusion/internal.hpp:121-150, */
