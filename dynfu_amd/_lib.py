@@ -11,7 +11,7 @@ _LIB = None
 SYMBOLS = [
     "dfa_last_error", "dfa_version", "dfa_abi_version", "dfa_abi_struct_size", "dfa_compute_dists", "dfa_tsdf_clear", "dfa_tsdf_integrate",
     "dfa_tsdf_clear_integrate", "dfa_tsdf_raycast_points", "dfa_tsdf_raycast_depth", "dfa_tsdf_raycast_tally", "dfa_tsdf_raycast_render", "dfa_render_image_points", "dfa_render_image_depth", "dfa_render_tangent_colors", "dfa_mesh_rasterize", "dfa_visible_vertices", "dfa_tsdf_vertex_normals", "dfa_tsdf_extract_cloud", "dfa_tsdf_extract_cloud_occ", "dfa_tsdf_extract_normals", "dfa_correspond_projective", "dfa_knn", "dfa_warp_to_live",
-    "dfa_calc_dqb", "dfa_unsupported_vertices", "dfa_icp_sums", "dfa_rigid_sums_cloud", "dfa_repack_points", "dfa_compact_points", "dfa_transform_points", "dfa_warp_to_live_graph",
+    "dfa_calc_dqb", "dfa_unsupported_vertices", "dfa_icp_sums", "dfa_rigid_sums_cloud", "dfa_rigid_align_cloud", "dfa_repack_points", "dfa_compact_points", "dfa_transform_points", "dfa_warp_to_live_graph",
     "dfa_correspond", "dfa_marching_cubes", "dfa_mc_default_tables",
     "dfa_tsdf_occupancy_bytes", "dfa_tsdf_clear_occ", "dfa_tsdf_integrate_occ", "dfa_tsdf_clear_integrate_occ", "dfa_tsdf_clear_integrate_known_occ", "dfa_tsdf_integrate_warped", "dfa_tsdf_integrate_warped6", "dfa_marching_cubes_occ", "dfa_marching_cubes_indexed", "dfa_marching_cubes_indexed_min_weight",
     "dfa_knn_field_create", "dfa_knn_field_destroy", "dfa_knn_field_build", "dfa_knn_field_append", "dfa_knn_field_info", "dfa_knn_field_lookup",
@@ -234,6 +234,8 @@ def load(path=None):
     L.dfa_mc_default_tables.argtypes = [vp, vp]
     L.dfa_icp_sums.argtypes = [i, vp, i, vp, i, vp, i, vp, i, i, i, vp, f, f, f, f, f, f, vp, vp, vp]
     L.dfa_rigid_sums_cloud.argtypes = [vp, vp, i, i, vp, vp, i, vp, i, i, i, f, f, f, f, f, f, vp, vp, vp]
+    L.dfa_rigid_align_cloud.argtypes = [vp, vp, i, i, vp, vp, i, vp, i, i, i, f, f, f, f, f, f, C.POINTER(C.c_int), C.POINTER(C.c_int), i, f,
+                                        f, vp, vp, vp]
     L.dfa_calc_dqb.argtypes = [vp, vp, vp, i, i, vp, i, vp, vp]
     L.dfa_unsupported_vertices.argtypes = [vp, vp, i, i, vp, i, vp, vp]
     L.dfa_correspond.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp]
@@ -1221,3 +1223,53 @@ def rigid_sums_cloud(vertices, normals, aff, vmap, nmap, intr, dist_thresh, cos_
                                            _dev(nmap, torch.float32, "nmap"), nmap.stride(0) * 4, cols, rows, fx, fy, cx, cy,
                                            float(dist_thresh), float(cos_thresh), _dev(sums), _dev(matched), _stream()))
         return sums, int(matched.item())
+
+
+class RigidAlignReport(C.Structure):
+    """dfa_rigid_align_report (include/dynfu_amd.h)"""
+    _fields_ = [("aff", C.c_float * 12), ("status", C.c_int), ("iters_run", C.c_int * 4), ("matched_first", C.c_uint),
+                ("matched_last", C.c_uint), ("last_rot", C.c_float), ("last_trans", C.c_float)]
+
+
+def rigid_align_cloud(vertices, normals, aff0, vmap, nmap, intr, dist_thresh, cos_thresh, level_step, level_iters, stop_rot=0.0,
+                      stop_trans=0.0, trace=False, stream=None):
+    """dfa_rigid_align_cloud: the whole rigid Gauss-Newton of rigid_sums_cloud's linearisation on the device.  Arguments up to
+    cos_thresh as rigid_sums_cloud (aff0: the pose the loop starts from); level_step / level_iters: one entry per level, run in
+    the order given (every level_step[l]-th vertex, at most level_iters[l] iterations; 1 to 4 levels, 64 iterations in all);
+    an accepted step with |rvec| < stop_rot and |tvec| < stop_trans ends its level, 0 never stops.  Everything is enqueued on
+    the stream; the report is read back once, here.  -> dict(aff (12,) float32 numpy, status (0 ok, 1 singular: aff is aff0),
+    iters_run (one int per level), matched_first, matched_last, last_rot, last_trans, trace: an (iters, 40) CUDA float tensor
+    (27 sums, the matched count's bits, the 12 floats of the pose linearised at; NaN rows for iterations that did not run) or
+    None)."""
+    import numpy as np
+    torch = _torch()
+    if vertices.dim() != 2 or vertices.shape[1] not in (3, 4) or not vertices.is_contiguous():
+        raise DynfuAmdError("vertices must be a contiguous (N, 3) or (N, 4) float32 tensor")
+    if normals is not None and (normals.shape != vertices.shape or not normals.is_contiguous()):
+        raise DynfuAmdError("normals must be a contiguous tensor of the vertices' shape")
+    for m, name in ((vmap, "vmap"), (nmap, "nmap")):
+        if m.dim() != 3 or m.shape[2] != 4 or m.stride(2) != 1 or m.stride(1) != 4:
+            raise DynfuAmdError("%s must be a (rows, cols, 4) float32 tensor of packed float4 pixels" % name)
+    if vmap.shape != nmap.shape:
+        raise DynfuAmdError("vmap and nmap differ in size")
+    steps, iters = [int(v) for v in level_step], [int(v) for v in level_iters]
+    if len(steps) != len(iters):
+        raise DynfuAmdError("level_step and level_iters differ in length")
+    N, stride = int(vertices.shape[0]), int(vertices.shape[1])
+    rows, cols = int(vmap.shape[0]), int(vmap.shape[1])
+    fx, fy, cx, cy = (float(v) for v in intr)
+    total = sum(max(v, 0) for v in iters)
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        report = torch.empty(C.sizeof(RigidAlignReport), dtype=torch.uint8, device="cuda")
+        tr = torch.empty((total, 40), dtype=torch.float32, device="cuda") if trace else None
+        _check(load().dfa_rigid_align_cloud(_dev(vertices, torch.float32, "vertices") if N else None,
+                                            _dev(normals, torch.float32, "normals") if N else None, stride, N, _aff12(aff0),
+                                            _dev(vmap, torch.float32, "vmap"), vmap.stride(0) * 4,
+                                            _dev(nmap, torch.float32, "nmap"), nmap.stride(0) * 4, cols, rows, fx, fy, cx, cy,
+                                            float(dist_thresh), float(cos_thresh), (C.c_int * max(len(steps), 1))(*steps),
+                                            (C.c_int * max(len(iters), 1))(*iters), len(steps), float(stop_rot), float(stop_trans),
+                                            _dev(report), _dev(tr) if total else None, _stream()))
+        r = RigidAlignReport.from_buffer_copy(report.cpu().numpy().tobytes())  # the one read-back
+    return dict(aff=np.array(r.aff, np.float32), status=int(r.status), iters_run=[int(r.iters_run[l]) for l in range(len(steps))],
+                matched_first=int(r.matched_first), matched_last=int(r.matched_last), last_rot=float(r.last_rot),
+                last_trans=float(r.last_trans), trace=tr)

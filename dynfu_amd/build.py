@@ -144,13 +144,13 @@ def build_cpp_tests(force=False, verbose=False):
                         ("test_tsdf_classify", ["oracle", "ieee"]), ("test_launch_budget", []), ("test_host_io", ["host"]), ("test_host_kinfu", ["host"]),
                         ("test_host_extract", ["host"]), ("test_host_render", ["host"]), ("test_host_mc_indexed", ["host"]), ("test_host_mesh_view", ["host"]), ("test_host_visible_term", ["host"]),
                         ("test_host_tsdf_warped", ["host"]), ("test_host_tsdf_warped6", ["host"]), ("test_host_regrow", ["host"]), ("test_host_rigid_align", ["host"]),
-                        ("test_knn_field_size", []), ("test_host_knn_field", ["host"])):
+                        ("test_knn_field_size", []), ("test_host_knn_field", ["host"]), ("test_rigid_step", []), ("test_host_rigid_loop", ["host"])):
         src = os.path.join(tdir, name + ".cpp")
         exe = os.path.join(out, name)
         if not os.path.exists(src):  # a tests/ tree from before this program was added: the rest still builds
             continue
         deps = [src, os.path.join(tdir, "minitest.hpp"), host, os.path.join(CSRC, "tsdf_classify.hpp"), os.path.join(CSRC, "launch_budget.hpp"),
-                os.path.join(CSRC, "warped_bricks.hpp")]
+                os.path.join(CSRC, "warped_bricks.hpp"), os.path.join(CSRC, "rigid_step.hpp")]
         if force or _stale(exe, deps):
             cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-I" + inc, src, "-o", exe]
             if "ieee" in needs:  # CPU model of a kernel: same arithmetic contract as the oracle, hardware fma

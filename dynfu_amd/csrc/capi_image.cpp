@@ -10,6 +10,7 @@ using dfa::stream_scratch;
 namespace {
 struct IcpScratch : DeviceBuffer<float> {};        // partial sums of dfa_icp_sums
 struct VisScratch : DeviceBuffer<int32_t> {};      // per-workgroup counts of dfa_visible_vertices
+struct RigidLoopScratch : DeviceBuffer<float> {};  // dfa_rigid_align_cloud: the state of the call, then its partial sums
 }  // namespace
 
 extern "C" {
@@ -205,6 +206,39 @@ int dfa_rigid_sums_cloud(const float* vertices, const float* normals, int stride
     HIP_TRY(dfa::launch_rigid_sums_cloud(vertices, normals, stride, N, aff, live_vertex_map, vertex_step, live_normal_map,
                                          normal_step, cols, rows, fx, fy, cx, cy, dist_thresh, cos_thresh, partial.data, sums27,
                                          matched, S(stream)));
+    return DFA_OK;
+}
+
+int dfa_rigid_align_cloud(const float* vertices, const float* normals, int stride, int N, const float aff0[12],
+                          const float* live_vertex_map, int vertex_step, const float* live_normal_map, int normal_step,
+                          int cols, int rows, float fx, float fy, float cx, float cy, float dist_thresh, float cos_thresh,
+                          const int* level_step, const int* level_iters, int levels, float stop_rot, float stop_trans,
+                          dfa_rigid_align_report* report, float* trace, dfa_stream_t stream) {
+    REQUIRE(N >= 0, "negative vertex count");
+    REQUIRE(stride == 3 || stride == 4, "stride must be 3 or 4 floats");
+    REQUIRE(N == 0 || vertices, "null vertices");
+    REQUIRE(aff0 && live_vertex_map && live_normal_map && report, "null argument");
+    REQUIRE(cols > 0 && rows > 0, "bad image size");
+    REQUIRE(vertex_step >= cols * 16 && normal_step >= cols * 16, "row step smaller than a float4 row");
+    REQUIRE((((uintptr_t)live_vertex_map | (uintptr_t)live_normal_map | (uintptr_t)vertex_step | (uintptr_t)normal_step) & 15) == 0,
+            "map rows must be 16-byte aligned");
+    REQUIRE((((uintptr_t)vertices | (uintptr_t)normals | (uintptr_t)report | (uintptr_t)trace) & 3) == 0,
+            "vertices / normals / report / trace must be 4-byte aligned");
+    REQUIRE(fx != 0.f && fy != 0.f && dist_thresh >= 0.f, "bad intrinsics / threshold");
+    REQUIRE(level_step && level_iters && levels >= 1 && levels <= 4, "the schedule has 1 to 4 levels");
+    int total = 0;
+    for (int l = 0; l < levels; ++l) {
+        REQUIRE(level_step[l] >= 1, "a level's step must be at least 1");
+        REQUIRE(level_iters[l] >= 0 && level_iters[l] <= 64, "a level's iterations must be 0 to 64");
+        total += level_iters[l];
+    }
+    REQUIRE(total <= 64, "more than 64 iterations in all");
+    REQUIRE(stop_rot >= 0.f && stop_trans >= 0.f, "negative or NaN stop threshold");
+    RigidLoopScratch& scratch = stream_scratch<RigidLoopScratch>(S(stream));
+    HIP_TRY(scratch.reserve(dfa::rigid_align_scratch_floats(N, level_step, levels)));
+    HIP_TRY(dfa::launch_rigid_align_cloud(vertices, normals, stride, N, aff0, live_vertex_map, vertex_step, live_normal_map,
+                                          normal_step, cols, rows, fx, fy, cx, cy, dist_thresh, cos_thresh, level_step,
+                                          level_iters, levels, stop_rot, stop_trans, report, trace, scratch.data, S(stream)));
     return DFA_OK;
 }
 

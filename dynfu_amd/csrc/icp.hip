@@ -10,10 +10,18 @@
 // rigid_rows_cloud_kernel (dfa_rigid_sums_cloud; no reference counterpart) is the same linearisation over a CLOUD against
 // the live maps: one lane per vertex, the pixel rule and the gates of the north-star solve's data term
 // (solve6_linearise.hip), the same reduction and the same closing launch.
+//
+// rigid_loop_rows_kernel / rigid_loop_step_kernel (dfa_rigid_align_cloud) run that linearisation's whole Gauss-Newton loop
+// without the host: the same row over every step-th vertex at a pose kept on the device, then one workgroup that adds the
+// 27 sums in the closing launch's order and runs the 6x6 step and the loop's rules (rigid_step.hpp) in one lane.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
+#include "../../include/dynfu_amd.h"
 #include "device_math.hpp"
 #include "kernels.hpp"
+#include "rigid_step.hpp"
 
 namespace dfa {
 
@@ -134,18 +142,15 @@ struct __attribute__((packed, aligned(4))) Packed3 {  // one 12-byte load
 //   L, Ln the float4 pixels of the two maps; no row if L.x or Ln.x is NaN
 //   gates: sqrtf(|s - L|^2) <= dist_thresh, and with normals dot(R n0, Ln) >= cos_thresh (signed)
 //   row (s x Ln, Ln | Ln . (L - s))
-__global__ __launch_bounds__(256) void rigid_rows_cloud_kernel(const RigidCloudArgs a, float* __restrict__ partial, int nblocks,
-                                                               unsigned int* __restrict__ matched) {
-    __shared__ float sh[4][27];
-    __shared__ unsigned int sh_count[4];
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    float row[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    bool ok = false;
-    if (i < (size_t)a.n) {
+// (row and ok are out-parameters the caller has zeroed: in this form the compiler makes of rigid_rows_cloud_kernel what it made
+// of it with the row written out in its body)
+__device__ __forceinline__ void rigid_cloud_row(const RigidCloudArgs& a, const Aff3& aff, size_t i, bool in_range, float (&row)[7],
+                                                bool& ok) {
+    if (in_range) {
         const Packed3 c = *reinterpret_cast<const Packed3*>(a.vertices + i * (size_t)a.stride);
         Packed3 n0{0.f, 0.f, 0.f};
         if (a.normals) n0 = *reinterpret_cast<const Packed3*>(a.normals + i * (size_t)a.stride);  // (uniform)
-        const f3 s = mulR(a.aff, mk3(c.x, c.y, c.z)) + mk3(a.aff.t[0], a.aff.t[1], a.aff.t[2]);
+        const f3 s = mulR(aff, mk3(c.x, c.y, c.z)) + mk3(aff.t[0], aff.t[1], aff.t[2]);
         if (c.x == c.x && s.z > 0.f) {
             const float u = rintf(a.fx * (s.x / s.z) + a.cx), w = rintf(a.fy * (s.y / s.z) + a.cy);
             if (u >= 0.f && w >= 0.f && u < (float)a.cols && w < (float)a.rows) {
@@ -157,7 +162,7 @@ __global__ __launch_bounds__(256) void rigid_rows_cloud_kernel(const RigidCloudA
                     const f3 l = mk3(L.x, L.y, L.z), n = mk3(Ln.x, Ln.y, Ln.z);
                     const f3 sl = s - l;
                     ok = sqrtf(dot(sl, sl)) <= a.dist_thresh;
-                    if (ok && a.normals) ok = dot(mulR(a.aff, mk3(n0.x, n0.y, n0.z)), n) >= a.cos_thresh;
+                    if (ok && a.normals) ok = dot(mulR(aff, mk3(n0.x, n0.y, n0.z)), n) >= a.cos_thresh;
                     if (ok) {
                         row[0] = s.y * n.z - s.z * n.y, row[1] = s.z * n.x - s.x * n.z, row[2] = s.x * n.y - s.y * n.x;
                         row[3] = n.x, row[4] = n.y, row[5] = n.z;
@@ -167,6 +172,12 @@ __global__ __launch_bounds__(256) void rigid_rows_cloud_kernel(const RigidCloudA
             }
         }
     }
+}
+
+// the 27 products of a workgroup's rows and its matched count: per wave with DPP adds, per workgroup through LDS, one
+// partial per product at partial[q * nblocks + blockIdx.x]; the count is added to *matched (may be null)
+__device__ __forceinline__ void rigid_cloud_reduce(const float row[7], bool ok, float (&sh)[4][27], unsigned int (&sh_count)[4],
+                                                   float* __restrict__ partial, int nblocks, unsigned int* __restrict__ matched) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int q = 0;
 #pragma unroll
@@ -185,6 +196,105 @@ __global__ __launch_bounds__(256) void rigid_rows_cloud_kernel(const RigidCloudA
     if (threadIdx.x == 27 && matched) {
         const unsigned int c = (sh_count[0] + sh_count[1]) + (sh_count[2] + sh_count[3]);
         if (c) atomicAdd(matched, c);
+    }
+}
+
+__global__ __launch_bounds__(256) void rigid_rows_cloud_kernel(const RigidCloudArgs a, float* __restrict__ partial, int nblocks,
+                                                               unsigned int* __restrict__ matched) {
+    __shared__ float sh[4][27];
+    __shared__ unsigned int sh_count[4];
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    float row[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    bool ok = false;
+    rigid_cloud_row(a, a.aff, i, i < (size_t)a.n, row, ok);
+    rigid_cloud_reduce(row, ok, sh, sh_count, partial, nblocks, matched);
+}
+
+// The row kernel of dfa_rigid_align_cloud: rigid_rows_cloud_kernel, but the pose comes from the device-resident state of the
+// call (a.aff is the call's aff0, the pose until an update was accepted), a launch whose level is finished or whose call met
+// a singular system returns at entry, and the launch visits every `step`-th vertex: vertex j of the level is vertex j * step
+// of the cloud, workgroup b takes vertices 256 b ... 256 b + 255 of the level's n_level = ceil(a.n / step).  The matched
+// count goes into the iteration's own slot of the state.
+__global__ __launch_bounds__(256) void rigid_loop_rows_kernel(const RigidCloudArgs a, RigidLoopState* __restrict__ state, int level,
+                                                              int iter, int step, int n_level, float* __restrict__ partial,
+                                                              int nblocks) {
+    __shared__ float sh[4][27];
+    __shared__ unsigned int sh_count[4];
+    if (!rigid_loop_active(*state, level)) return;
+    Aff3 aff = a.aff;
+    if (state->have_pose) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) aff.m[k] = state->aff[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) aff.t[k] = state->aff[9 + k];
+    }
+    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+    float row[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    bool ok = false;
+    rigid_cloud_row(a, aff, j * (size_t)step, j < (size_t)n_level, row, ok);
+    rigid_cloud_reduce(row, ok, sh, sh_count, partial, nblocks, &state->matched[iter]);
+}
+
+// The step kernel of dfa_rigid_align_cloud, ONE workgroup of 16 waves.  Each of the 27 sums is added by one wave in double in
+// icp_final_kernel's order (lane-strided by 64, then the wave sum) and rounded to float: the bits dfa_rigid_sums_cloud returns
+// for that pose and that subsampled cloud.  Lane 0 then runs rigid_loop_advance (rigid_step.hpp: the 6x6 step and the rules
+// of the loop) and writes the iteration's trace row.  The last launch of a call (report != null) fills the report whether
+// or not its iteration still ran; iter < 0 is a call without iterations: the report only.
+__global__ __launch_bounds__(1024) void rigid_loop_step_kernel(RigidLoopState* __restrict__ state, const Aff3 aff0,
+                                                               const float* __restrict__ partial, int nblocks, int level, int iter,
+                                                               float stop_rot, float stop_trans, float* __restrict__ trace,
+                                                               dfa_rigid_align_report* __restrict__ report) {
+    __shared__ float sums[27];
+    const bool active = iter >= 0 && rigid_loop_active(*state, level);  // (uniform)
+    if (!active && !report) return;
+    float a0[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) a0[k] = k < 9 ? aff0.m[k] : aff0.t[k - 9];
+    if (active) {
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        // a wave adds sums `wave` and `wave + 16` side by side, eight partials of each in flight: the ADDS of a sum stay in
+        // icp_final_kernel's order, the loads do not wait for one another (one workgroup has this to itself: at a million
+        // vertices a lane would otherwise make 2 x 66 round trips to the L2, one behind the other)
+        const bool two  = wave + 16 < 27;
+        const float* p0 = partial + (size_t)wave * nblocks;
+        const float* p1 = partial + (size_t)(two ? wave + 16 : wave) * nblocks;
+        double acc0 = 0.0, acc1 = 0.0;
+        int i = lane;
+        for (; i + 7 * 64 < nblocks; i += 8 * 64) {
+            float x0[8], x1[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x0[k] = p0[i + 64 * k], x1[k] = p1[i + 64 * k];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) acc0 += (double)x0[k], acc1 += (double)x1[k];
+        }
+        for (; i < nblocks; i += 64) acc0 += (double)p0[i], acc1 += (double)p1[i];
+        acc0 = wave_sum_all(acc0), acc1 = wave_sum_all(acc1);
+        if (lane == 0) {
+            sums[wave] = (float)acc0;
+            if (two) sums[wave + 16] = (float)acc1;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            if (trace) {
+                float* row = trace + 40 * (size_t)iter;
+                float at[12];
+                rigid_loop_pose(*state, a0, at);
+                for (int q = 0; q < 27; ++q) row[q] = sums[q];
+                row[27] = __uint_as_float(state->matched[iter]);
+                for (int k = 0; k < 12; ++k) row[28 + k] = at[k];
+            }
+            rigid_loop_advance(*state, a0, level, iter, sums, stop_rot, stop_trans);
+        }
+    }
+    if (report && threadIdx.x == 0) {
+        const bool good = state->status == 0;
+        for (int k = 0; k < 12; ++k) report->aff[k] = good && state->have_pose ? state->aff[k] : a0[k];
+        report->status = state->status;
+        for (int l = 0; l < RIGID_MAX_LEVELS; ++l) report->iters_run[l] = state->iters_run[l];
+        report->matched_first = iter >= 0 ? state->matched[0] : 0u;
+        report->matched_last  = iter >= 0 ? state->matched[state->last_iter] : 0u;
+        report->last_rot      = state->last_rot;
+        report->last_trans    = state->last_trans;
     }
 }
 
@@ -236,6 +346,49 @@ hipError_t launch_rigid_sums_cloud(const float* vertices, const float* normals, 
     const int nblocks = (int)(((long)n + 255) / 256);
     rigid_rows_cloud_kernel<<<nblocks, 256, 0, s>>>(a, partial, nblocks, matched);
     icp_final_kernel<<<27, 64, 0, s>>>(partial, nblocks, sums27);
+    return hipGetLastError();
+}
+
+static int rigid_level_vertices(int n, int step) { return (int)(((long)n + step - 1) / step); }
+
+size_t rigid_align_scratch_floats(int n, const int* level_step, int levels) {
+    int most = 0;
+    for (int l = 0; l < levels; ++l) most = std::max(most, rigid_level_vertices(n, level_step[l]));
+    return RIGID_STATE_FLOATS + rigid_cloud_partial_floats(std::max(most, 1));
+}
+
+hipError_t launch_rigid_align_cloud(const float* vertices, const float* normals, int stride, int n, const float aff0[12],
+                                    const float* vmap, int vstep, const float* nmap, int nstep, int cols, int rows, float fx,
+                                    float fy, float cx, float cy, float dist_thresh, float cos_thresh, const int* level_step,
+                                    const int* level_iters, int levels, float stop_rot, float stop_trans,
+                                    dfa_rigid_align_report* report, float* trace, float* scratch, hipStream_t s) {
+    static_assert(sizeof(RigidLoopState) <= RIGID_STATE_FLOATS * sizeof(float), "the state's room in the scratch");
+    RigidLoopState* state = reinterpret_cast<RigidLoopState*>(scratch);
+    float* partial        = scratch + RIGID_STATE_FLOATS;
+    int total             = 0;
+    for (int l = 0; l < levels; ++l) total += level_iters[l];
+    hipError_t e = hipMemsetAsync(state, 0, sizeof(RigidLoopState), s);  // once per call: every iteration has its own slots
+    if (e != hipSuccess) return e;
+    if (trace && total > 0 && (e = hipMemsetAsync(trace, 0xff, sizeof(float) * 40 * (size_t)total, s)) != hipSuccess) return e;
+    RigidCloudArgs a;
+    a.vertices = vertices, a.normals = normals, a.stride = stride, a.n = n;
+    a.aff  = aff3_from(aff0);
+    a.vmap = vmap, a.nmap = nmap, a.vstep = vstep, a.nstep = nstep, a.cols = cols, a.rows = rows;
+    a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy, a.dist_thresh = dist_thresh, a.cos_thresh = cos_thresh;
+    if (total == 0) {
+        rigid_loop_step_kernel<<<1, 1024, 0, s>>>(state, a.aff, partial, 0, 0, -1, stop_rot, stop_trans, nullptr, report);
+        return hipGetLastError();
+    }
+    int iter = 0;
+    for (int l = 0; l < levels; ++l) {
+        const int n_level = rigid_level_vertices(n, level_step[l]);
+        const int nblocks = std::max((n_level + 255) / 256, 1);  // an empty cloud: one workgroup of zeros, a singular system
+        for (int it = 0; it < level_iters[l]; ++it, ++iter) {
+            rigid_loop_rows_kernel<<<nblocks, 256, 0, s>>>(a, state, l, iter, level_step[l], n_level, partial, nblocks);
+            rigid_loop_step_kernel<<<1, 1024, 0, s>>>(state, a.aff, partial, nblocks, l, iter, stop_rot, stop_trans, trace,
+                                                      iter == total - 1 ? report : nullptr);
+        }
+    }
     return hipGetLastError();
 }
 

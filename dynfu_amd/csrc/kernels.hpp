@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct dfa_rigid_align_report;  // include/dynfu_amd.h
+
 namespace dfa {
 
 // tsdf.hip
@@ -243,6 +245,17 @@ hipError_t launch_rigid_sums_cloud(const float* vertices, const float* normals, 
                                    const float* vmap, int vstep, const float* nmap, int nstep, int cols, int rows, float fx,
                                    float fy, float cx, float cy, float dist_thresh, float cos_thresh, float* partial,
                                    float* sums27, unsigned int* matched, hipStream_t s);
+// the whole rigid Gauss-Newton on the device (dfa_rigid_align_cloud; rigid_step.hpp states the step and the rules): two
+// launches per iteration, all enqueued on s, nothing waits for the host.  scratch: rigid_align_scratch_floats(...) floats
+// — the state of the call (RIGID_STATE_FLOATS), then the partial sums of the largest level.  The schedule is checked by
+// the caller: 1 <= levels <= 4, steps >= 1, iters >= 0, at most 64 iterations in all
+constexpr size_t RIGID_STATE_FLOATS = 128;
+size_t rigid_align_scratch_floats(int n, const int* level_step, int levels);
+hipError_t launch_rigid_align_cloud(const float* vertices, const float* normals, int stride, int n, const float aff0[12],
+                                    const float* vmap, int vstep, const float* nmap, int nstep, int cols, int rows, float fx,
+                                    float fy, float cx, float cy, float dist_thresh, float cos_thresh, const int* level_step,
+                                    const int* level_iters, int levels, float stop_rot, float stop_trans,
+                                    dfa_rigid_align_report* report, float* trace, float* scratch, hipStream_t s);
 
 
 // Several kernels publish partial results with write-through stores and then arrive at a ticket / raise a flag word, ordering

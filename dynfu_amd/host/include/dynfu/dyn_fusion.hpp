@@ -123,6 +123,19 @@ struct DynFuParams {  // dyn_fusion.hpp:25-42
     // with rigid_prealign_iters = 0, nothing of this runs and a frame's outputs are what they were, bit for bit.
     bool north_star_rigid_prealign = false;
     int rigid_prealign_iters       = 10;
+    // Extension — the same step with its whole Gauss-Newton loop on the device (dfa_rigid_align_cloud; needs
+    // north_star_rigid_prealign: otherwise the constructor throws dfa::Error): a coarse-to-fine schedule over every
+    // rigid_prealign_steps[l]-th vertex of the warped cloud, at most rigid_prealign_level_iters[l] iterations per level
+    // (KinFu's {10, 5, 4}, coarsest first; rigid_prealign_iters is not used), a level ended early by an accepted step of
+    // less than rigid_prealign_stop_rot radians AND rigid_prealign_stop_trans metres — two decades under the 1 mm depth
+    // quantum, two decades above the converged step noise of the float32 loop (at most 1.5e-7 on the 80 x 60 scene of
+    // tests/rigid_loop_cases.py) —, everything enqueued at once, one read-back per frame instead of one per iteration.
+    // DynFusion::northStarRigidIterations() reports what ran.  Off, nothing of this runs and a frame keeps its bits.
+    bool rigid_prealign_device                  = false;
+    std::vector<int> rigid_prealign_steps       = {16, 4, 1};
+    std::vector<int> rigid_prealign_level_iters = {4, 5, 10};
+    float rigid_prealign_stop_rot               = 1e-5f;
+    float rigid_prealign_stop_trans             = 1e-5f;
 };
 
 struct dfa_solver6;  // include/dynfu_amd.h
@@ -180,6 +193,9 @@ public:
     };
     RigidMatched northStarRigidMatched() const { return RigidMatched{rigid_matched_first_, rigid_matched_last_}; }
     int rigidSkippedFrames() const { return rigid_skipped_; }
+    // rigid_prealign_device: the iterations each level of the schedule ran in the last frame (empty before it, or with the
+    // switch off)
+    std::vector<int> northStarRigidIterations() const { return rigid_iters_run_; }
     // north_star_visible_only: canonical vertices the last frame's solve could take data rows from (one small read from the
     // device); -1 before the first such frame, or with the switch off
     long long northStarVisibleVertices() const;
@@ -255,6 +271,7 @@ private:
     dfa::Affine3f rigid_pose_;
     long long rigid_matched_first_ = 0, rigid_matched_last_ = 0;
     int rigid_skipped_ = 0;
+    std::vector<int> rigid_iters_run_;
     // north_star_regrow_canonical: the nodes appended since there were `nodes_before` start from the north-star blend of the
     // nodes before them (Warpfield::update's calcDQB composes its k neighbours' transforms: see dyn_fusion.cpp)
     void startNewNodesFromBlend(size_t nodes_before);

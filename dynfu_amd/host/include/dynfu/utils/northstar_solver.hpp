@@ -11,6 +11,7 @@
 // the depth frame must be in ONE frame: the camera's.
 #pragma once
 #include <memory>
+#include <vector>
 
 #include <dynfu/utils/frame.hpp>
 #include <dynfu/warp_field.hpp>
@@ -61,6 +62,19 @@ public:
     // nothing is composed, the call returns false.  iters <= 0: nothing is enqueued, T is the identity, true.
     bool alignRigid(const kfusion::cuda::Cloud& liveVertexMap, const kfusion::cuda::Normals& liveNormalMap,
                     const kfusion::Intr& intr, int iters, dfa::Affine3f& T);
+    // The same estimate with the whole Gauss-Newton loop on the device (dfa_rigid_align_cloud): one warp, one call that
+    // enqueues every iteration of the schedule — level l over every steps[l]-th vertex of the warped cloud for at most
+    // iters[l] iterations, a level ended early by an accepted step with |rvec| < stopRot and |tvec| < stopTrans (0: never) —
+    // and ONE read-back, of the report.  T is then composed as above.  A singular system: T is the identity, nothing is
+    // composed, false.  A schedule without iterations: nothing is enqueued, T is the identity, true.
+    struct RigidSchedule {
+        std::vector<int> steps, iters;  // one entry per level, in the order they run (coarsest first); 1 to 4 levels
+        float stopRot = 0.f, stopTrans = 0.f;  // radians, metres
+    };
+    bool alignRigid(const kfusion::cuda::Cloud& liveVertexMap, const kfusion::cuda::Normals& liveNormalMap,
+                    const kfusion::Intr& intr, const RigidSchedule& schedule, dfa::Affine3f& T);
+    // iterations (accepted or refused) each level of the last schedule ran; empty after the host-loop overload
+    const std::vector<int>& rigidIterationsRun() const { return rigid_iters_run_; }
     // vertices that took a row in the first / the last iteration of the last alignRigid (0 before it)
     long long rigidMatchedFirst() const { return rigid_matched_first_; }
     long long rigidMatchedLast() const { return rigid_matched_last_; }
@@ -100,4 +114,5 @@ private:
     int pcg_short_        = 0;
     int gn_solves_ = 0, gn_rejected_ = 0;
     long long rigid_matched_first_ = 0, rigid_matched_last_ = 0;
+    std::vector<int> rigid_iters_run_;
 };

@@ -67,6 +67,20 @@ DynFusion::DynFusion(const DynFuParams& params) : kfusion::KinFu(params.kinfuPar
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_rigid_prealign needs north_star (reference mode has no rigid step: KinFu tracks rigidly)");
     if (params.north_star_rigid_prealign && params.rigid_prealign_iters < 0)
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: negative rigid_prealign_iters");
+    if (params.rigid_prealign_device) {
+        if (!params.north_star_rigid_prealign)
+            throw dfa::Error(DFA_ERR_INVALID, "DynFusion: rigid_prealign_device needs north_star_rigid_prealign (it is that step's loop, on the device)");
+        const std::vector<int>&st = params.rigid_prealign_steps, &it = params.rigid_prealign_level_iters;
+        long total = 0;
+        for (int n : it) total += n;
+        bool ok = !st.empty() && st.size() <= 4 && st.size() == it.size() && total <= 64;
+        for (int v : st) ok = ok && v >= 1;
+        for (int n : it) ok = ok && n >= 0;
+        if (!ok)
+            throw dfa::Error(DFA_ERR_INVALID, "DynFusion: rigid_prealign_steps / rigid_prealign_level_iters: 1 to 4 levels, steps >= 1, iterations >= 0 and at most 64 in all");
+        if (!(params.rigid_prealign_stop_rot >= 0.f) || !(params.rigid_prealign_stop_trans >= 0.f))
+            throw dfa::Error(DFA_ERR_INVALID, "DynFusion: negative or NaN rigid_prealign_stop_rot / rigid_prealign_stop_trans");
+    }
     solverParams.numIter       = 24;  // dyn_fusion.cpp:183-189
     solverParams.nonLinearIter = 16;
     solverParams.linearIter    = 256;
@@ -331,12 +345,22 @@ bool DynFusion::northStarFrame(const kfusion::cuda::Depth& depth) {
                            dynfuParams.lambda, dynfuParams.psi_reg);
     solver.initializeProblemInstance(canonicalFrame);
     clk.mark("  initializeProblemInstance");
-    const bool prealign = dynfuParams.north_star_rigid_prealign && dynfuParams.rigid_prealign_iters > 0;
+    const bool prealign = dynfuParams.north_star_rigid_prealign && (dynfuParams.rigid_prealign_device || dynfuParams.rigid_prealign_iters > 0);
     if (prealign) {
         // the global rigid motion first: the start transforms and the shared nodes come out composed with it, so everything
         // below — the model view, the visibility test, the solve, the fusion — sees the aligned field
         kfusion::cuda::computePointNormals(p.intr, depth_filtered_, live_points_, live_normals_);
-        if (!solver.alignRigid(live_points_, live_normals_, p.intr, dynfuParams.rigid_prealign_iters, rigid_pose_)) ++rigid_skipped_;
+        bool aligned;
+        if (dynfuParams.rigid_prealign_device) {
+            NorthStarSolver::RigidSchedule schedule;
+            schedule.steps = dynfuParams.rigid_prealign_steps, schedule.iters = dynfuParams.rigid_prealign_level_iters;
+            schedule.stopRot = dynfuParams.rigid_prealign_stop_rot, schedule.stopTrans = dynfuParams.rigid_prealign_stop_trans;
+            aligned          = solver.alignRigid(live_points_, live_normals_, p.intr, schedule, rigid_pose_);
+            rigid_iters_run_ = solver.rigidIterationsRun();
+        } else {
+            aligned = solver.alignRigid(live_points_, live_normals_, p.intr, dynfuParams.rigid_prealign_iters, rigid_pose_);
+        }
+        if (!aligned) ++rigid_skipped_;
         rigid_matched_first_ = solver.rigidMatchedFirst(), rigid_matched_last_ = solver.rigidMatchedLast();
         clk.mark("  alignRigid");
     }

@@ -176,6 +176,7 @@ bool NorthStarSolver::alignRigid(const kfusion::cuda::Cloud& vmap, const kfusion
     Impl& I = *impl;
     T = dfa::Affine3f();
     rigid_matched_first_ = rigid_matched_last_ = 0;
+    rigid_iters_run_.clear();
     if (!I.plan) throw dfa::Error(DFA_ERR_INVALID, "alignRigid before initializeProblemInstance");
     if (vmap.rows() != nmap.rows() || vmap.cols() != nmap.cols() || vmap.empty())
         throw dfa::Error(DFA_ERR_INVALID, "NorthStarSolver: vertex / normal maps differ in size or are empty");
@@ -202,6 +203,46 @@ bool NorthStarSolver::alignRigid(const kfusion::cuda::Cloud& vmap, const kfusion
             return false;
         }
     }
+    Warpfield::composeRigid(T, I.host_dq.data(), (size_t)I.D);
+    I.node_dq.upload(I.host_dq);
+    dfa::check(dfa_solver6_set_node_transforms(I.plan, I.node_dq.ptr()), "NorthStarSolver::alignRigid (set_node_transforms)");
+    m_warpfield.composeRigid(T);
+    return true;
+}
+
+bool NorthStarSolver::alignRigid(const kfusion::cuda::Cloud& vmap, const kfusion::cuda::Normals& nmap, const kfusion::Intr& intr,
+                                 const RigidSchedule& schedule, dfa::Affine3f& T) {
+    Impl& I = *impl;
+    T = dfa::Affine3f();
+    rigid_matched_first_ = rigid_matched_last_ = 0;
+    rigid_iters_run_.assign(schedule.steps.size(), 0);
+    if (!I.plan) throw dfa::Error(DFA_ERR_INVALID, "alignRigid before initializeProblemInstance");
+    if (vmap.rows() != nmap.rows() || vmap.cols() != nmap.cols() || vmap.empty())
+        throw dfa::Error(DFA_ERR_INVALID, "NorthStarSolver: vertex / normal maps differ in size or are empty");
+    if (schedule.steps.size() != schedule.iters.size())
+        throw dfa::Error(DFA_ERR_INVALID, "NorthStarSolver::alignRigid: one step and one iteration count per level");
+    int total = 0;
+    for (int n : schedule.iters) total += n > 0 ? n : 0;
+    if (total == 0) return true;  // as iters <= 0 of the host loop: nothing is enqueued
+    dfa::DeviceArray<float> wv(3 * (size_t)I.N), wn(3 * (size_t)I.N);
+    if (I.N) dfa::check(dfa_solver6_warp_with(I.plan, I.node_dq.ptr(), wv.ptr(), wn.ptr(), nullptr), "NorthStarSolver::alignRigid (warp)");
+    static_assert(sizeof(dfa_rigid_align_report) % sizeof(float) == 0, "the report travels as words");
+    dfa::DeviceArray<float> out(sizeof(dfa_rigid_align_report) / sizeof(float));
+    float aff0[12];
+    T.to12(aff0);
+    dfa::check(dfa_rigid_align_cloud(wv.ptr(), wn.ptr(), 3, I.N, aff0, (const float*)vmap.ptr(), (int)vmap.step(),
+                                     (const float*)nmap.ptr(), (int)nmap.step(), vmap.cols(), vmap.rows(), intr.fx, intr.fy, intr.cx,
+                                     intr.cy, m_params.distThresh, m_params.cosThresh, schedule.steps.data(), schedule.iters.data(),
+                                     (int)schedule.steps.size(), schedule.stopRot, schedule.stopTrans,
+                                     reinterpret_cast<dfa_rigid_align_report*>(out.ptr()), nullptr, nullptr),
+               "NorthStarSolver::alignRigid (device loop)");
+    dfa_rigid_align_report rep;
+    dfa_host_copy_from_device(&rep, out.ptr(), sizeof(rep));  // the one read-back
+    rigid_matched_first_ = rep.matched_first, rigid_matched_last_ = rep.matched_last;
+    for (size_t l = 0; l < rigid_iters_run_.size(); ++l) rigid_iters_run_[l] = rep.iters_run[l];
+    if (rep.status != 0) return false;
+    for (int i = 0; i < 9; ++i) T.R[i] = rep.aff[i];
+    for (int i = 0; i < 3; ++i) T.t[i] = rep.aff[9 + i];
     Warpfield::composeRigid(T, I.host_dq.data(), (size_t)I.D);
     I.node_dq.upload(I.host_dq);
     dfa::check(dfa_solver6_set_node_transforms(I.plan, I.node_dq.ptr()), "NorthStarSolver::alignRigid (set_node_transforms)");

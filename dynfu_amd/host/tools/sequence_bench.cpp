@@ -8,6 +8,8 @@
 // fuse_unsupported_rigid added, and with north_star_regrow_canonical added to both (canonical_min_weight 2); the JSON then
 // also holds the canonical cloud's size per frame.  "+prealign" on any northstar mode adds north_star_rigid_prealign
 // (tools/rigid_align_timing.py): the JSON then holds the frames whose alignment was skipped and the last frame's matched counts.
+// "+prealign+device" runs that step's loop on the device with the default schedule (rigid_prealign_device), "+prealign+device10"
+// with ten iterations at full resolution and no stop, the host loop's work; the JSON then also holds the last frame's iterations.
 //
 // FRAMES.u16: N frames of W x H little-endian uint16 millimetres, back to back (bench.py writes its synthetic
 // sequence there).  Prints one JSON object: per-frame milliseconds (the device is synchronised inside the timed region,
@@ -34,6 +36,7 @@ int main(int argc, char** argv) {
     const bool fuse = ns && std::strstr(argv[6], "+fuse"), regrow = ns && std::strstr(argv[6], "+regrow");
     const bool rigid = regrow || (ns && std::strstr(argv[6], "+rigid"));
     const bool prealign = ns && std::strstr(argv[6], "+prealign");
+    const bool device = prealign && std::strstr(argv[6], "+device"), device10 = prealign && std::strstr(argv[6], "+device10");
     std::vector<uint16_t> all((size_t)W * H * N);
     std::ifstream f(argv[1], std::ios::binary);
     if (!f.read((char*)all.data(), (std::streamsize)(all.size() * 2))) {
@@ -50,6 +53,8 @@ int main(int argc, char** argv) {
         p.north_star  = ns;
         p.north_star_fuse_canonical = fuse || regrow, p.fuse_unsupported_rigid = rigid, p.north_star_regrow_canonical = regrow;
         p.north_star_rigid_prealign = prealign;
+        p.rigid_prealign_device     = device;
+        if (device10) p.rigid_prealign_steps = {1}, p.rigid_prealign_level_iters = {10}, p.rigid_prealign_stop_rot = p.rigid_prealign_stop_trans = 0.f;
         if (argc > 7) p.epsilon = (float)std::atof(argv[7]);
         else if (ns) p.epsilon = 0.05f;
         DynFusion dynfu(p);
@@ -78,6 +83,12 @@ int main(int argc, char** argv) {
         if (prealign)
             std::printf(", \"rigid_skipped\": %d, \"rigid_matched_first\": %lld, \"rigid_matched_last\": %lld", dynfu.rigidSkippedFrames(),
                         dynfu.northStarRigidMatched().first, dynfu.northStarRigidMatched().last);
+        if (device) {
+            std::printf(", \"rigid_iterations\": [");
+            const std::vector<int> ran = dynfu.northStarRigidIterations();
+            for (size_t i = 0; i < ran.size(); ++i) std::printf("%s%d", i ? ", " : "", ran[i]);
+            std::printf("]");
+        }
         if (fuse || regrow) {
             std::printf(", \"regrow_skipped\": %d, \"canonical_vertices_by_frame\": [", dynfu.regrowSkippedFrames());
             for (size_t i = 0; i < cloud.size(); ++i) std::printf("%s%zu", i ? ", " : "", cloud[i]);

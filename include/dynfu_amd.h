@@ -328,6 +328,38 @@ int dfa_rigid_sums_cloud(const float* vertices, const float* normals, int stride
                          int cols, int rows, float fx, float fy, float cx, float cy, float dist_thresh, float cos_thresh,
                          float* sums27, unsigned int* matched, dfa_stream_t stream);
 
+/* The whole rigid Gauss-Newton of that linearisation on the device: a coarse-to-fine schedule over a subsampled cloud, the
+ * 6 x 6 solve and the pose update of kfusion::cuda::icp_update, and an early stop on the twist's norms — enqueued whole on
+ * `stream` (two launches per iteration), never synchronising with the host.  Arguments up to cos_thresh as
+ * dfa_rigid_sums_cloud (alignment, steps, NULL normals, N = 0 valid); aff0 = the pose the loop starts from.
+ * Schedule: `levels` (1..4) levels run in the order given; level l linearises over every level_step[l]-th vertex (vertex j of
+ * the level is vertex j * level_step[l] of the cloud, ceil(N / level_step[l]) of them; level_step[l] >= 1) for at most
+ * level_iters[l] >= 0 iterations, at most 64 iterations in all levels together.  Both arrays are HOST memory, read before
+ * the call returns.  A bad schedule is DFA_ERR_INVALID.
+ * Rules: every iteration's sums are, bit for bit, what dfa_rigid_sums_cloud returns for that pose and a contiguous copy of
+ * the level's vertices; the update is icp_update's (refused when the factorisation fails, |det| < 1e-15 or det is NaN).
+ * A refused update: status = 1, every later launch returns at entry, the reported pose is aff0 (N = 0 ends so in its first
+ * iteration).  An accepted update with |rvec| < stop_rot (radians) and |tvec| < stop_trans (metres) finishes the current
+ * level: its remaining launches return at entry and the next level starts from the pose reached.  Thresholds of 0 never
+ * stop the loop.
+ * report (device): written by the call's last launch.  trace (device, optional): sum(level_iters) x 40 floats, first filled
+ * with 0xff bytes (NaN); each iteration that runs writes its row — the 27 sums, the matched count as an unsigned word, the
+ * 12 floats of the pose it linearised at; rows of iterations that returned at entry stay NaN.
+ * The same inputs give the same bits on every call. */
+typedef struct dfa_rigid_align_report {   /* device memory, written by the call */
+    float aff[12];                /* the pose reached; aff0 when status != 0 */
+    int status;                   /* 0 ok, 1 singular system */
+    int iters_run[4];             /* accepted or refused iterations per level */
+    unsigned matched_first, matched_last;   /* of the first / the last iteration that ran */
+    float last_rot, last_trans;   /* the last accepted twist's norms */
+} dfa_rigid_align_report;
+
+int dfa_rigid_align_cloud(const float* vertices, const float* normals, int stride, int N, const float aff0[12],
+                          const float* live_vertex_map, int vertex_step, const float* live_normal_map, int normal_step,
+                          int cols, int rows, float fx, float fy, float cx, float cy, float dist_thresh, float cos_thresh,
+                          const int* level_step, const int* level_iters, int levels, float stop_rot, float stop_trans,
+                          dfa_rigid_align_report* report, float* trace, dfa_stream_t stream);
+
 /* ===================================================================================== */
 /* Marching-cubes seam — replaces kfusion::device::{bindTextures, getOccupiedVoxels,        */
 /* computeOffsetsAndTotalVertices, generateTriangles} (include/kfusion/internal.hpp:121-150, */
