@@ -22,6 +22,7 @@ SYMBOLS = [
     "dfa_solver6_solve", "dfa_solver6_set_node_transforms", "dfa_solver6_set_vertex_mask", "dfa_solver6_node_dq", "dfa_solver6_warp", "dfa_solver6_warp_with", "dfa_solver6_get_stats",
     "dfa_solver6_enable_timing", "dfa_solver6_get_timing", "dfa_solver6_matrix_blocks", "dfa_solver6_matrix_columns",
     "dfa_solver6_matrix_row_blocks", "dfa_solver6_gradient", "dfa_solver6_step", "dfa_solver6_data_graph", "dfa_solver6_reg_graph",
+    "dfa_node_levels", "dfa_solver6_set_reg_hierarchy", "dfa_solver6_node_levels",
     "dfa_solver_create", "dfa_solver_destroy", "dfa_solver_set_problem", "dfa_solver_solve", "dfa_solver_set_deterministic", "dfa_solver_matrix_entries", "dfa_solver_matrix_row_lengths", "dfa_solver_gradient",
     "dfa_solver_translations", "dfa_solver_node_dq", "dfa_solver_tukey_weights", "dfa_solver_huber_weights",
     "dfa_solver_data_graph", "dfa_solver_reg_graph", "dfa_solver_get_stats", "dfa_solver_enable_timing",
@@ -223,7 +224,9 @@ def load(path=None):
     L.dfa_solver6_get_stats.argtypes = [vp, C.POINTER(_Solve6Stats), vp]
     L.dfa_solver6_enable_timing.argtypes = [vp, i]
     L.dfa_solver6_get_timing.argtypes = [vp, C.POINTER(_Solve6Timing), vp]
-    for n in ("matrix_blocks", "matrix_columns", "matrix_row_blocks", "gradient", "step", "data_graph", "reg_graph"):
+    L.dfa_node_levels.argtypes = [vp, i, f, i, i, vp, vp]
+    L.dfa_solver6_set_reg_hierarchy.argtypes = [vp, i, C.POINTER(C.c_int), f, i]
+    for n in ("matrix_blocks", "matrix_columns", "matrix_row_blocks", "gradient", "step", "data_graph", "reg_graph", "node_levels"):
         fn = getattr(L, "dfa_solver6_" + n)
         fn.argtypes = [vp]
         fn.restype = vp
@@ -761,6 +764,16 @@ def knn(node_pos, node_w, query, k, want_weights=True):
     return idx, w
 
 
+def node_levels(node_pos, epsilon, beta, levels):
+    """dfa_node_levels: (D,) int32, the level 0 .. levels - 1 of every node in the regularisation hierarchy of cell size
+    epsilon beta^l (the rule: include/dynfu_amd.h, dfa_solver6_set_reg_hierarchy)"""
+    torch = _torch()
+    D = node_pos.shape[0]
+    out = torch.empty((D,), dtype=torch.int32, device=node_pos.device)
+    _check(load().dfa_node_levels(_dev(node_pos, torch.float32, "node_pos"), D, epsilon, beta, levels, _dev(out), _stream()))
+    return out
+
+
 def warp_to_live(node_pos, node_dq, node_w, k, verts, normals=None):
     torch = _torch()
     out_v = torch.empty_like(verts)
@@ -1028,6 +1041,19 @@ class Solver6:
         """the same graphs, new starting transforms (dfa_solver6_set_node_transforms)"""
         self._keep = self._keep[:1] + (node_dq,) + self._keep[2:]
         _check(self._L.dfa_solver6_set_node_transforms(self._h, _dev(node_dq, _torch().float32, "node_dq")))
+
+    def set_reg_hierarchy(self, slots, epsilon=0.0, beta=0):
+        """dfa_solver6_set_reg_hierarchy: slots[l] columns of every reg_graph row for level l, cells of epsilon beta^l; holds
+        for the set_problem calls that follow.  None or a single level: the flat graph again."""
+        n = len(slots) if slots is not None else 0
+        arr = (C.c_int * n)(*slots) if n else None
+        _check(self._L.dfa_solver6_set_reg_hierarchy(self._h, n, arr, epsilon, beta))
+
+    def node_levels(self):
+        """(D,) int32 levels of the last set_problem's nodes; None while the graph is flat"""
+        if not self._L.dfa_solver6_node_levels(self._h):
+            return None
+        return self._view("node_levels", (self.D,), _torch().int32)
 
     def set_vertex_mask(self, mask):
         """dfa_solver6_set_vertex_mask: mask (N,) uint8 or bool in the vertex order of set_problem, non-zero = the vertex may

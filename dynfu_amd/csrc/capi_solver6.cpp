@@ -38,6 +38,11 @@ struct dfa_solver6 {
     // use); has_mask: the linearisations read it
     uint8_t* vmask = nullptr;
     bool has_mask  = false;
+    // dfa_solver6_set_reg_hierarchy: the configuration and its buffers (max_D levels, a table for S6_REG_LEVELS levels,
+    // allocated by the first call that asks for a hierarchy); hierarchical: the set_problem calls that follow build it
+    dfa::S6RegHierarchy hier{};
+    bool hierarchical = false;
+    bool graph_levels = false;  // the graph of the last set_problem is a hierarchy: hier.level holds its D levels
 };
 
 namespace {
@@ -189,9 +194,65 @@ int dfa_solver6_set_problem(dfa_solver6* s, const float* node_pos, const float* 
     HIP_TRY(dfa::launch_knn(node_pos, node_w, D, canon_vertices, N, s->k, v.idx_nat, s->raw_w, grid, S(stream)));
     const int kreg = s->k + 1;
     HIP_TRY(dfa::launch_knn(node_pos, node_w, D, node_pos, D, kreg, s->raw_reg, nullptr, grid, S(stream)));
-    HIP_TRY(dfa::s6_build_graph(v, s->state, canon_vertices, canon_normals, s->raw_w, s->raw_reg, kreg, S(stream)));
-    s->has_problem = true;
-    s->has_mask    = false;  // a mask belongs to the vertex order it was given in
+    HIP_TRY(dfa::s6_build_graph(v, s->state, canon_vertices, canon_normals, s->raw_w, s->raw_reg, kreg, S(stream),
+                                s->hierarchical ? &s->hier : nullptr));
+    s->has_problem  = true;
+    s->graph_levels = s->hierarchical;
+    s->has_mask     = false;  // a mask belongs to the vertex order it was given in
+    return DFA_OK;
+}
+
+namespace {
+// scratch of dfa_node_levels, which has no plan to keep it in
+struct LevelScratch {
+    dfa::DeviceBuffer<unsigned long long> table;
+    dfa::DeviceBuffer<unsigned int> rep;
+};
+}  // namespace
+
+int dfa_node_levels(const float* node_pos, int D, float epsilon, int beta, int levels, int32_t* out_level, dfa_stream_t stream) {
+    REQUIRE(D >= 0 && (D == 0 || (node_pos && out_level)), "bad node arrays");
+    REQUIRE(levels >= 1 && levels <= dfa::S6_REG_LEVELS, "levels out of range 1..8");
+    REQUIRE(epsilon > 0.f && epsilon <= 3.0e38f, "epsilon must be positive");  // (false for NaN)
+    REQUIRE(beta >= 2, "beta must be at least 2");
+    if (D == 0) return DFA_OK;
+    LevelScratch& sc = dfa::stream_scratch<LevelScratch>(S(stream));
+    const size_t cap = dfa::reg_hierarchy_table(D, levels);
+    HIP_TRY(sc.table.reserve(cap));
+    HIP_TRY(sc.rep.reserve(cap));
+    HIP_TRY(dfa::reg_hierarchy_levels(node_pos, D, epsilon, beta, levels, out_level, sc.table.data, sc.rep.data, S(stream)));
+    return DFA_OK;
+}
+
+int dfa_solver6_set_reg_hierarchy(dfa_solver6* s, int levels, const int* slots, float epsilon, int beta) {
+    if (levels > 1 && slots) {  // (the configuration before the plan: what is wrong with it does not depend on one)
+        REQUIRE(levels <= dfa::S6_REG_LEVELS, "levels out of range 1..8");
+        REQUIRE(epsilon > 0.f && epsilon <= 3.0e38f, "epsilon must be positive");
+        REQUIRE(beta >= 2, "beta must be at least 2");
+        REQUIRE(slots[0] >= 1, "level 0 needs at least one slot");
+        for (int l = 1; l < levels; ++l) REQUIRE(slots[l] >= 0, "negative slot count");
+    }
+    REQUIRE(s, "null plan");
+    if (levels <= 1 || !slots) {
+        s->hierarchical = false;
+        return DFA_OK;
+    }
+    long sum = 0;
+    for (int l = 0; l < levels; ++l) sum += slots[l];
+    REQUIRE(sum <= s->k, "more slots than the plan's k");
+    if (!s->hier.level) {
+        s->mem.alloc(&s->hier.level, (size_t)s->max_D);
+        s->mem.alloc(&s->hier.table, dfa::reg_hierarchy_table(s->max_D, dfa::S6_REG_LEVELS));
+        s->mem.alloc(&s->hier.rep, dfa::reg_hierarchy_table(s->max_D, dfa::S6_REG_LEVELS));
+        const int rc = plan_status(s->mem);
+        if (rc != DFA_OK) {
+            s->hier.level = nullptr;
+            return rc;
+        }
+    }
+    s->hier.levels = levels, s->hier.epsilon = epsilon, s->hier.beta = beta;
+    for (int l = 0; l < dfa::S6_REG_LEVELS; ++l) s->hier.slots[l] = l < levels ? slots[l] : 0;
+    s->hierarchical = true;
     return DFA_OK;
 }
 
@@ -330,6 +391,7 @@ const float* dfa_solver6_gradient(const dfa_solver6* s) { return s ? s->v.g : nu
 const float* dfa_solver6_step(const dfa_solver6* s) { return s ? s->v.x : nullptr; }
 const int32_t* dfa_solver6_data_graph(const dfa_solver6* s) { return s ? s->v.idx_nat : nullptr; }
 const int32_t* dfa_solver6_reg_graph(const dfa_solver6* s) { return s ? s->v.reg_idx : nullptr; }
+const int32_t* dfa_solver6_node_levels(const dfa_solver6* s) { return s && s->graph_levels ? s->hier.level : nullptr; }
 
 int dfa_solver6_warp(dfa_solver6* s, float* out_vertices, float* out_normals, dfa_stream_t stream) {
     REQUIRE(s && s->has_problem, "no problem set");

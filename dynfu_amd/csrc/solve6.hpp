@@ -3,6 +3,7 @@
 // projective point-to-plane data term against the live vertex / normal maps, ARAP-style edge regulariser, Gauss-Newton
 // with a block-Jacobi (6x6) preconditioned CG on the block-sparse normal equations.  One translation unit per stage:
 //   solve6_graph.hip      vertex order, normalised weights, regularisation graph, node -> rows lists   (once per frame)
+//   reg_hierarchy.hip     the multi-level regularisation graph, where the plan was given one       (once per frame)
 //   solve6_pattern.hip    block-row pattern, pair lists by slot, work units of the assembly            (once per frame)
 //   solve6_linearise.hip  data rows and regularisation edges, energy, Gauss-Newton stopping rule; s6_forcing
 //   solve6_assemble.hip   normal equations: block rows, gradient, inverse diagonal blocks, start of the PCG
@@ -181,10 +182,34 @@ constexpr int S6_NODES_PER_BLOCK = 8;  // matvec: one wave per node, 512 threads
 __host__ __device__ inline int s6_matvec_blocks(int D) { return (D + S6_NODES_PER_BLOCK - 1) / S6_NODES_PER_BLOCK; }
 __host__ __device__ inline int s6_update_blocks(int D) { return (6 * D + 255) / 256; }
 
+// reg_hierarchy.hip — the multi-level regularisation graph (rule: include/dynfu_amd.h, dfa_solver6_set_reg_hierarchy)
+constexpr int S6_REG_LEVELS = 8;
+struct S6RegHierarchy {
+    int levels, slots[S6_REG_LEVELS];
+    float epsilon;
+    int beta;
+    int32_t* level;             // D: the level of every node of the last graph
+    unsigned long long* table;  // reg_hierarchy_table(D, levels) words: (level, cell) keys
+    unsigned int* rep;          // ... and each key's representative
+};
+// words of the open-addressing table: a power of two, at least twice the D (levels - 1) keys that can arrive
+inline size_t reg_hierarchy_table(int D, int levels) {
+    size_t cap = 64;
+    while (cap < 2 * (size_t)(D > 0 ? D : 0) * (size_t)(levels > 1 ? levels - 1 : 1)) cap <<= 1;
+    return cap;
+}
+// level[n] in 0 .. levels - 1 of D nodes (levels 1 .. S6_REG_LEVELS; table, rep: scratch of reg_hierarchy_table words)
+hipError_t reg_hierarchy_levels(const float* node_pos, int D, float epsilon, int beta, int levels, int32_t* level,
+                                unsigned long long* table, unsigned int* rep, hipStream_t st);
+// h.level and the finished rows reg_idx (D x k, k <= 8) from the flat search's list raw_reg (D x kreg, kreg > h.slots[0])
+hipError_t reg_hierarchy_rows(const float* node_pos, int D, const int32_t* raw_reg, int kreg, const S6RegHierarchy& h, int k,
+                              int32_t* reg_idx, hipStream_t st);
+
 // canon_user / canon_n_user: the caller's vertices (and normals or null) in the caller's order; raw_w and s.idx_nat hold
-// the k-NN pass's output for them
+// the k-NN pass's output for them.  hierarchy: null = the flat graph (s6_reg_graph_kernel), else reg_hierarchy_rows
 hipError_t s6_build_graph(const Solve6View& s, Solve6State* state, const float* canon_user, const float* canon_n_user,
-                          const float* raw_w /* N x k */, const int32_t* raw_reg /* D x (k+1) */, int kreg, hipStream_t st);
+                          const float* raw_w /* N x k */, const int32_t* raw_reg /* D x (k+1) */, int kreg, hipStream_t st,
+                          const S6RegHierarchy* hierarchy = nullptr);
 // slots: history slots the solve will enqueue when gn_tol > 0 (they start as "skipped"), 0 otherwise
 hipError_t s6_begin(const Solve6View& s, Solve6State* state, const float* node_dq, int slots, hipStream_t st);
 // gn_tol > 0: the launch also sums the energy and applies the Gauss-Newton stopping rule for history slot gi (gn_in_outer:

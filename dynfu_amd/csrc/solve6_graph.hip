@@ -119,7 +119,8 @@ hipError_t s6_gather_mask(const Solve6View& s, const uint8_t* mask, uint8_t* out
 }
 
 hipError_t s6_build_graph(const Solve6View& s, Solve6State* state, const float* canon_user, const float* canon_n_user,
-                          const float* raw_w, const int32_t* raw_reg, int kreg, hipStream_t st) {
+                          const float* raw_w, const int32_t* raw_reg, int kreg, hipStream_t st,
+                          const S6RegHierarchy* hierarchy) {
     s6_pattern_reset_kernel<<<1, 1, 0, st>>>(state);
     hipError_t e = hipSuccess;
     if (s.N > 0) {
@@ -129,7 +130,11 @@ hipError_t s6_build_graph(const Solve6View& s, Solve6State* state, const float* 
         if (e != hipSuccess) return e;
         K6DISPATCH(s6_permute_kernel, s.k, <<<s.D, 256, 0, st>>>(s, canon_user, canon_n_user, raw_w));
     }
-    s6_reg_graph_kernel<<<(s.D + 255) / 256, 256, 0, st>>>(raw_reg, s.D, kreg, s.k, s.reg_idx);
+    if (hierarchy) {  // the rows of the multi-level graph instead (reg_hierarchy.hip)
+        e = reg_hierarchy_rows(s.node_pos, s.D, raw_reg, kreg, *hierarchy, s.k, s.reg_idx, st);
+        if (e != hipSuccess) return e;
+    } else
+        s6_reg_graph_kernel<<<(s.D + 255) / 256, 256, 0, st>>>(raw_reg, s.D, kreg, s.k, s.reg_idx);
     e = solve_transpose_graph(s.idx, (size_t)s.N * s.k, s.D, s.blk_hist, s.node_ptr, s.node_list, st);
     if (e != hipSuccess) return e;
     e = solve_transpose_graph(s.reg_idx, (size_t)s.D * s.k, s.D, s.blk_hist, s.rnode_ptr, s.rnode_list, st);

@@ -136,6 +136,16 @@ struct DynFuParams {  // dyn_fusion.hpp:25-42
     std::vector<int> rigid_prealign_level_iters = {4, 5, 10};
     float rigid_prealign_stop_rot               = 1e-5f;
     float rigid_prealign_stop_trans             = 1e-5f;
+    // Extension — the regularisation hierarchy of DynamicFusion, which L, beta and epsilon above were declared for and the
+    // reference never reads (needs north_star: otherwise the constructor throws dfa::Error).  The north-star solve's
+    // regularisation graph becomes multi-level (NorthStarSolver::setRegHierarchy; the rule: dfa_solver6_set_reg_hierarchy in
+    // include/dynfu_amd.h): min(L + 1, reg_level_slots.size()) levels, reg_level_slots[l] of a node's k columns for level l,
+    // cells of epsilon beta^l — a node reaches a few far nodes besides its nearest ones, so a PCG iteration carries a step
+    // further than one node spacing.  A slot sum above the k the solve blends (the warp field's KNN, at most 8), slots[0] < 1,
+    // a negative slot, more than 8 levels, beta < 2 or epsilon <= 0 throw.  DynFusion::northStarNodeLevels() reports the
+    // levels' sizes.  Off, nothing of this runs and a frame's outputs are what they were, bit for bit.
+    bool north_star_reg_hierarchy    = false;
+    std::vector<int> reg_level_slots = {4, 2, 2};
 };
 
 struct dfa_solver6;  // include/dynfu_amd.h
@@ -184,6 +194,9 @@ public:
     double northStarInitialCost() const { return ns_initial_cost_; }
     double northStarFinalCost() const { return ns_final_cost_; }
     long long northStarValidRows() const { return ns_valid_rows_; }
+    // ... the PCG iterations of that solve, over all its Gauss-Newton iterations, and the normal equations it solved
+    int northStarPcgIterations() const { return ns_pcg_iters_; }
+    int northStarGnSolves() const { return ns_gn_solves_; }
     // north_star_rigid_prealign: the last frame's rigid estimate — it maps the model, warped by the transforms that frame's
     // solve would have started from, into the live camera's frame (the identity when the step was skipped, or is off) —, the
     // vertices that took a row in its first and its last iteration, and the frames whose system was singular
@@ -196,6 +209,10 @@ public:
     // rigid_prealign_device: the iterations each level of the schedule ran in the last frame (empty before it, or with the
     // switch off)
     std::vector<int> northStarRigidIterations() const { return rigid_iters_run_; }
+    // north_star_reg_hierarchy: how many nodes of the last frame's graph have level 0, 1, ... (one entry per level used;
+    // empty before the first solved frame, or with the switch off), and the levels themselves, one per node
+    std::vector<int> northStarNodeLevels() const { return reg_level_counts_; }
+    std::vector<int> northStarNodeLevelOfEach() const { return reg_node_levels_; }
     // north_star_visible_only: canonical vertices the last frame's solve could take data rows from (one small read from the
     // device); -1 before the first such frame, or with the switch off
     long long northStarVisibleVertices() const;
@@ -248,6 +265,7 @@ private:
     bool mesh_downloaded_ = false;
     double ns_initial_cost_ = 0.0, ns_final_cost_ = 0.0;
     long long ns_valid_rows_ = 0;
+    int ns_pcg_iters_ = 0, ns_gn_solves_ = 0;
     void seedNodes(const std::vector<dfa::PointXYZ>& canonicalVertices);
     // vertices of the volume's zero level set as a point cloud (dyn_fusion.cpp:73-88 / :119-134), device-resident
     std::shared_ptr<dynfu::Frame> extractSurface(int frame_id, bool with_normals);
@@ -272,6 +290,8 @@ private:
     long long rigid_matched_first_ = 0, rigid_matched_last_ = 0;
     int rigid_skipped_ = 0;
     std::vector<int> rigid_iters_run_;
+    std::vector<int> reg_level_counts_, reg_node_levels_;  // north_star_reg_hierarchy
+    int regLevels() const;                                 // ... min(L + 1, reg_level_slots.size())
     // north_star_regrow_canonical: the nodes appended since there were `nodes_before` start from the north-star blend of the
     // nodes before them (Warpfield::update's calcDQB composes its k neighbours' transforms: see dyn_fusion.cpp)
     void startNewNodesFromBlend(size_t nodes_before);

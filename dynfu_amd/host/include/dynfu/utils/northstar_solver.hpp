@@ -92,6 +92,14 @@ public:
     void setVertexMask(const dfa::DeviceArray<unsigned char>& mask);
     void clearVertexMask();
 
+    // The multi-level regularisation graph (dfa_solver6_set_reg_hierarchy in include/dynfu_amd.h states the rule) for the
+    // initializeProblemInstance calls that follow: slots[l] columns of a node's row for level l, cells of epsilon beta^l.
+    // One level or none: the flat graph.  Throws dfa::Error for what that call refuses — more than 8 levels, slots[0] < 1, a
+    // negative slot, a slot sum above the k the plan blends (the warp field's, at most 8), epsilon <= 0, beta < 2.
+    void setRegHierarchy(std::vector<int> slots, float epsilon, int beta);
+    // the level of every node of the last initializeProblemInstance's graph (one read from the device); empty while it is flat
+    std::vector<int> nodeLevels() const;
+
     double initialCost() const { return initial_cost_; }
     double finalCost() const { return final_cost_; }
     long long validRows() const { return valid_rows_; }  // data rows with an association at the last linearisation
@@ -115,4 +123,7 @@ private:
     int gn_solves_ = 0, gn_rejected_ = 0;
     long long rigid_matched_first_ = 0, rigid_matched_last_ = 0;
     std::vector<int> rigid_iters_run_;
+    std::vector<int> reg_slots_;  // setRegHierarchy (empty: flat)
+    float reg_epsilon_ = 0.f;
+    int reg_beta_      = 0;
 };

@@ -81,6 +81,16 @@ DynFusion::DynFusion(const DynFuParams& params) : kfusion::KinFu(params.kinfuPar
         if (!(params.rigid_prealign_stop_rot >= 0.f) || !(params.rigid_prealign_stop_trans >= 0.f))
             throw dfa::Error(DFA_ERR_INVALID, "DynFusion: negative or NaN rigid_prealign_stop_rot / rigid_prealign_stop_trans");
     }
+    if (params.north_star_reg_hierarchy) {
+        if (!params.north_star)
+            throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_reg_hierarchy needs north_star (the reference-mode solve keeps its flat graph)");
+        const int levels = regLevels();
+        long sum         = 0;
+        bool ok = levels >= 1 && levels <= 8 && params.reg_level_slots[0] >= 1 && params.beta >= 2 && params.epsilon > 0.f;
+        for (int l = 0; l < levels; ++l) ok = ok && params.reg_level_slots[l] >= 0, sum += params.reg_level_slots[l];
+        if (!ok || sum > std::min(KNN, 8))  // (the field is created with KNN neighbours; a k set later is checked by the frame)
+            throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_reg_hierarchy: 1 to 8 levels (min(L + 1, reg_level_slots.size())), reg_level_slots[0] >= 1, no negative slot, a slot sum of at most the warp field's k (and 8), beta >= 2, epsilon > 0");
+    }
     solverParams.numIter       = 24;  // dyn_fusion.cpp:183-189
     solverParams.nonLinearIter = 16;
     solverParams.linearIter    = 256;
@@ -91,6 +101,10 @@ DynFusion::DynFusion(const DynFuParams& params) : kfusion::KinFu(params.kinfuPar
 DynFusion::~DynFusion() = default;
 
 DynFuParams& DynFusion::params() { return dynfuParams; }
+
+int DynFusion::regLevels() const {
+    return (int)std::min<size_t>((size_t)std::max(dynfuParams.L + 1, 0), dynfuParams.reg_level_slots.size());
+}
 
 kfusion::cuda::TsdfVolume::UnsupportedMode DynFusion::unsupportedMode() const {
     return dynfuParams.fuse_unsupported_rigid ? kfusion::cuda::TsdfVolume::UnsupportedMode::Rigid
@@ -343,7 +357,15 @@ bool DynFusion::northStarFrame(const kfusion::cuda::Depth& depth) {
     clk.mark("pre-process + fuse + marching cubes");
     NorthStarSolver solver(*warpfield, dynfuParams.northStarParams, dynfuParams.tukeyOffset, dynfuParams.psi_data,
                            dynfuParams.lambda, dynfuParams.psi_reg);
+    if (dynfuParams.north_star_reg_hierarchy)
+        solver.setRegHierarchy(std::vector<int>(dynfuParams.reg_level_slots.begin(), dynfuParams.reg_level_slots.begin() + regLevels()),
+                               dynfuParams.epsilon, dynfuParams.beta);
     solver.initializeProblemInstance(canonicalFrame);
+    if (dynfuParams.north_star_reg_hierarchy) {
+        reg_node_levels_ = solver.nodeLevels();
+        reg_level_counts_.assign((size_t)regLevels(), 0);
+        for (int lv : reg_node_levels_) ++reg_level_counts_[(size_t)lv];
+    }
     clk.mark("  initializeProblemInstance");
     const bool prealign = dynfuParams.north_star_rigid_prealign && (dynfuParams.rigid_prealign_device || dynfuParams.rigid_prealign_iters > 0);
     if (prealign) {
@@ -383,6 +405,7 @@ bool DynFusion::northStarFrame(const kfusion::cuda::Depth& depth) {
     solver.solveAll(live_points_, live_normals_, p.intr);
     clk.mark("  solveAll");
     ns_initial_cost_ = solver.initialCost(), ns_final_cost_ = solver.finalCost(), ns_valid_rows_ = solver.validRows();
+    ns_pcg_iters_ = solver.pcgIterations(), ns_gn_solves_ = solver.gnSolves();
     if (dynfuParams.north_star_fuse_canonical) {
         // this frame's depth into the canonical volume through the solved field: the nodes hold the solved transforms now, and
         // the field has not grown yet.  The node frame is frame 0's camera — `camera`: it stays at the origin

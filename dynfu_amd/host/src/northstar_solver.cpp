@@ -27,6 +27,9 @@ struct Built {
     dfa::DeviceArray<float> node_pos, node_w, canon, canon_n;
     int D = 0, N = 0, k = 0;
     uint64_t nodes_hash = 0;
+    std::vector<int> reg_slots;  // the regularisation hierarchy the graph was built with (empty: flat)
+    float reg_epsilon = 0.f;
+    int reg_beta      = 0;
 };
 std::mutex g_built_mu;
 std::map<dfa_solver6*, Built> g_built;
@@ -87,6 +90,12 @@ void NorthStarSolver::initializeProblemInstance(const std::shared_ptr<dynfu::Fra
         I.plan_D = D + D / 4 + 16, I.plan_N = N + N / 4 + 1024;
         dfa::check(dfa_solver6_create(I.plan_D, I.plan_N, k, &I.plan), "NorthStarSolver: dfa_solver6_create");
     }
+    // (a plan from the cache may have served a solver with another hierarchy, or none)
+    const bool hierarchy = reg_slots_.size() > 1;
+    dfa::check(dfa_solver6_set_reg_hierarchy(I.plan, hierarchy ? (int)reg_slots_.size() : 0, hierarchy ? reg_slots_.data() : nullptr,
+                                             reg_epsilon_, reg_beta_),
+               "NorthStarSolver: set_reg_hierarchy");
+    const std::vector<int> slots_now = hierarchy ? reg_slots_ : std::vector<int>();
     I.node_dq.upload(dq);
     I.host_dq = dq;
     const uint64_t nodes_hash = fnv1a(w, fnv1a(pos, 1469598103934665603ull));
@@ -96,7 +105,8 @@ void NorthStarSolver::initializeProblemInstance(const std::shared_ptr<dynfu::Fra
         if (it != g_built.end() && !dfa::host_switch("DFA_HOST_NO_GRAPH_REUSE")) {
             const Built& b = it->second;
             if (b.D == D && b.N == N && b.k == k && b.nodes_hash == nodes_hash && b.canon.ptr() == I.canon.ptr() &&
-                b.canon_n.ptr() == I.canon_n.ptr()) {
+                b.canon_n.ptr() == I.canon_n.ptr() && b.reg_slots == slots_now &&
+                (!hierarchy || (b.reg_epsilon == reg_epsilon_ && b.reg_beta == reg_beta_))) {
                 I.node_pos = b.node_pos, I.node_w = b.node_w;  // shared: the plan reads them
                 dfa::check(dfa_solver6_set_node_transforms(I.plan, I.node_dq.ptr()), "NorthStarSolver: set_node_transforms");
                 // a mask stays across set_node_transforms, and the plan may have served another solver: a frame starts without
@@ -114,6 +124,33 @@ void NorthStarSolver::initializeProblemInstance(const std::shared_ptr<dynfu::Fra
     Built& b = g_built[I.plan];
     b.node_pos = I.node_pos, b.node_w = I.node_w, b.canon = I.canon, b.canon_n = I.canon_n;
     b.D = D, b.N = N, b.k = k, b.nodes_hash = nodes_hash;
+    b.reg_slots = slots_now, b.reg_epsilon = reg_epsilon_, b.reg_beta = reg_beta_;
+}
+
+void NorthStarSolver::setRegHierarchy(std::vector<int> slots, float epsilon, int beta) {
+    if (slots.size() > 1) {
+        // the plan's own checks, on no plan: a configuration it refuses is refused here, before a frame is under way
+        long sum = 0;
+        for (int v : slots) sum += v;
+        const int k = std::min(m_warpfield.getKnn(), 8);
+        bool ok = slots.size() <= 8 && slots[0] >= 1 && sum <= k && epsilon > 0.f && beta >= 2;
+        for (int v : slots) ok = ok && v >= 0;
+        if (!ok)
+            throw dfa::Error(DFA_ERR_INVALID, "NorthStarSolver::setRegHierarchy: at most 8 levels, slots[0] >= 1, no negative slot, "
+                                              "a slot sum of at most the field's k, epsilon > 0, beta >= 2");
+    }
+    reg_slots_ = std::move(slots), reg_epsilon_ = epsilon, reg_beta_ = beta;
+}
+
+std::vector<int> NorthStarSolver::nodeLevels() const {
+    const Impl& I = *impl;
+    const int32_t* lv = I.plan ? dfa_solver6_node_levels(I.plan) : nullptr;
+    std::vector<int> out;
+    if (lv && I.D > 0) {
+        out.resize((size_t)I.D);
+        dfa_host_copy_from_device(out.data(), lv, out.size() * sizeof(int));
+    }
+    return out;
 }
 
 void NorthStarSolver::solveAll(const kfusion::cuda::Depth& liveDepth, const kfusion::Intr& intr) {

@@ -11,6 +11,10 @@
 // "+prealign+device" runs that step's loop on the device with the default schedule (rigid_prealign_device), "+prealign+device10"
 // with ten iterations at full resolution and no stop, the host loop's work; the JSON then also holds the last frame's iterations.
 //
+// "+hier" on any northstar mode adds north_star_reg_hierarchy with the default slots (tools/reg_hierarchy_timing.py): the JSON
+// then holds, per frame, the PCG iterations, the normal equations solved, the final energy and the valid rows, and the last
+// frame's level sizes.
+//
 // FRAMES.u16: N frames of W x H little-endian uint16 millimetres, back to back (bench.py writes its synthetic
 // sequence there).  Prints one JSON object: per-frame milliseconds (the device is synchronised inside the timed region,
 // so nothing of a frame hides behind the next one), node / vertex counts, the north-star energies.  No files are
@@ -37,6 +41,7 @@ int main(int argc, char** argv) {
     const bool rigid = regrow || (ns && std::strstr(argv[6], "+rigid"));
     const bool prealign = ns && std::strstr(argv[6], "+prealign");
     const bool device = prealign && std::strstr(argv[6], "+device"), device10 = prealign && std::strstr(argv[6], "+device10");
+    const bool hier = ns && std::strstr(argv[6], "+hier");
     std::vector<uint16_t> all((size_t)W * H * N);
     std::ifstream f(argv[1], std::ios::binary);
     if (!f.read((char*)all.data(), (std::streamsize)(all.size() * 2))) {
@@ -55,6 +60,7 @@ int main(int argc, char** argv) {
         p.north_star_rigid_prealign = prealign;
         p.rigid_prealign_device     = device;
         if (device10) p.rigid_prealign_steps = {1}, p.rigid_prealign_level_iters = {10}, p.rigid_prealign_stop_rot = p.rigid_prealign_stop_trans = 0.f;
+        p.north_star_reg_hierarchy = hier;
         if (argc > 7) p.epsilon = (float)std::atof(argv[7]);
         else if (ns) p.epsilon = 0.05f;
         DynFusion dynfu(p);
@@ -62,6 +68,9 @@ int main(int argc, char** argv) {
         kfusion::cuda::Depth depth;
         std::vector<double> ms;
         std::vector<size_t> nodes, cloud;
+        std::vector<int> pcg_iters, gn_solves;
+        std::vector<double> final_cost;
+        std::vector<long long> valid;
         for (int i = 0; i < N; ++i) {
             depth.upload(all.data() + (size_t)i * W * H, (size_t)W * sizeof(uint16_t), H, W);  // demo.cpp:90
             (void)hipDeviceSynchronize();
@@ -71,6 +80,10 @@ int main(int argc, char** argv) {
             ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
             nodes.push_back(dynfu.getWarpfield()->getNodes().size());
             cloud.push_back(dynfu.canonicalVertexCount());
+            if (ns) {
+                pcg_iters.push_back(dynfu.northStarPcgIterations()), gn_solves.push_back(dynfu.northStarGnSolves());
+                final_cost.push_back(dynfu.northStarFinalCost()), valid.push_back(dynfu.northStarValidRows());
+            }
         }
         std::printf("{\"mode\": \"%s\", \"dim\": %d, \"width\": %d, \"height\": %d, \"frames\": %d, \"canonical_vertices\": %zu, "
                     "\"live_vertices_last\": %zu, \"nodes_first\": %zu, \"nodes_last\": %zu, \"epsilon\": %g, \"node_step\": %d",
@@ -92,6 +105,23 @@ int main(int argc, char** argv) {
         if (fuse || regrow) {
             std::printf(", \"regrow_skipped\": %d, \"canonical_vertices_by_frame\": [", dynfu.regrowSkippedFrames());
             for (size_t i = 0; i < cloud.size(); ++i) std::printf("%s%zu", i ? ", " : "", cloud[i]);
+            std::printf("]");
+        }
+        if (ns) {
+            std::printf(", \"pcg_iters_by_frame\": [");
+            for (size_t i = 0; i < pcg_iters.size(); ++i) std::printf("%s%d", i ? ", " : "", pcg_iters[i]);
+            std::printf("], \"gn_solves_by_frame\": [");
+            for (size_t i = 0; i < gn_solves.size(); ++i) std::printf("%s%d", i ? ", " : "", gn_solves[i]);
+            std::printf("], \"final_cost_by_frame\": [");
+            for (size_t i = 0; i < final_cost.size(); ++i) std::printf("%s%.6g", i ? ", " : "", final_cost[i]);
+            std::printf("], \"valid_rows_by_frame\": [");
+            for (size_t i = 0; i < valid.size(); ++i) std::printf("%s%lld", i ? ", " : "", valid[i]);
+            std::printf("]");
+        }
+        if (hier) {
+            std::printf(", \"node_levels\": [");
+            const std::vector<int> lv = dynfu.northStarNodeLevels();
+            for (size_t i = 0; i < lv.size(); ++i) std::printf("%s%d", i ? ", " : "", lv[i]);
             std::printf("]");
         }
         std::printf(", \"frame_ms\": [");

@@ -886,6 +886,31 @@ int dfa_solver6_set_problem(dfa_solver6* s, const float* node_pos, const float* 
  * set_problem).  What a per-frame caller does instead of rebuilding k-NN, transposition and pair lists (~0.5 ms at 232 k
  * vertices) when nothing they depend on has moved. */
 int dfa_solver6_set_node_transforms(dfa_solver6* s, const float* node_dq);
+/* The multi-level regularisation graph (DynamicFusion's hierarchy: DynFuParams::L and beta, which the reference declares
+ * and never reads).  The coarse levels' nodes are not extra unknowns: they are representatives among the nodes themselves,
+ * and a row of reg_graph (D x k, what everything after the graph reads) is shared out between the levels.  THE RULE, for a
+ * configuration levels (1..8), slots[levels], epsilon > 0, beta >= 2:
+ *   cells   c0 = floor(p / epsilon) per coordinate: correctly rounded float32 division, floorf, a signed integer;
+ *           c_l = floor_div(c0, beta^l), integer floor division (towards minus infinity).  A node with a non-finite
+ *           coordinate or with |c0| >= 2^20 in any coordinate represents no cell: its level is 0.
+ *   level   a node represents level l >= 1 when it is the lowest-indexed node of its cell c_l; level(n) is the highest level
+ *           it represents (at most levels - 1), or 0.  Integer cells nest: a representative of level l + 1 is one of level l.
+ *           Nodes are only ever appended, and an appended node has the highest index: the level of a node that was there
+ *           does not change.
+ *   rows    row n is filled level by level, l = 0 .. level(n): the slots[l] nearest nodes m with level(m) >= l, m != n and m
+ *           not yet in the row — an entry already there is skipped and the next nearest taken —, ascending squared distance
+ *           by dfa_knn's contract (ties to the lower index).  The row is compact: levels ascending, distance ascending
+ *           inside a level, -1 padded.
+ * Edge weights stay lambda / (D k), and so does every stage after the graph.
+ * dfa_solver6_set_reg_hierarchy holds for the dfa_solver6_set_problem calls that follow (dfa_solver6_set_node_transforms
+ * keeps the graph it finds).  levels <= 1 or slots == NULL: the flat graph again, built by exactly the launches of a plan
+ * that was never given a hierarchy.  DFA_ERR_INVALID: levels > 8, epsilon <= 0, beta < 2, slots[0] < 1, a negative slot, a
+ * slot sum above the plan's k.
+ * dfa_solver6_node_levels: device, D int32, level(n) of the last dfa_solver6_set_problem's graph; NULL while that graph is flat.
+ * dfa_node_levels: the level rule alone, for D nodes (device arrays; D == 0: nothing is read or written). */
+int dfa_node_levels(const float* node_pos, int D, float epsilon, int beta, int levels, int32_t* out_level, dfa_stream_t stream);
+int dfa_solver6_set_reg_hierarchy(dfa_solver6* s, int levels, const int* slots, float epsilon, int beta);
+const int32_t* dfa_solver6_node_levels(const dfa_solver6* s);
 /* Which vertices may take a data row in the solves that follow — dfa_visible_vertices' flags, say, so that the data term runs
  * over the visible surface of the model only.
  * mask: N bytes (device), the caller's vertex order of the last dfa_solver6_set_problem; non-zero = the vertex may take a
