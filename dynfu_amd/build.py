@@ -84,7 +84,8 @@ def build(force=False, verbose=False, dev=False):
 HOST = os.path.join(HERE, "host")
 HOST_LIB = os.path.join(HERE, "libdynfu_amd_host.so")
 HOST_SOURCES = ["device.cpp", "frame.cpp", "tsdf_volume.cpp", "warp_field.cpp", "opt_solver.cpp", "northstar_solver.cpp", "dyn_fusion.cpp",
-                "marching_cubes.cpp", "imgproc.cpp", "projective_icp.cpp", "io.cpp", "kinfu.cpp", "mesh_render.cpp"]
+                "dyn_fusion_northstar.cpp", "dyn_fusion_model_view.cpp", "marching_cubes.cpp", "imgproc.cpp", "projective_icp.cpp", "io.cpp",
+                "kinfu.cpp", "mesh_render.cpp"]
 
 
 def build_host(force=False, verbose=False):
@@ -94,7 +95,7 @@ def build_host(force=False, verbose=False):
     lib = build(force=force, verbose=verbose)
     inc = os.path.join(HOST, "include")
     srcs = [os.path.join(HOST, "src", f) for f in HOST_SOURCES]
-    deps = srcs + [lib, os.path.abspath(__file__)]
+    deps = srcs + [os.path.join(HOST, "src", "stage_clock.hpp"), lib, os.path.abspath(__file__)]
     for root, _, files in os.walk(inc):
         deps += [os.path.join(root, f) for f in files]
     if force or _stale(HOST_LIB, deps):
@@ -152,6 +153,9 @@ def build_cpp_tests(force=False, verbose=False):
             continue
         deps = [src, os.path.join(tdir, "minitest.hpp"), host, os.path.join(CSRC, "tsdf_classify.hpp"), os.path.join(CSRC, "launch_budget.hpp"),
                 os.path.join(CSRC, "warped_bricks.hpp"), os.path.join(CSRC, "rigid_step.hpp")]
+        fixtures = os.path.join(tdir, "dynfu_fixtures.hpp")
+        if os.path.exists(fixtures):  # (a tests/ tree from before the header was added has none, and needs none)
+            deps.append(fixtures)
         if force or _stale(exe, deps):
             cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-I" + inc, src, "-o", exe]
             if "ieee" in needs:  # CPU model of a kernel: same arithmetic contract as the oracle, hardware fma

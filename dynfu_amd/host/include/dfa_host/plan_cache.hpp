@@ -7,6 +7,13 @@
 
 namespace dfa {
 
+// the capacity a dfa_solver6 plan is created with for D nodes / N vertices that may grow from frame to frame (the nodes
+// Warpfield::update adds, the vertices a regrown model adds): a quarter more, so that most frames reuse their plan
+template <class I>
+I grown_node_capacity(I D) { return D + D / 4 + 16; }
+template <class I>
+I grown_vertex_capacity(I N) { return N + N / 4 + 1024; }
+
 template <class Plan, void (*Destroy)(Plan*)>
 class PlanCache {
     struct Entry {

@@ -146,9 +146,15 @@ struct DynFuParams {  // dyn_fusion.hpp:25-42
     // levels' sizes.  Off, nothing of this runs and a frame's outputs are what they were, bit for bit.
     bool north_star_reg_hierarchy    = false;
     std::vector<int> reg_level_slots = {4, 2, 2};
+    int regLevels() const;  // ... min(L + 1, reg_level_slots.size())
+    // every rule stated above, each switch with its prerequisites and ranges: throws dfa::Error (DFA_ERR_INVALID) naming the
+    // switch at fault.  DynFusion's constructor calls it first.
+    void validate() const;
 };
 
-struct dfa_solver6;  // include/dynfu_amd.h
+namespace dfa {
+struct StageClock;  // src/stage_clock.hpp
+}
 
 class DynFusion : public kfusion::KinFu {  // include/dynfu/dyn_fusion.hpp:45
 public:
@@ -191,28 +197,28 @@ public:
     // canonical cloud, three indices per triangle; views that stay valid while this object lives
     kfusion::cuda::MarchingCubes::IndexedMesh getCanonicalMesh() const { return canonical_mesh_; }
     // north-star mode: energy before / after the last frame's solve and the data rows that found an association
-    double northStarInitialCost() const { return ns_initial_cost_; }
-    double northStarFinalCost() const { return ns_final_cost_; }
-    long long northStarValidRows() const { return ns_valid_rows_; }
+    double northStarInitialCost() const { return report_.initial_cost; }
+    double northStarFinalCost() const { return report_.final_cost; }
+    long long northStarValidRows() const { return report_.valid_rows; }
     // ... the PCG iterations of that solve, over all its Gauss-Newton iterations, and the normal equations it solved
-    int northStarPcgIterations() const { return ns_pcg_iters_; }
-    int northStarGnSolves() const { return ns_gn_solves_; }
+    int northStarPcgIterations() const { return report_.pcg_iters; }
+    int northStarGnSolves() const { return report_.gn_solves; }
     // north_star_rigid_prealign: the last frame's rigid estimate — it maps the model, warped by the transforms that frame's
     // solve would have started from, into the live camera's frame (the identity when the step was skipped, or is off) —, the
     // vertices that took a row in its first and its last iteration, and the frames whose system was singular
-    dfa::Affine3f northStarRigidPose() const { return rigid_pose_; }
+    dfa::Affine3f northStarRigidPose() const { return report_.rigid_pose; }
     struct RigidMatched {
         long long first, last;
     };
-    RigidMatched northStarRigidMatched() const { return RigidMatched{rigid_matched_first_, rigid_matched_last_}; }
-    int rigidSkippedFrames() const { return rigid_skipped_; }
+    RigidMatched northStarRigidMatched() const { return RigidMatched{report_.rigid_matched_first, report_.rigid_matched_last}; }
+    int rigidSkippedFrames() const { return report_.rigid_skipped; }
     // rigid_prealign_device: the iterations each level of the schedule ran in the last frame (empty before it, or with the
     // switch off)
-    std::vector<int> northStarRigidIterations() const { return rigid_iters_run_; }
+    std::vector<int> northStarRigidIterations() const { return report_.rigid_iters_run; }
     // north_star_reg_hierarchy: how many nodes of the last frame's graph have level 0, 1, ... (one entry per level used;
     // empty before the first solved frame, or with the switch off), and the levels themselves, one per node
-    std::vector<int> northStarNodeLevels() const { return reg_level_counts_; }
-    std::vector<int> northStarNodeLevelOfEach() const { return reg_node_levels_; }
+    std::vector<int> northStarNodeLevels() const { return report_.reg_level_counts; }
+    std::vector<int> northStarNodeLevelOfEach() const { return report_.reg_node_levels; }
     // north_star_visible_only: canonical vertices the last frame's solve could take data rows from (one small read from the
     // device); -1 before the first such frame, or with the switch off
     long long northStarVisibleVertices() const;
@@ -230,7 +236,7 @@ public:
     std::shared_ptr<dynfu::Frame> getCanonicalFrame() { return canonicalFrame; }
     size_t canonicalVertexCount() const { return canonicalFrame ? canonicalFrame->size() : 0; }
     // north_star_regrow_canonical: frames whose re-extraction was empty (the cloud before it was kept)
-    int regrowSkippedFrames() const { return regrow_skipped_; }
+    int regrowSkippedFrames() const { return report_.regrow_skipped; }
 
     // private in the reference (dyn_fusion.hpp:86-89); public here so that it can be tested alone
     std::shared_ptr<dynfu::Frame> findCorrespondingFrame(dfa::PointCloud<dfa::PointXYZ> canonicalVertices,
@@ -263,13 +269,35 @@ private:
     dfa::DeviceArray<kfusion::cuda::MarchingCubes::PointType> mc_buffer_, mesh_source_;
     std::vector<dfa::PointXYZ> mesh_triangles_;
     bool mesh_downloaded_ = false;
-    double ns_initial_cost_ = 0.0, ns_final_cost_ = 0.0;
-    long long ns_valid_rows_ = 0;
-    int ns_pcg_iters_ = 0, ns_gn_solves_ = 0;
+    // what the northStar* / *SkippedFrames accessors read: the numbers of the last north-star frame that ran the stage (a
+    // frame resets nothing it does not write), the skip counters over all frames
+    struct FrameReport {
+        double initial_cost = 0.0, final_cost = 0.0;
+        long long valid_rows = 0;
+        int pcg_iters = 0, gn_solves = 0;
+        dfa::Affine3f rigid_pose;  // north_star_rigid_prealign
+        long long rigid_matched_first = 0, rigid_matched_last = 0;
+        int rigid_skipped = 0;
+        std::vector<int> rigid_iters_run;
+        std::vector<int> reg_level_counts, reg_node_levels;  // north_star_reg_hierarchy
+        dfa::DeviceArray<int> visible_count;                 // north_star_visible_only: on the device
+        bool visible_counted = false;
+        int regrow_skipped = 0;  // north_star_regrow_canonical
+    } report_;
     void seedNodes(const std::vector<dfa::PointXYZ>& canonicalVertices);
     // vertices of the volume's zero level set as a point cloud (dyn_fusion.cpp:73-88 / :119-134), device-resident
     std::shared_ptr<dynfu::Frame> extractSurface(int frame_id, bool with_normals);
-    bool northStarFrame(const kfusion::cuda::Depth& depth);  // operator() in north-star mode
+    // operator() in north-star mode, and its stages in the order they run (dyn_fusion_northstar.cpp): each
+    // reads its switch and returns at once when it is off
+    bool northStarFrame(const kfusion::cuda::Depth& depth);
+    bool northStarFirstFrame();
+    void buildNorthStarProblem(NorthStarSolver& solver, dfa::StageClock& clk);
+    bool prealignRigid(NorthStarSolver& solver, dfa::StageClock& clk);  // true: it ran, and live_points_ / live_normals_ are this frame's
+    void maskHiddenVertices(NorthStarSolver& solver, dfa::StageClock& clk);
+    void solveNorthStar(NorthStarSolver& solver, dfa::StageClock& clk);
+    void fuseThroughSolvedField(dfa::StageClock& clk);
+    void growModelAndField(dfa::StageClock& clk);
+    void volumeToCamera(float aff[12]);  // camera_pose^-1 * volume_pose, the camera at the origin: the inverse of what integrate() applies
     std::shared_ptr<kfusion::cuda::TsdfVolume> canonical_volume_;  // fuse_canonical, north_star_fuse_canonical
     bool knn_field_dropped_ = false;  // fuse_knn_field: the field exceeded fuse_knn_field_max_bytes and is not tried again
     void createCanonicalVolume();  // frame 0: a copy of the live volume
@@ -279,21 +307,15 @@ private:
     // model_view: the canonical mesh (frame 0) as a frame for Warpfield::warpToLive and as float4 vertices + indices, the
     // buffers behind them, and what the last renderWarpedModel made
     void keepCanonicalMesh(const float* to_canonical_frame /* 12 floats, or null: the volume's frame */);
+    // ... the kept mesh and its frame replaced (frame 0 and every frame of north_star_regrow_canonical): the view's plan rebuilds
+    void setCanonicalMesh(std::shared_ptr<dynfu::Frame> frame, const kfusion::cuda::MarchingCubes::IndexedMesh& mesh);
     // the welded mesh of a volume at a weight floor (in mesh_vertex_buffer_ / mesh_index_buffer_) and its vertices with
     // gradient normals as a frame; null when there is no surface.  keepCanonicalMesh's extraction, and the regrown model's
     std::shared_ptr<dynfu::Frame> extractWeldedModel(const kfusion::cuda::TsdfVolume& volume, int min_weight, const float* to_frame,
                                                      kfusion::cuda::MarchingCubes::IndexedMesh& mesh);
     kfusion::cuda::TsdfVolume::UnsupportedMode unsupportedMode() const;  // fuse_unsupported_rigid
-    int regrow_skipped_ = 0;
-    // north_star_rigid_prealign
-    dfa::Affine3f rigid_pose_;
-    long long rigid_matched_first_ = 0, rigid_matched_last_ = 0;
-    int rigid_skipped_ = 0;
-    std::vector<int> rigid_iters_run_;
-    std::vector<int> reg_level_counts_, reg_node_levels_;  // north_star_reg_hierarchy
-    int regLevels() const;                                 // ... min(L + 1, reg_level_slots.size())
     // north_star_regrow_canonical: the nodes appended since there were `nodes_before` start from the north-star blend of the
-    // nodes before them (Warpfield::update's calcDQB composes its k neighbours' transforms: see dyn_fusion.cpp)
+    // nodes before them (Warpfield::update's calcDQB composes its k neighbours' transforms: see dyn_fusion_northstar.cpp)
     void startNewNodesFromBlend(size_t nodes_before);
     std::shared_ptr<dynfu::Frame> canonical_mesh_frame_;
     kfusion::cuda::MarchingCubes::IndexedMesh canonical_mesh_;
@@ -301,23 +323,16 @@ private:
     dfa::DeviceArray<int> mesh_index_buffer_;
     dfa::DeviceArray<dfa::Normal> warped_normals_;
     dfa::DeviceArray<uint64_t> model_zbuffer_;
-    // north-star mode: a dfa_solver6 plan over (nodes, mesh vertices) that only ever warps, its graphs rebuilt when the
-    // node set has grown; the arrays it borrows, and the node set they were built from
-    std::shared_ptr<dfa_solver6> mesh_plan_;
-    int mesh_plan_D_ = 0;
-    size_t mesh_plan_N_ = 0;        // the plan's vertex capacity
-    bool mesh_plan_stale_ = false;  // the kept mesh was replaced after the plan's last set_problem
-    dfa::DeviceArray<float> mesh_node_pos_, mesh_node_w_, mesh_node_dq_;
-    std::vector<float> mesh_nodes_built_pos_, mesh_nodes_built_w_;
+    // north-star mode: a dfa_solver6 plan over (nodes, mesh vertices) that only ever warps (dyn_fusion_model_view.cpp)
+    class MeshWarpPlan;
+    std::shared_ptr<MeshWarpPlan> mesh_warp_;
     kfusion::cuda::Cloud model_points_;
     kfusion::cuda::Normals model_normals_;
     // the warped mesh as float4 vertices / normals rasterised into model_points_ / model_normals_ / model_zbuffer_
     // (renderWarpedModel's first half; north_star_visible_only runs it alone)
     void rasterizeWarpedModel();
-    // north_star_visible_only: the frame's flags (one per canonical vertex) and their count, on the device
+    // north_star_visible_only: the frame's flags (one per canonical vertex), on the device
     dfa::DeviceArray<unsigned char> visible_flags_;
-    dfa::DeviceArray<int> visible_count_;
-    bool visible_counted_ = false;
 };
 
 // DynFuApp::execute of the reference's demo (src/apps/demo.cpp:68-124) without its windows and command line: every

@@ -10,6 +10,7 @@
 // and the shared Nodes come out with their dg_se3 REPLACED by the solved transforms.  The canonical cloud, the nodes and
 // the depth frame must be in ONE frame: the camera's.
 #pragma once
+#include <algorithm>
 #include <memory>
 #include <vector>
 
@@ -38,6 +39,10 @@ struct NorthStarParameters {
     // reference, which runs Opt with earlyOut = true (src/dynfu/dyn_fusion.cpp:183-189).  0: every iteration runs.
     float gnTol = 1e-3f;
 };
+
+// the k the north-star blend reads, of a warp field with `field_knn` neighbours: a dfa_solver6 plan blends at most 8 nodes
+// (the reference's KNN)
+inline int northStarKnn(int field_knn) { return std::min(field_knn, 8); }
 
 class NorthStarSolver {
 public:
@@ -97,6 +102,9 @@ public:
     // One level or none: the flat graph.  Throws dfa::Error for what that call refuses — more than 8 levels, slots[0] < 1, a
     // negative slot, a slot sum above the k the plan blends (the warp field's, at most 8), epsilon <= 0, beta < 2.
     void setRegHierarchy(std::vector<int> slots, float epsilon, int beta);
+    // that rule on the host, for a plan that blends k nodes: 1 to 8 levels, slots[0] >= 1, no negative slot, a slot sum of at
+    // most k, epsilon > 0, beta >= 2.  (setRegHierarchy asks it of two levels or more, DynFuParams::validate of any.)
+    static bool regHierarchyAccepted(const std::vector<int>& slots, float epsilon, int beta, int k);
     // the level of every node of the last initializeProblemInstance's graph (one read from the device); empty while it is flat
     std::vector<int> nodeLevels() const;
 
@@ -116,6 +124,12 @@ private:
     float tukeyOffset, psi_data, lambda, psi_reg;
     struct Impl;
     std::shared_ptr<Impl> impl;
+    // alignRigid's frame around its two loops.  begin: T and the report reset, the checks (`schedule`, or null and the host
+    // loop's `iters`), and — with iterations to run — cloud and normals warped by the start transforms; false: nothing to
+    // run.  commit: T composed onto the start transforms, host and device, and onto the shared Nodes
+    bool beginAlignRigid(const kfusion::cuda::Cloud& vmap, const kfusion::cuda::Normals& nmap, const RigidSchedule* schedule, int iters,
+                         dfa::Affine3f& T, dfa::DeviceArray<float>& warped, dfa::DeviceArray<float>& warped_normals);
+    void commitAlignRigid(const dfa::Affine3f& T);
     double initial_cost_ = 0.0, final_cost_ = 0.0;
     long long valid_rows_ = 0;
     int pcg_iters_        = 0;

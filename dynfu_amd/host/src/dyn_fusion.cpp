@@ -2,8 +2,6 @@
 // (reference: src/dynfu/dyn_fusion.cpp:6-31,147-242).
 #include <dynfu/dyn_fusion.hpp>
 
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -13,6 +11,7 @@
 #include <dfa_host/device.hpp>
 
 #include "../../../include/dynfu_amd.h"
+#include "stage_clock.hpp"
 
 kfusion::KinFuParams kfusion::KinFuParams::default_params() {  // src/kfusion/kinfu.cpp:10-44
     KinFuParams p;
@@ -46,31 +45,33 @@ DynFuParams DynFuParams::defaultParams() {  // dyn_fusion.cpp:6-31
     return p;
 }
 
-DynFusion::DynFusion(const DynFuParams& params) : kfusion::KinFu(params.kinfuParams), dynfuParams(params) {  // dyn_fusion.cpp:33
-    if (params.fuse_canonical && params.north_star)
+int DynFuParams::regLevels() const { return (int)std::min<size_t>((size_t)std::max(L + 1, 0), reg_level_slots.size()); }
+
+void DynFuParams::validate() const {
+    if (fuse_canonical && north_star)
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: fuse_canonical is a reference-mode extension (north_star blends otherwise, in the camera frame: north_star_fuse_canonical)");
-    if (params.north_star_fuse_canonical && !params.north_star)
+    if (north_star_fuse_canonical && !north_star)
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_fuse_canonical needs north_star (reference mode: fuse_canonical)");
-    if (params.fuse_knn_field && !params.fuse_canonical && !params.north_star_fuse_canonical)
+    if (fuse_knn_field && !fuse_canonical && !north_star_fuse_canonical)
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: fuse_knn_field serves the canonical fusion (fuse_canonical or north_star_fuse_canonical)");
-    if (params.north_star_visible_only && !(params.north_star && params.model_view))
+    if (north_star_visible_only && !(north_star && model_view))
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_visible_only needs north_star and model_view (the rasterised canonical mesh is what hides a vertex)");
-    if (params.fuse_unsupported_rigid && !params.fuse_canonical && !params.north_star_fuse_canonical)
+    if (fuse_unsupported_rigid && !fuse_canonical && !north_star_fuse_canonical)
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: fuse_unsupported_rigid serves the canonical fusion (fuse_canonical or north_star_fuse_canonical)");
-    if (params.north_star_regrow_canonical && !params.north_star)
+    if (north_star_regrow_canonical && !north_star)
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_regrow_canonical needs north_star (reference mode keeps frame 0's cloud)");
-    if (params.north_star_regrow_canonical && !params.north_star_fuse_canonical)
+    if (north_star_regrow_canonical && !north_star_fuse_canonical)
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_regrow_canonical needs north_star_fuse_canonical (the canonical volume is what the cloud is re-extracted from)");
-    if (params.north_star_regrow_canonical && (params.canonical_min_weight < 1 || params.canonical_min_weight > 65535))
+    if (north_star_regrow_canonical && (canonical_min_weight < 1 || canonical_min_weight > 65535))
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: canonical_min_weight outside 1..65535");
-    if (params.north_star_rigid_prealign && !params.north_star)
+    if (north_star_rigid_prealign && !north_star)
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_rigid_prealign needs north_star (reference mode has no rigid step: KinFu tracks rigidly)");
-    if (params.north_star_rigid_prealign && params.rigid_prealign_iters < 0)
+    if (north_star_rigid_prealign && rigid_prealign_iters < 0)
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: negative rigid_prealign_iters");
-    if (params.rigid_prealign_device) {
-        if (!params.north_star_rigid_prealign)
+    if (rigid_prealign_device) {
+        if (!north_star_rigid_prealign)
             throw dfa::Error(DFA_ERR_INVALID, "DynFusion: rigid_prealign_device needs north_star_rigid_prealign (it is that step's loop, on the device)");
-        const std::vector<int>&st = params.rigid_prealign_steps, &it = params.rigid_prealign_level_iters;
+        const std::vector<int>&st = rigid_prealign_steps, &it = rigid_prealign_level_iters;
         long total = 0;
         for (int n : it) total += n;
         bool ok = !st.empty() && st.size() <= 4 && st.size() == it.size() && total <= 64;
@@ -78,19 +79,21 @@ DynFusion::DynFusion(const DynFuParams& params) : kfusion::KinFu(params.kinfuPar
         for (int n : it) ok = ok && n >= 0;
         if (!ok)
             throw dfa::Error(DFA_ERR_INVALID, "DynFusion: rigid_prealign_steps / rigid_prealign_level_iters: 1 to 4 levels, steps >= 1, iterations >= 0 and at most 64 in all");
-        if (!(params.rigid_prealign_stop_rot >= 0.f) || !(params.rigid_prealign_stop_trans >= 0.f))
+        if (!(rigid_prealign_stop_rot >= 0.f) || !(rigid_prealign_stop_trans >= 0.f))
             throw dfa::Error(DFA_ERR_INVALID, "DynFusion: negative or NaN rigid_prealign_stop_rot / rigid_prealign_stop_trans");
     }
-    if (params.north_star_reg_hierarchy) {
-        if (!params.north_star)
+    if (north_star_reg_hierarchy) {
+        if (!north_star)
             throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_reg_hierarchy needs north_star (the reference-mode solve keeps its flat graph)");
-        const int levels = regLevels();
-        long sum         = 0;
-        bool ok = levels >= 1 && levels <= 8 && params.reg_level_slots[0] >= 1 && params.beta >= 2 && params.epsilon > 0.f;
-        for (int l = 0; l < levels; ++l) ok = ok && params.reg_level_slots[l] >= 0, sum += params.reg_level_slots[l];
-        if (!ok || sum > std::min(KNN, 8))  // (the field is created with KNN neighbours; a k set later is checked by the frame)
+        // (the field is created with KNN neighbours; a k set later is checked by the frame)
+        const std::vector<int> slots(reg_level_slots.begin(), reg_level_slots.begin() + regLevels());
+        if (!NorthStarSolver::regHierarchyAccepted(slots, epsilon, beta, northStarKnn(KNN)))
             throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_reg_hierarchy: 1 to 8 levels (min(L + 1, reg_level_slots.size())), reg_level_slots[0] >= 1, no negative slot, a slot sum of at most the warp field's k (and 8), beta >= 2, epsilon > 0");
     }
+}
+
+DynFusion::DynFusion(const DynFuParams& params) : kfusion::KinFu(params.kinfuParams), dynfuParams(params) {  // dyn_fusion.cpp:33
+    params.validate();
     solverParams.numIter       = 24;  // dyn_fusion.cpp:183-189
     solverParams.nonLinearIter = 16;
     solverParams.linearIter    = 256;
@@ -101,10 +104,6 @@ DynFusion::DynFusion(const DynFuParams& params) : kfusion::KinFu(params.kinfuPar
 DynFusion::~DynFusion() = default;
 
 DynFuParams& DynFusion::params() { return dynfuParams; }
-
-int DynFusion::regLevels() const {
-    return (int)std::min<size_t>((size_t)std::max(dynfuParams.L + 1, 0), dynfuParams.reg_level_slots.size());
-}
 
 kfusion::cuda::TsdfVolume::UnsupportedMode DynFusion::unsupportedMode() const {
     return dynfuParams.fuse_unsupported_rigid ? kfusion::cuda::TsdfVolume::UnsupportedMode::Rigid
@@ -152,25 +151,10 @@ void DynFusion::addLiveFrame(int frameID, dfa::PointCloud<dfa::PointXYZ>& vertic
     liveFrame = std::make_shared<dynfu::Frame>(frameID, vertices, normals);
 }
 
-namespace {
-// DFA_HOST_PROFILE=1: wall time of the stages of a frame (device synchronised at every mark) on stderr
-struct StageClock {
-    bool on = dfa::host_switch("DFA_HOST_PROFILE");
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void mark(const char* what) {
-        if (!on) return;
-        (void)hipDeviceSynchronize();
-        const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[dfa host] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
-        t = now;
-    }
-};
-}  // namespace
-
 void DynFusion::warpCanonicalToLiveOpt(dfa::Affine3f affine) {
     if (!warpfield || !canonicalFrame || !liveFrame)
         throw dfa::Error(DFA_ERR_INVALID, "warpCanonicalToLiveOpt before init / addLiveFrame");
-    StageClock clk;
+    dfa::StageClock clk;
     CombinedSolver combinedSolver(*warpfield, solverParams, dynfuParams.tukeyOffset, dynfuParams.psi_data,
                                   dynfuParams.lambda, dynfuParams.psi_reg);
     clk.mark("  CombinedSolver ctor");
@@ -212,7 +196,8 @@ void DynFusion::fuse(const kfusion::cuda::Depth& depth, kfusion::cuda::TsdfVolum
     volume.clearAndIntegrate(dists_, camera_pose, dynfuParams.intr);   // :113-114
 }
 
-// ------------------------------------------------------------------------- the per-frame sequence
+// ------------------------------------------------------------------------- the per-frame sequence (north-star mode:
+// dyn_fusion_northstar.cpp; the view of the canonical model: dyn_fusion_model_view.cpp)
 
 std::shared_ptr<dynfu::Frame> DynFusion::extractSurface(int frame_id, bool with_normals) {
     auto triangles = mc_->run(tsdf(), mc_buffer_);  // :73-75 / :119-121 (one host sync: the vertex count)
@@ -270,7 +255,7 @@ void DynFusion::syncKnnField() {
     bool ok = true;
     if (!vol.knnField()) {
         const dfa::Affine3f camera;  // north-star mode: the node frame is frame 0's camera, which stays at the origin
-        ok = vol.buildKnnField(nodes.pos, nodes.w, nodes.D, dynfuParams.north_star ? std::min(warpfield->getKnn(), 8) : warpfield->getKnn(),
+        ok = vol.buildKnnField(nodes.pos, nodes.w, nodes.D, dynfuParams.north_star ? northStarKnn(warpfield->getKnn()) : warpfield->getKnn(),
                                dynfuParams.north_star ? &camera : nullptr, dynfuParams.fuse_knn_field_max_bytes);
     } else if (vol.knnFieldNodes() < nodes.D) {
         ok = vol.appendKnnField(nodes.pos, nodes.w, nodes.D);
@@ -294,7 +279,7 @@ bool DynFusion::operator()(const kfusion::cuda::Depth& depth) {
         if (dynfuParams.fuse_canonical) createCanonicalVolume();
         return ++frame_counter_, false;
     }
-    StageClock clk;
+    dfa::StageClock clk;
     tsdf().clearAndIntegrate(dists_, camera, p.intr);  // :113-114 as one sweep
     clk.mark("pre-process + fuse");
     auto live = extractSurface(frame_counter_, dynfuParams.mesh_normals);
@@ -311,290 +296,6 @@ bool DynFusion::operator()(const kfusion::cuda::Depth& depth) {
     warpfield->update(getCanonicalWarpedToLive());    // :142
     clk.mark("warpfield->update");
     return ++frame_counter_, true;
-}
-
-// The same frame sequence with the north-star solve in the middle: the live side of the solve is the depth frame itself
-// (vertex / normal maps of the filtered depth, as KinFu builds them for its tracker, kinfu.cpp:150-175), so neither the
-// live marching-cubes cloud nor the nearest-neighbour correspondence is on the path; everything the solve sees is in
-// the camera frame.
-bool DynFusion::northStarFrame(const kfusion::cuda::Depth& depth) {
-    const kfusion::KinFuParams& p = params_;
-    kfusion::cuda::Depth& depth_filtered_ = curr_.depth_pyr[0];
-    const dfa::Affine3f camera;  // the camera stays at the origin, as in the reference's operator() (:100-105)
-    if (frame_counter_ == 0) {
-        tsdf().integrate(dists_, camera, p.intr);
-        if (dynfuParams.north_star_regrow_canonical) {
-            // the canonical cloud is the WELDED vertex set (frame 0 holds weight 1 only: no floor), and with model_view the
-            // kept mesh is the cloud's mesh; every later frame replaces both from the canonical volume
-            float aff[12];
-            (camera.inv() * tsdf().getPose()).to12(aff);
-            kfusion::cuda::MarchingCubes::IndexedMesh mesh;
-            auto welded = extractWeldedModel(tsdf(), 1, aff, mesh);
-            if (!welded) throw dfa::Error(DFA_ERR_INVALID, "DynFusion (north-star mode): the first frame has no surface");
-            initFromFrame(welded);
-            if (dynfuParams.model_view) canonical_mesh_frame_ = welded, canonical_mesh_ = mesh;
-            createCanonicalVolume();
-            return ++frame_counter_, false;
-        }
-        auto vol_frame = extractSurface(0, true);  // volume frame, normals from the TSDF gradient
-        const size_t n = vol_frame->size();
-        if (n == 0) throw dfa::Error(DFA_ERR_INVALID, "DynFusion (north-star mode): the first frame has no surface");
-        // volume frame -> camera frame: camera_pose^-1 * volume_pose, the inverse of what integrate() applies (tsdf_volume.cpp:83)
-        float aff[12];
-        (camera.inv() * tsdf().getPose()).to12(aff);
-        const dynfu::Frame::DeviceView v = vol_frame->device();
-        dfa::DeviceArray<float> cv(3 * n), cn(3 * n);
-        dfa::check(dfa_transform_points(v.vertices, (int)n, aff, 1, cv.ptr(), nullptr), "DynFusion: canonical vertices to the camera frame");
-        dfa::check(dfa_transform_points(v.normals, (int)n, aff, 0, cn.ptr(), nullptr), "DynFusion: canonical normals to the camera frame");
-        initFromFrame(dynfu::Frame::fromDevice(0, cv, cn, n));
-        if (dynfuParams.model_view) keepCanonicalMesh(aff);
-        if (dynfuParams.north_star_fuse_canonical) createCanonicalVolume();
-        return ++frame_counter_, false;
-    }
-    StageClock clk;
-    tsdf().clearAndIntegrate(dists_, camera, p.intr);
-    addLiveFrame(frame_counter_, extractSurface(frame_counter_, dynfuParams.mesh_normals));  // for getLiveFrame() / getMesh()
-    clk.mark("pre-process + fuse + marching cubes");
-    NorthStarSolver solver(*warpfield, dynfuParams.northStarParams, dynfuParams.tukeyOffset, dynfuParams.psi_data,
-                           dynfuParams.lambda, dynfuParams.psi_reg);
-    if (dynfuParams.north_star_reg_hierarchy)
-        solver.setRegHierarchy(std::vector<int>(dynfuParams.reg_level_slots.begin(), dynfuParams.reg_level_slots.begin() + regLevels()),
-                               dynfuParams.epsilon, dynfuParams.beta);
-    solver.initializeProblemInstance(canonicalFrame);
-    if (dynfuParams.north_star_reg_hierarchy) {
-        reg_node_levels_ = solver.nodeLevels();
-        reg_level_counts_.assign((size_t)regLevels(), 0);
-        for (int lv : reg_node_levels_) ++reg_level_counts_[(size_t)lv];
-    }
-    clk.mark("  initializeProblemInstance");
-    const bool prealign = dynfuParams.north_star_rigid_prealign && (dynfuParams.rigid_prealign_device || dynfuParams.rigid_prealign_iters > 0);
-    if (prealign) {
-        // the global rigid motion first: the start transforms and the shared nodes come out composed with it, so everything
-        // below — the model view, the visibility test, the solve, the fusion — sees the aligned field
-        kfusion::cuda::computePointNormals(p.intr, depth_filtered_, live_points_, live_normals_);
-        bool aligned;
-        if (dynfuParams.rigid_prealign_device) {
-            NorthStarSolver::RigidSchedule schedule;
-            schedule.steps = dynfuParams.rigid_prealign_steps, schedule.iters = dynfuParams.rigid_prealign_level_iters;
-            schedule.stopRot = dynfuParams.rigid_prealign_stop_rot, schedule.stopTrans = dynfuParams.rigid_prealign_stop_trans;
-            aligned          = solver.alignRigid(live_points_, live_normals_, p.intr, schedule, rigid_pose_);
-            rigid_iters_run_ = solver.rigidIterationsRun();
-        } else {
-            aligned = solver.alignRigid(live_points_, live_normals_, p.intr, dynfuParams.rigid_prealign_iters, rigid_pose_);
-        }
-        if (!aligned) ++rigid_skipped_;
-        rigid_matched_first_ = solver.rigidMatchedFirst(), rigid_matched_last_ = solver.rigidMatchedLast();
-        clk.mark("  alignRigid");
-    }
-    if (dynfuParams.north_star_visible_only) {
-        // the model as the solve finds it: mesh and cloud warped by the transforms the solve starts from, the mesh rasterised
-        // from this frame's camera; a vertex behind the rasterised surface takes no data row
-        rasterizeWarpedModel();
-        const dfa::DeviceArray<float> start = solver.warpCanonicalByStart();
-        float z_tol = dynfuParams.visibility_z_tol;
-        if (z_tol == 0.f) {
-            const kfusion::Vec3f vs = tsdf().getVoxelSize();
-            z_tol = 2.f * std::max(vs[0], std::max(vs[1], vs[2]));
-        }
-        kfusion::cuda::visibleVertices(start.ptr(), 3, canonicalFrame->size(), model_points_, p.intr, z_tol, visible_flags_, &visible_count_);
-        solver.setVertexMask(visible_flags_);
-        visible_counted_ = true;
-        clk.mark("  visible vertices");
-    }
-    if (!prealign) kfusion::cuda::computePointNormals(p.intr, depth_filtered_, live_points_, live_normals_);
-    solver.solveAll(live_points_, live_normals_, p.intr);
-    clk.mark("  solveAll");
-    ns_initial_cost_ = solver.initialCost(), ns_final_cost_ = solver.finalCost(), ns_valid_rows_ = solver.validRows();
-    ns_pcg_iters_ = solver.pcgIterations(), ns_gn_solves_ = solver.gnSolves();
-    if (dynfuParams.north_star_fuse_canonical) {
-        // this frame's depth into the canonical volume through the solved field: the nodes hold the solved transforms now, and
-        // the field has not grown yet.  The node frame is frame 0's camera — `camera`: it stays at the origin
-        if (dynfuParams.fuse_knn_field) syncKnnField();
-        const Warpfield::DeviceNodeView nodes = warpfield->deviceNodes();
-        canonical_volume_->integrateWarped6(dists_, camera, p.intr, camera, nodes.pos, nodes.dq, nodes.w, nodes.D,
-                                            std::min(warpfield->getKnn(), 8), unsupportedMode());
-        clk.mark("integrateWarped6");
-    }
-    canonicalFrameWarpedToLive = solver.warpCanonicalToLive();  // the cloud the solve used
-    if (dynfuParams.north_star_regrow_canonical) {
-        // the canonical model grows: the cloud (and the kept mesh) of the next frame is the canonical volume's surface as it is
-        // now, from the voxels seen canonical_min_weight times, and the field is extended where THAT cloud — in canonical
-        // space — has no support.  An empty extraction keeps the old model.
-        float aff[12];
-        (camera.inv() * tsdf().getPose()).to12(aff);
-        kfusion::cuda::MarchingCubes::IndexedMesh mesh;
-        if (auto grown = extractWeldedModel(*canonical_volume_, dynfuParams.canonical_min_weight, aff, mesh)) {
-            canonicalFrame = grown;
-            if (dynfuParams.model_view) canonical_mesh_frame_ = grown, canonical_mesh_ = mesh, mesh_plan_stale_ = true;
-        } else {
-            ++regrow_skipped_;
-        }
-        clk.mark("warp + regrow");
-        const size_t nodes_before = warpfield->nodesRef().size();
-        warpfield->update(canonicalFrame);
-        startNewNodesFromBlend(nodes_before);
-        clk.mark("warpfield->update");
-        return ++frame_counter_, true;
-    }
-    warpfield->update(canonicalFrameWarpedToLive);
-    clk.mark("warp + warpfield->update");
-    return ++frame_counter_, true;
-}
-
-// north_star_regrow_canonical: the transforms the nodes Warpfield::update has just appended start from.  update gives a new
-// node calcDQB of the field before it — the reference's blend, a PRODUCT of the k neighbours' weighted transforms, which
-// composes them: harmless for the translations of a few millimetres it was written for and for seeds at the edge of the
-// support, but a seed of the regrown cloud may lie half a model away from the nearest node, and the north-star nodes hold
-// whole rigid transforms: k of them composed threw the new part of the model a metre off on the half-sphere sequence of
-// tests/cpp/test_host_regrow.cpp.  Here a new node takes what the north-star blend (csrc/blend6_device.hpp) gives a point
-// at its position from the nodes that existed before: the k nearest, radial basis weights normalised, every transform in the
-// hemisphere of the nearest, real and dual parts summed and divided by the real part's norm.  Host arithmetic in double over
-// the handful of new nodes; the weights are taken relative to the nearest node's, so that no distance underflows them all.
-void DynFusion::startNewNodesFromBlend(size_t nodes_before) {
-    const auto& nodes = warpfield->nodesRef();
-    if (nodes_before == 0 || nodes.size() <= nodes_before) return;
-    std::vector<float> pos, w, dq;
-    warpfield->hostArrays(pos, w, dq);
-    const int k = (int)std::min<size_t>((size_t)std::min(warpfield->getKnn(), 8), nodes_before);
-    std::vector<std::pair<double, size_t>> near(nodes_before);
-    for (size_t i = nodes_before; i < nodes.size(); ++i) {
-        for (size_t j = 0; j < nodes_before; ++j) {
-            const double dx = (double)pos[3 * i] - pos[3 * j], dy = (double)pos[3 * i + 1] - pos[3 * j + 1],
-                         dz = (double)pos[3 * i + 2] - pos[3 * j + 2];
-            near[j] = {dx * dx + dy * dy + dz * dz, j};
-        }
-        std::partial_sort(near.begin(), near.begin() + k, near.end());  // ascending distance, ties to the lower index
-        double e[8], e_max = -1e300, a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
-        for (int q = 0; q < k; ++q) {
-            const double r = (double)w[near[q].second];
-            e[q] = -near[q].first / (2 * r * r), e_max = std::max(e_max, e[q]);
-        }
-        const float* first = &dq[8 * near[0].second];
-        for (int q = 0; q < k; ++q) {
-            const float* t = &dq[8 * near[q].second];
-            const double dot = (double)t[0] * first[0] + (double)t[1] * first[1] + (double)t[2] * first[2] + (double)t[3] * first[3];
-            const double wt = std::exp(e[q] - e_max) * (dot < 0 ? -1.0 : 1.0);
-            for (int c = 0; c < 4; ++c) a[c] += wt * t[c], b[c] += wt * t[4 + c];
-        }
-        const double norm = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2] + a[3] * a[3]);
-        if (!(norm > 0)) continue;  // (opposite rotations cancelling exactly: the node keeps update's transform)
-        nodes[i]->setTransformation(std::make_shared<DualQuaternion<float>>(
-            dfa::quaternion<float>((float)(a[0] / norm), (float)(a[1] / norm), (float)(a[2] / norm), (float)(a[3] / norm)),
-            dfa::quaternion<float>((float)(b[0] / norm), (float)(b[1] / norm), (float)(b[2] / norm), (float)(b[3] / norm))));
-    }
-}
-
-// ------------------------------------------------------------------------- the view of the canonical model
-
-// frame 0, model_view: the volume just fused as a welded mesh with normals from the TSDF gradient, moved to the frame of the
-// canonical cloud exactly as the cloud is (north-star mode: the camera frame)
-void DynFusion::keepCanonicalMesh(const float* to_canonical_frame) {
-    kfusion::cuda::MarchingCubes::IndexedMesh mesh;
-    auto frame = extractWeldedModel(tsdf(), 1, to_canonical_frame, mesh);
-    if (!frame) throw dfa::Error(DFA_ERR_INVALID, "DynFusion (model_view): the first frame has no surface");
-    canonical_mesh_frame_ = frame;
-    canonical_mesh_       = mesh;
-}
-
-// `volume` as a welded mesh (views of mesh_vertex_buffer_ / mesh_index_buffer_: the mesh extracted before is overwritten) from
-// the voxels of weight >= min_weight, and its vertices with normals from the TSDF gradient as a frame, both moved by
-// `to_frame` (12 floats, or null).  Null when the volume has no such surface: the buffers are then untouched.
-std::shared_ptr<dynfu::Frame> DynFusion::extractWeldedModel(const kfusion::cuda::TsdfVolume& volume, int min_weight,
-                                                            const float* to_frame,
-                                                            kfusion::cuda::MarchingCubes::IndexedMesh& mesh) {
-    mesh = mc_->runIndexed(volume, mesh_vertex_buffer_, mesh_index_buffer_, min_weight);
-    if (mesh.vertices.empty() && mc_->totalUniqueVertices() > 0) {  // it did not fit the default buffers: size them and run again
-        mesh_vertex_buffer_.create((size_t)mc_->totalUniqueVertices());
-        mesh_index_buffer_.create((size_t)mc_->totalVertices());
-        mesh = mc_->runIndexed(volume, mesh_vertex_buffer_, mesh_index_buffer_, min_weight);
-    }
-    const size_t n = mesh.vertices.size();
-    if (n == 0) return nullptr;
-    dfa::DeviceArray<dfa::Normal> normals4;
-    mc_->computeNormals(volume, mesh.vertices, normals4);
-    dfa::DeviceArray<float> v3(3 * n), n3(3 * n);
-    dfa::check(dfa_repack_points((const float*)mesh.vertices.ptr(), 4, v3.ptr(), 3, (int)n, 0.f, nullptr), "DynFusion: mesh vertices");
-    dfa::check(dfa_repack_points((const float*)normals4.ptr(), 4, n3.ptr(), 3, (int)n, 0.f, nullptr), "DynFusion: mesh normals");
-    if (to_frame) {
-        dfa::check(dfa_transform_points(v3.ptr(), (int)n, to_frame, 1, v3.ptr(), nullptr), "DynFusion: mesh vertices to the camera frame");
-        dfa::check(dfa_transform_points(n3.ptr(), (int)n, to_frame, 0, n3.ptr(), nullptr), "DynFusion: mesh normals to the camera frame");
-        // the float4 vertices getCanonicalMesh() hands out follow (in place: the buffer is this object's)
-        dfa::check(dfa_repack_points(v3.ptr(), 3, (float*)mesh.vertices.ptr(), 4, (int)n, 1.f, nullptr), "DynFusion: mesh vertices");
-    }
-    return dynfu::Frame::fromDevice(0, v3, n3, n);
-}
-
-// The mesh moves as the canonical cloud does: by the blend of the solve that fitted the transforms.  Reference mode:
-// Warpfield::warpToLive.  North-star mode: the solve's own warp (solve6_update.hip, s6_warp) on a plan that holds the mesh as its
-// cloud and never solves — the frame's plan is not touched, so a frame cannot notice the view.
-std::shared_ptr<dynfu::Frame> DynFusion::warpCanonicalMesh() {
-    if (!dynfuParams.model_view) throw dfa::Error(DFA_ERR_INVALID, "DynFusion::renderWarpedModel: DynFuParams::model_view is off");
-    if (!canonical_mesh_frame_ || !warpfield) throw dfa::Error(DFA_ERR_INVALID, "DynFusion::renderWarpedModel before the first frame");
-    if (!dynfuParams.north_star) return warpfield->warpToLive(canonical_mesh_frame_);
-    std::vector<float> pos, w, dq;
-    warpfield->hostArrays(pos, w, dq);
-    const int D = (int)w.size();
-    const size_t n = canonical_mesh_frame_->size();
-    if (D == 0) throw dfa::Error(DFA_ERR_INVALID, "DynFusion::renderWarpedModel: the warp field has no nodes");
-    mesh_node_dq_.upload(dq);
-    // (mesh_plan_stale_: north_star_regrow_canonical has replaced the mesh — the plan holds the old one's vertices)
-    if (!mesh_plan_ || mesh_plan_stale_ || pos != mesh_nodes_built_pos_ || w != mesh_nodes_built_w_) {
-        if (!mesh_plan_ || D > mesh_plan_D_ || n > mesh_plan_N_) {
-            mesh_plan_.reset();
-            dfa_solver6* plan = nullptr;
-            const int cap = D + D / 4 + 16;  // (room for the nodes Warpfield::update adds, as NorthStarSolver sizes its plan)
-            // (... and, where the mesh grows from frame to frame, for the vertices the next extractions add)
-            const size_t cap_n = dynfuParams.north_star_regrow_canonical ? n + n / 4 + 1024 : n;
-            dfa::check(dfa_solver6_create(cap, (int)cap_n, std::min(warpfield->getKnn(), 8), &plan), "DynFusion (model_view): dfa_solver6_create");
-            mesh_plan_ = std::shared_ptr<dfa_solver6>(plan, dfa_solver6_destroy);
-            mesh_plan_D_ = cap, mesh_plan_N_ = cap_n;
-        }
-        // fresh arrays: the plan borrows them until the next set_problem
-        mesh_node_pos_ = dfa::DeviceArray<float>(), mesh_node_w_ = dfa::DeviceArray<float>();
-        mesh_node_pos_.upload(pos), mesh_node_w_.upload(w);
-        const dynfu::Frame::DeviceView m = canonical_mesh_frame_->device();
-        dfa::check(dfa_solver6_set_problem(mesh_plan_.get(), mesh_node_pos_.ptr(), mesh_node_dq_.ptr(), mesh_node_w_.ptr(), D, m.vertices,
-                                           m.normals, (int)n, nullptr),
-                   "DynFusion (model_view): dfa_solver6_set_problem");
-        mesh_nodes_built_pos_ = pos, mesh_nodes_built_w_ = w, mesh_plan_stale_ = false;
-    }
-    dfa::DeviceArray<float> ov(3 * n), on(3 * n);
-    dfa::check(dfa_solver6_warp_with(mesh_plan_.get(), mesh_node_dq_.ptr(), ov.ptr(), on.ptr(), nullptr), "DynFusion (model_view): dfa_solver6_warp_with");
-    return dynfu::Frame::fromDevice(0, ov, on, n);
-}
-
-long long DynFusion::northStarVisibleVertices() const {
-    if (!visible_counted_) return -1;
-    std::vector<int> n;
-    visible_count_.download(n);  // (a blocking copy on the default stream: behind the frame's work)
-    return n.empty() ? -1 : n[0];
-}
-
-void DynFusion::rasterizeWarpedModel() {
-    const auto warped = warpCanonicalMesh();
-    const kfusion::KinFuParams& p = params_;
-    const dynfu::Frame::DeviceView w = warped->device();
-    if (w.n != canonical_mesh_frame_->size()) throw dfa::Error(DFA_ERR_INVALID, "DynFusion::renderWarpedModel: the warp field has no nodes");
-    if (warped_vertices_.size() != w.n) warped_vertices_.create(w.n), warped_normals_.create(w.n);
-    dfa::check(dfa_repack_points(w.vertices, 3, (float*)warped_vertices_.ptr(), 4, (int)w.n, 1.f, nullptr), "DynFusion: warped vertices");
-    dfa::check(dfa_repack_points(w.normals, 3, (float*)warped_normals_.ptr(), 4, (int)w.n, 0.f, nullptr), "DynFusion: warped normals");
-    // north-star mode keeps the model in the camera frame; otherwise it is in the volume's frame, as the canonical cloud is
-    const dfa::Affine3f world2cam = dynfuParams.north_star ? dfa::Affine3f() : getCameraPose().inv() * tsdf().getPose();
-    kfusion::cuda::rasterizeMesh(warped_vertices_, warped_normals_, canonical_mesh_.indices, world2cam, p.intr, p.cols, p.rows,
-                                 dynfuParams.model_view_z_near, model_points_, model_normals_, model_zbuffer_);
-}
-
-void DynFusion::renderWarpedModel(kfusion::cuda::Image& image, int flag) {
-    rasterizeWarpedModel();
-    const kfusion::KinFuParams& p = params_;
-    image.create(p.rows, flag != 3 ? p.cols : p.cols * 2);  // as KinFu::renderImage
-    if (flag == 2) kfusion::cuda::renderTangentColors(model_normals_, image);
-    else if (flag != 3) kfusion::cuda::renderImage(model_points_, model_normals_, p.intr, p.light_pose, image);
-    else {
-        kfusion::cuda::Image i1(p.rows, p.cols, image.ptr(), image.step()), i2(p.rows, p.cols, image.ptr() + p.cols, image.step());
-        kfusion::cuda::renderImage(model_points_, model_normals_, p.intr, p.light_pose, i1);
-        kfusion::cuda::renderTangentColors(model_normals_, i2);
-    }
 }
 
 SequenceReport runSequence(DynFusion& dynfu, const std::string& dir, int max_frames) {

@@ -77,7 +77,7 @@ void NorthStarSolver::initializeProblemInstance(const std::shared_ptr<dynfu::Fra
     Impl& I = *impl;
     I.D = D, I.N = N;
     canonicalFrame->deviceArrays(I.canon, I.canon_n);
-    const int k = std::min(m_warpfield.getKnn(), 8);  // a dfa_solver6 plan blends at most 8 nodes (the reference's KNN)
+    const int k = northStarKnn(m_warpfield.getKnn());
     if (I.plan && !(I.plan_k == k && I.plan_D >= D && I.plan_N >= N)) {
         plan_cache().park(I.plan, I.plan_D, I.plan_N, I.plan_k);
         I.plan = nullptr;
@@ -87,7 +87,7 @@ void NorthStarSolver::initializeProblemInstance(const std::shared_ptr<dynfu::Fra
         I.plan_k = k;
     }
     if (!I.plan) {
-        I.plan_D = D + D / 4 + 16, I.plan_N = N + N / 4 + 1024;
+        I.plan_D = dfa::grown_node_capacity(D), I.plan_N = dfa::grown_vertex_capacity(N);
         dfa::check(dfa_solver6_create(I.plan_D, I.plan_N, k, &I.plan), "NorthStarSolver: dfa_solver6_create");
     }
     // (a plan from the cache may have served a solver with another hierarchy, or none)
@@ -128,18 +128,18 @@ void NorthStarSolver::initializeProblemInstance(const std::shared_ptr<dynfu::Fra
 }
 
 void NorthStarSolver::setRegHierarchy(std::vector<int> slots, float epsilon, int beta) {
-    if (slots.size() > 1) {
-        // the plan's own checks, on no plan: a configuration it refuses is refused here, before a frame is under way
-        long sum = 0;
-        for (int v : slots) sum += v;
-        const int k = std::min(m_warpfield.getKnn(), 8);
-        bool ok = slots.size() <= 8 && slots[0] >= 1 && sum <= k && epsilon > 0.f && beta >= 2;
-        for (int v : slots) ok = ok && v >= 0;
-        if (!ok)
-            throw dfa::Error(DFA_ERR_INVALID, "NorthStarSolver::setRegHierarchy: at most 8 levels, slots[0] >= 1, no negative slot, "
-                                              "a slot sum of at most the field's k, epsilon > 0, beta >= 2");
-    }
+    // the plan's own checks, on no plan: a configuration it refuses is refused here, before a frame is under way
+    if (slots.size() > 1 && !regHierarchyAccepted(slots, epsilon, beta, northStarKnn(m_warpfield.getKnn())))
+        throw dfa::Error(DFA_ERR_INVALID, "NorthStarSolver::setRegHierarchy: at most 8 levels, slots[0] >= 1, no negative slot, "
+                                          "a slot sum of at most the field's k, epsilon > 0, beta >= 2");
     reg_slots_ = std::move(slots), reg_epsilon_ = epsilon, reg_beta_ = beta;
+}
+
+bool NorthStarSolver::regHierarchyAccepted(const std::vector<int>& slots, float epsilon, int beta, int k) {
+    long sum = 0;
+    bool ok  = !slots.empty() && slots.size() <= 8 && slots[0] >= 1 && epsilon > 0.f && beta >= 2;
+    for (int v : slots) ok = ok && v >= 0, sum += v;
+    return ok && sum <= k;
 }
 
 std::vector<int> NorthStarSolver::nodeLevels() const {
@@ -208,18 +208,40 @@ void NorthStarSolver::solveAll(const kfusion::cuda::Cloud& vmap, const kfusion::
     }
 }
 
-bool NorthStarSolver::alignRigid(const kfusion::cuda::Cloud& vmap, const kfusion::cuda::Normals& nmap, const kfusion::Intr& intr,
-                                 int iters, dfa::Affine3f& T) {
+bool NorthStarSolver::beginAlignRigid(const kfusion::cuda::Cloud& vmap, const kfusion::cuda::Normals& nmap, const RigidSchedule* schedule,
+                                      int iters, dfa::Affine3f& T, dfa::DeviceArray<float>& wv, dfa::DeviceArray<float>& wn) {
     Impl& I = *impl;
     T = dfa::Affine3f();
     rigid_matched_first_ = rigid_matched_last_ = 0;
-    rigid_iters_run_.clear();
+    rigid_iters_run_.assign(schedule ? schedule->steps.size() : 0, 0);
     if (!I.plan) throw dfa::Error(DFA_ERR_INVALID, "alignRigid before initializeProblemInstance");
     if (vmap.rows() != nmap.rows() || vmap.cols() != nmap.cols() || vmap.empty())
         throw dfa::Error(DFA_ERR_INVALID, "NorthStarSolver: vertex / normal maps differ in size or are empty");
-    if (iters <= 0) return true;
-    dfa::DeviceArray<float> wv(3 * (size_t)I.N), wn(3 * (size_t)I.N);
+    if (schedule) {
+        if (schedule->steps.size() != schedule->iters.size())
+            throw dfa::Error(DFA_ERR_INVALID, "NorthStarSolver::alignRigid: one step and one iteration count per level");
+        iters = 0;
+        for (int n : schedule->iters) iters += n > 0 ? n : 0;
+    }
+    if (iters <= 0) return false;
+    wv = dfa::DeviceArray<float>(3 * (size_t)I.N), wn = dfa::DeviceArray<float>(3 * (size_t)I.N);
     if (I.N) dfa::check(dfa_solver6_warp_with(I.plan, I.node_dq.ptr(), wv.ptr(), wn.ptr(), nullptr), "NorthStarSolver::alignRigid (warp)");
+    return true;
+}
+
+void NorthStarSolver::commitAlignRigid(const dfa::Affine3f& T) {
+    Impl& I = *impl;
+    Warpfield::composeRigid(T, I.host_dq.data(), (size_t)I.D);
+    I.node_dq.upload(I.host_dq);
+    dfa::check(dfa_solver6_set_node_transforms(I.plan, I.node_dq.ptr()), "NorthStarSolver::alignRigid (set_node_transforms)");
+    m_warpfield.composeRigid(T);
+}
+
+bool NorthStarSolver::alignRigid(const kfusion::cuda::Cloud& vmap, const kfusion::cuda::Normals& nmap, const kfusion::Intr& intr,
+                                 int iters, dfa::Affine3f& T) {
+    Impl& I = *impl;
+    dfa::DeviceArray<float> wv, wn;
+    if (!beginAlignRigid(vmap, nmap, nullptr, iters, T, wv, wn)) return true;
     dfa::DeviceArray<float> out(28);  // the 27 sums, then the matched count: one read-back per iteration
     float h[28];
     for (int it = 0; it < iters; ++it) {
@@ -240,29 +262,15 @@ bool NorthStarSolver::alignRigid(const kfusion::cuda::Cloud& vmap, const kfusion
             return false;
         }
     }
-    Warpfield::composeRigid(T, I.host_dq.data(), (size_t)I.D);
-    I.node_dq.upload(I.host_dq);
-    dfa::check(dfa_solver6_set_node_transforms(I.plan, I.node_dq.ptr()), "NorthStarSolver::alignRigid (set_node_transforms)");
-    m_warpfield.composeRigid(T);
+    commitAlignRigid(T);
     return true;
 }
 
 bool NorthStarSolver::alignRigid(const kfusion::cuda::Cloud& vmap, const kfusion::cuda::Normals& nmap, const kfusion::Intr& intr,
                                  const RigidSchedule& schedule, dfa::Affine3f& T) {
     Impl& I = *impl;
-    T = dfa::Affine3f();
-    rigid_matched_first_ = rigid_matched_last_ = 0;
-    rigid_iters_run_.assign(schedule.steps.size(), 0);
-    if (!I.plan) throw dfa::Error(DFA_ERR_INVALID, "alignRigid before initializeProblemInstance");
-    if (vmap.rows() != nmap.rows() || vmap.cols() != nmap.cols() || vmap.empty())
-        throw dfa::Error(DFA_ERR_INVALID, "NorthStarSolver: vertex / normal maps differ in size or are empty");
-    if (schedule.steps.size() != schedule.iters.size())
-        throw dfa::Error(DFA_ERR_INVALID, "NorthStarSolver::alignRigid: one step and one iteration count per level");
-    int total = 0;
-    for (int n : schedule.iters) total += n > 0 ? n : 0;
-    if (total == 0) return true;  // as iters <= 0 of the host loop: nothing is enqueued
-    dfa::DeviceArray<float> wv(3 * (size_t)I.N), wn(3 * (size_t)I.N);
-    if (I.N) dfa::check(dfa_solver6_warp_with(I.plan, I.node_dq.ptr(), wv.ptr(), wn.ptr(), nullptr), "NorthStarSolver::alignRigid (warp)");
+    dfa::DeviceArray<float> wv, wn;
+    if (!beginAlignRigid(vmap, nmap, &schedule, 0, T, wv, wn)) return true;  // as iters <= 0 of the host loop
     static_assert(sizeof(dfa_rigid_align_report) % sizeof(float) == 0, "the report travels as words");
     dfa::DeviceArray<float> out(sizeof(dfa_rigid_align_report) / sizeof(float));
     float aff0[12];
@@ -280,10 +288,7 @@ bool NorthStarSolver::alignRigid(const kfusion::cuda::Cloud& vmap, const kfusion
     if (rep.status != 0) return false;
     for (int i = 0; i < 9; ++i) T.R[i] = rep.aff[i];
     for (int i = 0; i < 3; ++i) T.t[i] = rep.aff[9 + i];
-    Warpfield::composeRigid(T, I.host_dq.data(), (size_t)I.D);
-    I.node_dq.upload(I.host_dq);
-    dfa::check(dfa_solver6_set_node_transforms(I.plan, I.node_dq.ptr()), "NorthStarSolver::alignRigid (set_node_transforms)");
-    m_warpfield.composeRigid(T);
+    commitAlignRigid(T);
     return true;
 }
 

@@ -17,32 +17,13 @@
 #include <kfusion/cuda/mesh_render.hpp>
 
 #include "../../include/dynfu_amd.h"
+#include "dynfu_fixtures.hpp"
 #include "minitest.hpp"
 
 using namespace kfusion;
+using namespace dynfu_fixtures::sphere_scene;
 
 namespace {
-const int W = 160, H = 120;
-const float F = 131.25f;
-
-// a sphere of radius 0.5 m at `cz` metres and nothing behind it (test_host_dynfusion.cpp's north-star frames): a third of the
-// view is surface, the rest has no depth — the wall of test_host_render.cpp would fill the model's view from this camera
-std::vector<unsigned short> sphere_depth(float cz) {
-    std::vector<unsigned short> d((size_t)W * H);
-    const float cx = W / 2 - 0.5f, cy = H / 2 - 0.5f, R = 0.5f;
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) {
-            float dir[3] = {(x - cx) / F, (y - cy) / F, 1.f};
-            const float n = std::sqrt(dir[0] * dir[0] + dir[1] * dir[1] + 1.f);
-            for (float& v : dir) v /= n;
-            const float b = dir[2] * cz, disc = b * b - (cz * cz - R * R);
-            float z = 0.f;
-            if (disc > 0) z = (b - std::sqrt(disc)) * dir[2];
-            d[(size_t)y * W + x] = (unsigned short)std::lround(z * 1000.f);
-        }
-    return d;
-}
-
 DynFuParams small_params(bool model_view, bool north_star) {
     DynFuParams p = DynFuParams::defaultParams();
     p.kinfuParams.cols = W, p.kinfuParams.rows = H;

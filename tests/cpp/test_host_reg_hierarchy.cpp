@@ -14,31 +14,15 @@
 #include <kfusion/cuda/tsdf_volume.hpp>
 
 #include "../../include/dynfu_amd.h"
+#include "dynfu_fixtures.hpp"
 #include "minitest.hpp"
 
 using namespace kfusion;
+using namespace dynfu_fixtures;
+using namespace dynfu_fixtures::sphere_scene;
 
 namespace {
-const int W = 160, H = 120, DIM = 64;
-const float F = 131.25f;
-
-// a sphere of radius 0.5 m at `cz` metres and nothing behind it (test_host_regrow.cpp); left_only: no depth right of the centre
-std::vector<unsigned short> sphere_depth(float cz, bool left_only) {
-    std::vector<unsigned short> d((size_t)W * H);
-    const float cx = W / 2 - 0.5f, cy = H / 2 - 0.5f, R = 0.5f;
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) {
-            float dir[3] = {(x - cx) / F, (y - cy) / F, 1.f};
-            const float n = std::sqrt(dir[0] * dir[0] + dir[1] * dir[1] + 1.f);
-            for (float& v : dir) v /= n;
-            const float b = dir[2] * cz, disc = b * b - (cz * cz - R * R);
-            float z = 0.f;
-            if (disc > 0) z = (b - std::sqrt(disc)) * dir[2];
-            if (left_only && x >= W / 2) z = 0.f;
-            d[(size_t)y * W + x] = (unsigned short)std::lround(z * 1000.f);
-        }
-    return d;
-}
+const int DIM = 64;
 
 DynFuParams params(bool hierarchy) {
     DynFuParams p = DynFuParams::defaultParams();
@@ -59,15 +43,6 @@ struct Depths {
     }
 };
 
-bool construction_throws(const DynFuParams& p) {
-    try {
-        DynFusion df(p);
-    } catch (const dfa::Error& e) {
-        return e.code == DFA_ERR_INVALID;
-    }
-    return false;
-}
-
 // what a frame leaves: the warped cloud, the node arrays, the canonical volume, the energies
 struct Outputs {
     std::vector<float> warped, pos, w, dq;
@@ -86,10 +61,7 @@ Outputs outputs(DynFusion& df) {
     o.cost0 = df.northStarInitialCost(), o.cost1 = df.northStarFinalCost(), o.valid = df.northStarValidRows();
     return o;
 }
-template <class T>
-bool same(const std::vector<T>& a, const std::vector<T>& b) {
-    return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
-}
+using dynfu_fixtures::same;  // (the overload below would hide it)
 bool same(const Outputs& a, const Outputs& b) {
     return same(a.warped, b.warped) && same(a.pos, b.pos) && same(a.w, b.w) && same(a.dq, b.dq) && same(a.volume, b.volume) &&
            std::memcmp(&a.cost0, &b.cost0, sizeof(double)) == 0 && std::memcmp(&a.cost1, &b.cost1, sizeof(double)) == 0 &&

@@ -16,44 +16,16 @@
 #include <kfusion/cuda/tsdf_volume.hpp>
 
 #include "../../include/dynfu_amd.h"
+#include "dynfu_fixtures.hpp"
 #include "minitest.hpp"
 
 using namespace kfusion;
+using namespace dynfu_fixtures;
+using namespace dynfu_fixtures::sphere_scene;
 
 namespace {
-const int W = 160, H = 120, DIM = 64;
-const float F = 131.25f;
+const int DIM = 64;
 const float VOXEL = 3.f / DIM;
-
-// a sphere of radius 0.5 m at `cz` metres and nothing behind it (test_host_tsdf_warped6.cpp); left_only: no depth right of the
-// image centre
-std::vector<unsigned short> sphere_depth(float cz, bool left_only) {
-    std::vector<unsigned short> d((size_t)W * H);
-    const float cx = W / 2 - 0.5f, cy = H / 2 - 0.5f, R = 0.5f;
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) {
-            float dir[3] = {(x - cx) / F, (y - cy) / F, 1.f};
-            const float n = std::sqrt(dir[0] * dir[0] + dir[1] * dir[1] + 1.f);
-            for (float& v : dir) v /= n;
-            const float b = dir[2] * cz, disc = b * b - (cz * cz - R * R);
-            float z = 0.f;
-            if (disc > 0) z = (b - std::sqrt(disc)) * dir[2];
-            if (left_only && x >= W / 2) z = 0.f;
-            d[(size_t)y * W + x] = (unsigned short)std::lround(z * 1000.f);
-        }
-    return d;
-}
-
-std::vector<uint32_t> voxels(const cuda::TsdfVolume& vol) {
-    std::vector<uint32_t> h((size_t)DIM * DIM * DIM);
-    vol.data().download(h.data(), h.size() * sizeof(uint32_t));
-    return h;
-}
-
-template <class T>
-bool same(const std::vector<T>& a, const std::vector<T>& b) {
-    return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
-}
 
 struct Switches {
     bool rigid = true, regrow = true, knn_field = false, view = false;
@@ -120,15 +92,6 @@ Cloud3 by_public_calls(const cuda::TsdfVolume& vol, int min_weight, const Affine
     dfa::check(dfa_transform_points(n3.ptr(), (int)n, aff, 0, n3.ptr(), nullptr), "transform");
     v3.download(c.v), n3.download(c.n);
     return c;
-}
-
-bool construction_throws(const DynFuParams& p) {
-    try {
-        DynFusion df(p);
-    } catch (const dfa::Error& e) {
-        return e.code == DFA_ERR_INVALID;
-    }
-    return false;
 }
 }  // namespace
 

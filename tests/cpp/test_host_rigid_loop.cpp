@@ -16,72 +16,16 @@
 #include <dynfu/dyn_fusion.hpp>
 
 #include "../../include/dynfu_amd.h"
+#include "dynfu_fixtures.hpp"
 #include "minitest.hpp"
 
 using namespace kfusion;
+using namespace dynfu_fixtures;
+using namespace dynfu_fixtures::planted_motion_scene;
 
 namespace {
 // -------------------------------------------------------------------------------------------------------- the sequence
-// test_host_icp.cpp's image.  The volume is the smallest cube that holds the scene: 2.2 m from z = 1 m — the spheres reach
-// from x = -0.85 to 0.7 and from z = 1.15, the wall crosses the cube between z = 2.01 and 3.19 — at 256 voxels a side.  The
-// voxel size matters to the first check below: the integration takes voxel i at i * voxel, marching cubes puts its vertices
-// at (i + 0.5) * voxel (both as the reference does), so the canonical model stands half a voxel, 4.3 mm, off the scene it
-// was fused from, along every axis.  The rigid estimate maps the MODEL into the live camera, offset included: 4.3 of the
-// 5 mm of the translation bar are that offset (measured: 4.1, 4.5, 4.3 mm; at 128 voxels a side and 3 m it is 11.7 mm).
-const int W = 320, H = 240, DIM = 256;
-const float F = 262.5f, VOLUME = 2.2f, VOLUME_Z0 = 1.0f;
-
-// test_host_icp.cpp's scene: depth of two spheres in front of a tilted wall seen from camera pose X_world = R X_cam + t
-std::vector<unsigned short> render(const float R[9], const float t[3]) {
-    std::vector<unsigned short> d((size_t)W * H, 0);
-    const float cx = W / 2 - 0.5f, cy = H / 2 - 0.5f;
-    const float C[2][3] = {{0.25f, -0.1f, 1.6f}, {-0.55f, 0.3f, 2.0f}}, rad[2] = {0.45f, 0.3f};
-    const float pn[3] = {0.3f, 0.2f, -0.933f}, pd = -2.6f * 0.933f;  // wall: pn . X = pd
-    for (int y = 3; y < H - 3; ++y)
-        for (int x = 3; x < W - 3; ++x) {
-            const float dc[3] = {(x - cx) / F, (y - cy) / F, 1.f};
-            float dw[3], best = 1e9f;
-            for (int i = 0; i < 3; ++i) dw[i] = R[3 * i] * dc[0] + R[3 * i + 1] * dc[1] + R[3 * i + 2] * dc[2];
-            for (int k = 0; k < 2; ++k) {
-                const float oc[3] = {t[0] - C[k][0], t[1] - C[k][1], t[2] - C[k][2]};
-                const float a = dw[0] * dw[0] + dw[1] * dw[1] + dw[2] * dw[2], b = 2 * (oc[0] * dw[0] + oc[1] * dw[1] + oc[2] * dw[2]),
-                            c = oc[0] * oc[0] + oc[1] * oc[1] + oc[2] * oc[2] - rad[k] * rad[k], disc = b * b - 4 * a * c;
-                if (disc > 0) {
-                    const float s = (-b - std::sqrt(disc)) / (2 * a);
-                    if (s > 0 && s < best) best = s;
-                }
-            }
-            const float den = pn[0] * dw[0] + pn[1] * dw[1] + pn[2] * dw[2];
-            if (std::fabs(den) > 1e-6f) {
-                const float s = (pd - (pn[0] * t[0] + pn[1] * t[1] + pn[2] * t[2])) / den;
-                if (s > 0 && s < best) best = s;
-            }
-            if (best < 1e8f && best < 60.f) d[(size_t)y * W + x] = (unsigned short)std::lround(best * 1000.f);
-        }
-    return d;
-}
-
-// the planted motion of test_host_icp.cpp: 1.2 degrees about y, (15, -8, 10) mm: X_before = M X_after
-Affine3f motion() {
-    const float a = 0.021f;
-    Affine3f m;
-    const float R[9] = {std::cos(a), 0, std::sin(a), 0, 1, 0, -std::sin(a), 0, std::cos(a)};
-    for (int i = 0; i < 9; ++i) m.R[i] = R[i];
-    m.t[0] = 0.015f, m.t[1] = -0.008f, m.t[2] = 0.010f;
-    return m;
-}
-
-struct Depths {
-    cuda::Depth d[4], empty;
-    Depths() {
-        Affine3f pose;  // frame f's camera: X_world = M^f X_cam
-        for (int f = 0; f < 4; ++f) {
-            d[f].upload(render(pose.R, pose.t), W);
-            pose = pose * motion();
-        }
-        empty.upload(std::vector<unsigned short>((size_t)W * H, 0), W);
-    }
-};
+// (the planted-motion scene of dynfu_fixtures.hpp: 320 x 240, 256^3 voxels over 2.2 m)
 
 struct Switches {
     bool prealign = false, device = false;
@@ -125,35 +69,6 @@ void pose_difference(const Affine3f& a, const Affine3f& b, double& angle, double
     const double x = 0.5 * (D[7] - D[5]), y = 0.5 * (D[2] - D[6]), z = 0.5 * (D[3] - D[1]);
     angle = std::asin(std::fmin(1.0, std::sqrt(x * x + y * y + z * z)));
     dist  = std::sqrt(std::pow((double)a.t[0] - b.t[0], 2) + std::pow((double)a.t[1] - b.t[1], 2) + std::pow((double)a.t[2] - b.t[2], 2));
-}
-
-template <class T>
-bool same(const std::vector<T>& a, const std::vector<T>& b) {
-    return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
-}
-std::vector<float> warped_vertices(DynFusion& df) {
-    std::vector<float> v;
-    dfa::DeviceArray<float> v3, n3;
-    df.getCanonicalWarpedToLive()->deviceArrays(v3, n3);
-    if (df.getCanonicalWarpedToLive()->size()) v3.download(v);
-    return v;
-}
-std::vector<float> node_transforms(DynFusion& df) {
-    std::vector<float> pos, w, dq;
-    df.getWarpfield()->hostArrays(pos, w, dq);
-    return dq;
-}
-bool is_identity(const Affine3f& a) {
-    const Affine3f i;
-    return std::memcmp(a.R, i.R, sizeof a.R) == 0 && std::memcmp(a.t, i.t, sizeof a.t) == 0;
-}
-bool construction_throws(const DynFuParams& p) {
-    try {
-        DynFusion df(p);
-    } catch (const dfa::Error& e) {
-        return e.code == DFA_ERR_INVALID;
-    }
-    return false;
 }
 }  // namespace
 

@@ -13,36 +13,15 @@
 #include <kfusion/cuda/tsdf_volume.hpp>
 
 #include "../../include/dynfu_amd.h"
+#include "dynfu_fixtures.hpp"
 #include "minitest.hpp"
 
 using namespace kfusion;
+using namespace dynfu_fixtures;
+using namespace dynfu_fixtures::sphere_scene;
 
 namespace {
-const int W = 160, H = 120, DIM = 64;
-const float F = 131.25f;
-
-// a sphere of radius 0.5 m at `cz` metres and nothing behind it (test_host_mesh_view.cpp)
-std::vector<unsigned short> sphere_depth(float cz) {
-    std::vector<unsigned short> d((size_t)W * H);
-    const float cx = W / 2 - 0.5f, cy = H / 2 - 0.5f, R = 0.5f;
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) {
-            float dir[3] = {(x - cx) / F, (y - cy) / F, 1.f};
-            const float n = std::sqrt(dir[0] * dir[0] + dir[1] * dir[1] + 1.f);
-            for (float& v : dir) v /= n;
-            const float b = dir[2] * cz, disc = b * b - (cz * cz - R * R);
-            float z = 0.f;
-            if (disc > 0) z = (b - std::sqrt(disc)) * dir[2];
-            d[(size_t)y * W + x] = (unsigned short)std::lround(z * 1000.f);
-        }
-    return d;
-}
-
-std::vector<uint32_t> voxels(const cuda::TsdfVolume& vol) {
-    std::vector<uint32_t> h((size_t)DIM * DIM * DIM);
-    vol.data().download(h.data(), h.size() * sizeof(uint32_t));
-    return h;
-}
+const int DIM = 64;
 
 // a volume of the KinFu set-up with the sphere at 1.5 m fused, the dists of the sphere at 1.48 m, and 9 x 9 nodes on a
 // plane through the sphere's front (volume frame), each with a small rigid transform
@@ -91,10 +70,6 @@ FrameOutputs outputs(DynFusion& df, bool flag) {
     df.getWarpfield()->hostArrays(o.pos, o.w, o.dq);
     o.live_volume = voxels(static_cast<const cuda::TsdfVolume&>(df.tsdf()));
     return o;
-}
-template <class T>
-bool same(const std::vector<T>& a, const std::vector<T>& b) {
-    return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
 }
 
 DynFuParams small_params(bool fuse_canonical) {

@@ -17,31 +17,14 @@
 #include <kfusion/cuda/mesh_render.hpp>
 
 #include "../../include/dynfu_amd.h"
+#include "dynfu_fixtures.hpp"
 #include "minitest.hpp"
 
 using namespace kfusion;
+using dynfu_fixtures::construction_throws;
+using namespace dynfu_fixtures::sphere_scene;
 
 namespace {
-const int W = 160, H = 120;
-const float F = 131.25f;
-
-// (test_host_mesh_view.cpp's sphere: radius 0.5 m at `cz` metres, nothing behind it)
-std::vector<unsigned short> sphere_depth(float cz) {
-    std::vector<unsigned short> d((size_t)W * H);
-    const float cx = W / 2 - 0.5f, cy = H / 2 - 0.5f, R = 0.5f;
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) {
-            float dir[3] = {(x - cx) / F, (y - cy) / F, 1.f};
-            const float n = std::sqrt(dir[0] * dir[0] + dir[1] * dir[1] + 1.f);
-            for (float& v : dir) v /= n;
-            const float b = dir[2] * cz, disc = b * b - (cz * cz - R * R);
-            float z = 0.f;
-            if (disc > 0) z = (b - std::sqrt(disc)) * dir[2];
-            d[(size_t)y * W + x] = (unsigned short)std::lround(z * 1000.f);
-        }
-    return d;
-}
-
 // The sphere frames run on a 128^3 volume, not test_host_mesh_view.cpp's 64^3.  At 64^3 (47 mm voxels, 16 nodes at frame 0)
 // frame 1's solve leaves the model 34 mm from the canonical one on average for a 10 mm step, Warpfield::update then adds 46
 // nodes with identity transforms at the rim, and the model frame 2 starts from folds over itself there: 71.3 % of the cloud
@@ -87,15 +70,6 @@ bool same(const FrameOutputs& a, const FrameOutputs& b) {
            a.valid == b.valid;
 }
 
-bool ctor_throws(const DynFuParams& p) {
-    try {
-        DynFusion df(p);
-    } catch (const dfa::Error&) {
-        return true;
-    }
-    return false;
-}
-
 // the rule of dfa_visible_vertices (include/dynfu_amd.h) on host copies: float32 operations in its order, std::fmaf and
 // std::nearbyintf (round to nearest even) where it has fmaf and rintf
 unsigned char visible_by_rule(const float* p, const std::vector<Point>& map, int cols, int rows, const Intr& intr, float z_tol) {
@@ -113,11 +87,11 @@ unsigned char visible_by_rule(const float* p, const std::vector<Point>& map, int
 }  // namespace
 
 TEST(VisibleTermTest, ConstructorNeedsNorthStarAndModelView) {
-    ASSERT_TRUE(ctor_throws(small_params(false, true, true)));   // without model_view
-    ASSERT_TRUE(ctor_throws(small_params(true, false, true)));   // without north_star
-    ASSERT_TRUE(ctor_throws(small_params(false, false, true)));
-    ASSERT_TRUE(!ctor_throws(small_params(true, true, true)));
-    ASSERT_TRUE(!ctor_throws(small_params(true, true, false)));
+    ASSERT_TRUE(construction_throws(small_params(false, true, true)));   // without model_view
+    ASSERT_TRUE(construction_throws(small_params(true, false, true)));   // without north_star
+    ASSERT_TRUE(construction_throws(small_params(false, false, true)));
+    ASSERT_TRUE(!construction_throws(small_params(true, true, true)));
+    ASSERT_TRUE(!construction_throws(small_params(true, true, false)));
     DynFusion df(small_params(true, true, true));
     ASSERT_EQ(df.northStarVisibleVertices(), -1ll);  // before a frame
 }
