@@ -15,7 +15,7 @@ SYMBOLS = [
     "dfa_correspond", "dfa_marching_cubes", "dfa_mc_default_tables",
     "dfa_tsdf_occupancy_bytes", "dfa_tsdf_clear_occ", "dfa_tsdf_integrate_occ", "dfa_tsdf_clear_integrate_occ", "dfa_tsdf_clear_integrate_known_occ", "dfa_tsdf_integrate_warped", "dfa_tsdf_integrate_warped6", "dfa_marching_cubes_occ", "dfa_marching_cubes_indexed", "dfa_marching_cubes_indexed_min_weight",
     "dfa_knn_field_create", "dfa_knn_field_destroy", "dfa_knn_field_build", "dfa_knn_field_append", "dfa_knn_field_info", "dfa_knn_field_lookup",
-    "dfa_tsdf_integrate_warped_field", "dfa_tsdf_integrate_warped6_field",
+    "dfa_tsdf_integrate_warped_field", "dfa_tsdf_integrate_warped6_field", "dfa_tsdf_integrate_warped6_color", "dfa_color_sample",
     "dfa_depth_bilateral_filter", "dfa_depth_truncate", "dfa_depth_build_pyramid", "dfa_compute_normals_mask_depth",
     "dfa_resize_depth_normals", "dfa_resize_points_normals",
     "dfa_compute_points_normals", "dfa_solver6_create", "dfa_solver6_destroy", "dfa_solver6_set_problem",
@@ -174,6 +174,8 @@ def load(path=None):
     L.dfa_tsdf_integrate_warped6.argtypes = integ[:8] + [vp] + integ[8:11] + [vp] + integ[11:-1] + [vp, vp, vp, i, i, i, vp]
     L.dfa_tsdf_integrate_warped_field.argtypes = L.dfa_tsdf_integrate_warped.argtypes[:-1] + [vp, vp]
     L.dfa_tsdf_integrate_warped6_field.argtypes = L.dfa_tsdf_integrate_warped6.argtypes[:-1] + [vp, vp]
+    L.dfa_tsdf_integrate_warped6_color.argtypes = [vp, i, i, i, vp, i, vp, vp, i, i, i, vp, vp, f, i, i, vp, vp, f, f, f, f, vp, vp, vp, i, i, i, vp, vp]
+    L.dfa_color_sample.argtypes = [vp, i, i, i, vp, vp, i, i, vp, vp, vp]
     L.dfa_knn_field_create.argtypes = [i, i, i, vp, i, vp, C.c_size_t, C.POINTER(vp)]
     L.dfa_knn_field_destroy.argtypes = [vp]
     L.dfa_knn_field_destroy.restype = None
@@ -418,6 +420,48 @@ def tsdf_integrate_warped6(vol, dists, voxel_size, trunc, max_weight, vol2node, 
               _dev(node_pos, f32, "node_pos") if D else None,
               _dev(node_dq, f32, "node_dq") if D else None, _dev(node_w, f32, "node_w") if D else None,
               D, k, WARPED_MODES[unsupported], *extra, _stream()))
+
+
+def tsdf_integrate_warped6_color(vol, colors, image, dists, voxel_size, trunc, max_weight, max_color_weight, vol2node, node2cam,
+                                 fx, fy, cx, cy, node_pos, node_dq, node_w, k, unsupported="skip", occupancy=None, field=None):
+    """dfa_tsdf_integrate_warped6_color: tsdf_integrate_warped6 (with `field`: from a KnnField) that also fuses the frame's
+    colour image into the colour volume `colors` — a contiguous (Z, Y, X) 32-bit tensor, bytes b, g, r and an 8-bit weight per
+    voxel — in the same sweep.  image: (rows, cols, 4) uint8, b, g, r, x, registered to dists.  vol: the TSDF volume (it and
+    the occupancy map come out as from the plain call, bit for bit) or None: colours only, no TSDF word is touched."""
+    torch = _torch()
+    if unsupported not in WARPED_MODES:
+        raise DynfuAmdError("unsupported must be 'skip' or 'rigid', got %r" % (unsupported,))
+    X, Y, Z = _vol_dims(colors)
+    if vol is not None and _vol_dims(vol) != (X, Y, Z):
+        raise DynfuAmdError("the volume and the colour volume differ in shape")
+    rows, cols = dists.shape
+    if image.dim() != 3 or tuple(image.shape) != (rows, cols, 4) or image.stride(2) != 1 or image.stride(1) != 4:
+        raise DynfuAmdError("image must be a (rows, cols, 4) uint8 tensor of the dists image's size, pixels contiguous")
+    D = 0 if node_pos is None else int(node_pos.shape[0])
+    f32 = torch.float32
+    _check(load().dfa_tsdf_integrate_warped6_color(
+        _dev(dists, torch.uint16, "dists"), dists.stride(0) * 2, cols, rows, _dev(image, torch.uint8, "image"), image.stride(0),
+        _dev(vol), _dev(colors), X, Y, Z, _dev(occupancy, torch.uint8, "occupancy"), _farr(voxel_size, 3), trunc, max_weight,
+        max_color_weight, None if vol2node is None else _aff12(vol2node), None if node2cam is None else _aff12(node2cam),
+        fx, fy, cx, cy, _dev(node_pos, f32, "node_pos") if D else None, _dev(node_dq, f32, "node_dq") if D else None,
+        _dev(node_w, f32, "node_w") if D else None, D, k, WARPED_MODES[unsupported], None if field is None else field._handle(),
+        _stream()))
+
+
+def color_sample(colors, voxel_size, vertices, to_volume=None):
+    """dfa_color_sample: the colour volume `colors` ((Z, Y, X), 32-bit) at `vertices` ((N, 3) or (N, 4) float32, contiguous),
+    taken to the volume's frame by to_volume (12 floats, None: identity) -> (N, 4) uint8 b, g, r, a; a = 0 where the volume
+    holds (next to) no colour around the vertex."""
+    torch = _torch()
+    X, Y, Z = _vol_dims(colors)
+    if vertices.dim() != 2 or vertices.shape[1] not in (3, 4) or not vertices.is_contiguous():
+        raise DynfuAmdError("vertices must be a contiguous (N, 3) or (N, 4) tensor")
+    N = int(vertices.shape[0])
+    out = torch.empty((N, 4), dtype=torch.uint8, device=colors.device)
+    _check(load().dfa_color_sample(_dev(colors), X, Y, Z, _farr(voxel_size, 3), _dev(vertices, torch.float32, "vertices") if N else None,
+                                   int(vertices.shape[1]), N, None if to_volume is None else _aff12(to_volume),
+                                   _dev(out) if N else None, _stream()))
+    return out
 
 
 class KnnField:

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libdynfu_amd.so")
-SOURCES = ["tsdf.hip", "tsdf_warped.hip", "knn_field.hip", "warp.hip", "solve_graph.hip", "solve_linearise.hip", "solve_assemble.hip", "solve_pcg.hip",
+SOURCES = ["tsdf.hip", "tsdf_warped.hip", "tsdf_warped_color.hip", "color.hip", "knn_field.hip", "warp.hip", "solve_graph.hip", "solve_linearise.hip", "solve_assemble.hip", "solve_pcg.hip",
            "solve_pcg_launched.hip", "solve_pcg_team.hip", "solve6_graph.hip", "reg_hierarchy.hip", "solve6_pattern.hip", "solve6_linearise.hip",
            "solve6_assemble.hip", "solve6_pcg.hip", "solve6_update.hip", "mc.hip", "extract.hip", "img.hip", "render.hip", "raster.hip", "visibility.hip", "icp.hip", "points.hip",
            "capi.cpp", "capi_tsdf.cpp", "capi_field.cpp", "capi_image.cpp", "capi_warp.cpp", "capi_solver.cpp", "capi_solver6.cpp"]
@@ -146,7 +146,7 @@ def build_cpp_tests(force=False, verbose=False):
                         ("test_host_extract", ["host"]), ("test_host_render", ["host"]), ("test_host_mc_indexed", ["host"]), ("test_host_mesh_view", ["host"]), ("test_host_visible_term", ["host"]),
                         ("test_host_tsdf_warped", ["host"]), ("test_host_tsdf_warped6", ["host"]), ("test_host_regrow", ["host"]), ("test_host_rigid_align", ["host"]),
                         ("test_knn_field_size", []), ("test_host_knn_field", ["host"]), ("test_rigid_step", []), ("test_host_rigid_loop", ["host"]),
-                        ("test_host_reg_hierarchy", ["host"])):
+                        ("test_host_reg_hierarchy", ["host"]), ("test_host_color", ["host"])):
         src = os.path.join(tdir, name + ".cpp")
         exe = os.path.join(out, name)
         if not os.path.exists(src):  # a tests/ tree from before this program was added: the rest still builds

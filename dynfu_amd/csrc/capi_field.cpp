@@ -1,6 +1,7 @@
-// capi_field.cpp — C ABI (include/dynfu_amd.h), the k-NN field of a volume: dfa_knn_field_* and the two warped
-// integrations served from a field.  Argument checks, the field's memory and launcher calls only (capi_internal.hpp); the
-// field's kernels are in knn_field.hip, the sweeps in tsdf_warped.hip, the size arithmetic in warped_bricks.hpp.
+// capi_field.cpp — C ABI (include/dynfu_amd.h), the k-NN field of a volume: dfa_knn_field_*, the two warped integrations
+// served from a field and the coloured north-star integration (searching or from a field: its one entry point takes either).
+// Argument checks, the field's memory and launcher calls only (capi_internal.hpp); the field's kernels are in knn_field.hip,
+// the sweeps in tsdf_warped.hip and tsdf_warped_color.hip, the size arithmetic in warped_bricks.hpp.
 #include <algorithm>
 #include <cstring>
 
@@ -182,6 +183,45 @@ int dfa_tsdf_integrate_warped6_field(const uint16_t* dists, int dists_step, int 
     dfa_knn_field* f = const_cast<dfa_knn_field*>(field);
     HIP_TRY(dfa::launch_tsdf_integrate_warped6_field(dists, dists_step, cols, rows, volume, occupancy, trunc_dist, max_weight, node2cam,
                                                      fx, fy, cx, cy, node_pos, node_dq, node_w, rigid, f->view(), f->records,
+                                                     S(stream)));
+    return DFA_OK;
+}
+
+int dfa_tsdf_integrate_warped6_color(const uint16_t* dists, int dists_step, int cols, int rows, const uint8_t* image, int image_step,
+                                     uint32_t* volume, uint32_t* colors, int X, int Y, int Z, uint8_t* occupancy,
+                                     const float voxel_size[3], float trunc_dist, int max_weight, int max_color_weight,
+                                     const float vol2node[12], const float node2cam[12], float fx, float fy, float cx, float cy,
+                                     const float* node_pos, const float* node_dq, const float* node_w, int D, int k,
+                                     int unsupported_mode, const dfa_knn_field* field, dfa_stream_t stream) {
+    REQUIRE(colors, "null colour volume");
+    REQUIRE(image, "null colour image");
+    REQUIRE(max_color_weight >= 1 && max_color_weight <= 255, "max_color_weight outside 1..255 (the colour weight is 8 bits)");
+    // (volume may be null — colours only —: the colour volume stands in where the checks ask for the volume's geometry)
+    if (int rc = warped_args_ok(__func__, false, dists, dists_step, cols, rows, colors, X, Y, Z, voxel_size, nullptr, trunc_dist,
+                                max_weight, node_pos, node_dq, node_w, D, k, unsupported_mode))
+        return rc;
+    REQUIRE(cols <= 0x1fffffff && image_step >= cols * 4, "image row step smaller than a pixel row");
+    REQUIRE((((uintptr_t)image | (uintptr_t)image_step) & 3) == 0, "image rows must be 4-byte aligned");
+    const bool rigid = unsupported_mode == DFA_WARPED_RIGID;
+    const dfa::ColorArgs color{image, image_step, colors, max_color_weight};
+    if (field) {
+        if (int rc = field_matches(__func__, field, X, Y, Z, voxel_size, k, D, vol2node, false)) return rc;
+        if (D == 0 && !rigid) return DFA_OK;  // no node supports anything: every voxel is left alone
+        dfa_knn_field* f = const_cast<dfa_knn_field*>(field);
+        HIP_TRY(dfa::launch_tsdf_integrate_warped6_color_field(dists, dists_step, cols, rows, color, volume, occupancy, trunc_dist,
+                                                               max_weight, node2cam, fx, fy, cx, cy, node_pos, node_dq, node_w, rigid,
+                                                               f->view(), f->records, S(stream)));
+        return DFA_OK;
+    }
+    float node2vol[12], stretch, tmax;
+    REQUIRE(dfa::warped6_frame(vol2node, node2vol, &stretch, &tmax), "vol2node must be rigid");
+    if (D == 0 && !rigid) return DFA_OK;  // no node supports anything: every voxel is left alone
+    WarpedScratch* ws;
+    const dfa::KnnGridView* grid;
+    if (int rc = warped_scratch(X, Y, Z, node_pos, D, stream, &ws, &grid)) return rc;
+    HIP_TRY(dfa::launch_tsdf_integrate_warped6_color(dists, dists_step, cols, rows, color, volume, X, Y, Z, occupancy, voxel_size,
+                                                     trunc_dist, max_weight, vol2node, node2cam, node2vol, stretch, tmax, fx, fy, cx,
+                                                     cy, node_pos, node_dq, node_w, D, k, rigid, grid, ws->bricks.data, ws->wmax.data,
                                                      S(stream)));
     return DFA_OK;
 }

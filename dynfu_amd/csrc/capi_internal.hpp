@@ -11,6 +11,7 @@
 #include "../../include/dynfu_amd.h"
 #include "kernels.hpp"
 #include "device_memory.hpp"
+#include "warped_bricks.hpp"
 
 #pragma GCC visibility push(hidden)  // internal to the library: nothing here joins its exported symbols
 namespace dfa {
@@ -121,6 +122,25 @@ inline int warped_node_grid(const float* node_pos, int D, hipStream_t st, const 
         *grid = &gs.v;
     }
     return DFA_OK;
+}
+
+// scratch of dfa_tsdf_integrate_warped and dfa_tsdf_integrate_warped6: the brick flags of the support pre-pass and the largest node radius
+struct WarpedScratch {
+    DeviceBuffer<uint8_t> bricks;
+    DeviceBuffer<float> wmax;
+};
+
+// behind the argument checks of both warped integrations: the stream's WarpedScratch at the volume's size and, for 64 nodes
+// and more, the node grid.  Every voxel of a marked brick searches: the grid wherever it is exact and cheaper than a scan of
+// all the nodes (null: the scan)
+inline int warped_scratch(int X, int Y, int Z, const float* node_pos, int D, dfa_stream_t stream, WarpedScratch** scratch,
+                   const dfa::KnnGridView** grid) {
+    WarpedScratch& ws = stream_scratch<WarpedScratch>(S(stream));
+    // (the words this reservation failed under while the count had a name of its own)
+    HIP_TRY_AS(ws.bricks.reserve(dfa::knn_field_bricks(X, Y, Z)), "ws.bricks.reserve(dfa::warped_brick_count(X, Y, Z))");
+    HIP_TRY(ws.wmax.reserve(1));
+    *scratch = &ws;
+    return warped_node_grid(node_pos, D, S(stream), grid);
 }
 
 // behind the field list of a plan: the arena's first failure as the C ABI reports it

@@ -2,7 +2,6 @@
 // integrations, marching cubes and the point-cloud extraction, with the scratch each keeps per stream.  Argument checks
 // and launcher calls only (capi_internal.hpp); the kernels are in tsdf.hip, tsdf_warped.hip, mc.hip and extract.hip.
 #include "capi_internal.hpp"
-#include "warped_bricks.hpp"
 
 using namespace dfa::capi;
 using dfa::DeviceBuffer;
@@ -27,25 +26,6 @@ struct McIndexedScratch {
         return e != hipSuccess ? e : idx_off.reserve((size_t)nsegs + 1);
     }
 };
-// scratch of dfa_tsdf_integrate_warped and dfa_tsdf_integrate_warped6: the brick flags of the support pre-pass and the largest node radius
-struct WarpedScratch {
-    DeviceBuffer<uint8_t> bricks;
-    DeviceBuffer<float> wmax;
-};
-
-// behind the argument checks of both warped integrations: the stream's WarpedScratch at the volume's size and, for 64 nodes
-// and more, the node grid.  Every voxel of a marked brick searches: the grid wherever it is exact and cheaper than a scan of
-// all the nodes (null: the scan)
-int warped_scratch(int X, int Y, int Z, const float* node_pos, int D, dfa_stream_t stream, WarpedScratch** scratch,
-                   const dfa::KnnGridView** grid) {
-    WarpedScratch& ws = stream_scratch<WarpedScratch>(S(stream));
-    // (the words this reservation failed under while the count had a name of its own)
-    HIP_TRY_AS(ws.bricks.reserve(dfa::knn_field_bricks(X, Y, Z)), "ws.bricks.reserve(dfa::warped_brick_count(X, Y, Z))");
-    HIP_TRY(ws.wmax.reserve(1));
-    *scratch = &ws;
-    return warped_node_grid(node_pos, D, S(stream), grid);
-}
-
 }  // namespace
 
 extern "C" {
@@ -334,6 +314,17 @@ int dfa_tsdf_extract_normals(const uint32_t* volume, int X, int Y, int Z, const 
     REQUIRE((((uintptr_t)points | (uintptr_t)normals) & 15) == 0, "points / normals must be 16-byte aligned");
     HIP_TRY(dfa::launch_extract_normals(volume, X, Y, Z, voxel_size, vol2world, Rinv, gradient_delta_factor, points, n,
                                         normals, S(stream)));
+    return DFA_OK;
+}
+
+int dfa_color_sample(const uint32_t* colors, int X, int Y, int Z, const float voxel_size[3], const float* vertices, int stride,
+                     int N, const float to_volume[12], uint8_t* out, dfa_stream_t stream) {
+    REQUIRE(volume_args_ok(colors, X, Y, Z), "bad colour volume");
+    REQUIRE(voxel_size && voxel_size[0] > 0.f && voxel_size[1] > 0.f && voxel_size[2] > 0.f, "voxel size must be positive");
+    REQUIRE(stride == 3 || stride == 4, "stride must be 3 or 4 floats");
+    REQUIRE(N >= 0 && (N == 0 || (vertices && out)), "null vertices / out");
+    REQUIRE(((uintptr_t)out & 3) == 0, "out must be 4-byte aligned");
+    HIP_TRY(dfa::launch_color_sample(colors, X, Y, Z, voxel_size, vertices, stride, N, to_volume, out, S(stream)));
     return DFA_OK;
 }
 

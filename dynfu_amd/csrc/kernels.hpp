@@ -133,6 +133,35 @@ hipError_t launch_tsdf_integrate_warped6_field(const uint16_t* dists, int dists_
                                                const float* node_w, bool rigid, const KnnFieldView& f, size_t records,
                                                hipStream_t s);
 
+// tsdf_warped_color.hip — dfa_tsdf_integrate_warped6_color: the two north-star sweeps above (searching: grid, bricks, wmax
+// as launch_tsdf_integrate_warped6; or from the field) with the colour rule of warped_color_device.hpp behind the distance.
+// vol null: colours only — no TSDF word and no byte of occ is read or written.
+struct ColorArgs {
+    const uint8_t* image;  // b, g, r, x pixels, the dists image's cols x rows; rows 4-byte aligned
+    int image_step;
+    uint32_t* colors;      // X Y Z words, the volume's order
+    int max_color_weight;  // 1..255
+};
+// tsdf_warped.hip — the support pre-pass of the searching north-star sweeps: bricks cleared, then marked by the nodes
+hipError_t launch_warped6_mark_bricks(const float* node_pos, const float* node_w, int D, bool has_vol2node, const float node2vol[12],
+                                      float stretch, float tmax, int X, int Y, int Z, const float voxel_size[3], uint8_t* bricks,
+                                      float* wmax, hipStream_t s);
+hipError_t launch_tsdf_integrate_warped6_color(const uint16_t* dists, int dists_step, int cols, int rows, const ColorArgs& color,
+                                               uint32_t* vol, int X, int Y, int Z, uint8_t* occ, const float voxel_size[3],
+                                               float trunc_dist, int max_weight, const float* vol2node, const float* node2cam,
+                                               const float node2vol[12], float stretch, float tmax, float fx, float fy, float cx,
+                                               float cy, const float* node_pos, const float* node_dq, const float* node_w, int D,
+                                               int k, bool rigid, const KnnGridView* grid, uint8_t* bricks, float* wmax,
+                                               hipStream_t s);
+hipError_t launch_tsdf_integrate_warped6_color_field(const uint16_t* dists, int dists_step, int cols, int rows, const ColorArgs& color,
+                                                     uint32_t* vol, uint8_t* occ, float trunc_dist, int max_weight,
+                                                     const float* node2cam, float fx, float fy, float cx, float cy,
+                                                     const float* node_pos, const float* node_dq, const float* node_w, bool rigid,
+                                                     const KnnFieldView& f, size_t records, hipStream_t s);
+// color.hip — dfa_color_sample: per vertex, the colour volume's words blended over the 8 corners of its cell
+hipError_t launch_color_sample(const uint32_t* colors, int X, int Y, int Z, const float voxel_size[3], const float* vertices,
+                               int stride, int N, const float* to_volume, uint8_t* out, hipStream_t s);
+
 hipError_t launch_correspond_projective(const float* verts, const float* normals, int n, const float* vmap, int vmap_step,
                                         const float* nmap, int nmap_step, int cols, int rows, float fx, float fy, float cx,
                                         float cy, float dist_thres, float min_cosine, float* out_v, float* out_n,

@@ -82,17 +82,6 @@ __global__ __launch_bounds__(64) void mark_bricks6_kernel(const float* __restric
 // moves a supported voxel, and runs warped_sweep_brick.  K holds k: 4, 8 or 16 in reference mode, 4 or 8 (k = 1..8) for the
 // north-star field.
 
-// (uniform) the pre-pass's mark of this workgroup's brick: a brick no node marked holds no supported voxel
-__device__ __forceinline__ bool brick_marked(const uint8_t* __restrict__ bricks) {
-    return bricks[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] != 0;
-}
-
-// the transforms of the north-star sweep
-struct Warped6Frames {
-    Aff3 vol2node, node2cam;  // read only where the flag below is set
-    int has_vol2node, has_node2cam;
-};
-
 template <int K, bool GRID>
 __global__ __launch_bounds__(256) void integrate_warped_kernel(const IntegrateArgs a, const float* __restrict__ node_pos,
                                                                const float* __restrict__ node_dq,
@@ -145,34 +134,6 @@ __global__ __launch_bounds__(256) void integrate_warped6_field_kernel(const Inte
 }
 
 // ------------------------------------------------------------------------------------------ launchers
-namespace {
-
-// the argument block of a warped sweep; vol2cam null: the identity (the sweep's frames are elsewhere and it is not read)
-IntegrateArgs warped_args(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol, int X, int Y, int Z, uint8_t* occ,
-                          const float voxel_size[3], float trunc_dist, int max_weight, const float* vol2cam, float fx, float fy,
-                          float cx, float cy) {
-    IntegrateArgs a;
-    a.dists = dists, a.dists_step = dists_step, a.cols = cols, a.rows = rows;
-    a.vol = vol, a.X = X, a.Y = Y, a.Z = Z;
-    const OccDims od = occ_dims(X, Y, Z);
-    a.occ = occ, a.ox = od.ox, a.oy = od.oy, a.occ_known = 0;
-    a.vsx = voxel_size[0], a.vsy = voxel_size[1], a.vsz = voxel_size[2];
-    a.trunc      = trunc_dist;
-    a.trunc_inv  = 1.f / trunc_dist;  // tsdf_volume.cu:106
-    a.max_weight = max_weight;
-    a.vol2cam    = aff3_from(vol2cam);
-    a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy;
-    a.zchunk = WBZ;
-    return a;
-}
-
-// the grid of a cached sweep.  SKIP: one workgroup per stored brick.  RIGID: every brick.
-dim3 field_sweep_grid(const KnnFieldView& f, bool rigid, size_t records) {
-    return rigid ? brick_grid(f.X, f.Y, f.Z) : dim3((unsigned)records);
-}
-
-}  // namespace
-
 hipError_t launch_tsdf_integrate_warped(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol, int X, int Y,
                                         int Z, uint8_t* occ, const float voxel_size[3], float trunc_dist, int max_weight,
                                         const float vol2cam[12], float fx, float fy, float cx, float cy, const float* node_pos,
@@ -229,6 +190,20 @@ bool warped6_frame(const float* vol2node, float node2vol[12], float* stretch, fl
     return true;
 }
 
+// the support pre-pass of the searching north-star sweeps (here and in tsdf_warped_color.hip): the flags cleared, then marked
+hipError_t launch_warped6_mark_bricks(const float* node_pos, const float* node_w, int D, bool has_vol2node, const float node2vol[12],
+                                      float stretch, float tmax, int X, int Y, int Z, const float voxel_size[3], uint8_t* bricks,
+                                      float* wmax, hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(bricks, 0, knn_field_bricks(X, Y, Z), s);
+    if (e != hipSuccess) return e;
+    if (D > 0) {
+        node_wmax_kernel<<<1, 1024, 0, s>>>(node_w, D, wmax);
+        mark_bricks6_kernel<<<D, 64, 0, s>>>(node_pos, D, wmax, aff3_from(node2vol), has_vol2node ? 1 : 0, stretch, tmax, X, Y, Z,
+                                             voxel_size[0], voxel_size[1], voxel_size[2], bricks);
+    }
+    return hipSuccess;
+}
+
 hipError_t launch_tsdf_integrate_warped6(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol, int X, int Y,
                                          int Z, uint8_t* occ, const float voxel_size[3], float trunc_dist, int max_weight,
                                          const float* vol2node, const float* node2cam, const float node2vol[12], float stretch,
@@ -238,13 +213,9 @@ hipError_t launch_tsdf_integrate_warped6(const uint16_t* dists, int dists_step, 
     const IntegrateArgs a = warped_args(dists, dists_step, cols, rows, vol, X, Y, Z, occ, voxel_size, trunc_dist, max_weight, nullptr,
                                         fx, fy, cx, cy);  // (vol2cam is not read: the frames are in f)
     const Warped6Frames f{aff3_from(vol2node), aff3_from(node2cam), vol2node ? 1 : 0, node2cam ? 1 : 0};
-    hipError_t e = hipMemsetAsync(bricks, 0, knn_field_bricks(X, Y, Z), s);
+    const hipError_t e = launch_warped6_mark_bricks(node_pos, node_w, D, vol2node != nullptr, node2vol, stretch, tmax, X, Y, Z,
+                                                    voxel_size, bricks, wmax, s);
     if (e != hipSuccess) return e;
-    if (D > 0) {
-        node_wmax_kernel<<<1, 1024, 0, s>>>(node_w, D, wmax);
-        mark_bricks6_kernel<<<D, 64, 0, s>>>(node_pos, D, wmax, aff3_from(node2vol), vol2node ? 1 : 0, stretch, tmax, X, Y, Z, a.vsx,
-                                             a.vsy, a.vsz, bricks);
-    }
     const dim3 block(WBX, WBY), g3 = brick_grid(X, Y, Z);
     const KnnGridView gv = grid ? *grid : KnnGridView{};
     if (grid) KDISPATCH8(k, integrate_warped6_kernel<KK, true><<<g3, block, 0, s>>>(a, f, node_pos, node_dq, node_w, D, k, rigid ? 1 : 0, bricks, gv));

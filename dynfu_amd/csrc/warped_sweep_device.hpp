@@ -172,4 +172,42 @@ __device__ __forceinline__ void warped_sweep_brick(const IntegrateArgs& a, int r
     }
 }
 
+// ------------------------------------------------------------------------------------------ what the sweeps' units share
+// (tsdf_warped.hip and tsdf_warped_color.hip: the kernels' small parts and the launchers' argument block)
+
+// (uniform) the pre-pass's mark of this workgroup's brick: a brick no node marked holds no supported voxel
+__device__ __forceinline__ bool brick_marked(const uint8_t* __restrict__ bricks) {
+    return bricks[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] != 0;
+}
+
+// the transforms of the north-star sweep
+struct Warped6Frames {
+    Aff3 vol2node, node2cam;  // read only where the flag below is set
+    int has_vol2node, has_node2cam;
+};
+
+// the argument block of a warped sweep; vol2cam null: the identity (the sweep's frames are elsewhere and it is not read)
+inline IntegrateArgs warped_args(const uint16_t* dists, int dists_step, int cols, int rows, uint32_t* vol, int X, int Y, int Z,
+                                 uint8_t* occ, const float voxel_size[3], float trunc_dist, int max_weight, const float* vol2cam,
+                                 float fx, float fy, float cx, float cy) {
+    IntegrateArgs a;
+    a.dists = dists, a.dists_step = dists_step, a.cols = cols, a.rows = rows;
+    a.vol = vol, a.X = X, a.Y = Y, a.Z = Z;
+    const OccDims od = occ_dims(X, Y, Z);
+    a.occ = occ, a.ox = od.ox, a.oy = od.oy, a.occ_known = 0;
+    a.vsx = voxel_size[0], a.vsy = voxel_size[1], a.vsz = voxel_size[2];
+    a.trunc      = trunc_dist;
+    a.trunc_inv  = 1.f / trunc_dist;  // tsdf_volume.cu:106
+    a.max_weight = max_weight;
+    a.vol2cam    = aff3_from(vol2cam);
+    a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy;
+    a.zchunk = WBZ;
+    return a;
+}
+
+// the grid of a cached sweep.  SKIP: one workgroup per stored brick.  RIGID: every brick.
+inline dim3 field_sweep_grid(const KnnFieldView& f, bool rigid, size_t records) {
+    return rigid ? brick_grid(f.X, f.Y, f.Z) : dim3((unsigned)records);
+}
+
 }  // namespace dfa

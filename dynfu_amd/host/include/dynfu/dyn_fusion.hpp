@@ -70,6 +70,16 @@ struct DynFuParams {  // dyn_fusion.hpp:25-42
     // (TsdfVolume::integrateWarped6; the node frame is frame 0's camera).  Off, nothing of this runs; on or off every other
     // output of a frame is the same, bit for bit.
     bool north_star_fuse_canonical = false;
+    // Extension — the COLOURED canonical model (DESIGN.md §4.1 "Colour fusion"; needs north_star_fuse_canonical: otherwise
+    // validate() throws).  Frames come with a registered colour image: operator()(depth, color) — the depth-only overload
+    // throws dfa::Error while the switch is on.  Frame 0: the canonical volume gets a colour volume (TsdfVolume::createColors)
+    // and frame 0's colours by one colours-only call (no nodes, every voxel where it stands: frame 0's geometry stays the
+    // copied volume, bit for bit).  Every later frame: the warped integration is TsdfVolume::integrateWarped6Color instead of
+    // integrateWarped6 — the same voxels, and the frame's colours fused in the same sweep, colour weights capped at
+    // canonical_max_color_weight (1..255).  DynFusion::canonicalColors() samples the result at the canonical vertices.  Off,
+    // nothing of this runs; on, every other output of a frame is what north_star_fuse_canonical alone gives, bit for bit.
+    bool north_star_fuse_color     = false;
+    int canonical_max_color_weight = 255;
     // Extension — the canonical fusion without its per-voxel search.  With fuse_canonical or north_star_fuse_canonical (alone
     // it means nothing: the constructor throws dfa::Error) the canonical volume gets a k-NN field when it is created
     // (TsdfVolume::buildKnnField over frame 0's nodes), and before every warped integrate the field is brought up to date when
@@ -169,6 +179,9 @@ public:
     // does: false for the first frame, true afterwards.  The volume, its dimensions and the case tables come from
     // params().kinfuParams / the MarchingCubes passed to useMarchingCubes() (default: the library's tables).
     bool operator()(const kfusion::cuda::Depth& depth);
+    // the same frame with its colour image (b, g, r, x pixels, registered to the depth frame: the same size).  With
+    // north_star_fuse_color the image is fused into the canonical volume's colours; without it the image is not read.
+    bool operator()(const kfusion::cuda::Depth& depth, const kfusion::cuda::Image& color);
     void useMarchingCubes(std::shared_ptr<kfusion::cuda::MarchingCubes> mc) { mc_ = mc; }
     std::shared_ptr<dynfu::Frame> getLiveFrame() { return liveFrame; }
     // KinFu::getMesh (kinfu.cpp:262): the marching-cubes triangles of the last frame, KinFu::convertToMesh's layout
@@ -235,6 +248,12 @@ public:
     // re-extraction), and its size
     std::shared_ptr<dynfu::Frame> getCanonicalFrame() { return canonicalFrame; }
     size_t canonicalVertexCount() const { return canonicalFrame ? canonicalFrame->size() : 0; }
+    // north_star_fuse_color: one b, g, r, a per vertex of getCanonicalFrame() (a = 0: the colour volume holds nothing around
+    // the vertex), on the device — sampled after the frame's regrow when north_star_regrow_canonical is on, else when asked
+    // for.  With model_view, canonicalMeshColors() is the same for the vertices of getCanonicalMesh().  Both throw
+    // dfa::Error with the switch off or before frame 0.
+    dfa::DeviceArray<kfusion::RGB> canonicalColors();
+    dfa::DeviceArray<kfusion::RGB> canonicalMeshColors();
     // north_star_regrow_canonical: frames whose re-extraction was empty (the cloud before it was kept)
     int regrowSkippedFrames() const { return report_.regrow_skipped; }
 
@@ -289,6 +308,12 @@ private:
     std::shared_ptr<dynfu::Frame> extractSurface(int frame_id, bool with_normals);
     // operator() in north-star mode, and its stages in the order they run (dyn_fusion_northstar.cpp): each
     // reads its switch and returns at once when it is off
+    bool frame(const kfusion::cuda::Depth& depth);  // operator()'s body, either overload
+    const kfusion::cuda::Image* frame_color_ = nullptr;  // north_star_fuse_color: this frame's colour image, while the frame runs
+    void fuseFirstFrameColors();                         // ... frame 0: the canonical volume's colours, by one colours-only call
+    void sampleModelColors();                            // ... after a regrow: the new cloud's (and mesh's) colours
+    dfa::DeviceArray<kfusion::RGB> cloud_colors_, mesh_colors_;
+    bool model_colors_current_ = false;
     bool northStarFrame(const kfusion::cuda::Depth& depth);
     bool northStarFirstFrame();
     void buildNorthStarProblem(NorthStarSolver& solver, dfa::StageClock& clk);

@@ -34,6 +34,9 @@ class TsdfVolume {
     // writable data() handle, a swap, a copy of the object (either side may write afterwards) or a sweep run while another
     // handle is alive all make it unknown until the next clear / fused sweep by a sole owner.
     CudaData occ_;
+    // The colour volume (dynfu_amd.h: dfa_tsdf_integrate_warped6_color), when createColors() has made one: X*Y*Z words
+    // {b, g, r, 8-bit weight} in the voxels' order, zeroed.  Copies of the object share it, as they share the voxels.
+    CudaData colors_;
     mutable bool occ_known_ = false;  // (mutable: copying a volume makes the SOURCE's map unknown too)
     // The k-NN field of the volume (dynfu_amd.h: dfa_knn_field_*), when one has been built: the neighbour rows of the voxels,
     // which integrateWarped / integrateWarped6 read instead of searching while the field matches their call.  What it was
@@ -54,9 +57,9 @@ class TsdfVolume {
 public:
     // --- construction / storage -----------------------------------------------------------------------------
     explicit TsdfVolume(const Vec3i& dims) { cfg_.dims = dims, create(dims); }
-    TsdfVolume(const TsdfVolume& o) : cfg_(o.cfg_), blob_(o.blob_), occ_(o.occ_), field_(o.field_) { o.occ_known_ = false; }
+    TsdfVolume(const TsdfVolume& o) : cfg_(o.cfg_), blob_(o.blob_), occ_(o.occ_), colors_(o.colors_), field_(o.field_) { o.occ_known_ = false; }
     TsdfVolume& operator=(const TsdfVolume& o) {
-        if (this != &o) cfg_ = o.cfg_, blob_ = o.blob_, occ_ = o.occ_, field_ = o.field_, occ_known_ = false, o.occ_known_ = false;
+        if (this != &o) cfg_ = o.cfg_, blob_ = o.blob_, occ_ = o.occ_, colors_ = o.colors_, field_ = o.field_, occ_known_ = false, o.occ_known_ = false;
         return *this;
     }
     virtual ~TsdfVolume() {}
@@ -88,6 +91,24 @@ public:
     void integrateWarped6(const Dists& dists, const Affine3f& camera_pose, const Intr& intr, const Affine3f& node_frame_pose,
                           const float* node_pos, const float* node_dq, const float* node_w, int D, int k,
                           UnsupportedMode mode = UnsupportedMode::Skip);
+    // Colour (dfa_tsdf_integrate_warped6_color, dfa_color_sample).  createColors: a zeroed colour volume of the volume's
+    // dimensions, owned by the object (a second call zeroes it again); colors(): its words on the device, nullptr without one.
+    // integrateWarped6Color: integrateWarped6 — the same voxels and map, bit for bit, the k-NN field used exactly when
+    // integrateWarped6 would use it — that also fuses `image` (b, g, r, x pixels registered to dists) into the colour volume
+    // in the same sweep, weights capped at max_color_weight (1..255); update_tsdf = false: colours only, no voxel and no
+    // byte of the map is touched.  sampleColors: b, g, r, a per vertex (N vertices of `stride` floats, 3 or 4, on the
+    // device, in the frame whose pose in the world is frame_pose), a = 0 where the volume holds no colour around it.
+    // lattice_offset, in voxels per axis: how far the vertices stand off the lattice the sweeps integrate on.  The sweeps take
+    // voxel i at i * voxel, marching cubes puts the vertex of a lattice edge at (i + 0.5 + t) * voxel (both as the reference
+    // does), so the vertices of MarchingCubes::run / runIndexed take 0.5: the sample then lies ON the vertex's lattice edge,
+    // between the two voxels it was interpolated from — of which the one behind the surface always has a colour —, not half
+    // a voxel diagonal away among voxels that may be clamped or unseen.  0 for points that are where the surface is.
+    void createColors();
+    const unsigned int* colors() const { return colors_.empty() ? nullptr : colors_.ptr<unsigned int>(); }
+    void integrateWarped6Color(const Dists& dists, const Image& image, const Affine3f& camera_pose, const Intr& intr,
+                               const Affine3f& node_frame_pose, const float* node_pos, const float* node_dq, const float* node_w, int D,
+                               int k, UnsupportedMode mode = UnsupportedMode::Skip, bool update_tsdf = true, int max_color_weight = 255);
+    dfa::DeviceArray<RGB> sampleColors(const float* vertices, int N, int stride, const Affine3f& frame_pose, float lattice_offset = 0.f) const;
     // The k-NN field (dfa_knn_field_*): the neighbours of every voxel near a node searched once — buildKnnField — and brought
     // up to date when nodes have been appended — appendKnnField: the arrays hold the old nodes, unchanged, followed by the new
     // ones —, so that integrateWarped / integrateWarped6 with the same k, node count and (integrateWarped6: node_frame_pose

@@ -52,6 +52,10 @@ void DynFuParams::validate() const {
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: fuse_canonical is a reference-mode extension (north_star blends otherwise, in the camera frame: north_star_fuse_canonical)");
     if (north_star_fuse_canonical && !north_star)
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_fuse_canonical needs north_star (reference mode: fuse_canonical)");
+    if (north_star_fuse_color && !north_star_fuse_canonical)
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_fuse_color needs north_star_fuse_canonical (colour rides on that fusion's sweep)");
+    if (north_star_fuse_color && (canonical_max_color_weight < 1 || canonical_max_color_weight > 255))
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_fuse_color: canonical_max_color_weight outside 1..255");
     if (fuse_knn_field && !fuse_canonical && !north_star_fuse_canonical)
         throw dfa::Error(DFA_ERR_INVALID, "DynFusion: fuse_knn_field serves the canonical fusion (fuse_canonical or north_star_fuse_canonical)");
     if (north_star_visible_only && !(north_star && model_view))
@@ -264,6 +268,27 @@ void DynFusion::syncKnnField() {
 }
 
 bool DynFusion::operator()(const kfusion::cuda::Depth& depth) {
+    if (dynfuParams.north_star_fuse_color)
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion: north_star_fuse_color is on: a frame needs its colour image, operator()(depth, color)");
+    return frame(depth);
+}
+
+bool DynFusion::operator()(const kfusion::cuda::Depth& depth, const kfusion::cuda::Image& color) {
+    if (!dynfuParams.north_star_fuse_color) return frame(depth);  // (the image is not read)
+    if (color.rows() != depth.rows() || color.cols() != depth.cols())
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion: the colour image is not the depth frame's size (north_star_fuse_color takes registered frames)");
+    frame_color_ = &color;
+    try {
+        const bool tracked = frame(depth);
+        frame_color_ = nullptr;
+        return tracked;
+    } catch (...) {
+        frame_color_ = nullptr;
+        throw;
+    }
+}
+
+bool DynFusion::frame(const kfusion::cuda::Depth& depth) {
     const kfusion::KinFuParams& p = params_;                                                       // :51
     kfusion::cuda::Depth& depth_filtered_ = curr_.depth_pyr[0];
     kfusion::cuda::computeDists(depth, dists_, p.intr);                                            // :58

@@ -54,6 +54,8 @@ bool DynFusion::northStarFirstFrame() {
         initFromFrame(welded);
         if (dynfuParams.model_view) setCanonicalMesh(welded, mesh);
         createCanonicalVolume();
+        fuseFirstFrameColors();
+        sampleModelColors();
         return ++frame_counter_, false;
     }
     auto vol_frame = extractSurface(0, true);  // volume frame, normals from the TSDF gradient
@@ -66,6 +68,7 @@ bool DynFusion::northStarFirstFrame() {
     initFromFrame(dynfu::Frame::fromDevice(0, cv, cn, n));
     if (dynfuParams.model_view) keepCanonicalMesh(aff);
     if (dynfuParams.north_star_fuse_canonical) createCanonicalVolume();
+    fuseFirstFrameColors();
     return ++frame_counter_, false;
 }
 
@@ -140,9 +143,57 @@ void DynFusion::fuseThroughSolvedField(dfa::StageClock& clk) {
     const dfa::Affine3f camera;
     if (dynfuParams.fuse_knn_field) syncKnnField();
     const Warpfield::DeviceNodeView nodes = warpfield->deviceNodes();
+    if (dynfuParams.north_star_fuse_color) {  // the one fused call: the same voxels, and the frame's colours
+        canonical_volume_->integrateWarped6Color(dists_, *frame_color_, camera, params_.intr, camera, nodes.pos, nodes.dq, nodes.w, nodes.D,
+                                                 northStarKnn(warpfield->getKnn()), unsupportedMode(), true,
+                                                 dynfuParams.canonical_max_color_weight);
+        model_colors_current_ = false;
+        clk.mark("integrateWarped6Color");
+        return;
+    }
     canonical_volume_->integrateWarped6(dists_, camera, params_.intr, camera, nodes.pos, nodes.dq, nodes.w, nodes.D,
                                         northStarKnn(warpfield->getKnn()), unsupportedMode());
     clk.mark("integrateWarped6");
+}
+
+// north_star_fuse_color, frame 0 — the canonical volume is a copy of the live one: only its colours are missing.  One
+// colours-only call with no nodes, every voxel where it stands (Rigid): what integrate() saw of each voxel, its texel's colour
+void DynFusion::fuseFirstFrameColors() {
+    if (!dynfuParams.north_star_fuse_color) return;
+    const dfa::Affine3f camera;
+    canonical_volume_->createColors();
+    canonical_volume_->integrateWarped6Color(dists_, *frame_color_, camera, params_.intr, camera, nullptr, nullptr, nullptr, 0,
+                                             northStarKnn(warpfield->getKnn()), kfusion::cuda::TsdfVolume::UnsupportedMode::Rigid, false,
+                                             dynfuParams.canonical_max_color_weight);
+    model_colors_current_ = false;
+}
+
+// north_star_fuse_color — the colours of the canonical cloud (camera frame of frame 0: the origin) and, with model_view, of
+// the kept mesh's vertices, from the canonical volume's colours as they are now.  Both are marching-cubes vertices: half a voxel
+// off the lattice the colours were fused on (TsdfVolume::sampleColors: lattice_offset)
+void DynFusion::sampleModelColors() {
+    if (!dynfuParams.north_star_fuse_color) return;
+    const dfa::Affine3f camera;
+    const dynfu::Frame::DeviceView v = canonicalFrame->device();
+    cloud_colors_ = canonical_volume_->sampleColors(v.vertices, (int)canonicalFrame->size(), 3, camera, 0.5f);
+    mesh_colors_  = dfa::DeviceArray<kfusion::RGB>();
+    if (dynfuParams.model_view && canonical_mesh_.vertices.size() > 0)
+        mesh_colors_ = canonical_volume_->sampleColors((const float*)canonical_mesh_.vertices.ptr(), (int)canonical_mesh_.vertices.size(), 4, camera, 0.5f);
+    model_colors_current_ = true;
+}
+
+dfa::DeviceArray<kfusion::RGB> DynFusion::canonicalColors() {
+    if (!dynfuParams.north_star_fuse_color || !canonical_volume_)
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion::canonicalColors: north_star_fuse_color is off, or no frame has run");
+    if (!model_colors_current_) sampleModelColors();
+    return cloud_colors_;
+}
+
+dfa::DeviceArray<kfusion::RGB> DynFusion::canonicalMeshColors() {
+    if (!dynfuParams.north_star_fuse_color || !canonical_volume_ || !dynfuParams.model_view)
+        throw dfa::Error(DFA_ERR_INVALID, "DynFusion::canonicalMeshColors: north_star_fuse_color or model_view is off, or no frame has run");
+    if (!model_colors_current_) sampleModelColors();
+    return mesh_colors_;
 }
 
 // The field grows where the warped cloud has no support.  north_star_regrow_canonical — the canonical model grows first: the
@@ -164,6 +215,7 @@ void DynFusion::growModelAndField(dfa::StageClock& clk) {
     } else {
         ++report_.regrow_skipped;
     }
+    sampleModelColors();  // north_star_fuse_color: the colours of the model as it is now
     clk.mark("warp + regrow");
     const size_t nodes_before = warpfield->nodesRef().size();
     warpfield->update(canonicalFrame);

@@ -101,6 +101,49 @@ void TsdfVolume::integrateWarped6(const Dists& dists, const Affine3f& camera_pos
     dfa::device_synchronize();  // (as integrate())
 }
 
+// ---- colour
+void TsdfVolume::createColors() {
+    colors_.create((size_t)cfg_.dims[0] * cfg_.dims[1] * cfg_.dims[2] * sizeof(uint32_t));
+    if (hipMemset(colors_.ptr<void>(), 0, colors_.sizeBytes()) != hipSuccess)
+        throw dfa::Error(DFA_ERR_HIP, "TsdfVolume::createColors: hipMemset");
+}
+
+void TsdfVolume::integrateWarped6Color(const Dists& dists, const Image& image, const Affine3f& camera_pose, const Intr& intr,
+                                       const Affine3f& node_frame_pose, const float* node_pos, const float* node_dq,
+                                       const float* node_w, int D, int k, UnsupportedMode mode, bool update_tsdf, int max_color_weight) {
+    if (colors_.empty()) throw dfa::Error(DFA_ERR_INVALID, "TsdfVolume::integrateWarped6Color: the volume has no colours (createColors)");
+    if (image.rows() != dists.rows() || image.cols() != dists.cols())
+        throw dfa::Error(DFA_ERR_INVALID, "TsdfVolume::integrateWarped6Color: the colour image is not the depth frame's size");
+    float vol2node[12], node2cam[12];  // as integrateWarped6 forms them
+    (node_frame_pose.inv() * cfg_.pose).to12(vol2node);
+    (camera_pose.inv() * node_frame_pose).to12(node2cam);
+    const Vec3f vsz = getVoxelSize();
+    const int unsupported = mode == UnsupportedMode::Rigid ? DFA_WARPED_RIGID : DFA_WARPED_SKIP;
+    const dfa_knn_field* field = matchingField(k, D, vol2node);  // (null: the call searches)
+    dfa::check(dfa_tsdf_integrate_warped6_color(dists.ptr(), (int)dists.step(), dists.cols(), dists.rows(), (const uint8_t*)image.ptr(),
+                                                (int)image.step(), update_tsdf ? blob_.ptr<uint32_t>() : nullptr, colors_.ptr<uint32_t>(),
+                                                cfg_.dims[0], cfg_.dims[1], cfg_.dims[2],
+                                                update_tsdf && mapTrusted() ? occ_.ptr<uint8_t>() : nullptr, vsz.v, cfg_.trunc,
+                                                cfg_.max_weight, max_color_weight, vol2node, node2cam, intr.fx, intr.fy, intr.cx, intr.cy,
+                                                node_pos, node_dq, node_w, D, k, unsupported, field, nullptr),
+               field ? "TsdfVolume::integrateWarped6Color (k-NN field)" : "TsdfVolume::integrateWarped6Color");
+    dfa::device_synchronize();  // (as integrate())
+}
+
+dfa::DeviceArray<RGB> TsdfVolume::sampleColors(const float* vertices, int N, int stride, const Affine3f& frame_pose,
+                                               float lattice_offset) const {
+    if (colors_.empty()) throw dfa::Error(DFA_ERR_INVALID, "TsdfVolume::sampleColors: the volume has no colours (createColors)");
+    dfa::DeviceArray<RGB> out((size_t)N);
+    float to_volume[12];
+    (cfg_.pose.inv() * frame_pose).to12(to_volume);
+    const Vec3f vsz = getVoxelSize();
+    for (int a = 0; a < 3; ++a) to_volume[9 + a] -= lattice_offset * vsz[a];  // onto the lattice of the sweeps
+    dfa::check(dfa_color_sample(colors_.ptr<uint32_t>(), cfg_.dims[0], cfg_.dims[1], cfg_.dims[2], vsz.v, vertices, stride, N, to_volume,
+                                (uint8_t*)out.ptr(), nullptr),
+               "TsdfVolume::sampleColors");
+    return out;
+}
+
 // ---- the k-NN field
 bool TsdfVolume::buildKnnField(const float* node_pos, const float* node_w, int D, int k, const Affine3f* node_frame_pose, size_t max_bytes) {
     KnnFieldState f;

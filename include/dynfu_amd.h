@@ -577,6 +577,51 @@ int dfa_tsdf_integrate_warped6_field(const uint16_t* dists, int dists_step, int 
                                      const float* node_w, int D, int k /* 1..8 */, int unsupported_mode, const dfa_knn_field* field,
                                      dfa_stream_t stream);
 
+/* Colour fusion: a registered depth + colour frame fused through the north-star warp field in ONE sweep.
+ *
+ * A colour volume is X * Y * Z uint32 words in the TSDF volume's memory order, one per voxel: bytes 0, 1, 2 are b, g, r (the
+ * byte order of the images: pixels b, g, r, x), byte 3 is an 8-bit colour weight; an all-zero word is "no colour".
+ *
+ * Per voxel, steps 1-6 and the TSDF half are those of dfa_tsdf_integrate_warped6 — with a field (NULL: search) those of
+ * dfa_tsdf_integrate_warped6_field, its refusals included —, the same expressions on the same values: with `volume` given,
+ * the TSDF volume and the occupancy map after the call are bit for bit those of the plain call.  With volume == NULL (colours
+ * only) no TSDF word is read or written and the occupancy map is not touched.
+ *
+ * The colour rule applies to a voxel that the integrate updates (tsdf_volume.cu:65-80 passed) with a distance of this
+ * frame tsdf < 1.0f — inside the truncation band, not clamped:
+ *   - the pixel is the texel (px, py) the distance was fetched from (image: the dists image's cols x rows, registered);
+ *   - o the voxel's colour word, w = o >> 24; for each channel c with the pixel's byte `in`:
+ *       c' = (c * w + in + ((w + 1) >> 1)) / (w + 1)      integers, truncating division
+ *     w' = min(w + 1, max_color_weight);
+ *   - the word is stored only when it changed; no other voxel's colour word is written.
+ * A colour word is read only where the rule applies (a few percent of the updated voxels).
+ *
+ * DFA_ERR_INVALID, before any HIP call and with a text in dfa_last_error(): colors == NULL, image == NULL,
+ * max_color_weight outside 1..255; then the checks of the plain calls (the geometry checked on `colors` when volume is
+ * NULL); image_step < 4 * cols, or image / image_step not 4-byte aligned (a pixel is read as one word). */
+int dfa_tsdf_integrate_warped6_color(const uint16_t* dists, int dists_step, int cols, int rows,
+                                     const uint8_t* image, int image_step, /* b,g,r,x pixels, same cols x rows as dists */
+                                     uint32_t* volume /* may be NULL: colours only */, uint32_t* colors, int X, int Y, int Z,
+                                     uint8_t* occupancy, const float voxel_size[3], float trunc_dist, int max_weight,
+                                     int max_color_weight /* 1..255 */, const float vol2node[12] /* may be NULL: identity */,
+                                     const float node2cam[12] /* may be NULL: identity */, float fx, float fy, float cx, float cy,
+                                     const float* node_pos, const float* node_dq, const float* node_w, int D, int k /* 1..8 */,
+                                     int unsupported_mode, const dfa_knn_field* field /* may be NULL: search */, dfa_stream_t stream);
+
+/* The colour of N vertices, read from a colour volume.  One vertex p (vertices: N x stride floats, stride 3 or 4, device),
+ * float32 throughout:
+ *   q = R p + t with to_volume (12 floats: the vertices' frame -> the volume's metric frame; the fused dot of the rigid
+ *   integrate, then + t), q = p when to_volume is NULL;
+ *   g = q / voxel_size per axis — voxels sit at (x, y, z) * voxel_size, as in the sweeps —, i0 = floor(g), f = g - i0;
+ *   over the 8 corners i0 + (dx, dy, dz) of the cell: t = (wx * wy) * wz, each factor f (d = 1) or 1 - f (d = 0); a corner
+ *   COUNTS when it is inside the volume and the weight byte of its word is > 0; den = sum of t, s_c = sum of t * c per
+ *   channel (fmaf(t, c, s_c)), over the counting corners in the order dz, dy, dx (dx fastest);
+ *   den < 0.25, or a coordinate of g not finite: out = 0, 0, 0, 0; otherwise b, g, r = rintf(s_c / den) and a = 255.
+ * out: N x 4 bytes b, g, r, a, device, 4-byte aligned.  N == 0 succeeds (no launch). */
+int dfa_color_sample(const uint32_t* colors, int X, int Y, int Z, const float voxel_size[3], const float* vertices,
+                     int stride /* 3 or 4 */, int N, const float to_volume[12] /* may be NULL: identity */, uint8_t* out,
+                     dfa_stream_t stream);
+
 /* Point-cloud plumbing between the seams (no arithmetic, bit copies).  The reference moves clouds between its
  * stages as pcl::PointCloud objects on the host; with the clouds resident in HBM the same two steps are:
  *
