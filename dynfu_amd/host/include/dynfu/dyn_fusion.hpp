@@ -235,6 +235,17 @@ public:
     // north_star_visible_only: canonical vertices the last frame's solve could take data rows from (one small read from the
     // device); -1 before the first such frame, or with the switch off
     long long northStarVisibleVertices() const;
+    // ... and that frame's flags themselves, on the device: one byte per vertex of the canonical cloud that frame's solve
+    // ran over, non-zero = seen (empty before the first such frame, or with the switch off)
+    dfa::DeviceArray<unsigned char> northStarVisibleFlags() const { return visible_flags_; }
+    // north-star mode: the live vertex and normal maps the last solved frame's solve (and pre-alignment) read, camera frame
+    // (empty before the first such frame).  What a test needs to state the pre-alignment and the solve's initial cost from the
+    // frame's own inputs (tests/cpp/test_host_northstar_frames.cpp)
+    struct LiveMaps {
+        kfusion::cuda::Cloud points;
+        kfusion::cuda::Normals normals;
+    };
+    LiveMaps northStarLiveMaps() const { return LiveMaps{live_points_, live_normals_}; }
 
     void init(dfa::PointCloud<dfa::PointXYZ>& canonicalVertices, dfa::PointCloud<dfa::Normal>& canonicalNormals);
     void initCanonicalFrame(dfa::PointCloud<dfa::PointXYZ>& vertices, dfa::PointCloud<dfa::Normal>& normals);

@@ -30,14 +30,14 @@ def pose_at(i, motion=1.0):
     return R, motion * i * np.array([0.006, -0.003, 0.004])
 
 
-def render(W, H, fx, fy, R, t):
+def render(W, H, fx, fy, R, t, spheres=None, wall=True):
     """depth (uint16 mm) of two spheres in front of a tilted wall from camera pose X_world = R X_cam + t; a border of 3
-    pixels stays empty"""
+    pixels stays empty.  spheres: another list of (centre, radius) instead of SPHERES; wall=False: nothing behind them"""
     cx, cy = W // 2 - 0.5, H // 2 - 0.5
     u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
     dw = np.stack([(u - cx) / fx, (v - cy) / fy, np.ones_like(u)], -1) @ np.asarray(R, np.float64).T
     best = np.full((H, W), 1e9)
-    for c, rad in SPHERES:
+    for c, rad in (SPHERES if spheres is None else spheres):
         oc = np.asarray(t, np.float64) - np.array(c)
         a, b, cc = (dw * dw).sum(-1), 2 * (dw @ oc), oc @ oc - rad * rad
         disc = b * b - 4 * a * cc
@@ -47,7 +47,8 @@ def render(W, H, fx, fy, R, t):
     den = dw @ WALL_N
     with np.errstate(divide="ignore", invalid="ignore"):
         s = (WALL_D - WALL_N @ np.asarray(t, np.float64)) / den
-    best = np.where((np.abs(den) > 1e-6) & (s > 0) & (s < best), s, best)
+    if wall:
+        best = np.where((np.abs(den) > 1e-6) & (s > 0) & (s < best), s, best)
     d = np.where(best < 60.0, np.rint(best * 1000.0), 0).astype(np.uint16)
     out = np.zeros((H, W), np.uint16)
     out[3:H - 3, 3:W - 3] = d[3:H - 3, 3:W - 3]

@@ -225,7 +225,8 @@ class Statement6:
     Attributes: D, k, N; cols / row_ptr (block CSR in the device's layout: diagonal, then ascending), blocks (nb, 6, 6),
     bud (nb, 6, 6); g (D, 6), g_bud; cost, cost_bud; valid (vertices with an association and rho > 0), n_amb (ambiguous
     vertices), amb (N,) bool; pixel (N, 2) int (-1: none), assoc (N,) bool; counts: pairs (c_ab per block), T (records
-    per node), edges_in (regularisation edges arriving per node), H (scipy csr 6D x 6D)."""
+    per node), edges_in (regularisation edges arriving per node), H (scipy csr 6D x 6D); p (N, 3) the blended vertices and
+    dp (N,) the float32 error of p budgeted above, nw / dn the same for the normals (with canon_n), supported (N,) bool."""
 
     def __init__(self, node_pos, node_dq, node_w, canon, canon_n, vmap, nmap, intr, params, data_idx, reg_idx,
                  frozen=None, wn=None, pattern="graph"):
@@ -269,6 +270,7 @@ class Statement6:
         # float32 error of p, r (see the module docstring)
         pmag = np.linalg.norm(c, axis=1) + 2.0 * np.linalg.norm(bmag, axis=1) + np.linalg.norm(p, axis=1)
         dp = (40 + 2 * k) * U32 * pmag / np.minimum(1.0, ms)
+        self.p, self.dp, self.supported = p, dp, sup  # the blended vertices, their float32 error budget, who has a blend
 
         # ---- association
         H_, W_ = vmap.shape[:2]
@@ -298,6 +300,7 @@ class Statement6:
         if canon_n is not None:
             cn = np.asarray(canon_n, np.float64).reshape(N, 3)
             nw = qmul(qmul(a, pure(cn)), conj(a))[:, 1:] / ms[:, None]
+            self.nw, self.dn = nw, (24 + 2 * k) * U32 / np.minimum(1.0, ms)  # the blended normals, the budget of the cos gate
             cosv = (nw * Ln).sum(1)
             cth = float(P["cos_thresh"])
             gc = ok & (np.abs(cosv - cth) <= np.maximum(1e-5 * abs(cth), (24 + 2 * k) * U32 / np.minimum(1.0, ms)))

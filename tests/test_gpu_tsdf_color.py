@@ -19,6 +19,7 @@ import tsdf_color_statement as CST  # noqa: E402
 import tsdf_warped6_cases as C6  # noqa: E402
 import tsdf_warped6_statement as W6  # noqa: E402
 from gpu_util import dev, host  # noqa: E402
+from tsdf_color_check import check_colors  # noqa: E402  (checks 2 and 3)
 
 MODE = {W6.SKIP: "skip", W6.RIGID: "rigid"}
 NAMES = list(C6.CASES)
@@ -99,32 +100,6 @@ def _run(A, name, with_field):
     if f is not None:
         f.close()
     return out
-
-
-def check_colors(got, want, before, c):
-    """checks 2 and 3 of `got` against the statement's `want`, from the colour volume `before`"""
-    cref = c["cref"]
-    dec = cref["decided"]
-    col = cref["coloured"]
-    print("%s: %d voxels, %d coloured by the statement, %d undecided; decided words differing: %d" %
-          (c["name"], got.size, int(col.sum()), int((~dec).sum()), int((got != want)[dec].sum())))
-    assert np.array_equal(got[dec], want[dec]), "colour words of decided voxels"
-    assert np.array_equal(got[dec & ~col], before[dec & ~col]), "decided voxels the statement leaves alone"
-    und = np.flatnonzero(~dec.ravel())
-    pix = CST.pixels(c["image"])
-    rows, cols = pix.shape
-    g, b = got.ravel()[und], before.ravel()[und]
-    qx, qy = cref["qx"].ravel()[und], cref["qy"].ravel()[und]
-    ok = g == b
-    for dy in (-1, 0, 1):
-        for dx in (-1, 0, 1):
-            x, y = qx + dx, qy + dy
-            inside = (x >= 0) & (x < cols) & (y >= 0) & (y < rows)
-            p = pix[np.where(inside, y, 0), np.where(inside, x, 0)]
-            ok |= inside & (CST.rule(b, p, c["max_color_weight"]) == g)
-    for i in np.flatnonzero(~ok & (qx == CST.FAR)):  # no projection in the statement: any texel of the image
-        ok[i] = bool((CST.rule(np.full(pix.size, b[i], np.uint32), pix.ravel(), c["max_color_weight"]) == g[i]).any())
-    assert ok.all(), "an undecided voxel holds neither its input nor an update from a texel next to the statement's"
 
 
 @pytest.mark.parametrize("with_field", FIELD)

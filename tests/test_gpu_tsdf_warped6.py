@@ -13,8 +13,8 @@ pytestmark = pytest.mark.gpu
 import tsdf_warped6_cases as C6  # noqa: E402
 import tsdf_warped6_statement as W6  # noqa: E402
 import tsdf_warped_statement as WST  # noqa: E402
-from extract_statement import unpack  # noqa: E402
 from gpu_util import dev, host  # noqa: E402
+from tsdf_warped6_check import check  # noqa: E402  (the bar of the module docstring)
 
 MODE = {W6.SKIP: "skip", W6.RIGID: "rigid"}
 
@@ -33,43 +33,6 @@ def run(A, c, occupancy=None):
     A.tsdf_integrate_warped6(vol, dev(c["dists"]), c["voxel_size"], float(c["trunc"]), C6.MAX_WEIGHT, c["vol2node"], c["node2cam"],
                              *c["intr"], nodes, dq, w, c["k"], unsupported=MODE[c["mode"]], occupancy=occupancy)
     return host(vol, np.uint32)
-
-
-def valid_update(before, after, tol):
-    """`after` is some update of `before` by the rule of tsdf_volume.cu:82-90: the weight one up (capped) and the distance the
-    running average of the old one with a value in [-1, 1]"""
-    F0, W0 = unpack(before)
-    F1, W1 = unpack(after)
-    Wf = W0.astype(np.float64)
-    lo, hi = (F0 * Wf - 1) / (Wf + 1), (F0 * Wf + 1) / (Wf + 1)
-    return (W1 == np.minimum(W0 + 1, C6.MAX_WEIGHT)) & (F1 >= lo - tol) & (F1 <= hi + tol)
-
-
-def check(got, c, want=None):
-    """`got` against the statement's volume (or `want`) under the bar above"""
-    ref = c["ref"]
-    want = ref["vol"] if want is None else want
-    dec, upd, vol_in = ref["decided"], ref["updated"], c["vol"]
-    tol = WST.tsdf_tolerance(ref["rho"], c["trunc"])
-    Fg, Wg = unpack(got)
-    Fw, Ww = unpack(want)
-    m = dec & upd
-    print("%s: %d voxels, %d updated by the statement, %d undecided, rho %.3g, tolerance %.3g" %
-          (c["name"], got.size, int(upd.sum()), int((~dec).sum()), ref["rho"], tol))
-    if m.any():
-        print("  largest |tsdf - statement| on decided voxels: %.3g; weights differing: %d" %
-              (float(np.abs(Fg[m] - Fw[m]).max()), int((Wg[m] != Ww[m]).sum())))
-    print("  decided voxels the statement leaves alone that changed: %d" % int((got != vol_in)[dec & ~upd].sum()))
-    sup = dec & upd & ref["supported"]
-    sat = (vol_in >> 16) == C6.MAX_WEIGHT
-    print("  decided, supported, updated voxels that did not change (unsaturated): %d of %d" %
-          (int((got == vol_in)[sup & ~sat].sum()), int((sup & ~sat).sum())))
-    assert np.array_equal(Wg[m], Ww[m]), "weights of decided, updated voxels"
-    assert np.all(np.abs(Fg[m] - Fw[m]) <= tol), "distances of decided, updated voxels"
-    assert np.array_equal(got[dec & ~upd], vol_in[dec & ~upd]), "decided voxels the statement leaves alone"
-    und = ~dec
-    ok = (got[und] == vol_in[und]) | valid_update(vol_in[und], got[und], 2.0 ** -11)
-    assert ok.all(), "an undecided voxel holds neither its input nor a valid update"
 
 
 @pytest.mark.parametrize("name", list(C6.CASES))
