@@ -143,8 +143,9 @@ int dfa_solver_create(int max_D, int max_N, int k, dfa_solver** out) {
         mem.alloc(&s->state, 1);
         mem.alloc(&s->iters_total, 1, true);
         s->host_flag = mem.pinned<int>(4);  // (none: the solve does without the read-backs)
-        // (per linearise workgroup, at most 1024 of them: its share of the energy; behind those its largest matrix addend)
-        mem.alloc(&s->cost_partials, std::max<size_t>((R + 255) / 256 + 1, 1024) + 1024);
+        // (per linearise workgroup, at most 1024 of them: its share of the energy; behind those its largest matrix addend,
+        // as a double and once more as a float: solve_internal.hpp)
+        mem.alloc(&s->cost_partials, dfa::solve_cost_partials_len());
         mem.alloc(&s->ticket, 64, true);
         rc = plan_status(mem);
     }
@@ -286,11 +287,16 @@ int dfa_solver_solve(dfa_solver* s, const dfa_solve_params* p, dfa_stream_t stre
                 continue;
             }
             const bool with_huber = gn == 0 && outer == p->num_iter - 1;
-            HIP_TRY(dfa::solve_linearise(v, s->state, s->cost_partials, s->ticket, gn == 0, gn == 0 ? 0 : 1,
-                                         p->gn_tol, p->tukey_offset, p->psi_data, w_reg_sq, with_huber ? p->psi_reg : 0.f, nullptr, st));
+            // the re-weighting linearisation ends with its rows; the assembly launch forms amax and books the cost, so the
+            // assembly's timing bracket contains that booking and the state block is complete behind the assembly, which
+            // is where dfa_solver_get_stats reads it.  DFA_LIN_HANDOFF=0 (development builds): the linearisation's own tail.
+            const bool handoff = dfa::solve_lin_handoff(gn == 0, gn == 0 ? 0 : 1, p->gn_tol) && dfa::dev_env_int("DFA_LIN_HANDOFF", 1) != 0;
+            HIP_TRY(dfa::solve_linearise(v, s->state, s->cost_partials, s->ticket, gn == 0, gn == 0 ? 0 : 1, p->gn_tol,
+                                         p->tukey_offset, p->psi_data, w_reg_sq, with_huber ? p->psi_reg : 0.f, nullptr, handoff, st));
             huber_done |= with_huber;
             const int ev = bracket_open(s, st);
-            HIP_TRY(dfa::solve_assemble(v, s->state, gn == 0 && p->nonlinear_iter > 1, w_reg_sq, s->asm_resident, st));
+            HIP_TRY(dfa::solve_assemble(v, s->state, gn == 0 && p->nonlinear_iter > 1, w_reg_sq, s->asm_resident,
+                                        handoff ? s->cost_partials : nullptr, st));
             if (int rc = run_pcg(ev)) return rc;
         }
     }
@@ -300,7 +306,7 @@ int dfa_solver_solve(dfa_solver* s, const dfa_solve_params* p, dfa_stream_t stre
     const bool no_weights = p->num_iter == 0 || p->nonlinear_iter == 0;
     if (!huber_done) HIP_TRY(dfa::solve_huber(v, p->psi_reg, st));  // no outer iteration, or the host stopped launching before the last
     HIP_TRY(dfa::solve_linearise(v, s->state, s->cost_partials, s->ticket, no_weights ? 1 : 0, 2, 0.f,
-                                 p->tukey_offset, p->psi_data, w_reg_sq, 0.f, s->timing ? s->iters_total : nullptr, st));
+                                 p->tukey_offset, p->psi_data, w_reg_sq, 0.f, s->timing ? s->iters_total : nullptr, false, st));
     // (postSingleSolve -> copyResultToCPUFromFloat3, opt_solver.cpp:133,270-285: composed once, by that same launch)
     return DFA_OK;
 }

@@ -78,6 +78,9 @@ struct SolveState {
     float amax;     // largest addend tau w_a w_b of the normal matrix under the current robust weights (the re-weighting
                     // linearisation's last workgroup): the scale of the assembly's fixed-point sums
     long long prof[8];  // DFA_PCG_PROFILE builds: shader cycles per PCG phase (thread 0)
+    int lin_pending;  // a linearisation that ends with its rows has left partials in cost_partials that nobody has booked
+                      // yet: set by that launch when it really runs (not when it returns at entry), consumed by the
+                      // booking workgroup of the assembly launch behind it (appended: tests mirror the layout up to amax)
 };
 
 // All pointers are device pointers owned by the plan unless marked (borrowed).
@@ -170,19 +173,29 @@ hipError_t solve_build_graph_rows(const SolveView& s, const KnnGridView& grid, S
 hipError_t solve_transpose_graph(const int32_t* ridx, size_t total, int D, int32_t* blk_hist, int32_t* node_ptr,
                                  uint32_t* node_list, hipStream_t st);
 int solve_residual_blocks(const SolveView& s);
-// robust weights (optional) + residuals + cost + Gauss-Newton control, one launch
+size_t solve_cost_partials_len();  // doubles of the cost_partials array of solve_linearise / solve_assemble
+// robust weights (optional) + residuals + cost + Gauss-Newton control, one launch.
+// handoff: the launch ends with its rows' partial sums in cost_partials and leaves the cost, amax and the control to the
+// solve_assemble launch that MUST follow it with the same cost_partials (only for update_weights == 1, mode 0, gn_tol == 0:
+// solve_lin_handoff)
 hipError_t solve_linearise(const SolveView& s, SolveState* state, double* cost_partials, unsigned int* ticket,
                            int update_weights, int mode, float gn_tol, float tukey_offset, float psi_data,
                            float w_reg_sq, float huber_psi /* > 0: the nodes' Huber weights too */,
-                           long long* iters_total /* mode 2: += the solve's PCG iterations (optional, device) */, hipStream_t st);
+                           long long* iters_total /* mode 2: += the solve's PCG iterations (optional, device) */, bool handoff,
+                           hipStream_t st);
+// which linearisations hand their tail to the assembly: the re-weighting one of an outer iteration (mode 0) without a
+// cost-decrease tolerance, whose control decides nothing the assembly's workgroups read at entry
+inline bool solve_lin_handoff(int update_weights, int mode, float gn_tol) { return update_weights == 1 && mode == 0 && gn_tol == 0.f; }
 hipError_t solve_huber(const SolveView& s, float psi_reg, hipStream_t st);
 hipError_t solve_reset(const SolveView& s, SolveState* state, unsigned int* ticket, int nticket, hipStream_t st);
 // w_reg_sq: the weight of the regularisation rows — with 1 (the data rows) the bound of an addend's magnitude, which sets the
 // scale of the assembly's fixed-point sums
 // resident_blocks: solve_assemble_resident_blocks of the plan's k — a plan of at most that many nodes walks its lists in
 // flight (assemble_kernel, solve_assemble.hip)
+// handoff_partials: the cost_partials of a solve_linearise(..., handoff = true) in front of this launch (else nullptr) —
+// every workgroup forms amax from the per-workgroup maxima itself and one extra workgroup books the cost
 hipError_t solve_assemble(const SolveView& s, SolveState* state, int save_base /* g, t -> g_base, t_base */, float w_reg_sq,
-                          int resident_blocks, hipStream_t st);
+                          int resident_blocks, const double* handoff_partials, hipStream_t st);
 // workgroups of the in-flight assembly the device holds at once (CUs x the occupancy the runtime reports; 0: this k has the
 // plain loop only).  A runtime query: asked once per plan, not per launch.
 int solve_assemble_resident_blocks(int k);

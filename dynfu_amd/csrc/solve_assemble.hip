@@ -73,6 +73,55 @@ extern "C" __attribute__((visibility("default"))) int dfa_dev_asm_timing(unsigne
 }
 #endif
 
+// ------------------------------------------------------------------------------------------
+// Behind a linearisation that ends with its rows (the hand-off: solve_linearise.hip, header comment) the assembly launch
+// has the linearisation's nb per-workgroup partials (cost_partials != nullptr) in front of it instead of a finished
+// SolveState, and takes over two jobs.
+//
+// 1. Every workgroup forms amax itself: a thread's share of the nb <= LIN_MAX_BLOCKS maxima — four neighbouring floats,
+//    one 16-byte load, those past nb masked (the array is LIN_MAX_BLOCKS long whatever nb) — is asked for beside the
+//    node_ptr / node_list loads of its init, reduced by wave and handed through LDS across the barrier the init has
+//    anyway.  A maximum does not depend on the order, none is negative, and the floats are the doubles that the booking
+//    workgroup reduces: the bits of SolveState::amax.
+__device__ __forceinline__ float amax_partials_load(const double* cost_partials, int nb) {
+    static_assert(LIN_MAX_BLOCKS == 4 * 256, "one float4 per thread of a 256-thread workgroup");
+    const float4 m = reinterpret_cast<const float4*>(lin_max_floats(cost_partials))[threadIdx.x];
+    const int i    = 4 * (int)threadIdx.x;
+    return fmaxf(fmaxf(i < nb ? m.x : 0.f, i + 1 < nb ? m.y : 0.f), fmaxf(i + 2 < nb ? m.z : 0.f, i + 3 < nb ? m.w : 0.f));
+}
+// (the wave's maximum by the six DPP steps of wave_total, device_math.hpp: a lane without a source reads 0, which no
+// maximum of non-negative numbers minds)
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_max0(float v) {
+    return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false)));
+}
+__device__ __forceinline__ void amax_partials_publish(float am, float* amax_w /*[4], LDS: read behind the next barrier*/) {
+    am = dpp_max0<0x111, 0xf>(am), am = dpp_max0<0x112, 0xf>(am), am = dpp_max0<0x114, 0xf>(am), am = dpp_max0<0x118, 0xf>(am);
+    am = dpp_max0<0x142, 0xa>(am), am = dpp_max0<0x143, 0xc>(am);
+    // the wave's number and its maximum are scalars, and every lane stores the one word: a lane test here would be the
+    // kernel's `lane` and `wave` computed early and held in two vector registers across the whole list
+    const float wave_max = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(am), 63));
+    amax_w[__builtin_amdgcn_readfirstlane(threadIdx.x) >> 6] = wave_max;
+}
+// (the same number in every lane: handed to the scalar unit, so that the scale derived from it costs no vector registers)
+__device__ __forceinline__ float amax_partials_collect(const float* amax_w) {
+    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(fmaxf(fmaxf(amax_w[0], amax_w[1]), fmaxf(amax_w[2], amax_w[3])))));
+}
+// 2. One extra workgroup (index D) books the cost: what the linearisation's last workgroup does in the other form — the
+//    same clamped loads, masked adds in index order and 256-wide tree (lin_sum_partials), the same state update
+//    (lin_book_cost) — in front of the `done` / `converged` test of the entry, and only if the linearisation really ran
+//    (SolveState::lin_pending: one that returned at entry has left the partials of an earlier launch).  It writes `done`
+//    = 0 while the other workgroups read `done`: with gn_tol == 0, the only launches that hand off, nothing ever sets it.
+//    (sm, smx: 256 doubles each — the workgroup's hash values, which it has no other use for)
+__device__ __forceinline__ void assemble_book_cost(SolveState* st, const double* cost_partials, int nb, double* sm, double* smx) {
+    if (!st->lin_pending) return;
+    lin_sum_partials<false>(cost_partials, (unsigned int)nb, true, sm, smx);
+    if (threadIdx.x == 0) {
+        lin_book_cost(st, sm[0], smx[0], 1, 0, 0.f, false);
+        st->lin_pending = 0;
+    }
+}
+
 // One list entry of node a — slot `slot` of a row whose record is (idx, w, et = (e.x, e.y, e.z, tau)): its share of the gradient
 // and of the diagonal into the thread's registers, its off-diagonal pairs into the hash.
 template <int K>
@@ -149,12 +198,18 @@ __device__ __forceinline__ void assemble_entry(int a, int slot, const int (&idx)
 //           profile shows a fifth of the C2 grid starting only when the first workgroups leave, in either form, whatever
 //           the occupancy query says: not explained yet).
 template <int K, int T>
-__global__ __launch_bounds__(256) void assemble_kernel(SolveView s, SolveState* __restrict__ st, int save_base, float amax_unset) {
+__global__ __launch_bounds__(256) void assemble_kernel(SolveView s, SolveState* __restrict__ st, int save_base, float amax_unset,
+                                                       const double* __restrict__ cost_partials /* the hand-off, or nullptr */) {
     __shared__ int key[HASH];
     __shared__ long long val[2 * HASH];  // [0, HASH): sums of the non-negative addends, [HASH, 2 HASH): of the negative ones' magnitudes
     __shared__ float gpart[4][3];
+    __shared__ float amax_w[4];
     __shared__ int wave_cnt[4];
     __shared__ int ovf;
+    if ((int)blockIdx.x == s.D) {  // the booking workgroup (launched only with the hand-off)
+        assemble_book_cost(st, cost_partials, lin_blocks(s.N, s.D, s.k), reinterpret_cast<double*>(val), reinterpret_cast<double*>(val) + 256);
+        return;
+    }
     if (st->done || st->converged) return;
     // (workgroup -> node in launch order.  A contiguous node range per XCD — so that the rows a node shares with its
     // neighbours are fetched into one L2 instead of up to eight — left the launch at 345 us at C4: it was never bound by
@@ -166,15 +221,17 @@ __global__ __launch_bounds__(256) void assemble_kernel(SolveView s, SolveState* 
     const unsigned long long w0_ = wall_clock64();
 #endif
     const int beg = s.node_ptr[a], end = s.node_ptr[a + 1];
-    const float amax_st = st->amax;
     [[maybe_unused]] uint32_t ent[T];
     if constexpr (T > 1) {  // (an empty list reads entry 0 of the array, which every plan has, and uses nothing of it)
 #pragma unroll
         for (int t = 0; t < T; ++t) ent[t] = s.node_list[max(min(beg + 256 * t + (int)threadIdx.x, end - 1), 0)];
     }
+    float amax_st = cost_partials ? amax_partials_load(cost_partials, lin_blocks(s.N, s.D, s.k)) : st->amax;
     for (int i = threadIdx.x; i < HASH; i += 256) key[i] = -1, val[i] = val[i + HASH] = 0ll;
     if (threadIdx.x == 0) ovf = 0;
+    if (cost_partials) amax_partials_publish(amax_st, amax_w);
     __syncthreads();
+    if (cost_partials) amax_st = amax_partials_collect(amax_w);
 #ifdef DFA_PCG_PROFILE
     t1_ = clock64();
 #endif
@@ -315,19 +372,27 @@ __global__ __launch_bounds__(256) void assemble_kernel(SolveView s, SolveState* 
 // equal length by an atomic cursor (which thread owns which row decides the order of the inner products' partial
 // sums).  Here: lists sorted (sort_node_lists_kernel, solve_graph.hip), float sums per wave added in wave order, equal-length rows in index order.
 template <int K>
-__global__ __launch_bounds__(256) void assemble_det_kernel(SolveView s, SolveState* __restrict__ st, int save_base, float amax_unset) {
+__global__ __launch_bounds__(256) void assemble_det_kernel(SolveView s, SolveState* __restrict__ st, int save_base, float amax_unset,
+                                                           const double* __restrict__ cost_partials /* the hand-off, or nullptr */) {
     __shared__ int key[HASH];
     __shared__ long long val[2 * HASH];  // fixed-point sums (see FixedScale, fixed_add): integer adds commute, any order gives the same bits
-    __shared__ float gpart[4][3], dpart[4];
+    __shared__ float gpart[4][3], dpart[4], amax_w[4];
     __shared__ int ovf, nkeys;
+    if ((int)blockIdx.x == s.D) {  // the booking workgroup (launched only with the hand-off)
+        assemble_book_cost(st, cost_partials, lin_blocks(s.N, s.D, s.k), reinterpret_cast<double*>(val), reinterpret_cast<double*>(val) + 256);
+        return;
+    }
     if (st->done || st->converged) return;
     const int a    = blockIdx.x;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float amax_st  = cost_partials ? amax_partials_load(cost_partials, lin_blocks(s.N, s.D, s.k)) : st->amax;
     for (int i = threadIdx.x; i < HASH; i += 256) key[i] = -1, val[i] = val[i + HASH] = 0ll;
     if (threadIdx.x == 0) ovf = 0, nkeys = 0;
+    if (cost_partials) amax_partials_publish(amax_st, amax_w);
     __syncthreads();
+    if (cost_partials) amax_st = amax_partials_collect(amax_w);
     const int beg = s.node_ptr[a], end = s.node_ptr[a + 1];
-    const FixedScale fx = fixed_scale_for_rows(solve_fixed_scale(st->amax > 0.f ? st->amax : amax_unset), end - beg);
+    const FixedScale fx = fixed_scale_for_rows(solve_fixed_scale(amax_st > 0.f ? amax_st : amax_unset), end - beg);
     // pass 1: the set of columns (keys only), the gradient and the diagonal
     float gx = 0.f, gy = 0.f, gz = 0.f, dsum = 0.f;
     for (int p = beg + (int)threadIdx.x; p < end; p += 256) {
@@ -457,27 +522,31 @@ int solve_assemble_resident_blocks(int k) {
 }
 
 template <int K>
-static void launch_assemble(const SolveView& s, SolveState* state, int save_base, float amax_unset, bool in_flight, hipStream_t st) {
-    if (asm_chunk(K) > 1 && in_flight && s.k == K) assemble_kernel<K, asm_chunk(K)><<<s.D, 256, 0, st>>>(s, state, save_base, amax_unset);
-    else assemble_kernel<K, 1><<<s.D, 256, 0, st>>>(s, state, save_base, amax_unset);
+static void launch_assemble(const SolveView& s, SolveState* state, int save_base, float amax_unset, bool in_flight, const double* partials,
+                            int nb, hipStream_t st) {
+    const int grid = s.D + (nb > 0 ? 1 : 0);  // (the hand-off's booking workgroup: the last index)
+    if (asm_chunk(K) > 1 && in_flight && s.k == K) assemble_kernel<K, asm_chunk(K)><<<grid, 256, 0, st>>>(s, state, save_base, amax_unset, partials);
+    else assemble_kernel<K, 1><<<grid, 256, 0, st>>>(s, state, save_base, amax_unset, partials);
 }
 
-hipError_t solve_assemble(const SolveView& s, SolveState* state, int save_base, float w_reg_sq, int resident_blocks, hipStream_t st) {
+hipError_t solve_assemble(const SolveView& s, SolveState* state, int save_base, float w_reg_sq, int resident_blocks,
+                          const double* handoff_partials, hipStream_t st) {
     // The rows carry w_reg^2 as their tau; the scale of the fixed-point sums comes from SolveState::amax, which the
     // re-weighting linearisation in front of this launch has found.  Should no such linearisation have stored one (amax is
     // still the 0 of solve_reset — nothing in the driver does that today), the sums take the bound every addend obeys,
     // max(1, w_reg^2), instead of a grid for addends of 1e-30 that the first real one would overflow.
     const float amax_unset = std::max(1.0f, w_reg_sq);
-    if (s.deterministic) KDISPATCH(assemble_det_kernel, s.k, <<<s.D, 256, 0, st>>>(s, state, save_base, amax_unset));
+    const int nb           = handoff_partials ? solve_residual_blocks(s) : 0;  // the linearisation's workgroups
+    if (s.deterministic) KDISPATCH(assemble_det_kernel, s.k, <<<s.D + (nb > 0 ? 1 : 0), 256, 0, st>>>(s, state, save_base, amax_unset, handoff_partials));
     else {
         // the list in flight only where the whole grid is resident in one round; larger plans keep the plain loop, which
         // won there (assemble_kernel).  DFA_ASM_IN_FLIGHT=0 / 1 (development builds): one form for every plan (A/B, tests).
         bool in_flight  = s.D <= resident_blocks;
         const int force = dev_env_int("DFA_ASM_IN_FLIGHT", -1);
         if (force >= 0) in_flight = force != 0;
-        if (s.k <= 4) launch_assemble<4>(s, state, save_base, amax_unset, in_flight, st);
-        else if (s.k <= 8) launch_assemble<8>(s, state, save_base, amax_unset, in_flight, st);
-        else launch_assemble<16>(s, state, save_base, amax_unset, in_flight, st);
+        if (s.k <= 4) launch_assemble<4>(s, state, save_base, amax_unset, in_flight, handoff_partials, nb, st);
+        else if (s.k <= 8) launch_assemble<8>(s, state, save_base, amax_unset, in_flight, handoff_partials, nb, st);
+        else launch_assemble<16>(s, state, save_base, amax_unset, in_flight, handoff_partials, nb, st);
     }
     return hipGetLastError();
 }
