@@ -146,13 +146,13 @@ def build_cpp_tests(force=False, verbose=False):
                         ("test_host_extract", ["host"]), ("test_host_render", ["host"]), ("test_host_mc_indexed", ["host"]), ("test_host_mesh_view", ["host"]), ("test_host_visible_term", ["host"]),
                         ("test_host_tsdf_warped", ["host"]), ("test_host_tsdf_warped6", ["host"]), ("test_host_regrow", ["host"]), ("test_host_rigid_align", ["host"]),
                         ("test_knn_field_size", []), ("test_host_knn_field", ["host"]), ("test_rigid_step", []), ("test_host_rigid_loop", ["host"]),
-                        ("test_host_reg_hierarchy", ["host"]), ("test_host_color", ["host"])):
+                        ("test_host_reg_hierarchy", ["host"]), ("test_host_color", ["host"]), ("test_knn_walk", [])):
         src = os.path.join(tdir, name + ".cpp")
         exe = os.path.join(out, name)
         if not os.path.exists(src):  # a tests/ tree from before this program was added: the rest still builds
             continue
         deps = [src, os.path.join(tdir, "minitest.hpp"), host, os.path.join(CSRC, "tsdf_classify.hpp"), os.path.join(CSRC, "launch_budget.hpp"),
-                os.path.join(CSRC, "warped_bricks.hpp"), os.path.join(CSRC, "rigid_step.hpp")]
+                os.path.join(CSRC, "warped_bricks.hpp"), os.path.join(CSRC, "rigid_step.hpp"), os.path.join(CSRC, "knn_walk.hpp")]
         fixtures = os.path.join(tdir, "dynfu_fixtures.hpp")
         if os.path.exists(fixtures):  # (a tests/ tree from before the header was added has none, and needs none)
             deps.append(fixtures)

@@ -5,9 +5,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "dev_switch.hpp"
 #include "device_math.hpp"
 #include "dq_device.hpp"
 #include "kernels.hpp"
+#include "knn_walk.hpp"
 
 namespace dfa {
 
@@ -131,9 +133,23 @@ __device__ __forceinline__ void cell_of(const KnnGridDesc& g, f3 p, int& cx, int
 // TIGHT: the stop bound also counts the query's distance to the nearest wall of its own cell (the
 // visited block of cells extends r cells beyond that wall), which lets a 1-NN search stop inside
 // shell 0 / 1 of a fine grid.  Same result either way — the bound only decides when to stop.
-template <int K, bool TIGHT = false>
+// ONE_LOOP: the nine rows of the 3 x 3 x 3 block in one candidate loop per lane (knn_walk.hpp) instead of nine wave-wide
+// loops.  `count` is the length of the sorted array, `walk` the lane's own column of KNN_WALK_ROWS slots in LDS, KNN_WALK_STRIDE
+// entries apart (the kernel declares KnnWalkSlots<true> and passes slots.of_lane()).  The same candidates, hence — the list
+// keeps the K smallest of unique keys, in whatever order they are pushed — the same list.
+constexpr int KNN_WALK_STRIDE = 256;  // threads of a workgroup of every kernel that walks
+inline bool knn_one_loop() { return dev_env_int("DFA_KNN_ONE_LOOP", 1) != 0; }  // (development builds: 0 keeps the nine loops)
+template <bool ONE_LOOP>
+struct KnnWalkSlots {
+    int2 slot[ONE_LOOP ? KNN_WALK_ROWS * KNN_WALK_STRIDE : 1];
+    __device__ __forceinline__ int2* of_lane() { return ONE_LOOP ? slot + threadIdx.x : nullptr; }  // block = (256)
+};
+
+template <int K, bool TIGHT = false, bool ONE_LOOP = false>
 __device__ __forceinline__ void knn_grid_query(const KnnGridDesc& g, const int32_t* __restrict__ cell_start,
-                                               const float4* __restrict__ sorted, f3 q, KnnList<K>& best, bool rescan = false) {
+                                               const float4* __restrict__ sorted, f3 q, KnnList<K>& best, bool rescan = false,
+                                               int count = 0, int2* walk = nullptr) {
+    static_assert(!(TIGHT && ONE_LOOP), "the tight search keeps its own loops");
     // TIGHT scans the query's own cell twice (alone, then inside the 3 x 3 x 3 block): harmless for K = 1, where a repeated
     // candidate cannot displace anything, but a K > 1 list would hold the same node twice
     static_assert(!TIGHT || K == 1, "the tight stop bound re-scans the own cell: 1-NN only");
@@ -171,9 +187,8 @@ __device__ __forceinline__ void knn_grid_query(const KnnGridDesc& g, const int32
     // the 3 x 3 x 3 block around the query's cell as nine x-rows of cells (the cells of an x-row are consecutive in the sorted
     // node array): the rows' ranges requested together — unconditional loads from clamped cells, a row outside the grid is
     // empty —, then every row's candidates
-    auto scan_block3 = [&]() __attribute__((always_inline)) {
+    auto block3_rows = [&](int (&rbeg)[9], int (&rend)[9]) __attribute__((always_inline)) {
         const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
-        int rbeg[9], rend[9];
 #pragma unroll
         for (int i = 0; i < 9; ++i) {
             const int z = cz - 1 + i / 3, y = cy - 1 + i % 3;
@@ -182,11 +197,39 @@ __device__ __forceinline__ void knn_grid_query(const KnnGridDesc& g, const int32
             const int b = cell_start[c + x0], e = cell_start[c + x1 + 1];
             rbeg[i] = in ? b : 0, rend[i] = in ? e : 0;
         }
+    };
+    auto scan_block3 = [&]() __attribute__((always_inline)) {
+        int rbeg[9], rend[9];
+        block3_rows(rbeg, rend);
         // (the row of the query's own cell first, then the four rows that share a face with it, then the corners: the list
         // fills with near candidates early, and a late candidate that no lane of the wave accepts skips the insertion)
         constexpr int order[9] = {4, 1, 3, 5, 7, 0, 2, 6, 8};
 #pragma unroll
         for (int i = 0; i < 9; ++i) scan_range(rbeg[order[i]], rend[order[i]]);
+    };
+    // the same nine rows in the same order as ONE loop: every lane walks its own ranges, a batch of four inside one range at a
+    // time, and the wave leaves when its last lane has finished.  A lane's trip count is fixed before the loop from the
+    // eighteen table words, the ranges clamped to the array (knn_walk_plan): a damaged table can neither keep a wave here
+    // nor send a load outside `sorted`.  The ranges wait in the lane's LDS column, where a computed slot is an address.
+    auto walk_block3 = [&]() __attribute__((always_inline)) {
+        int rbeg[9], rend[9];
+        block3_rows(rbeg, rend);
+        const int steps = knn_walk_plan(rbeg, rend, count, [&](int slot, int b, int e) { walk[slot * KNN_WALK_STRIDE] = make_int2(b, e); });
+        const int cap   = KNN_WALK_ROWS * ((count + KNN_WALK_BATCH - 1) / KNN_WALK_BATCH);  // (uniform; steps <= cap)
+        KnnWalk w;
+        knn_walk_begin(w);
+        for (int s = 0; s < cap && __any(s < steps); ++s) {
+            if (s < steps) {
+                int j, end;
+                knn_walk_step(w, [&](int slot, int& b, int& e) { const int2 r = walk[slot * KNN_WALK_STRIDE]; b = r.x, e = r.y; }, j, end);
+                float4 n[KNN_WALK_BATCH];
+#pragma unroll
+                for (int t = 0; t < KNN_WALK_BATCH; ++t) n[t] = sorted[min(j + t, end - 1)];
+#pragma unroll
+                for (int t = 0; t < KNN_WALK_BATCH; ++t)
+                    if (j + t < end) best.push(dist2(q, n[t].x, n[t].y, n[t].z), __float_as_int(n[t].w));
+            }
+        }
     };
     if (TIGHT) {
         // shell 0 (the query's own cell) — a 1-NN search on a fine grid usually ends here —, then, if it does not, shells 0
@@ -297,7 +340,8 @@ __device__ __forceinline__ void knn_grid_query(const KnnGridDesc& g, const int32
         // instead of 27 cells (54) walked one by one.  Nearly every query ends here: the stop rule below is that of r = 1.
         // The query is a chain of dependent loads and little else (a wave of 64 queries is resident from launch to end:
         // 4 waves per SIMD at C2), so the loads are issued for memory-level parallelism (scan_block3 above).
-        scan_block3();
+        if (ONE_LOOP) walk_block3();
+        else scan_block3();
         if (best.dist(K - 1) < g.cs * g.cs * 0.9999f) return;  // (r = 1: every node not visited is at least one cell away)
         r_first = 2;  // (a grid of at most 2 cells per axis has been visited completely: the loop below does not run)
     }

@@ -188,16 +188,20 @@ __global__ __launch_bounds__(256) void prepare_rows_kernel(SolveView s, SolveSta
 //                                       write row N + n k + j; their first 3 D threads zero the unknowns, the first
 //                                       workgroup the state block and the tickets (reset_kernel)
 // Same searches, same expressions, same operands: every output holds the bits the three launches leave.
-template <int K>
+// ONE_LOOP: the data role's lanes walk the nine rows around their cell in one loop each (knn_walk.hpp; the ranges wait in
+// LDS, 18 KiB per workgroup); false — development builds, DFA_KNN_ONE_LOOP=0 — keeps the nine wave-wide loops.
+template <int K, bool ONE_LOOP>
 __global__ __launch_bounds__(256) void graph_rows_kernel(SolveView s, KnnGridView grid, SolveState* __restrict__ st,
                                                          unsigned int* __restrict__ ticket, int nticket, int data_blocks) {
     static_assert(K % 4 == 0, "rows by 16-byte stores");
+    static_assert(KNN_WALK_STRIDE == 256, "one column of slots per thread");
+    __shared__ KnnWalkSlots<ONE_LOOP> slots;
     if ((int)blockIdx.x < data_blocks) {
         const int v = blockIdx.x * blockDim.x + threadIdx.x;
         if (v >= s.N) return;
         const f3 q = mk3(s.canon[3 * (size_t)v], s.canon[3 * (size_t)v + 1], s.canon[3 * (size_t)v + 2]);
         KnnList<K> best;
-        knn_grid_query<K>(*grid.desc, grid.cell_start, grid.sorted, q, best);
+        knn_grid_query<K, false, ONE_LOOP>(*grid.desc, grid.cell_start, grid.sorted, q, best, false, s.D, slots.of_lane());
         int ids[K];
         float ws[K];
         knn_ids_weights<K>(best, K, s.node_pos, s.node_w, true, q, ids, ws);
@@ -303,7 +307,20 @@ bool solve_graph_rows_fits(const SolveView& s) {
 hipError_t solve_build_graph_rows(const SolveView& s, const KnnGridView& grid, SolveState* state, unsigned int* ticket,
                                   int nticket, hipStream_t st) {
     const int data_blocks = (s.N + 255) / 256, reg_blocks = (s.D + 3) / 4;
-    KDISPATCH(graph_rows_kernel, s.k, <<<data_blocks + reg_blocks, 256, 0, st>>>(s, grid, state, ticket, nticket, data_blocks));
+#define GRAPH_ROWS_LAUNCH(K, ONE_LOOP) \
+    graph_rows_kernel<K, ONE_LOOP><<<data_blocks + reg_blocks, 256, 0, st>>>(s, grid, state, ticket, nticket, data_blocks)
+#ifdef DFA_DEV_AB
+    if (!knn_one_loop()) {
+        if (s.k <= 4) GRAPH_ROWS_LAUNCH(4, false);
+        else if (s.k <= 8) GRAPH_ROWS_LAUNCH(8, false);
+        else GRAPH_ROWS_LAUNCH(16, false);
+        return transpose_rows(s, st);
+    }
+#endif
+    if (s.k <= 4) GRAPH_ROWS_LAUNCH(4, true);
+    else if (s.k <= 8) GRAPH_ROWS_LAUNCH(8, true);
+    else GRAPH_ROWS_LAUNCH(16, true);
+#undef GRAPH_ROWS_LAUNCH
     return transpose_rows(s, st);
 }
 

@@ -451,13 +451,17 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
         }
 }
 
-template <int K, bool GRID>
+// ONE_LOOP (grid searches): a lane walks the nine rows around its cell in one loop (knn_walk.hpp); false — development builds,
+// DFA_KNN_ONE_LOOP=0 — keeps the nine wave-wide loops
+template <int K, bool GRID, bool ONE_LOOP = GRID>
 __global__ __launch_bounds__(256) void knn_kernel(const float* __restrict__ node_pos,
                                                   const float* __restrict__ node_w, int D,
                                                   const float* __restrict__ query, int n_query, int k,
                                                   int32_t* __restrict__ idx, float* __restrict__ weights,
                                                   KnnGridView grid) {
+    static_assert(GRID || !ONE_LOOP, "the walk is the grid search's");
     __shared__ float4 tile[GRID ? 1 : KNN_TILE];
+    __shared__ KnnWalkSlots<ONE_LOOP> slots;
     const int v       = blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = v < n_query;
     f3 q              = mk3(0.f, 0.f, 0.f);
@@ -465,7 +469,7 @@ __global__ __launch_bounds__(256) void knn_kernel(const float* __restrict__ node
     KnnList<K> best;
     if (GRID) {
         if (!active) return;
-        knn_grid_query<K>(*grid.desc, grid.cell_start, grid.sorted, q, best);
+        knn_grid_query<K, false, ONE_LOOP>(*grid.desc, grid.cell_start, grid.sorted, q, best, false, D, slots.of_lane());
     } else {
         knn_scan<K>(node_pos, D, q, best, tile);
         if (!active) return;
@@ -710,6 +714,14 @@ hipError_t launch_knn(const float* node_pos, const float* node_w, int D, const f
         else knn_wave_kernel<16><<<wgrid, block, 0, s>>>(node_pos, node_w, D, query, n_query, k, idx, weights, g);
         return hipGetLastError();
     }
+#ifdef DFA_DEV_AB
+    if (use_grid && !knn_one_loop()) {
+        if (k <= 4) knn_kernel<4, true, false><<<gridDim, block, 0, s>>>(node_pos, node_w, D, query, n_query, k, idx, weights, g);
+        else if (k <= 8) knn_kernel<8, true, false><<<gridDim, block, 0, s>>>(node_pos, node_w, D, query, n_query, k, idx, weights, g);
+        else knn_kernel<16, true, false><<<gridDim, block, 0, s>>>(node_pos, node_w, D, query, n_query, k, idx, weights, g);
+        return hipGetLastError();
+    }
+#endif
     KGDISPATCH(knn_kernel, k, use_grid, <<<gridDim, block, 0, s>>>(node_pos, node_w, D, query, n_query, k, idx, weights, g));
     return hipGetLastError();
 }
