@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libdynfu_amd.so")
-SOURCES = ["tsdf.hip", "tsdf_warped.hip", "tsdf_warped_color.hip", "color.hip", "knn_field.hip", "warp.hip", "solve_graph.hip", "solve_linearise.hip", "solve_assemble.hip", "solve_pcg.hip",
+SOURCES = ["tsdf.hip", "tsdf_warped.hip", "tsdf_warped_color.hip", "color.hip", "knn_field.hip", "knn_grid.hip", "knn.hip", "correspond.hip", "warp.hip", "solve_graph.hip", "solve_linearise.hip", "solve_assemble.hip", "solve_pcg.hip",
            "solve_pcg_launched.hip", "solve_pcg_team.hip", "solve6_graph.hip", "reg_hierarchy.hip", "solve6_pattern.hip", "solve6_linearise.hip",
            "solve6_assemble.hip", "solve6_pcg.hip", "solve6_update.hip", "mc.hip", "extract.hip", "img.hip", "render.hip", "raster.hip", "visibility.hip", "icp.hip", "points.hip",
            "capi.cpp", "capi_tsdf.cpp", "capi_field.cpp", "capi_image.cpp", "capi_warp.cpp", "capi_solver.cpp", "capi_solver6.cpp"]

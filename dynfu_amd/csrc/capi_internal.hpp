@@ -69,7 +69,7 @@ inline int warped_args_ok(const char* fn, bool reference_mode, const uint16_t* d
     return DFA_OK;
 }
 
-// device scratch of one uniform grid (warp.hip): the node grid of the k-NN searches and, with more cells, the grid part
+// device scratch of one uniform grid (knn_grid.hip): the node grid of the k-NN searches and, with more cells, the grid part
 // of dfa_correspond's point grid.  (Declared in a named namespace: stream_scratch<GridScratch> is ONE table per process,
 // whichever unit asks for it; a type of an anonymous namespace would be another type, and another grid, in every unit.)
 struct GridScratch {

@@ -1,6 +1,6 @@
 // capi_warp.cpp — C ABI (include/dynfu_amd.h), the warp-field seam and the point utilities: k-NN, warping, blending,
 // repack / transform / compact, the two correspondence searches, with the scratch each keeps per stream.  Argument
-// checks and launcher calls only (capi_internal.hpp); the kernels are in warp.hip and points.hip.
+// checks and launcher calls only (capi_internal.hpp); the kernels are in knn_grid.hip, knn.hip, warp.hip, correspond.hip and points.hip.
 #include "capi_internal.hpp"
 
 using namespace dfa::capi;

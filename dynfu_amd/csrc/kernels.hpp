@@ -45,7 +45,7 @@ hipError_t launch_raycast_depth(const uint32_t* vol, int X, int Y, int Z, const 
                                 float step_factor, float delta_factor, uint16_t* depth, int depth_step,
                                 float* normals, int normals_step, int cols, int rows, hipStream_t s);
 
-// warp.hip
+// knn_grid.hip
 // Uniform grid over the deformation nodes (device-resident, geometry computed on the device).
 constexpr int KNN_GRID_MAX_DIM   = 32;
 constexpr int KNN_GRID_MAX_CELLS = KNN_GRID_MAX_DIM * KNN_GRID_MAX_DIM * KNN_GRID_MAX_DIM;
@@ -73,12 +73,31 @@ struct PointGridView {
 };
 hipError_t point_grid_build(const PointGridView& pg, const float* pts, int n, hipStream_t s);
 hipError_t knn_grid_build(const KnnGridView& g, const float* node_pos, int D, hipStream_t s);
+
+// knn.hip
 // grid == nullptr: exhaustive scan
 hipError_t launch_knn(const float* node_pos, const float* node_w, int D, const float* query, int n_query, int k,
                       int32_t* idx, float* weights, const KnnGridView* grid, hipStream_t s);
+
+// correspond.hip
+hipError_t launch_correspond_projective(const float* verts, const float* normals, int n, const float* vmap, int vmap_step,
+                                        const float* nmap, int nmap_step, int cols, int rows, float fx, float fy, float cx,
+                                        float cy, float dist_thres, float min_cosine, float* out_v, float* out_n,
+                                        int32_t* out_pixel, hipStream_t s);
+hipError_t launch_correspond(const float* canon_v, const float* canon_n, int n_canon, const float* live_v,
+                             int n_live, float* out_v, float* out_n, int32_t* out_idx, const KnnGridView* grid,
+                             hipStream_t s);
+
+// warp.hip
 hipError_t launch_warp_to_live(const float* node_pos, const float* node_dq, const float* node_w, int D, int k,
                                const float* verts, const float* normals, int N, float* out_verts, float* out_normals,
                                const KnnGridView* grid, hipStream_t s);
+hipError_t launch_dqb_support(const float* node_pos, const float* node_dq, const float* node_w, int D, int k,
+                              const float* pts, int n, float* out_dq, uint8_t* out_flag, const KnnGridView* grid,
+                              hipStream_t s);
+hipError_t launch_warp_graph(const float* node_pos, const float* node_dq, const float* node_w, int k, const int32_t* idx,
+                             const float* verts, const float* normals, int N, float* out_verts, float* out_normals,
+                             hipStream_t s);
 
 // tsdf_warped.hip — a depth frame integrated through the warp field, the four sweeps: searching (here) and served from a k-NN
 // field (below, behind KnnFieldView).  dfa_tsdf_integrate_warped: bricks: knn_field_bricks(X, Y, Z) bytes (warped_bricks.hpp)
@@ -161,22 +180,6 @@ hipError_t launch_tsdf_integrate_warped6_color_field(const uint16_t* dists, int 
 // color.hip — dfa_color_sample: per vertex, the colour volume's words blended over the 8 corners of its cell
 hipError_t launch_color_sample(const uint32_t* colors, int X, int Y, int Z, const float voxel_size[3], const float* vertices,
                                int stride, int N, const float* to_volume, uint8_t* out, hipStream_t s);
-
-hipError_t launch_correspond_projective(const float* verts, const float* normals, int n, const float* vmap, int vmap_step,
-                                        const float* nmap, int nmap_step, int cols, int rows, float fx, float fy, float cx,
-                                        float cy, float dist_thres, float min_cosine, float* out_v, float* out_n,
-                                        int32_t* out_pixel, hipStream_t s);
-hipError_t launch_correspond(const float* canon_v, const float* canon_n, int n_canon, const float* live_v,
-                             int n_live, float* out_v, float* out_n, int32_t* out_idx, const KnnGridView* grid,
-                             hipStream_t s);
-
-hipError_t launch_dqb_support(const float* node_pos, const float* node_dq, const float* node_w, int D, int k,
-                              const float* pts, int n, float* out_dq, uint8_t* out_flag, const KnnGridView* grid,
-                              hipStream_t s);
-
-hipError_t launch_warp_graph(const float* node_pos, const float* node_dq, const float* node_w, int k, const int32_t* idx,
-                             const float* verts, const float* normals, int N, float* out_verts, float* out_normals,
-                             hipStream_t s);
 
 // points.hip
 hipError_t launch_repack_points(const float* src, int sstride, float* dst, int dstride, int n, float pad, hipStream_t s);

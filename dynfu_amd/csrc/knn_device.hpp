@@ -1,7 +1,27 @@
-// knn_device.hpp — device side of the exact k-NN searches over the node grid, shared by the kernels of warp.hip and the
-// fused graph-build kernel of solve_graph.hip: the sorted candidate list, the distance expression, the one-lane-per-query grid
-// search (knn_grid_query) and the one-wave-per-query search (knn_wave_search) — and what a point does with its neighbour list:
-// the ordered blend (calc_dqb) and the support rule (support_min), shared with the warped sweeps (warped_sweep_device.hpp) and the k-NN field (knn_field.hip).  The grid itself is built in warp.hip.
+// knn_device.hpp — device side of the exact k-NN searches of the deformation nodes, shared by the kernels of knn.hip, warp.hip
+// and correspond.hip, the fused graph-build kernel of solve_graph.hip, the regularisation hierarchy, the k-NN field and the warped
+// sweeps: the sorted candidate list, the distance expression, the exhaustive scan (knn_scan), the one-lane-per-query grid search
+// (knn_grid_query) and the one-wave-per-query search (knn_wave_search).
+//
+// Reference semantics: src/dynfu/warp_field.cpp:99-171 (nanoflann KD-tree k-NN per vertex on
+// the CPU, three std::vector allocations per query) and src/dynfu/utils/node.cpp:29-36.
+//
+// MI355X design.  The result contract is "the k nodes with the smallest (squared distance,
+// node index) pairs, ascending" — what nanoflann returns up to the order of exact ties.  Two
+// exact searches produce it:
+//   * brute force (small problems): one lane per query, node positions staged through LDS in
+//     1024-node tiles (a wave reads one node per step -> LDS broadcast), the k best kept in
+//     registers as a sorted list updated by an unrolled compare-exchange chain;
+//   * uniform grid (n_query * D large): nodes are bucketed by a counting sort into at most 32^3
+//     cells sized ~2 node spacings (the grid geometry is computed ON the device from the node
+//     bounding box, no host round trip); a query walks Chebyshev shells of cells around its own
+//     cell and stops once its k-th distance is below the distance to the next shell.  At
+//     262 k vertices x 2 k nodes that is ~50 candidates per query instead of 2048.
+// Both use the same distance expression (nanoflann L2_Simple_Adaptor order of operations) so
+// the neighbour lists are bit-identical to the CPU oracle's.
+// The solver plan's graph build runs both of its searches inside one launch of its own (solve_graph.hip: graph_rows_kernel);
+// launch_knn (knn.hip) serves everyone else (dfa_knn, the host adaptor, plans whose nodes are not in the grid).  What a point
+// does with its list — the blend and the support rule — is in dqb_device.hpp.  The grid itself is built in knn_grid.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,6 +72,42 @@ __device__ __forceinline__ float dist2(f3 q, float gx, float gy, float gz) {
     return (d0 * d0 + d1 * d1) + d2 * d2;
 }
 
+// ---------------------------------------------------------------------------- brute force
+constexpr int KNN_TILE = 1024;
+// scans all D nodes (block-cooperative LDS staging); every thread of the block must call it
+template <int K>
+__device__ __forceinline__ void knn_scan(const float* __restrict__ node_pos, int D, f3 q, KnnList<K>& best,
+                                         float4* tile) {
+    best.init();
+    for (int base = 0; base < D; base += KNN_TILE) {
+        const int n = min(KNN_TILE, D - base);
+        __syncthreads();
+        for (int j = threadIdx.x; j < n; j += blockDim.x) {
+            const float* p = node_pos + 3 * (size_t)(base + j);
+            tile[j]        = make_float4(p[0], p[1], p[2], 0.f);
+        }
+        __syncthreads();
+        for (int j = 0; j < n; ++j) {
+            const float4 g = tile[j];
+            best.push(dist2(q, g.x, g.y, g.z), base + j);
+        }
+    }
+}
+
+// a kernel<K, GRID> by the bucket of k (4, 8, 16) and the search: the grid's or the exhaustive scan (launch_knn, launch_warp_to_live)
+#define KGDISPATCH(kernel, k, use_grid, ...)                         \
+    do {                                                             \
+        if (use_grid) {                                              \
+            if ((k) <= 4) kernel<4, true> __VA_ARGS__;               \
+            else if ((k) <= 8) kernel<8, true> __VA_ARGS__;          \
+            else kernel<16, true> __VA_ARGS__;                       \
+        } else {                                                     \
+            if ((k) <= 4) kernel<4, false> __VA_ARGS__;              \
+            else if ((k) <= 8) kernel<8, false> __VA_ARGS__;         \
+            else kernel<16, false> __VA_ARGS__;                      \
+        }                                                            \
+    } while (0)
+
 // the first k entries of a query's list as node ids and RBF weights (Warpfield::getWeightsAndNearestNeighbours,
 // warp_field.cpp:99-125); -1 / 0 for an absent neighbour and for the slots from k on
 template <int K>
@@ -68,57 +124,6 @@ __device__ __forceinline__ void knn_ids_weights(const KnnList<K>& best, int k, c
                 out_w[j] = transformation_weight(mk3(node_pos[3 * n], node_pos[3 * n + 1], node_pos[3 * n + 2]), node_w[n], q);
         }
     }
-}
-
-// Warpfield::calcDQB (warp_field.cpp:127-148) given the neighbour list
-template <int K>
-__device__ __forceinline__ DQ calc_dqb(const KnnList<K>& nb, int k, const float* __restrict__ node_pos,
-                                       const float* __restrict__ node_dq, const float* __restrict__ node_w, f3 p) {
-    DQ sum = dq_identity();  // :133
-    // the neighbours' positions, radii and transforms four at a time by unconditional loads (an absent neighbour reads node 0
-    // and is skipped): with the loads inside the `if` they were k dependent round trips.  Same products in the same order.
-    constexpr int G = K < 4 ? K : 4;
-#pragma unroll
-    for (int h = 0; h < K; h += G) {
-        f3 g[G];
-        float r[G];
-        DQ q[G];
-        bool on[G];
-#pragma unroll
-        for (int jj = 0; jj < G; ++jj) {
-            const int j = h + jj;
-            on[jj]      = j < k && nb.index(j) >= 0;
-            const int n = on[jj] ? nb.index(j) : 0;
-            g[jj] = mk3(node_pos[3 * n], node_pos[3 * n + 1], node_pos[3 * n + 2]), r[jj] = node_w[n];
-            q[jj] = dq_load(node_dq + 8 * (size_t)n);
-        }
-#pragma unroll
-        for (int jj = 0; jj < G; ++jj)
-            if (on[jj]) sum = dq_mul(sum, dq_scale(q[jj], transformation_weight(g[jj], r[jj], p)));  // :139-141
-    }
-    return dq_normalize(sum);  // :145
-}
-
-// Warpfield::getUnsupportedVertices (warp_field.cpp:34-62): the support quotient |p - g_m| / dg_w_m of one node (:45-46 —
-// pow(float, int) is double arithmetic, the root is rounded to float on assignment) ...
-__device__ __forceinline__ float support_quotient(f3 p, const float* __restrict__ node_pos, const float* __restrict__ node_w, int m) {
-    const double dx = (double)(p.x - node_pos[3 * m]), dy = (double)(p.y - node_pos[3 * m + 1]),
-                 dz = (double)(p.z - node_pos[3 * m + 2]);
-    return (float)sqrt(dx * dx + dy * dy + dz * dz) / node_w[m];
-}
-// ... and its minimum over the neighbour list: the point is unsupported when this is >= 1 (:53)
-template <int K>
-__device__ __forceinline__ float support_min(const KnnList<K>& best, int k, const float* __restrict__ node_pos,
-                                             const float* __restrict__ node_w, f3 p) {
-    float mn = __builtin_huge_valf();  // :40
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        if (j < k && best.index(j) >= 0) {
-            const float q = support_quotient(p, node_pos, node_w, best.index(j));
-            if (q <= mn) mn = q;  // :48-50
-        }
-    }
-    return mn;
 }
 
 __device__ __forceinline__ void cell_of(const KnnGridDesc& g, f3 p, int& cx, int& cy, int& cz) {

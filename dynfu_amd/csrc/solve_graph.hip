@@ -4,7 +4,7 @@
 // assembly gathers through.  Row graph and record head: solve_rows.hpp.
 //
 // Launches of one problem (dfa_solver_set_problem), nodes in the grid, k in {4, 8, 16}:
-//   grid_build_one_kernel (warp.hip) -> graph_rows_kernel<K> (both k-NN searches, rows, reset) -> tg_count_kernel ->
+//   grid_build_one_kernel (knn_grid.hip) -> graph_rows_kernel<K> (both k-NN searches, rows, reset) -> tg_count_kernel ->
 //   tg_colscan_kernel -> tg_fill_kernel [-> sort_node_lists_kernel, order-stable variant]
 // otherwise (no grid, another k, no vertices; DFA_GRAPH_ROWS=0 in development builds):
 //   [grid build ->] knn_kernel / knn_wave_kernel (vertices) -> knn_wave_kernel / knn_kernel (nodes) ->

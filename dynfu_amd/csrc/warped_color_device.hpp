@@ -16,6 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "dqb_device.hpp"
 #include "warped_sweep_device.hpp"
 
 namespace dfa {

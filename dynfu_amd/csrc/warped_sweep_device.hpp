@@ -11,6 +11,7 @@
 #include "blend6_device.hpp"
 #include "device_math.hpp"
 #include "dq_device.hpp"
+#include "dqb_device.hpp"
 #include "knn_device.hpp"
 #include "knn_field_device.hpp"
 #include "tsdf_integrate_device.hpp"

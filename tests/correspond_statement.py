@@ -1,7 +1,7 @@
 """CPU statement of the two correspondence searches in numpy: dfa_correspond (exact 1-NN of every live vertex among the
 canonical ones, and the gathered clouds) and dfa_correspond_projective (the gates of find_coresp), written from the
 contract in include/dynfu_amd.h — plus the choice between the four search forms of dfa_correspond (csrc/capi_warp.cpp) and the
-geometry of the two grids (grid_setup_kernel, pgrid_finalize_kernel in csrc/warp.hip) in float32, so that a test can say
+geometry of the two grids (grid_setup_kernel, pgrid_finalize_kernel in csrc/knn_grid.hip) in float32, so that a test can say
 in which cell, and how far from its walls, a query sits.
 
 Every result is exact: integers, or float32 values compared by their bits."""

@@ -1,5 +1,5 @@
 """CPU tests of tests/warp_statement.py (the numpy / fp64 statement of the warp-field seam the -m gpu tests compare
-csrc/warp.hip and csrc/dq_device.hpp with).  No GPU."""
+csrc/knn.hip, csrc/warp.hip, csrc/dqb_device.hpp and csrc/dq_device.hpp with).  No GPU."""
 import json
 import os
 
