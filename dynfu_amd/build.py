@@ -142,7 +142,7 @@ def build_cpp_tests(force=False, verbose=False):
     built = {}
     for name, needs in (("test_host_dq", []), ("test_host_solver", ["host"]), ("test_host_tsdf", ["host", "oracle"]),
                         ("test_host_dynfusion", ["host", "oracle"]), ("test_host_icp", ["host"]),
-                        ("test_tsdf_classify", ["oracle", "ieee"]), ("test_launch_budget", []), ("test_host_io", ["host"]), ("test_host_kinfu", ["host"]), ("test_host_northstar_frames", ["host"]),
+                        ("test_tsdf_classify", ["oracle", "ieee"]), ("test_launch_budget", []), ("test_host_io", ["host"]), ("test_host_kinfu", ["host"]), ("test_host_northstar_frames", ["host"]), ("test_host_dynfusion_frames", ["host"]),
                         ("test_host_extract", ["host"]), ("test_host_render", ["host"]), ("test_host_mc_indexed", ["host"]), ("test_host_mesh_view", ["host"]), ("test_host_visible_term", ["host"]),
                         ("test_host_tsdf_warped", ["host"]), ("test_host_tsdf_warped6", ["host"]), ("test_host_regrow", ["host"]), ("test_host_rigid_align", ["host"]),
                         ("test_knn_field_size", []), ("test_host_knn_field", ["host"]), ("test_rigid_step", []), ("test_host_rigid_loop", ["host"]),
@@ -153,9 +153,9 @@ def build_cpp_tests(force=False, verbose=False):
             continue
         deps = [src, os.path.join(tdir, "minitest.hpp"), host, os.path.join(CSRC, "tsdf_classify.hpp"), os.path.join(CSRC, "launch_budget.hpp"),
                 os.path.join(CSRC, "warped_bricks.hpp"), os.path.join(CSRC, "rigid_step.hpp"), os.path.join(CSRC, "knn_walk.hpp")]
-        fixtures = os.path.join(tdir, "dynfu_fixtures.hpp")
-        if os.path.exists(fixtures):  # (a tests/ tree from before the header was added has none, and needs none)
-            deps.append(fixtures)
+        for header in ("dynfu_fixtures.hpp", "frames_io.hpp"):
+            if os.path.exists(os.path.join(tdir, header)):  # (a tests/ tree from before the header was added has none, and needs none)
+                deps.append(os.path.join(tdir, header))
         if force or _stale(exe, deps):
             cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-I" + inc, src, "-o", exe]
             if "ieee" in needs:  # CPU model of a kernel: same arithmetic contract as the oracle, hardware fma

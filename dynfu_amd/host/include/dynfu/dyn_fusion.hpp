@@ -184,6 +184,12 @@ public:
     bool operator()(const kfusion::cuda::Depth& depth, const kfusion::cuda::Image& color);
     void useMarchingCubes(std::shared_ptr<kfusion::cuda::MarchingCubes> mc) { mc_ = mc; }
     std::shared_ptr<dynfu::Frame> getLiveFrame() { return liveFrame; }
+    // reference mode: what the last frame's solve took as its canonical cloud — for every live vertex the nearest vertex of
+    // the warped canonical cloud, with that vertex's normal (findCorrespondingFrame's result itself, not a copy; null before
+    // the first solved frame) — and CombinedSolver::initialCost() / finalCost() of that solve
+    std::shared_ptr<dynfu::Frame> getCorrespondingFrame() { return correspondingFrame; }
+    double solveInitialCost() const { return solve_initial_cost_; }
+    double solveFinalCost() const { return solve_final_cost_; }
     // KinFu::getMesh (kinfu.cpp:262): the marching-cubes triangles of the last frame, KinFu::convertToMesh's layout
     // (built on first use: one small vector per triangle is not something every frame should pay for)
     std::shared_ptr<dfa::PolygonMesh> getMesh();
@@ -292,6 +298,8 @@ private:
     std::shared_ptr<dynfu::Frame> canonicalFrame;
     std::shared_ptr<dynfu::Frame> canonicalFrameWarpedToLive;
     std::shared_ptr<dynfu::Frame> liveFrame;
+    std::shared_ptr<dynfu::Frame> correspondingFrame;  // kept for getCorrespondingFrame(): the next solved frame replaces it
+    double solve_initial_cost_ = 0.0, solve_final_cost_ = 0.0;
     std::shared_ptr<Warpfield> warpfield;
     std::shared_ptr<dfa::PolygonMesh> mesh_;
     // the last frame's marching-cubes output (:76 / :122): in HBM (a view of mc_buffer_, valid until the next frame),

@@ -48,6 +48,9 @@ public:
     // number of neighbours (the reference's compile-time KNN; run-time here, default 8)
     void setKnn(int k) { knn_ = k; }
     int getKnn() const { return knn_; }
+    // k-NN searches warpToLive has run for a device-resident cloud so far: a call that finds the cloud, N, D and k of the call
+    // before reuses that call's graph and does not count (0 before init)
+    int warpGraphSearches() const;
 
 private:
     float epsilon = 0.f;

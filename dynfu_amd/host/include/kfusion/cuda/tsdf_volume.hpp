@@ -122,6 +122,7 @@ public:
     void dropKnnField() { field_ = KnnFieldState(); }
     const dfa_knn_field* knnField() const { return field_.handle.get(); }
     int knnFieldNodes() const;  // the node count of the field's rows (0 without a field)
+    int knnFieldK() const { return field_.handle ? field_.k : 0; }  // ... and the ids per row it was built with
     // the voxels of another volume of the same dimensions, copied (a copy of the OBJECT shares them); the map comes along
     // when the source's is trusted.  Extension of the reference's interface.
     void copyVoxelsFrom(const TsdfVolume& src);

@@ -170,6 +170,8 @@ void DynFusion::warpCanonicalToLiveOpt(dfa::Affine3f affine) {
     clk.mark("  initializeProblemInstance");
     combinedSolver.solveAll();                                                   // :207
     clk.mark("  solveAll");
+    correspondingFrame  = corresponding;
+    solve_initial_cost_ = combinedSolver.initialCost(), solve_final_cost_ = combinedSolver.finalCost();
 }
 
 std::shared_ptr<dynfu::Frame> DynFusion::findCorrespondingFrame(dfa::PointCloud<dfa::PointXYZ> canonicalVertices,
@@ -257,10 +259,11 @@ void DynFusion::syncKnnField() {
     const Warpfield::DeviceNodeView nodes = warpfield->deviceNodes(false);
     kfusion::cuda::TsdfVolume& vol        = *canonical_volume_;
     bool ok = true;
-    if (!vol.knnField()) {
+    const int k = dynfuParams.north_star ? northStarKnn(warpfield->getKnn()) : warpfield->getKnn();
+    // (a field of another k — Warpfield::setKnn after frame 0 built it — serves no integration: it is built again)
+    if (!vol.knnField() || vol.knnFieldK() != k) {
         const dfa::Affine3f camera;  // north-star mode: the node frame is frame 0's camera, which stays at the origin
-        ok = vol.buildKnnField(nodes.pos, nodes.w, nodes.D, dynfuParams.north_star ? northStarKnn(warpfield->getKnn()) : warpfield->getKnn(),
-                               dynfuParams.north_star ? &camera : nullptr, dynfuParams.fuse_knn_field_max_bytes);
+        ok = vol.buildKnnField(nodes.pos, nodes.w, nodes.D, k, dynfuParams.north_star ? &camera : nullptr, dynfuParams.fuse_knn_field_max_bytes);
     } else if (vol.knnFieldNodes() < nodes.D) {
         ok = vol.appendKnnField(nodes.pos, nodes.w, nodes.D);
     }

@@ -20,6 +20,7 @@ struct Warpfield::DeviceNodes {
     dfa::DeviceArray<int32_t> knn_idx;
     size_t knn_N = 0;
     int knn_D = 0, knn_k = 0;
+    int knn_searches = 0;  // Warpfield::warpGraphSearches
 };
 
 Warpfield::Warpfield()  = default;
@@ -37,6 +38,7 @@ void Warpfield::addNode(std::shared_ptr<Node> newNode) {
     syncPositions();
 }
 std::vector<std::shared_ptr<Node>> Warpfield::getNodes() { return *nodes; }
+int Warpfield::warpGraphSearches() const { return dev ? dev->knn_searches : 0; }
 
 // node positions and radial basis weights never change after construction: uploaded once
 void Warpfield::syncPositions() {
@@ -190,6 +192,7 @@ std::shared_ptr<dynfu::Frame> Warpfield::warpToLive(std::shared_ptr<dynfu::Frame
             dfa::check(dfa_knn(d.pos.ptr(), d.w.ptr(), d.D, v3.ptr(), (int)N, knn_, d.knn_idx.ptr(), nullptr, nullptr),
                        "Warpfield::warpToLive (k-NN)");
             d.knn_verts = v3, d.knn_N = N, d.knn_D = d.D, d.knn_k = knn_;
+            ++d.knn_searches;
         }
         dfa::check(dfa_warp_to_live_graph(d.pos.ptr(), d.dq.ptr(), d.w.ptr(), d.D, knn_, d.knn_idx.ptr(), v3.ptr(), n3.ptr(),
                                           (int)N, ov.ptr(), on.ptr(), nullptr),
